@@ -5,7 +5,10 @@ A step = one full render (renderer::render semantics, reference src/cpu_renderer
 BASELINE.json configs[2]: closed-room scene with 10,000 triangles, 1920x1080, 256 spp, 5 bounces,
 all inputs (rays, triangles, materials) resident in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line; the figures that take work of their own (`cpu_baseline`,
+`worst_case_untimed`, this box's per-class VALU issue rates, the shader clock during the timed steps) need --full.
+--dump-outputs DIR writes what the last timed step computed -- the RGBA8 frame a caller receives, as float32 -- to DIR/image.npy.
 N > 1 without a torch.distributed environment: this process starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py`, before anything touches
 the GPU) and relays rank 0's JSON line; started under torch.distributed.run it is a rank.
@@ -13,7 +16,7 @@ the GPU) and relays rank 0's JSON line; started under torch.distributed.run it i
 N > 1: the same image is split into pixel-row tiles dealt round-robin to the ranks (strong
 scaling; spath_amd/dist.py); each step ends with one RCCL gather of the RGBA8 tiles to rank 0.
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus `roofline` and
+Prints ONE JSON line on rank 0 with the driver's contract fields plus `roofline` and (--full)
 `cpu_baseline`:
   roofline            the most loaded pipe of the dominant kernel: FP32 vector (VALU) instruction issue.
                       achieved = executed lane-instructions per second = ray-triangle tests/s x lane-instructions
@@ -137,6 +140,25 @@ def profile_entry(fname, key, lib_hash=None):
     return e, None
 
 
+DUMP_BYTES = 60 * 10**6            # --dump-outputs writes at most this much array data (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, image):
+    """The frame of the last timed step, [W*H, 4] RGBA8 in pixel order, as float32 DIR/image.npy.  A frame too large for DUMP_BYTES
+    is replaced by a fixed, seeded sample of its pixels, DIR/image.npy with their indices in DIR/image_pixel_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = image.shape[0]
+    index_path = os.path.join(out_dir, "image_pixel_index.npy")
+    if n * image.shape[1] * 4 > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (image.shape[1] * 4 + 8), replace=False))
+        image = image[idx]
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):
+        os.remove(index_path)
+    np.save(os.path.join(out_dir, "image.npy"), image.astype(np.float32))
+
+
 def host_cores() -> int:
     """Cores this process may actually use: the affinity mask capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -205,18 +227,26 @@ def main():
     ap.add_argument("--tile-rows", type=int, default=0, help="rows per tile of the round-robin shard plan; 0 = largest height <= 8 that balances the ranks")
     ap.add_argument("--kernel", type=str, default="auto", help="scan kernel variant (see sphip_kernel_name)")
     ap.add_argument("--primary-reuse", action="store_true", help="scan the primary ray once per pixel (fewer scans; off for roofline runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write the last step's frame (float32) to DIR/image.npy")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, untimed: the CPU baseline, the "
+                    "large-triangle scene, this box's per-class VALU issue rates, and the shader clock during the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--extras", action="store_true", help="after the timed region also run (untimed, reduced spp) the exact-only scan, "
                     "primary-hit reuse and the opt-in acceleration structure, and report them under reference_runs_untimed; "
                     "off by default so that a profile of the default command contains only the timed kernel")
-    ap.add_argument("--no-worst-case", action="store_true", help="skip the (untimed) large-triangle scene figure")
-    ap.add_argument("--no-valu-microbench", action="store_true", help="do not run build/valu_bench2 (the per-class VALU issue rates of THIS box, ~1 s, untimed)")
+    ap.add_argument("--no-worst-case", action="store_true", help="with --full: skip the (untimed) large-triangle scene figure")
+    ap.add_argument("--no-valu-microbench", action="store_true", help="with --full: do not run build/valu_bench2 (the per-class VALU issue rates of THIS box, ~1 s, untimed)")
     ap.add_argument("--cpu-w", type=int, default=192)
     ap.add_argument("--cpu-h", type=int, default=108)
     ap.add_argument("--cpu-spp", type=int, default=32, help="the CPU sample's spp (default: ~30 s of the reference on 16 threads, 0.25 s poll quantum < 1 %)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(sys.argv[1:], args.gpus))
+        argv = sys.argv[1:]
+        if args.dump_outputs:              # the ranks run from the repository root: pass them the directory as the caller meant it
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        sys.exit(self_launch(argv, args.gpus))
 
     import numpy as np
     import torch
@@ -303,7 +333,7 @@ def main():
         bus = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
     except Exception:
         bus = None
-    clock = ClockSampler(bus)
+    clock = ClockSampler(bus if args.full else None)
     if rank == 0:
         clock.start()
     t0 = time.perf_counter()
@@ -312,9 +342,11 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     sclk_mhz = clock.stop() if rank == 0 else None
-    # per-channel sums of the assembled RGBA8 frame (identical for every --gpus N: pixel-keyed RNG); taken now, the untimed
-    # runs below reuse the shard's output buffer
+    # per-channel sums of the assembled RGBA8 frame (identical for every --gpus N: pixel-keyed RNG) and the dump; taken now,
+    # the untimed runs below reuse the shard's output buffer
     image_sum = [int(x) for x in image[:, :3].to(torch.int64).sum(dim=0).tolist()] if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, image.cpu().numpy())
     st = ctx.stats()                       # figures of the last launch on this rank
     kernel_ms = [a.elapsed_time(b) for a, b in ev]
     # outside the timed region, for reference: the exact-only scan (every pair through the full Moeller-Trumbore test,
@@ -355,7 +387,7 @@ def main():
     # __graft_entry__.build() into build/valu_bench2; without it the committed rates of profiles/r03_valu_microbench_classes.log are used
     live_rates = None
     vb2 = os.path.join(ROOT, "build", "valu_bench2")
-    if world == 1 and not args.no_valu_microbench and os.path.exists(vb2):
+    if world == 1 and args.full and not args.no_valu_microbench and os.path.exists(vb2):
         try:
             import subprocess
             out = subprocess.run([vb2], capture_output=True, text=True, timeout=120).stdout
@@ -372,7 +404,7 @@ def main():
         except Exception as e:           # a measurement aid, never a reason to fail the bench
             live_rates = {"error": repr(e)}
     worst = None
-    if world == 1 and NT >= 64 and not args.no_worst_case:
+    if world == 1 and NT >= 64 and args.full and not args.no_worst_case:
         # large triangles (clutter x10: most rays cross most cylinders): how far the two-stage scan degrades.  Untimed, after
         # the timed region, with the same default kernel (a rocprofv3 pass of this command: --no-worst-case keeps the profile unmixed)
         wt, wm = scene.closed_room(NT, clutter_scale=10.0)
@@ -535,7 +567,7 @@ def main():
                          if kname == "rpl_cylm" else None),
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tris, mats, args)
         else:
             out["cpu_baseline"] = None

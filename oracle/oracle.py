@@ -187,9 +187,7 @@ def ref_run(mode, w, h, spp=1, tris=None, mats=None, threads=8, moves=(), rays=N
             rp = os.path.join(td, "rays.bin")
             np.ascontiguousarray(rays, dtype=F).tofile(rp)
             cmd += ["rays", rp]
-        # a profiler wrapped around the caller (rocprofv3 LD_PRELOADs its tool) must not follow into the CPU child
-        env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD" and not k.startswith(("ROCP", "ROCPROF"))}
-        env["ORACLE_THREADS"] = str(threads)
+        env = dict(os.environ, ORACLE_THREADS=str(threads))
         pr = subprocess.run(cmd, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, check=True)
         if mode == "viewport":
             res = np.fromfile(outp, dtype=F).reshape(w * h, 6)

@@ -33,6 +33,12 @@ def ref_images():
 
 
 @pytest.fixture(scope="session")
+def ref_outputs():
+    """What the compiled reference rendered for the cases of test_oracle_vs_reference.py and test_hip_parity.py."""
+    return dict(np.load(os.path.join(ROOT, "tests", "golden", "ref_outputs.npz")))
+
+
+@pytest.fixture(scope="session")
 def scenes():
     from spath_amd import scene
     return {

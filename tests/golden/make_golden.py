@@ -9,6 +9,7 @@ Writes
                           std::sin/cos hashes over the LCG's angles, flat_normal, ray_intersect, vec3_RGBA,
                           constants) and FNV-1a-64 hashes / channel sums of reference renders and viewports
   ref_default_64x48.npz -- small raw reference images (RGBA8) for byte-level comparison
+  ref_outputs.npz      -- the reference's viewports and images for the cases of test_oracle_vs_reference.py
 
 Everything in these files is OUTPUT DATA of the reference binary; no reference source text is stored.
 The scenes fed to it come from spath_amd/scene.py (values of the default scene: SURVEY.md Appendix C).
@@ -85,6 +86,31 @@ def main():
     json.dump(G, open(os.path.join(HERE, "golden.json"), "w"), indent=1)
     np.savez_compressed(os.path.join(HERE, "ref_small_images.npz"), **raw)
     print("wrote golden.json and ref_small_images.npz:", sorted(raw))
+    ref_outputs()
+
+
+def ref_outputs():
+    """ref_outputs.npz: the reference's viewports and RGBA8 images for the cases of test_oracle_vs_reference.py and
+    test_hip_parity.py::test_flat_equals_live_reference_binary."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_vs_reference as T     # noqa: E402  (the cases are defined once, in the test module)
+    assert O.have_ref(), "oracle/_ref/spath_ref is required (build container only)"
+    out = {}
+    t, m = scene.default_scene()
+    for w, h, spp, threads in T.DEFAULT_SHAPES:
+        out[f"default_viewport_{w}x{h}"] = O.ref_run("viewport", w, h)
+        out[f"default_render_{w}x{h}_s{spp}_T{threads}"] = O.ref_run("render", w, h, spp, t, m, threads=threads)
+        out[f"default_flat_{w}x{h}"] = O.ref_run("flat", w, h, 1, t, m)
+    for name, t, m, w, h, rays in T.synthetic_cases():
+        out[f"{name}_render_{w}x{h}_s2_T8_rays"] = O.ref_run("render", w, h, 2, t, m, threads=8, rays=rays)
+        out[f"{name}_flat_{w}x{h}_rays"] = O.ref_run("flat", w, h, 1, t, m, rays=rays)
+    t, m = T.degenerate_scene()
+    out["degenerate_render_40x30_s3_T8"] = O.ref_run("render", 40, 30, 3, t, m, threads=8)
+    out["degenerate_flat_40x30"] = O.ref_run("flat", 40, 30, 1, t, m)
+    t, m = scene.closed_room(2000)
+    out["closed_room_2000_flat_160x90"] = O.ref_run("flat", 160, 90, 1, t, m)
+    np.savez_compressed(os.path.join(HERE, "ref_outputs.npz"), **out)
+    print("wrote ref_outputs.npz:", sorted(out))
 
 
 if __name__ == "__main__":

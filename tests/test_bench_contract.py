@@ -1,9 +1,10 @@
-"""bench.py prints one JSON line with the driver's contract fields plus roofline and cpu_baseline (tiny workload)."""
+"""bench.py prints one JSON line with the driver's contract fields plus roofline, and with --full cpu_baseline (tiny workload)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +22,7 @@ def _run(args, env=None):
 
 @pytest.mark.gpu
 def test_bench_line_small_workload():
-    d = _run(["--steps", "2", "--warmup", "1", "--width", "256", "--height", "144", "--spp", "4", "--tris", "500",
+    d = _run(["--full", "--steps", "2", "--warmup", "1", "--width", "256", "--height", "144", "--spp", "4", "--tris", "500",
               "--cpu-w", "32", "--cpu-h", "18", "--cpu-spp", "2"])
     for k in REQUIRED:
         assert k in d, k
@@ -44,17 +45,40 @@ def test_bench_line_small_workload():
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_rehearsal_matches_one_rank():
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the line carries the headline and none of the untimed extras; --dump-outputs writes the last timed
+    step's frame, the same bits from run to run."""
+    args = ["--steps", "3", "--warmup", "1", "--width", "256", "--height", "144", "--spp", "4", "--tris", "500"]
+    frames = []
+    for k in range(2):
+        out = os.path.join(tmp_path, str(k))
+        d = _run(args + ["--dump-outputs", out])
+        for key in REQUIRED:
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "Mray/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - d["nominal_rays_per_step"] / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-3 + 1e-4 / d["ms_per_step"]
+        assert d["cpu_baseline"] is None and d["worst_case_untimed"] is None and d["roofline"]["sclk_observed_mhz"] is None
+        assert sorted(os.listdir(out)) == ["image.npy"]
+        img = np.load(os.path.join(out, "image.npy"))
+        assert img.dtype == np.float32 and img.shape == (256 * 144, 4)
+        assert [int(x) for x in img[:, :3].astype(np.int64).sum(axis=0)] == d["image_sum_rgb"] and img[:, :3].any()
+        frames.append(img)
+    assert np.array_equal(frames[0], frames[1])
+
+
+@pytest.mark.gpu
+def test_bench_two_ranks_rehearsal_matches_one_rank(tmp_path):
     """The N > 1 code path (row-tile sharding, gather, max-over-ranks timing) rehearsed on one GPU with gloo."""
     common = ["--steps", "1", "--warmup", "0", "--width", "160", "--height", "90", "--spp", "3", "--tris", "300", "--no-cpu-baseline"]
-    one = _run(common)
+    one = _run(common + ["--dump-outputs", os.path.join(tmp_path, "one")])
     # `python bench.py --gpus 2` with no torch.distributed environment: bench.py starts its own two ranks
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SPATH_BENCH_REHEARSAL"] = "1"
-    two = _run(["--gpus", "2"] + common, env=env)
+    two = _run(["--gpus", "2"] + common + ["--dump-outputs", os.path.join(tmp_path, "two")], env=env)
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and two["rccl_ranks"] == 2
     assert two["image_sum_rgb"] == one["image_sum_rgb"] and two["scans_per_step"] == one["scans_per_step"]
     assert two["kernel_ms_per_rank"]["min"] <= two["kernel_ms_per_rank"]["max"]
+    assert np.array_equal(np.load(os.path.join(tmp_path, "one", "image.npy")), np.load(os.path.join(tmp_path, "two", "image.npy")))
 
 
 def test_bench_self_launch_reports_a_failing_rank():
@@ -74,3 +98,8 @@ def test_bench_refuses_to_run_without_gpu():
         pytest.skip("GPU present")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"], capture_output=True, text=True, cwd=ROOT)
     assert p.returncode != 0 and "needs a GPU" in p.stderr
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, cwd=ROOT)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr

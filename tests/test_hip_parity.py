@@ -83,13 +83,11 @@ def test_flat_equals_reference_fixtures(hip, O, golden, ref_images, scenes):
     assert np.array_equal(hip.render(rays, 64, 48, 1, mode=capi.MODE_FLAT), ref_images["default_flat_64x48_s1_T8_moved"])
 
 
-def test_flat_equals_live_reference_binary(hip, O):
-    """Where the compiled reference travelled to the box: its render_flat on a synthetic scene, exact."""
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/spath_ref not present")
+def test_flat_equals_live_reference_binary(hip, O, ref_outputs):
+    """The compiled reference's render_flat on a synthetic scene (stored in tests/golden/ref_outputs.npz), exact."""
     t, m = scene.closed_room(2000)
     w, h = 160, 90
-    want = O.ref_run("flat", w, h, 1, t, m)
+    want = ref_outputs[f"closed_room_2000_flat_{w}x{h}"]
     hip.set_scene(t, m)
     for v in VARIANTS:
         assert np.array_equal(hip.render(O.viewport(w, h), w, h, 1, mode=capi.MODE_FLAT, flags=v), want), v

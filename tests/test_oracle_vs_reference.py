@@ -1,46 +1,54 @@
-"""Live leg A: C restatement vs the compiled reference on configurations not stored as fixtures.
-Runs wherever oracle/_ref/spath_ref exists (build container; the binary also travels to the GPU box)."""
+"""Leg A on configurations not in golden.json: the C restatement against what the compiled reference rendered for the
+cases below, stored in tests/golden/ref_outputs.npz (written by tests/golden/make_golden.py, which takes the cases from
+this module)."""
 import numpy as np
 import pytest
 
 from spath_amd import scene
 
-
-@pytest.fixture(scope="module")
-def ref(O):
-    if not O.have_ref():
-        pytest.skip("oracle/_ref/spath_ref not built (no /root/reference here)")
-    return O
+DEFAULT_SHAPES = [(50, 37, 3, 8), (50, 37, 3, 5), (16, 16, 6, 16), (81, 3, 2, 7), (5, 3, 2, 8)]
 
 
-@pytest.mark.parametrize("w,h,spp,T", [(50, 37, 3, 8), (50, 37, 3, 5), (16, 16, 6, 16), (81, 3, 2, 7), (5, 3, 2, 8)])
-def test_default_scene_shapes_and_threads(ref, scenes, w, h, spp, T):
-    t, m = scenes["default"]
-    rays = ref.viewport(w, h)
-    assert np.array_equal(ref.ref_run("viewport", w, h), rays)
-    assert np.array_equal(ref.ref_run("render", w, h, spp, t, m, threads=T), ref.render_mt(rays, w, h, t, m, spp, T))
-    assert np.array_equal(ref.ref_run("flat", w, h, 1, t, m), ref.render_flat(rays, w, h, t, m))
-
-
-def test_synthetic_scenes_and_arbitrary_rays(ref):
+def synthetic_cases():
+    """(name, tris, mats, w, h, rays) of two synthetic scenes with rays that are not a camera viewport: random origins inside
+    the room, random (unnormalised) directions."""
     rng = np.random.default_rng(3)
-    for t, m in (scene.closed_room(64, seed=11), scene.open_clutter(40, seed=5)):
+    cases = []
+    for name, (t, m) in (("closed_room_64_s11", scene.closed_room(64, seed=11)), ("open_clutter_40_s5", scene.open_clutter(40, seed=5))):
         w, h = 24, 18
-        # rays that are not a camera viewport: random origins inside the room, random (unnormalised) directions
         rays = np.concatenate([rng.uniform(-1.0, 1.0, (w * h, 3)), rng.normal(size=(w * h, 3))], axis=1).astype(np.float32)
-        a = ref.ref_run("render", w, h, 2, t, m, threads=8, rays=rays)
-        b = ref.render_mt(rays, w, h, t, m, 2, 8)
-        assert np.array_equal(a, b)
-        assert np.array_equal(ref.ref_run("flat", w, h, 1, t, m, rays=rays), ref.render_flat(rays, w, h, t, m))
+        cases.append((name, t, m, w, h, rays))
+    return cases
 
 
-def test_degenerate_triangles(ref):
-    """Zero-area and duplicate triangles, NaN normal of a degenerate triangle never reached."""
+def degenerate_scene():
+    """The default scene plus two duplicate triangles, one of its triangles squashed to a point."""
     t, m = scene.default_scene()
     t = np.concatenate([t, t[:2]]).copy()
     m = np.concatenate([m, m[:2]]).copy()
     t[7, 3:9] = t[7, 0:3].tolist() * 2          # all three vertices equal
+    return t, m
+
+
+@pytest.mark.parametrize("w,h,spp,T", DEFAULT_SHAPES)
+def test_default_scene_shapes_and_threads(O, ref_outputs, scenes, w, h, spp, T):
+    t, m = scenes["default"]
+    rays = O.viewport(w, h)
+    assert np.array_equal(ref_outputs[f"default_viewport_{w}x{h}"], rays)
+    assert np.array_equal(ref_outputs[f"default_render_{w}x{h}_s{spp}_T{T}"], O.render_mt(rays, w, h, t, m, spp, T))
+    assert np.array_equal(ref_outputs[f"default_flat_{w}x{h}"], O.render_flat(rays, w, h, t, m))
+
+
+def test_synthetic_scenes_and_arbitrary_rays(O, ref_outputs):
+    for name, t, m, w, h, rays in synthetic_cases():
+        assert np.array_equal(ref_outputs[f"{name}_render_{w}x{h}_s2_T8_rays"], O.render_mt(rays, w, h, t, m, 2, 8))
+        assert np.array_equal(ref_outputs[f"{name}_flat_{w}x{h}_rays"], O.render_flat(rays, w, h, t, m))
+
+
+def test_degenerate_triangles(O, ref_outputs):
+    """Zero-area and duplicate triangles, NaN normal of a degenerate triangle never reached."""
+    t, m = degenerate_scene()
     w, h = 40, 30
-    rays = ref.viewport(w, h)
-    assert np.array_equal(ref.ref_run("render", w, h, 3, t, m, threads=8), ref.render_mt(rays, w, h, t, m, 3, 8))
-    assert np.array_equal(ref.ref_run("flat", w, h, 1, t, m), ref.render_flat(rays, w, h, t, m))
+    rays = O.viewport(w, h)
+    assert np.array_equal(ref_outputs[f"degenerate_render_{w}x{h}_s3_T8"], O.render_mt(rays, w, h, t, m, 3, 8))
+    assert np.array_equal(ref_outputs[f"degenerate_flat_{w}x{h}"], O.render_flat(rays, w, h, t, m))

@@ -8,7 +8,7 @@ TAG=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
 B="python3 bench.py"
-$B > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+$B --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 # (--no-worst-case: the large-triangle scene is the same kernel; its one short launch would sit in the kernel's average)
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt -o p --output-format csv -- $B --no-cpu-baseline --no-worst-case --no-valu-microbench > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_kt.err
 P="--steps 1 --warmup 0 --no-cpu-baseline --no-worst-case --no-valu-microbench"
