@@ -112,8 +112,8 @@ int  sphip_create(int device_id, sphip_t** out);
  *   device_ids == NULL: every visible device, or the comma-separated list in the environment variable SPATH_HIP_DEVICES.
  *   A device may be listed more than once (several shards on one GPU: how a one-GPU box exercises this path).
  *   SPATH_HIP_GATHER=rccl|peer overrides the choice of exchange.
- * The host-pointer entry points (sphip_set_scene, sphip_render, sphip_render_camera, sphip_get_stats, sphip_description,
- * sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
+ * The host-pointer entry points (sphip_set_scene, sphip_render, sphip_render_camera, sphip_accum_begin, sphip_accum_step,
+ * sphip_get_stats, sphip_description, sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
 int  sphip_create_multi(const int* device_ids, int n_devices, sphip_t** out);
 int  sphip_device_count(const sphip_t* ctx);        /* devices behind ctx (1 for sphip_create) */
 void sphip_destroy(sphip_t* ctx);
@@ -211,6 +211,33 @@ int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void
  *                      appears nowhere is in the "big" class: no filter, tested by every ray)
  * Blocking; host pointers; single-device contexts. */
 int sphip_selftest_stage1(sphip_t* ctx, const float* rays, size_t n_rays, uint32_t* out_words, uint32_t* out_tri, int32_t* out_order, uint32_t* tiles_out);
+
+/* ---- progressive rendering: accumulate samples across calls while the view stands still.
+ * The counter RNG is keyed by (seed, global pixel, sample index, depth), and samples are added to an f32 sum one at a time in
+ * sample order, so after steps of n_1, n_2, ... samples the image (and the mean) is bit-identical to one render of
+ * n_1 + n_2 + ... samples: the outputs of every step are what sphip_render returns for the total so far.
+ *
+ * sphip_render_device_accum: the stateless device-pointer form (single-device contexts; asynchronous like sphip_render_device;
+ * path tracing only).  Renders global samples [sample_base, sample_base + n_samples) of the shard's rays into the running sum
+ * d_sum (n_rays*3 f32, AoS: the raw sum, not the mean; in place).  sample_base == 0 ignores d_sum's contents (no clearing
+ * needed).  d_out_rgba / d_out_mean (may be NULL) receive the image and the mean of all sample_base + n_samples samples.
+ * sample_base + n_samples must stay below 2^31. */
+int sphip_render_device_accum(sphip_t* ctx, const void* d_rays /* n_rays*6 f32 */, size_t n_rays, const sphip_shard* shard /* NULL = whole */,
+                              size_t image_width, uint64_t sample_base, size_t n_samples, uint64_t seed, int flags,
+                              void* d_sum /* n_rays*3 f32, in/out */, void* d_out_rgba /* n_rays*4 u8 */, void* d_out_mean /* n_rays*3 f32 or NULL */,
+                              void* stream);
+/* sphip_accum_begin: starts an accumulation of the w*h viewport given by exactly one of `rays` (host array, w*h*6 f32, uploaded
+ * once) and `cam` (generated on the device; cam->res_x/res_y must equal w/h).  The rays and the running sum live in buffers of
+ * the accumulation: sphip_render / sphip_render_camera calls in between do not disturb it.  Needs a scene (SPHIP_E_STATE).
+ * Accepted by multi-device contexts: every device keeps the rays and the sum of its row tiles resident.
+ * sphip_accum_step: n_samples more samples; blocking, host outputs like sphip_render (out_mean may be NULL); *total_out (may be
+ * NULL) = samples accumulated so far.  sphip_get_stats then describes this step.  SPHIP_E_STATE when no accumulation was begun
+ * or a scene has been set since the begin; SPHIP_E_INVALID for n_samples == 0 or a total reaching 2^31.  A step that fails on
+ * the device ends the accumulation (begin again). */
+int sphip_accum_begin(sphip_t* ctx, const float* rays /* w*h*6 f32 or NULL */, const sphip_camera* cam /* or NULL */,
+                      size_t w, size_t h, uint64_t seed, int flags);
+int sphip_accum_step(sphip_t* ctx, size_t n_samples, uint8_t* out_rgba /* w*h*4 */, float* out_mean /* w*h*3 or NULL */,
+                     uint64_t* total_out /* or NULL */);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

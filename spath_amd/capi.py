@@ -31,6 +31,7 @@ SYMBOLS = (
     "sphip_render_device", "sphip_closest_hit_device", "sphip_get_stats", "sphip_viewport_device", "sphip_render_camera",
     "sphip_create_multi", "sphip_device_count", "sphip_plan_tile_rows", "sphip_plan_shard", "sphip_selftest_device",
     "sphip_kernel_available", "sphip_selftest_stage1", "sphip_build_info",
+    "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -117,6 +118,12 @@ def load():
     if hasattr(L, "sphip_selftest_stage1"):
         L.sphip_selftest_stage1.restype = C.c_int
         L.sphip_selftest_stage1.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(C.c_uint32)]
+    L.sphip_render_device_accum.restype = C.c_int
+    L.sphip_render_device_accum.argtypes = [vp, vp, sz, C.POINTER(Shard), sz, C.c_uint64, sz, C.c_uint64, C.c_int, vp, vp, vp, vp]
+    L.sphip_accum_begin.restype = C.c_int
+    L.sphip_accum_begin.argtypes = [vp, vp, C.POINTER(CameraArgs), sz, sz, C.c_uint64, C.c_int]
+    L.sphip_accum_step.restype = C.c_int
+    L.sphip_accum_step.argtypes = [vp, sz, vp, vp, C.POINTER(C.c_uint64)]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -259,6 +266,17 @@ class Context:
         self._check(self._L.sphip_render_device(self._h, d_rays, n_rays, sh, image_width, n_samples, seed, mode, flags,
                                                 d_out_rgba, d_out_accum or None, stream or None), "sphip_render_device")
 
+    def render_device_accum(self, d_rays: int, n_rays: int, sample_base: int, n_samples: int, d_sum: int, d_out_rgba: int, *,
+                            seed=1, flags=0, shard=None, image_width=0, d_out_mean: int = 0, stream: int = 0):
+        """Progressive step on device pointers: global samples [sample_base, sample_base + n_samples) added to the running sum
+        d_sum (n_rays*3 f32, in place; not read when sample_base == 0); the outputs are those of a render of all of them."""
+        sh = None
+        if shard is not None:
+            sh = C.byref(Shard(*[int(v) for v in shard]))
+        self._check(self._L.sphip_render_device_accum(self._h, d_rays, n_rays, sh, image_width, sample_base, n_samples, seed, flags,
+                                                      d_sum or None, d_out_rgba, d_out_mean or None, stream or None),
+                    "sphip_render_device_accum")
+
     def closest_hit_device(self, d_rays: int, n_rays: int, d_out_idx: int, d_out_dist: int, *, d_src_idx: int = 0,
                            flags=0, stream: int = 0):
         self._check(self._L.sphip_closest_hit_device(self._h, d_rays, n_rays, d_src_idx or None, flags,
@@ -279,6 +297,38 @@ class Context:
         self._check(self._L.sphip_render_camera(self._h, C.byref(ca), n_samples, seed, mode, flags, out.ctypes.data,
                                                 acc.ctypes.data if want_accum else None), "sphip_render_camera")
         return (out, acc) if want_accum else out
+
+    # progressive rendering -------------------------------------------------------------------
+    def accum_begin(self, rays=None, cam=None, w=None, h=None, seed=1, flags=0):
+        """Start accumulating the viewport given by exactly one of `rays` (w*h rays, uploaded once) and `cam`
+        (spath_amd.view.Camera, generated on the device; w and h default to its resolution)."""
+        import numpy as np
+        ca = None
+        if cam is not None:
+            ca = CameraArgs.from_camera(cam)
+            w = cam.res_x if w is None else w
+            h = cam.res_y if h is None else h
+        ptr = None
+        if rays is not None:
+            rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+            if w is None or h is None or rays.shape[0] != w * h:
+                raise ValueError("rays must hold w*h entries")
+            ptr = rays.ctypes.data
+        self._accum_shape = (int(w or 0), int(h or 0))
+        self._check(self._L.sphip_accum_begin(self._h, ptr, C.byref(ca) if ca is not None else None, int(w or 0), int(h or 0), seed, flags),
+                    "sphip_accum_begin")
+
+    def accum_step(self, n, want_mean=False):
+        """n more samples of the current accumulation -> (img, total) or (img, mean, total): the image (and mean) of all
+        `total` samples so far, bit-identical to render(..., total, ...)."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        out = np.zeros((w * h, 4), dtype=np.uint8)
+        mean = np.zeros((w * h, 3), dtype=np.float32) if want_mean else None
+        total = C.c_uint64(0)
+        self._check(self._L.sphip_accum_step(self._h, n, out.ctypes.data if w * h else None, mean.ctypes.data if want_mean and w * h else None,
+                                             C.byref(total)), "sphip_accum_step")
+        return (out, mean, total.value) if want_mean else (out, total.value)
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2)}
 

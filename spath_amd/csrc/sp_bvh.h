@@ -113,9 +113,10 @@ SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int
 }
 
 // kernels: the same integrator / flat / hit bodies as the exact scans (sp_kernels.h), with the BVH as the scan
-template <int MODE /* 0 flat, 1 pt, 2 hits */>
+// (a trailing AccumArgs: progressive accumulation in path-tracing mode, sp_kernels.h)
+template <int MODE /* 0 flat, 1 pt, 2 hits */, typename... Acc>
 __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, const int* __restrict__ src_idx,
-                                               int* __restrict__ out_idx, float* __restrict__ out_d) {
+                                               int* __restrict__ out_idx, float* __restrict__ out_d, const Acc... acc_args) {
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = k < a.n_rays;
 	const uint32_t kk = valid ? k : a.n_rays - 1;
@@ -146,6 +147,12 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	const uint32_t pixel = (uint32_t)shard_pixel(a, kk);
 	uint32_t my_scans = 0;
 	f3 accum = mk3(0.0f, 0.0f, 0.0f);
+	uint32_t s0 = 0;                                  // global index of the launch's first sample
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		s0 = q.sample_base;
+		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
+	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		f3 o = po, dir = pdir;
 		int src = -1, hidx[5];
@@ -163,7 +170,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);
 					double r1, r2;
-					philox_uniforms(a.seed, pixel, s, (uint32_t)depth, &r1, &r2);
+					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
 					const f3 nd = rand_unit_vec(n, r1, r2);
 					hcos[depth] = dot3(nd, n);
 					hidx[depth] = bi;
@@ -186,6 +193,10 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 			}
 		}
 		accum = add3(accum, rec);
+	}
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		if (valid) { q.sum[(size_t)k * 3 + 0] = accum.x; q.sum[(size_t)k * 3 + 1] = accum.y; q.sum[(size_t)k * 3 + 2] = accum.z; }
 	}
 	accum = scale3(accum, a.inv_n);
 	if (valid) {

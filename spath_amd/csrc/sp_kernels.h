@@ -35,17 +35,39 @@ struct KArgs {
 	const float* prim_d;       // n_rays
 };
 
+// progressive accumulation (sphip_render_device_accum, sphip_accum_step): sample j of a launch is global sample
+// sample_base + j (what keys the counter RNG), and the per-pixel f32 sum starts from sum[3k..3k+2] and is written back there
+// raw, in place.  sample_base == 0: sum is not read (a fresh accumulation needs no cleared buffer).  inv_n is then
+// float(1.0/(sample_base + n_samples)), so a run of steps ends in the image of one render of all their samples, bit for bit:
+// the samples are added to the same f32 sum one at a time, in the same order.
+// The path-tracing kernels take it as an optional trailing argument (a parameter pack of zero or one AccumArgs): without it a
+// kernel is the same code as before the switch existed, which is what sphip_render launches.
+struct AccumArgs {
+	float* sum;                // n_rays * 3, AoS like out_accum
+	uint32_t sample_base;
+};
+SP_DEV const AccumArgs& accum_args(const AccumArgs& p) { return p; }
+
 // second pass of a sample-chunked launch: cpu_renderer.cpp:72-78 for one pixel -- zero, += sample in sample order,
 // * float(1.0/n_samples), clamp, quantise
-__global__ void __launch_bounds__(256) k_resolve(const KArgs a) {
+template <typename... Acc>
+__global__ void __launch_bounds__(256) k_resolve(const KArgs a, const Acc... acc_args) {
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	if (k >= a.n_rays) return;
 	float ax = 0.0f, ay = 0.0f, az = 0.0f;
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		if (q.sample_base) { ax = q.sum[(size_t)k * 3 + 0]; ay = q.sum[(size_t)k * 3 + 1]; az = q.sum[(size_t)k * 3 + 2]; }
+	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		const float* p = a.samp + (size_t)s * 3 * a.samp_stride + k;
 		ax = ax + p[0];
 		ay = ay + p[a.samp_stride];
 		az = az + p[(size_t)2 * a.samp_stride];
+	}
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		q.sum[(size_t)k * 3 + 0] = ax; q.sum[(size_t)k * 3 + 1] = ay; q.sum[(size_t)k * 3 + 2] = az;
 	}
 	const f3 av = scale3(mk3(ax, ay, az), a.inv_n);
 	a.out_rgba[k] = vec3_rgba(mk3(clamp01(av.x), clamp01(av.y), clamp01(av.z)));
@@ -283,8 +305,8 @@ __global__ void __launch_bounds__(256) k_hit(const KArgs a, const int* __restric
 // The recursion of render_step is run forward (store idx and cos(theta) per depth) and unwound
 // backward in the reference's own evaluation order  E + (((BRDF*rec)*cos)*(1/p))  (:67) -- the
 // shape the reference itself uses in its GLSL backend (render.comp:160-215).
-template <int VARIANT>
-__global__ void __launch_bounds__(256) k_pt(const KArgs a) {
+template <int VARIANT, typename... Acc>
+__global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args) {
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = k < a.n_rays;
 	const uint32_t kk = valid ? k : a.n_rays - 1;
@@ -299,6 +321,12 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a) {
 	if (reuse) { closest_hit<VARIANT>(a, po, pdir, -1, pd, pi); my_scans += valid ? 1u : 0u; }
 
 	f3 accum = mk3(0.0f, 0.0f, 0.0f);
+	uint32_t s0 = 0;                                             // global index of the launch's first sample
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		s0 = q.sample_base;
+		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
+	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		f3 o = po, dir = pdir;
 		int src = -1;
@@ -317,7 +345,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a) {
 				f3 n = mk3(tn[0], tn[1], tn[2]);                  // :55
 				if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);    // :56-57
 				double r1, r2;
-				philox_uniforms(a.seed, pixel, s, (uint32_t)depth, &r1, &r2);
+				philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
 				const f3 nd = rand_unit_vec(n, r1, r2);           // :58
 				const float ct = dot3(nd, n);                     // :62
 				o = add3(o, scale3(dir, bd));                     // geom.h:218 point = pos + dir*d
@@ -345,6 +373,10 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a) {
 			}
 		}
 		accum = add3(accum, rec);                                // :75
+	}
+	if constexpr (sizeof...(Acc) > 0) {
+		const AccumArgs& q = accum_args(acc_args...);
+		if (valid) { q.sum[(size_t)k * 3 + 0] = accum.x; q.sum[(size_t)k * 3 + 1] = accum.y; q.sum[(size_t)k * 3 + 2] = accum.z; }
 	}
 	accum = scale3(accum, a.inv_n);                              // :77
 	if (valid) {

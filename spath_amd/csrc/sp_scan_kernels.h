@@ -94,9 +94,11 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 // global work buffer between scans instead of being held in VGPRs through the scan loop: 52 B per slot,
 // touched once per bounce, against ~10^5 VALU instructions per bounce.
 //   work layout: hist[depth][k] = {idx, cos bits} (8 B), then acc[c][k] (3 floats), k < n_work
-template <int R, bool SPLIT, int SCAN>
+// With a trailing AccumArgs (progressive accumulation, sp_kernels.h) the running sum enters the slot's accumulator at the start
+// and leaves it at the end -- with SPLIT only slot 0 carries it; a sample-chunked launch leaves both to k_resolve.
+template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
-                                                   int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work) {
+                                                   int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work, const Acc... acc_args) {
 	const float rv = __uint_as_float(bounds[0]);
 	const uint32_t tid = threadIdx.x;
 	constexpr uint32_t B = scan_block<SCAN>();                // threads per workgroup
@@ -114,6 +116,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		pixel[r] = (uint32_t)shard_pixel(a, kk);
 #pragma unroll
 		for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = 0.0f;
+		if constexpr (sizeof...(Acc) > 0) {
+			const AccumArgs& q = accum_args(acc_args...);
+			if (q.sample_base && !chunked && (!SPLIT || r == 0) && k < a.n_rays) {
+#pragma unroll
+				for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = q.sum[(size_t)k * 3 + c];
+			}
+		}
 	}
 	// primary-hit reuse: cpu_renderer.cpp:74-76 starts every sample from the same vp.rays[idx], so the first
 	// scan of all samples of a pixel has one result; the host ran it once per pixel (k_hit_filter) before this launch
@@ -128,6 +137,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		pi[r] = reuse ? a.prim_idx[kk] : -1;
 	}
 
+	uint32_t s0 = 0;                                         // global index of the launch's first sample
+	if constexpr (sizeof...(Acc) > 0) s0 = accum_args(acc_args...).sample_base;
 	const uint32_t n_iter = SPLIT ? (a.n_samples + R - 1) / R : a.n_samples;
 	uint32_t it0 = 0, it1 = n_iter;
 	if (chunked) {
@@ -173,7 +184,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
 					double r1, r2;
-					philox_uniforms(a.seed, pixel[r], smp[r], (uint32_t)depth, &r1, &r2);
+					philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
 					const f3 nd = rand_unit_vec(n, r1, r2);
 					const float ct = dot3(nd, n);
 					s.o[r] = add3(s.o[r], scale3(s.dir[r], bd[r]));
@@ -216,6 +227,11 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		const uint32_t k = kr0 + r * kstep;
 		const uint32_t kw = k0 + r * B;
 		if (k < a.n_rays && !chunked) {
+			if constexpr (sizeof...(Acc) > 0) {
+				const AccumArgs& q = accum_args(acc_args...);
+#pragma unroll
+				for (int c = 0; c < 3; ++c) q.sum[(size_t)k * 3 + c] = acc[(size_t)c * n_work + kw];
+			}
 			const f3 av = scale3(mk3(acc[kw], acc[(size_t)n_work + kw], acc[(size_t)2 * n_work + kw]), a.inv_n);
 			a.out_rgba[k] = vec3_rgba(mk3(clamp01(av.x), clamp01(av.y), clamp01(av.z)));
 			if (a.out_accum) {

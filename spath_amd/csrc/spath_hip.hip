@@ -62,6 +62,15 @@ struct sphip_ctx {
 	DevBuf gath, gath_acc, img, img_acc;           // [n_dev][pad] tiles as gathered, and the image in pixel order
 	std::vector<hipEvent_t> ev_tile;               // child r's tiles have arrived on the first device
 	hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;
+	// ---- progressive accumulation (sphip_accum_begin / sphip_accum_step).  The rays and the running sum of the frame (of this
+	// device's shard, on a child of a multi-device context) live in buffers of their own, so that renders issued between two
+	// steps do not disturb them; the parameters are the parent's.
+	DevBuf acc_rays, acc_sum;
+	bool acc_on = false;                          // an accumulation has been begun
+	bool acc_stale = false;                       // ... and a scene has been set since
+	size_t acc_w = 0, acc_h = 0;
+	uint64_t acc_seed = 0, acc_total = 0;         // acc_total: samples accumulated so far
+	int acc_flags = 0;
 };
 
 namespace {
@@ -284,9 +293,11 @@ int ensure_bvh(sphip_ctx* c, hipStream_t st) {
 
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
+// prog != nullptr: progressive accumulation (path tracing only): the launch renders global samples
+// [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
 int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
                   size_t n_samples, uint64_t seed, int mode, int flags, void* d_rgba, void* d_accum, hipStream_t st,
-                  const int* d_src = nullptr) {
+                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr) {
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
 	if (!d_rays || !d_rgba) return fail(c, SPHIP_E_INVALID, "null ray or output pointer");
 	if (n_rays == 0 || n_rays > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n_rays);
@@ -294,6 +305,10 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (mode == kModeHits && !d_accum) return fail(c, SPHIP_E_INVALID, "null distance output");
 	if (mode == SPHIP_MODE_PT && (n_samples == 0 || n_samples > 0x7fffffffull))
 		return fail(c, SPHIP_E_INVALID, "n_samples must be in [1, 2^31) (the reference divides by it, cpu_renderer.cpp:77)");
+	if (prog && (mode != SPHIP_MODE_PT || !prog->sum)) return fail(c, SPHIP_E_INVALID, "progressive accumulation needs path tracing and a sum buffer");
+	if (prog && (uint64_t)prog->sample_base + n_samples > 0x7fffffffull)
+		return fail(c, SPHIP_E_INVALID, "sample_base + n_samples = %llu: the total must stay below 2^31", (unsigned long long)prog->sample_base + n_samples);
+	const uint64_t n_total = (prog ? (uint64_t)prog->sample_base : 0) + n_samples;
 	int rc = ensure(c, c->counter, 16 * sizeof(unsigned long long));
 	if (rc) return rc;
 
@@ -316,7 +331,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	} else {
 		a.pixel_base = 0; a.tile_px = n_rays; a.tile_stride_px = 0;
 	}
-	a.inv_n = (float)(1.0 / (double)(n_samples ? n_samples : 1));      // cpu_renderer.cpp:77
+	a.inv_n = (float)(1.0 / (double)(n_total ? n_total : 1));          // cpu_renderer.cpp:77 (all samples so far when accumulating)
 
 	const int variant = pick_variant(flags, c->n_tris);
 	if (variant == 16 && c->n_tris >= (1ull << sp::kMIdxBits))
@@ -428,6 +443,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (variant == kVariantAccel) {
 		if (mode == kModeHits)           hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
 		else if (mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
+		else if (prog)                    hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog);
 		else                              hipLaunchKernelGGL(sp::k_accel<1>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
 	} else if (mode == kModeHits) {
 		int* oi = (int*)d_rgba; float* od = (float*)d_accum;
@@ -460,7 +476,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		else                   hipLaunchKernelGGL(sp::k_flat<1>, grid, block, 0, st, a);
 	} else {
 		if (is_ts) {
-#define SP_PT(R_, SPLIT_, S_) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work)
+#define SP_PT(R_, SPLIT_, S_) do { if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
+                                   else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work); } while (0)
 			if (ts.scan == 3) SP_PT(1, false, 3);
 			else if (ts.scan == 4) SP_PT(1, false, 4);
 			else if (ts.scan == 2 && ts.split) SP_PT(4, true, 2);
@@ -476,10 +493,13 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #endif
 #undef SP_PT
 		}
+		else if (prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs>), grid, block, 0, st, a, *prog);
+		else if (prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs>), grid, block, 0, st, a, *prog);
 		else if (variant == 2) hipLaunchKernelGGL(sp::k_pt<2>, grid, block, 0, st, a);
 		else                   hipLaunchKernelGGL(sp::k_pt<1>, grid, block, 0, st, a);
 	}
-	if (chunks > 1) hipLaunchKernelGGL(sp::k_resolve, dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a);
+	if (chunks > 1 && prog) hipLaunchKernelGGL((sp::k_resolve<sp::AccumArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, *prog);
+	else if (chunks > 1) hipLaunchKernelGGL(sp::k_resolve<>, dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
 	c->have_render = true;
@@ -598,29 +618,27 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	return SPHIP_OK;
 }
 
-int multi_render_impl(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, size_t n_samples, uint64_t seed, int mode, int flags,
-                      uint8_t* out_rgba, float* out_accum);
-
-// rays != nullptr: the caller's viewport (host array, w*h rays); else cam: every device generates the rays of its own tiles.
-// Whatever goes wrong on one device, no device is left with work in flight when the call returns: the next call may free or
-// regrow the buffers that work reads and writes.
-int multi_render(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, size_t n_samples, uint64_t seed, int mode, int flags,
-                 uint8_t* out_rgba, float* out_accum) {
-	const int rc = multi_render_impl(c, rays, cam, w, h, n_samples, seed, mode, flags, out_rgba, out_accum);
-	if (rc != SPHIP_OK) {
-		for (sphip_ctx* k : c->kids)
-			if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
-		(void)hipGetLastError();
+// device r's rays of a frame, in its shard's order: its tiles of the caller's viewport (host array, one copy per tile), or,
+// with rays == nullptr, generated on the device from cam
+int deal_rays(sphip_ctx* k, const RowPlan& plan, int r, const float* rays, const sphip_camera* cam, void* d_rays, hipStream_t st) {
+	if (rays) {
+		size_t k0 = 0;
+		for (size_t t = (size_t)r; t < plan.n_tiles; t += (size_t)plan.g) {
+			const size_t cnt = std::min(plan.tile_px, plan.npix - t * plan.tile_px);
+			HIP_TRY(k, hipMemcpyAsync((char*)d_rays + k0 * 24, rays + t * plan.tile_px * 6, cnt * 24, hipMemcpyHostToDevice, st));
+			k0 += cnt;
+		}
+		return SPHIP_OK;
 	}
-	return rc;
+	const sphip_shard sh = plan.shard(r);
+	return launch_viewport(k, cam, d_rays, st, &sh, plan.n_rays(r));
 }
 
-int multi_render_impl(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, size_t n_samples, uint64_t seed, int mode, int flags,
-                      uint8_t* out_rgba, float* out_accum) {
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
-	if (!out_rgba || w == 0 || h == 0 || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad render arguments (w=%zu h=%zu)", w, h);
-	if (mode == SPHIP_MODE_PT && (n_samples == 0 || n_samples > 0x7fffffffull))
-		return fail(c, SPHIP_E_INVALID, "n_samples must be in [1, 2^31) (the reference divides by it, cpu_renderer.cpp:77)");
+// One frame on every device of a multi-device context.  render_shard(k, r, n, shard) enqueues device r's part on k->own_stream
+// (n > 0 rays), leaving the RGBA8 pixels in k->rgba and, when out_accum is wanted, the float triples in k->accum; the tiles are
+// then gathered to the first device, un-permuted there (k_assemble) and read back.
+template <class RenderShard>
+int multi_frame_impl(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float* out_accum, const RenderShard& render_shard) {
 	const int g = (int)c->kids.size();
 	const RowPlan plan(w, h, g, (size_t)plan_tile_rows(h, g));
 	const size_t pad = plan.max_rays(), npix = plan.npix;
@@ -642,18 +660,9 @@ int multi_render_impl(sphip_ctx* c, const float* rays, const sphip_camera* cam, 
 			HIP_TRY(k, hipSetDevice(k->device));
 			hipStream_t st = k->own_stream;
 			int rc2;
-			if ((rc2 = ensure(k, k->rays, n * 24)) || (rc2 = ensure(k, k->rgba, pad * 4))) return rc2;
+			if ((rc2 = ensure(k, k->rgba, pad * 4))) return rc2;
 			if (out_accum && (rc2 = ensure(k, k->accum, pad * 12))) return rc2;
-			const sphip_shard sh = plan.shard(r);
-			if (rays) {           // this device's tiles of the caller's viewport, one copy per tile
-				size_t k0 = 0;
-				for (size_t t = (size_t)r; t < plan.n_tiles; t += (size_t)g) {
-					const size_t cnt = std::min(plan.tile_px, npix - t * plan.tile_px);
-					HIP_TRY(k, hipMemcpyAsync((char*)k->rays.p + k0 * 24, rays + t * plan.tile_px * 6, cnt * 24, hipMemcpyHostToDevice, st));
-					k0 += cnt;
-				}
-			} else if ((rc2 = launch_viewport(k, cam, k->rays.p, st, &sh, n))) return rc2;
-			if ((rc2 = launch_render(k, k->rays.p, n, &sh, w, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, st))) return rc2;
+			if ((rc2 = render_shard(k, r, n, plan.shard(r)))) return rc2;
 			k->timed_upload = k->timed_download = false;
 			if (peer) {           // tiles -> slot r of the first device's gather buffer, in stream order behind the kernels
 				const bool same = k->device == root->device;      // a device listed twice, or the first device itself: a local copy
@@ -737,6 +746,69 @@ int multi_render_impl(sphip_ctx* c, const float* rays, const sphip_camera* cam, 
 	c->stats.n_pixels = npix;
 	c->stats.n_tris = c->n_tris;
 	return SPHIP_OK;
+}
+
+// Whatever goes wrong on one device, no device is left with work in flight when the call returns: the next call may free or
+// regrow the buffers that work reads and writes.
+template <class RenderShard>
+int multi_frame(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float* out_accum, const RenderShard& render_shard) {
+	const int rc = multi_frame_impl(c, w, h, out_rgba, out_accum, render_shard);
+	if (rc != SPHIP_OK) {
+		for (sphip_ctx* k : c->kids)
+			if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
+		(void)hipGetLastError();
+	}
+	return rc;
+}
+
+// rays != nullptr: the caller's viewport (host array, w*h rays); else cam: every device generates the rays of its own tiles.
+int multi_render(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, size_t n_samples, uint64_t seed, int mode, int flags,
+                 uint8_t* out_rgba, float* out_accum) {
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
+	if (!out_rgba || w == 0 || h == 0 || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad render arguments (w=%zu h=%zu)", w, h);
+	if (mode == SPHIP_MODE_PT && (n_samples == 0 || n_samples > 0x7fffffffull))
+		return fail(c, SPHIP_E_INVALID, "n_samples must be in [1, 2^31) (the reference divides by it, cpu_renderer.cpp:77)");
+	const RowPlan plan(w, h, (int)c->kids.size(), (size_t)plan_tile_rows(h, (int)c->kids.size()));
+	return multi_frame(c, w, h, out_rgba, out_accum, [&](sphip_ctx* k, int r, size_t n, const sphip_shard& sh) -> int {
+		int rc2;
+		if ((rc2 = ensure(k, k->rays, n * 24)) || (rc2 = deal_rays(k, plan, r, rays, cam, k->rays.p, k->own_stream))) return rc2;
+		return launch_render(k, k->rays.p, n, &sh, w, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, k->own_stream);
+	});
+}
+
+// sphip_accum_begin on a multi-device context: device r keeps the rays of its shard (the row-tile plan of the frame) and its
+// shard's running sum resident
+int multi_accum_begin(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h) {
+	const int g = (int)c->kids.size();
+	const RowPlan plan(w, h, g, (size_t)plan_tile_rows(h, g));
+	for (int r = 0; r < g; ++r) {
+		sphip_ctx* k = c->kids[(size_t)r];
+		const size_t n = plan.n_rays(r);
+		if (n == 0) continue;
+		auto body = [&]() -> int {
+			HIP_TRY(k, hipSetDevice(k->device));
+			int rc;
+			if ((rc = ensure(k, k->acc_rays, n * 24)) || (rc = ensure(k, k->acc_sum, n * 12)) ||
+			    (rc = deal_rays(k, plan, r, rays, cam, k->acc_rays.p, k->own_stream))) return rc;
+			HIP_TRY(k, hipStreamSynchronize(k->own_stream));       // the rays are borrowed
+			return SPHIP_OK;
+		};
+		if (const int rc = body()) {
+			for (sphip_ctx* q : c->kids)
+				if (hipSetDevice(q->device) == hipSuccess && q->own_stream) (void)hipStreamSynchronize(q->own_stream);
+			(void)hipGetLastError();
+			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+		}
+	}
+	return SPHIP_OK;
+}
+
+int multi_accum_step(sphip_ctx* c, size_t n_samples, uint8_t* out_rgba, float* out_mean) {
+	return multi_frame(c, c->acc_w, c->acc_h, out_rgba, out_mean, [&](sphip_ctx* k, int, size_t n, const sphip_shard& sh) -> int {
+		const sp::AccumArgs p{ (float*)k->acc_sum.p, (uint32_t)c->acc_total };
+		return launch_render(k, k->acc_rays.p, n, &sh, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, k->rgba.p,
+		                     out_mean ? k->accum.p : nullptr, k->own_stream, nullptr, &p);
+	});
 }
 
 int multi_get_stats(sphip_ctx* c, sphip_stats* out) {
@@ -921,7 +993,8 @@ void sphip_destroy(sphip_t* c) {
 	(void)hipSetDevice(c->device);
 	if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
-	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big };
+	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
+	                   &c->acc_rays, &c->acc_sum };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
@@ -936,6 +1009,7 @@ const char* sphip_description(const sphip_t* c) { return c ? c->desc.c_str() : "
 int sphip_set_scene(sphip_t* c, const float* tris, const float* mats, size_t n_tris) {
 	if (!c) return SPHIP_E_INVALID;
 	if (!tris || !mats || n_tris == 0 || n_tris > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad scene arguments (n_tris=%zu)", n_tris);
+	c->acc_stale = c->acc_on;                      // the running sum belongs to the old scene
 	if (!c->kids.empty()) return multi_set_scene(c, tris, mats, n_tris);
 	HIP_TRY(c, hipSetDevice(c->device));
 	int rc;
@@ -952,6 +1026,7 @@ int sphip_set_scene_device(sphip_t* c, const void* d_tris, const void* d_mats, s
 	if (!c) return SPHIP_E_INVALID;
 	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
 	if (!d_tris || !d_mats || n_tris == 0 || n_tris > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad scene arguments (n_tris=%zu)", n_tris);
+	c->acc_stale = c->acc_on;
 	HIP_TRY(c, hipSetDevice(c->device));
 	hipStream_t st = (hipStream_t)stream;
 	int rc;
@@ -969,6 +1044,92 @@ int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sph
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
 	return launch_render(c, d_rays, n_rays, shard, image_width, n_samples, seed, mode, flags, d_out_rgba, d_out_accum, (hipStream_t)stream);
+}
+
+int sphip_render_device_accum(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
+                              uint64_t sample_base, size_t n_samples, uint64_t seed, int flags, void* d_sum,
+                              void* d_out_rgba, void* d_out_mean, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (!d_sum) return fail(c, SPHIP_E_INVALID, "null sum pointer");
+	if (sample_base > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "sample_base %llu: the total must stay below 2^31", (unsigned long long)sample_base);
+	HIP_TRY(c, hipSetDevice(c->device));
+	c->timed_upload = c->timed_download = false;
+	const sp::AccumArgs p{ (float*)d_sum, (uint32_t)sample_base };
+	return launch_render(c, d_rays, n_rays, shard, image_width, n_samples, seed, SPHIP_MODE_PT, flags, d_out_rgba, d_out_mean, (hipStream_t)stream,
+	                     nullptr, &p);
+}
+
+int sphip_accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, uint64_t seed, int flags) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_accum_begin called before a scene was set");
+	if ((rays == nullptr) == (cam == nullptr)) return fail(c, SPHIP_E_INVALID, "sphip_accum_begin takes exactly one of rays and cam");
+	if (w == 0 || h == 0 || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad viewport size (w=%zu h=%zu)", w, h);
+	if (cam && (cam->res_x != w || cam->res_y != h))
+		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the camera's %ux%u", w, h, cam->res_x, cam->res_y);
+	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
+	if (!c->kids.empty()) {
+		const int rc = multi_accum_begin(c, rays, cam, w, h);
+		if (rc) return rc;
+	} else {
+		HIP_TRY(c, hipSetDevice(c->device));
+		const size_t n = w * h;
+		hipStream_t st = c->own_stream;
+		int rc;
+		if ((rc = ensure(c, c->acc_rays, n * 24)) || (rc = ensure(c, c->acc_sum, n * 12))) return rc;
+		if (rays) HIP_TRY(c, hipMemcpyAsync(c->acc_rays.p, rays, n * 24, hipMemcpyHostToDevice, st));      // once per accumulation
+		else if ((rc = launch_viewport(c, cam, c->acc_rays.p, st))) return rc;
+		HIP_TRY(c, hipStreamSynchronize(st));        // rays are borrowed
+	}
+	c->acc_on = true;
+	c->acc_stale = false;
+	c->acc_w = w; c->acc_h = h;
+	c->acc_seed = seed; c->acc_flags = flags;
+	c->acc_total = 0;                              // the first step's sample_base: the sum buffer's contents are not read
+	return SPHIP_OK;
+}
+
+int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out_mean, uint64_t* total_out) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->acc_on) return fail(c, SPHIP_E_STATE, "sphip_accum_step called with no accumulation begun (sphip_accum_begin)");
+	if (c->acc_stale) return fail(c, SPHIP_E_STATE, "the scene changed since sphip_accum_begin: begin a new accumulation");
+	if (!out_rgba) return fail(c, SPHIP_E_INVALID, "null output pointer");
+	if (n_samples == 0 || c->acc_total + n_samples > 0x7fffffffull)
+		return fail(c, SPHIP_E_INVALID, "n_samples = %zu after %llu: each step renders at least one sample, and the total must stay below 2^31",
+		            n_samples, (unsigned long long)c->acc_total);
+	int rc;
+	if (!c->kids.empty()) {
+		rc = multi_accum_step(c, n_samples, out_rgba, out_mean);
+	} else {
+		auto body = [&]() -> int {
+			HIP_TRY(c, hipSetDevice(c->device));
+			const size_t n = c->acc_w * c->acc_h;
+			hipStream_t st = c->own_stream;
+			int rc2;
+			if ((rc2 = ensure(c, c->rgba, n * 4))) return rc2;
+			if (out_mean && (rc2 = ensure(c, c->accum, n * 12))) return rc2;
+			const sp::AccumArgs p{ (float*)c->acc_sum.p, (uint32_t)c->acc_total };
+			if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
+			                         out_mean ? c->accum.p : nullptr, st, nullptr, &p))) return rc2;
+			HIP_TRY(c, hipEventRecord(c->ev_d0, st));
+			HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
+			if (out_mean) HIP_TRY(c, hipMemcpyAsync(out_mean, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
+			HIP_TRY(c, hipEventRecord(c->ev_d1, st));
+			HIP_TRY(c, hipStreamSynchronize(st));
+			c->timed_upload = false;
+			c->timed_download = true;
+			return SPHIP_OK;
+		};
+		rc = body();
+		if (rc) { (void)hipStreamSynchronize(c->own_stream); (void)hipGetLastError(); }
+	}
+	if (rc) {                                      // the sums may hold part of this step: nothing can continue from them
+		c->acc_on = false;
+		return rc;
+	}
+	c->acc_total += n_samples;
+	if (total_out) *total_out = c->acc_total;
+	return SPHIP_OK;
 }
 
 int sphip_viewport_device(sphip_t* c, const sphip_camera* cam, void* d_rays_out, void* stream) {

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace {
 
@@ -31,10 +32,22 @@ struct hip_r : public basic_renderer {
 	size_t scene_n;
 	sphip_stats stats;
 	bool have_stats;
+	// progressive mode (set_progressive): render() continues the accumulation while the viewport rays (or, for
+	// render_own_viewport, the camera), the scene, the seed and the flags are those it was begun with; otherwise it begins anew
+	bool progressive;
+	bool acc_live, acc_cam;
+	std::vector<geom::ray> acc_rays;
+	sphip_camera acc_camera;
+	size_t acc_w, acc_h, acc_scene_n;
+	unsigned long long acc_scene_hash, acc_seed;
+	int acc_flags;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
-	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false) {
+	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
+	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
+	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0) {
+		std::memset(&acc_camera, 0, sizeof acc_camera);
 		if (sphip_create_multi(ids, n_ids, &ctx) != SPHIP_OK)
 			throw std::runtime_error(std::string("hip_renderer: ") + sphip_last_error(0));
 		desc = sphip_description(ctx);
@@ -76,6 +89,18 @@ struct hip_r : public basic_renderer {
 		return c;
 	}
 
+	bool same_accumulation(size_t w, size_t h) const {
+		return acc_live && acc_w == w && acc_h == h && acc_scene_hash == scene_hash && acc_scene_n == scene_n && acc_seed == seed && acc_flags == flags;
+	}
+
+	// one progressive step of n_samples (the accumulation begun or continued by the caller) into out
+	void accum_step(const size_t n_samples, scene::bitmap& out) {
+		acc_live = false;                  // a failed step ends the accumulation on the library's side too
+		check(sphip_accum_step(ctx, n_samples, (uint8_t*)out.values.data(), 0, 0), "accum_step");
+		acc_live = true;
+		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
+	}
+
 	void frame_own_viewport(const geom::triangle* tris, const scene::material* mats, const size_t n_tris, const size_t n_samples,
 	                        scene::bitmap& out, const int mode) {
 		upload_scene(tris, mats, n_tris);
@@ -83,6 +108,17 @@ struct hip_r : public basic_renderer {
 		out.res_y = vc.res_y;
 		out.values.resize(out.res_x * out.res_y);
 		const sphip_camera c = camera_args();
+		if (progressive && mode == SPHIP_MODE_PT) {
+			if (!(same_accumulation(c.res_x, c.res_y) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0)) {
+				acc_live = false;
+				check(sphip_accum_begin(ctx, 0, &c, c.res_x, c.res_y, seed, flags), "accum_begin");
+				begun(c.res_x, c.res_y, true);
+				acc_camera = c;
+				acc_rays.clear();
+			}
+			accum_step(n_samples, out);
+			return;
+		}
 		check(sphip_render_camera(ctx, &c, n_samples, seed, mode, flags, (uint8_t*)out.values.data(), 0), "render_camera");
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
 	}
@@ -95,9 +131,28 @@ struct hip_r : public basic_renderer {
 		out.res_y = vp.res_y;
 		out.values.resize(out.res_x * out.res_y);
 		if (vp.rays.size() != out.values.size()) throw std::runtime_error("hip_renderer: viewport size and ray count disagree");
+		if (progressive && mode == SPHIP_MODE_PT) {
+			// the rays are compared bit for bit with those the accumulation was begun with
+			if (!(same_accumulation(vp.res_x, vp.res_y) && !acc_cam && acc_rays.size() == vp.rays.size() &&
+			      std::memcmp(acc_rays.data(), vp.rays.data(), vp.rays.size() * sizeof(geom::ray)) == 0)) {
+				acc_live = false;
+				check(sphip_accum_begin(ctx, (const float*)vp.rays.data(), 0, vp.res_x, vp.res_y, seed, flags), "accum_begin");
+				begun(vp.res_x, vp.res_y, false);
+				acc_rays.assign(vp.rays.begin(), vp.rays.end());
+			}
+			accum_step(n_samples, out);
+			return;
+		}
 		check(sphip_render(ctx, (const float*)vp.rays.data(), vp.res_x, vp.res_y, n_samples, seed, mode, flags,
 		                   (uint8_t*)out.values.data(), 0), "render");
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
+	}
+
+	void begun(size_t w, size_t h, bool cam) {
+		acc_live = true; acc_cam = cam;
+		acc_w = w; acc_h = h;
+		acc_scene_hash = scene_hash; acc_scene_n = scene_n;
+		acc_seed = seed; acc_flags = flags;
 	}
 
 	virtual void render_flat(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris, const size_t n_samples, scene::bitmap& out) {
@@ -139,6 +194,10 @@ namespace hip_renderer {
 
 	void set_flags(scene::renderer* r, int flags) {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = flags;
+	}
+
+	void set_progressive(scene::renderer* r, bool on) {
+		if (hip_r* p = dynamic_cast<hip_r*>(r)) { p->progressive = on; p->acc_live = false; }
 	}
 
 	bool render_own_viewport(scene::renderer* r, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,

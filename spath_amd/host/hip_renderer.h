@@ -20,6 +20,12 @@ namespace hip_renderer {
 	// frames and the C-ABI flags word (kernel variant, primary-hit reuse; see include/spath_hip.h).
 	extern void set_seed(scene::renderer* r, unsigned long long seed);
 	extern void set_flags(scene::renderer* r, int flags);
+	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
+	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
+	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one
+	// render of their sum; any change begins a new accumulation.  render_own_viewport does the same, keyed on the camera.
+	// render_flat is not accumulated.  Switching the mode (on or off) also begins anew.
+	extern void set_progressive(scene::renderer* r, bool on);
 	// get_viewport + render (or render_flat) with the viewport generated on the device from the renderer's own
 	// camera (bit-identical rays, no 24 B/pixel upload).  Returns false if r is not a hip renderer.
 	extern bool render_own_viewport(scene::renderer* r, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,

@@ -5,7 +5,9 @@
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
 //             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--out image.ppm|image.rgba] [--frames n]
-//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus]
+//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n]
+// --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
+//   a viewer refines a still view; prints every step, and the final image is byte-identical to the one rendered in one go
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
@@ -128,6 +130,7 @@ int main(int argc, char** argv) {
 		bool all_gpus = false;
 		int w = 640, h = 480, frames = 1, flags = 0;                 // window default of the reference (main.cpp:238-239)
 		size_t spp = 128;                                            // main.cpp:44
+		size_t progressive = 0;
 		unsigned long long seed = 1;
 		std::vector<std::pair<char, geom::vec3> > moves;
 		for (int i = 1; i < argc; ++i) {
@@ -141,6 +144,7 @@ int main(int argc, char** argv) {
 			else if (k == "--seed") { need(1); seed = std::strtoull(argv[++i], 0, 0); }
 			else if (k == "--flags") { need(1); flags = std::atoi(argv[++i]); }
 			else if (k == "--primary-reuse") flags |= SPHIP_FLAG_PRIMARY_REUSE;   // one primary scan per pixel (identical image)
+			else if (k == "--progressive") { need(1); progressive = (size_t)std::atoll(argv[++i]); }
 			else if (k == "--frames") { need(1); frames = std::atoi(argv[++i]); }
 			else if (k == "--out") { need(1); out_path = argv[++i]; }
 			else if (k == "--device-viewport") device_viewport = true;
@@ -170,7 +174,19 @@ int main(int argc, char** argv) {
 		scene::bitmap bmp;
 		for (int f = 0; f < frames; ++f) {
 			const auto t0 = std::chrono::steady_clock::now();
-			if (device_viewport) {                                       // rays generated on the GPU, never uploaded
+			if (progressive && mode == "pt") {
+				hip_renderer::set_progressive(r.get(), true);            // every frame begins a new accumulation
+				if (!device_viewport) r->get_viewport(vp);
+				for (size_t done = 0, step = 0; done < spp; ++step) {
+					const size_t n = std::min(progressive, spp - done);
+					if (device_viewport) hip_renderer::render_own_viewport(r.get(), tris.data(), mats.data(), tris.size(), n, bmp, false);
+					else r->render(vp, tris.data(), mats.data(), tris.size(), n, bmp);
+					done += n;
+					double kms = 0;
+					hip_renderer::last_stats(r.get(), &kms, 0);
+					std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms\n", step, n, done, kms);
+				}
+			} else if (device_viewport) {                                       // rays generated on the GPU, never uploaded
 				hip_renderer::render_own_viewport(r.get(), tris.data(), mats.data(), tris.size(), spp, bmp, mode != "pt");
 			} else {
 				r->get_viewport(vp);                                     // main.cpp:74

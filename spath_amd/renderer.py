@@ -71,12 +71,17 @@ class BasicRenderer(Renderer):
 class HipRenderer(BasicRenderer):
     """The MI355X backend behind the reference's plugin interface."""
 
-    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0):
+    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0, progressive: bool = False):
         super().__init__(x, y)
         self.ctx = capi.Context(device)      # raises like cl_r/vk_r constructors do on init failure
         self.seed = seed
         self.flags = flags
+        # progressive=True: render() / render_own_viewport() add their n_samples to those of the previous calls while the
+        # viewport rays (bit for bit) or the camera, the scene, the seed and the flags stay the same, and return the image of all
+        # of them (bit-identical to one render of the sum); any change begins a new accumulation.  render_flat is not accumulated.
+        self.progressive = progressive
         self._scene_key = None
+        self._accum_key = None
         self.last_stats = None
 
     def get_description(self) -> str:
@@ -91,9 +96,27 @@ class HipRenderer(BasicRenderer):
             self.ctx.set_scene(tris, mats)
             self._scene_key = key
 
+    def _accum_step(self, key, begin, n_samples, out):
+        if key != self._accum_key:
+            self._accum_key = None
+            begin()
+            self._accum_key = key
+        try:
+            out.values, _ = self.ctx.accum_step(n_samples)
+        except capi.SpathHipError:
+            self._accum_key = None                             # a failed step ends the accumulation in the library too
+            raise
+        self.last_stats = self.ctx.stats()
+
     def _render(self, vp, tris, mats, n_tris, n_samples, out, mode):
         self._upload_scene(tris, mats, n_tris)
         out.res_x, out.res_y = vp.res_x, vp.res_y          # cpu_renderer.cpp:120-122
+        if self.progressive and mode == capi.MODE_PT:
+            rays = np.ascontiguousarray(vp.rays, dtype=np.float32).reshape(-1, 6)
+            key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, self.flags)
+            self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=self.flags),
+                             n_samples, out)
+            return
         out.values = self.ctx.render(vp.rays, vp.res_x, vp.res_y, n_samples, seed=self.seed, mode=mode, flags=self.flags)
         self.last_stats = self.ctx.stats()
 
@@ -108,6 +131,11 @@ class HipRenderer(BasicRenderer):
         from this renderer's own camera (bit-identical to get_viewport)."""
         self._upload_scene(tris, mats, n_tris)
         out.res_x, out.res_y = self.vc.res_x, self.vc.res_y
+        if self.progressive and not flat:
+            ca = capi.CameraArgs.from_camera(self.vc)
+            key = ("cam", bytes(ca), self._scene_key, self.seed, self.flags)
+            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags), max(int(n_samples), 1), out)
+            return
         out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed,
                                             mode=capi.MODE_FLAT if flat else capi.MODE_PT, flags=self.flags)
         self.last_stats = self.ctx.stats()
