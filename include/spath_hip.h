@@ -239,6 +239,36 @@ int sphip_accum_begin(sphip_t* ctx, const float* rays /* w*h*6 f32 or NULL */, c
 int sphip_accum_step(sphip_t* ctx, size_t n_samples, uint8_t* out_rgba /* w*h*4 */, float* out_mean /* w*h*3 or NULL */,
                      uint64_t* total_out /* or NULL */);
 
+/* ---- adaptive sampling: a progressive accumulation that stops converged pixels.
+ * Every pixel starts active.  A step (sphip_accum_step) of n samples renders global samples [total, total + n) for the active
+ * pixels only (they all share the count `total`).  Per sample and pixel the library keeps, in double and in sample order,
+ * y = ((double)r + (double)g) + (double)b of the sample's f32 radiance, S1 += y and S2 += y * y.  After the step each pixel still
+ * active with count n >= min_samples is tested, in double, in this order:
+ *     m = S1 / n;  v = (S2 - S1 * m) / (n - 1);  r = m > floor ? m : floor;  d = rel_error * r;  stop iff v / n <= d * d
+ * A stopped pixel never restarts; its sum, S1, S2 and count stay frozen.  Every step returns the whole frame, each pixel from
+ * its own sum and count, so a pixel that stopped after n samples holds exactly what sphip_render of n samples gives for it.
+ * Decisions are taken at step ends only: the counts depend on how the samples are split into steps, not on the kernel
+ * variant, sample chunks, primary-hit reuse, SPHIP_FLAG_ACCEL, sharding or the number of devices.
+ * sphip_accum_step then sets *total_out to the count of the still-active pixels; a step with no active pixel renders nothing,
+ * returns the unchanged image, executes 0 scans and does not advance the total.  sphip_get_stats describes the step
+ * (scans_executed: the scans actually run). */
+typedef struct {
+	double   rel_error;    /* t >= 0 (finite) */
+	double   floor;        /* f >= 0 (finite): the mean below which the error is measured absolutely */
+	uint32_t min_samples;  /* >= 2: no pixel stops before this many samples */
+	uint32_t reserved;     /* must be 0 */
+} sphip_adaptive;
+
+/* sphip_accum_begin plus the rule (same rays / camera, seed, flags, reset rules and error contract); SPHIP_E_INVALID for a
+ * NULL a, min_samples < 2, a negative or non-finite rel_error or floor, reserved != 0.  Accepted by multi-device contexts:
+ * every device runs the rule on its own row tiles. */
+int sphip_accum_begin_adaptive(sphip_t* ctx, const float* rays /* w*h*6 f32 or NULL */, const sphip_camera* cam /* or NULL */,
+                               size_t w, size_t h, uint64_t seed, int flags, const sphip_adaptive* a);
+/* Per-pixel sample counts of the current accumulation in image order (out_counts may be NULL) and the number of active
+ * pixels (may be NULL).  A plain accumulation reports `total` for every pixel, all of them active.  Blocking; SPHIP_E_STATE
+ * when no accumulation has been begun. */
+int sphip_accum_counts(sphip_t* ctx, uint32_t* out_counts /* w*h or NULL */, uint64_t* n_active_out /* or NULL */);
+
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);
 

@@ -32,6 +32,7 @@ SYMBOLS = (
     "sphip_create_multi", "sphip_device_count", "sphip_plan_tile_rows", "sphip_plan_shard", "sphip_selftest_device",
     "sphip_kernel_available", "sphip_selftest_stage1", "sphip_build_info",
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
+    "sphip_accum_begin_adaptive", "sphip_accum_counts",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -50,6 +51,11 @@ class CameraArgs(C.Structure):
         """cam: spath_amd.view.Camera"""
         return cls((C.c_float * 3)(*[float(x) for x in cam.pos]), float(cam.cosY), float(cam.sinY), float(cam.cosX), float(cam.sinX),
                    float(cam.focal), int(cam.res_x), int(cam.res_y))
+
+
+class Adaptive(C.Structure):
+    """sphip_adaptive: the convergence rule of an adaptive accumulation (include/spath_hip.h)."""
+    _fields_ = [("rel_error", C.c_double), ("floor", C.c_double), ("min_samples", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -124,6 +130,10 @@ def load():
     L.sphip_accum_begin.argtypes = [vp, vp, C.POINTER(CameraArgs), sz, sz, C.c_uint64, C.c_int]
     L.sphip_accum_step.restype = C.c_int
     L.sphip_accum_step.argtypes = [vp, sz, vp, vp, C.POINTER(C.c_uint64)]
+    L.sphip_accum_begin_adaptive.restype = C.c_int
+    L.sphip_accum_begin_adaptive.argtypes = [vp, vp, C.POINTER(CameraArgs), sz, sz, C.c_uint64, C.c_int, C.POINTER(Adaptive)]
+    L.sphip_accum_counts.restype = C.c_int
+    L.sphip_accum_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -299,9 +309,11 @@ class Context:
         return (out, acc) if want_accum else out
 
     # progressive rendering -------------------------------------------------------------------
-    def accum_begin(self, rays=None, cam=None, w=None, h=None, seed=1, flags=0):
+    def accum_begin(self, rays=None, cam=None, w=None, h=None, seed=1, flags=0, adaptive=None):
         """Start accumulating the viewport given by exactly one of `rays` (w*h rays, uploaded once) and `cam`
-        (spath_amd.view.Camera, generated on the device; w and h default to its resolution)."""
+        (spath_amd.view.Camera, generated on the device; w and h default to its resolution).
+        adaptive=(t, floor, min_samples): adaptive sampling, converged pixels stop (sphip_accum_begin_adaptive); accum_step's
+        total is then the sample count of the still-active pixels, accum_counts() gives every pixel's."""
         import numpy as np
         ca = None
         if cam is not None:
@@ -315,8 +327,14 @@ class Context:
                 raise ValueError("rays must hold w*h entries")
             ptr = rays.ctypes.data
         self._accum_shape = (int(w or 0), int(h or 0))
-        self._check(self._L.sphip_accum_begin(self._h, ptr, C.byref(ca) if ca is not None else None, int(w or 0), int(h or 0), seed, flags),
-                    "sphip_accum_begin")
+        cap = C.byref(ca) if ca is not None else None
+        if adaptive is None:
+            self._check(self._L.sphip_accum_begin(self._h, ptr, cap, int(w or 0), int(h or 0), seed, flags), "sphip_accum_begin")
+            return
+        t, floor, min_samples = adaptive
+        rule = Adaptive(float(t), float(floor), int(min_samples), 0)
+        self._check(self._L.sphip_accum_begin_adaptive(self._h, ptr, cap, int(w or 0), int(h or 0), seed, flags, C.byref(rule)),
+                    "sphip_accum_begin_adaptive")
 
     def accum_step(self, n, want_mean=False):
         """n more samples of the current accumulation -> (img, total) or (img, mean, total): the image (and mean) of all
@@ -329,6 +347,17 @@ class Context:
         self._check(self._L.sphip_accum_step(self._h, n, out.ctypes.data if w * h else None, mean.ctypes.data if want_mean and w * h else None,
                                              C.byref(total)), "sphip_accum_step")
         return (out, mean, total.value) if want_mean else (out, total.value)
+
+    def accum_counts(self):
+        """-> (counts[h, w] uint32, n_active): every pixel's sample count in the current accumulation and the number of pixels
+        still active (a plain accumulation: `total` everywhere, all active)."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        counts = np.zeros((h, w), dtype=np.uint32)
+        n_active = C.c_uint64(0)
+        self._check(self._L.sphip_accum_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)) if w * h else None, C.byref(n_active)),
+                    "sphip_accum_counts")
+        return counts, n_active.value
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2)}
 

@@ -113,7 +113,7 @@ SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int
 }
 
 // kernels: the same integrator / flat / hit bodies as the exact scans (sp_kernels.h), with the BVH as the scan
-// (a trailing AccumArgs: progressive accumulation in path-tracing mode, sp_kernels.h)
+// (a trailing AccumArgs: progressive accumulation in path-tracing mode; AdaptArgs: adaptive sampling; sp_kernels.h)
 template <int MODE /* 0 flat, 1 pt, 2 hits */, typename... Acc>
 __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, const int* __restrict__ src_idx,
                                                int* __restrict__ out_idx, float* __restrict__ out_d, const Acc... acc_args) {
@@ -144,11 +144,21 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		wave_add_scans(a.scans, valid ? 1u : 0u);
 		return;
 	}
-	const uint32_t pixel = (uint32_t)shard_pixel(a, kk);
+	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_kernels.h AdaptArgs)
+	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
+	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
 	f3 accum = mk3(0.0f, 0.0f, 0.0f);
+	double s1 = 0.0, s2 = 0.0;
 	uint32_t s0 = 0;                                  // global index of the launch's first sample
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (adapt) {
+		const AdaptArgs& q = adapt_args(acc_args...);
+		s0 = q.sample_base;
+		if (s0 && valid) {
+			accum = mk3(q.sum[(size_t)pk * 3 + 0], q.sum[(size_t)pk * 3 + 1], q.sum[(size_t)pk * 3 + 2]);
+			s1 = q.s12[(size_t)pk * 2]; s2 = q.s12[(size_t)pk * 2 + 1];
+		}
+	} else if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);
 		s0 = q.sample_base;
 		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
@@ -193,6 +203,16 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 			}
 		}
 		accum = add3(accum, rec);
+		if constexpr (adapt) { const double y = lum_proxy(rec.x, rec.y, rec.z); s1 = s1 + y; s2 = s2 + y * y; }
+	}
+	if constexpr (adapt) {                            // the frame is resolved from sums and counts (k_adapt_resolve)
+		const AdaptArgs& q = adapt_args(acc_args...);
+		if (valid) {
+			q.sum[(size_t)pk * 3 + 0] = accum.x; q.sum[(size_t)pk * 3 + 1] = accum.y; q.sum[(size_t)pk * 3 + 2] = accum.z;
+			q.s12[(size_t)pk * 2] = s1; q.s12[(size_t)pk * 2 + 1] = s2;
+		}
+		wave_add_scans(a.scans, my_scans);
+		return;
 	}
 	if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);

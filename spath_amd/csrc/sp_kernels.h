@@ -48,26 +48,59 @@ struct AccumArgs {
 };
 SP_DEV const AccumArgs& accum_args(const AccumArgs& p) { return p; }
 
+// adaptive sampling (sphip_accum_begin_adaptive, sp_adaptive.h): a progressive launch over the still-active pixels only.  Ray k
+// of the launch is local pixel list[k]: the host gathers the active rays into a dense buffer in list order, so the ray reads
+// (and the primary-hit pre-pass) are those of a plain launch, while list[k] keys the RNG (shard_pixel) and indexes the running
+// sum and the statistics s12[2 list[k] + {0, 1}] = S1, S2 of the per-sample luminance proxy y (lum_proxy), added in sample
+// order like the f32 sum, in double.  The launch writes no pixels: k_adapt_resolve turns sums and counts into the whole frame.
+// wst: the two-stage kernels park S1, S2 of every work slot there (2 x n_work doubles), as they park the f32 accumulator.
+struct AdaptArgs : AccumArgs {
+	const uint32_t* list;      // n_rays local pixel indices, ascending
+	double* s12;               // n_local * 2
+	double* wst;               // 2 * n_work (two-stage kernels only)
+};
+template <typename... Acc> struct IsAdapt { static constexpr bool value = false; };
+template <> struct IsAdapt<AdaptArgs> { static constexpr bool value = true; };
+SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p) { return p; }
+// local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
+template <typename... Acc>
+SP_DEV uint32_t local_px(uint32_t k, const Acc&... acc_args) {
+	if constexpr (IsAdapt<Acc...>::value) return adapt_args(acc_args...).list[k];
+	else return k;
+}
+// the per-sample luminance proxy of the convergence rule: ((double)r + (double)g) + (double)b of the sample's f32 radiance
+SP_DEV double lum_proxy(float r, float g, float b) { return ((double)r + (double)g) + (double)b; }
+
 // second pass of a sample-chunked launch: cpu_renderer.cpp:72-78 for one pixel -- zero, += sample in sample order,
 // * float(1.0/n_samples), clamp, quantise
 template <typename... Acc>
 __global__ void __launch_bounds__(256) k_resolve(const KArgs a, const Acc... acc_args) {
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	if (k >= a.n_rays) return;
+	constexpr bool adapt = IsAdapt<Acc...>::value;
+	const uint32_t pk = local_px(k, acc_args...);             // where the pixel's running sum lives
 	float ax = 0.0f, ay = 0.0f, az = 0.0f;
+	double s1 = 0.0, s2 = 0.0;
 	if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);
-		if (q.sample_base) { ax = q.sum[(size_t)k * 3 + 0]; ay = q.sum[(size_t)k * 3 + 1]; az = q.sum[(size_t)k * 3 + 2]; }
+		if (q.sample_base) { ax = q.sum[(size_t)pk * 3 + 0]; ay = q.sum[(size_t)pk * 3 + 1]; az = q.sum[(size_t)pk * 3 + 2]; }
+		if constexpr (adapt) if (q.sample_base) { s1 = adapt_args(acc_args...).s12[(size_t)pk * 2]; s2 = adapt_args(acc_args...).s12[(size_t)pk * 2 + 1]; }
 	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		const float* p = a.samp + (size_t)s * 3 * a.samp_stride + k;
-		ax = ax + p[0];
-		ay = ay + p[a.samp_stride];
-		az = az + p[(size_t)2 * a.samp_stride];
+		const float rx = p[0], ry = p[a.samp_stride], rz = p[(size_t)2 * a.samp_stride];
+		ax = ax + rx;
+		ay = ay + ry;
+		az = az + rz;
+		if constexpr (adapt) { const double y = lum_proxy(rx, ry, rz); s1 = s1 + y; s2 = s2 + y * y; }
 	}
 	if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);
-		q.sum[(size_t)k * 3 + 0] = ax; q.sum[(size_t)k * 3 + 1] = ay; q.sum[(size_t)k * 3 + 2] = az;
+		q.sum[(size_t)pk * 3 + 0] = ax; q.sum[(size_t)pk * 3 + 1] = ay; q.sum[(size_t)pk * 3 + 2] = az;
+	}
+	if constexpr (adapt) {
+		adapt_args(acc_args...).s12[(size_t)pk * 2] = s1; adapt_args(acc_args...).s12[(size_t)pk * 2 + 1] = s2;
+		return;                                                  // the frame is resolved from sums and counts (k_adapt_resolve)
 	}
 	const f3 av = scale3(mk3(ax, ay, az), a.inv_n);
 	a.out_rgba[k] = vec3_rgba(mk3(clamp01(av.x), clamp01(av.y), clamp01(av.z)));
@@ -312,7 +345,9 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	const uint32_t kk = valid ? k : a.n_rays - 1;
 	const float* r = a.rays + (size_t)kk * 6;
 	const f3 po = mk3(r[0], r[1], r[2]), pdir = mk3(r[3], r[4], r[5]);
-	const uint32_t pixel = (uint32_t)shard_pixel(a, kk);
+	constexpr bool adapt = IsAdapt<Acc...>::value;
+	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
+	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = (a.flags & 0x100u) != 0;
 
 	uint32_t my_scans = 0;
@@ -321,8 +356,16 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	if (reuse) { closest_hit<VARIANT>(a, po, pdir, -1, pd, pi); my_scans += valid ? 1u : 0u; }
 
 	f3 accum = mk3(0.0f, 0.0f, 0.0f);
+	double s1 = 0.0, s2 = 0.0;                                   // adaptive: S1, S2 of the pixel (sp_kernels.h AdaptArgs)
 	uint32_t s0 = 0;                                             // global index of the launch's first sample
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (adapt) {
+		const AdaptArgs& q = adapt_args(acc_args...);
+		s0 = q.sample_base;
+		if (s0 && valid) {
+			accum = mk3(q.sum[(size_t)pk * 3 + 0], q.sum[(size_t)pk * 3 + 1], q.sum[(size_t)pk * 3 + 2]);
+			s1 = q.s12[(size_t)pk * 2]; s2 = q.s12[(size_t)pk * 2 + 1];
+		}
+	} else if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);
 		s0 = q.sample_base;
 		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
@@ -373,6 +416,16 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			}
 		}
 		accum = add3(accum, rec);                                // :75
+		if constexpr (adapt) { const double y = lum_proxy(rec.x, rec.y, rec.z); s1 = s1 + y; s2 = s2 + y * y; }
+	}
+	if constexpr (adapt) {                                       // the frame is resolved from sums and counts (k_adapt_resolve)
+		const AdaptArgs& q = adapt_args(acc_args...);
+		if (valid) {
+			q.sum[(size_t)pk * 3 + 0] = accum.x; q.sum[(size_t)pk * 3 + 1] = accum.y; q.sum[(size_t)pk * 3 + 2] = accum.z;
+			q.s12[(size_t)pk * 2] = s1; q.s12[(size_t)pk * 2 + 1] = s2;
+		}
+		wave_add_scans(a.scans, my_scans);
+		return;
 	}
 	if constexpr (sizeof...(Acc) > 0) {
 		const AccumArgs& q = accum_args(acc_args...);

@@ -96,6 +96,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 //   work layout: hist[depth][k] = {idx, cos bits} (8 B), then acc[c][k] (3 floats), k < n_work
 // With a trailing AccumArgs (progressive accumulation, sp_kernels.h) the running sum enters the slot's accumulator at the start
 // and leaves it at the end -- with SPLIT only slot 0 carries it; a sample-chunked launch leaves both to k_resolve.
+// With a trailing AdaptArgs (adaptive sampling) the same holds for S1, S2, parked in AdaptArgs::wst[2][n_work] (16 B per slot,
+// touched once per sample, never inside the scan), and ray k is local pixel list[k] for the RNG and the running sums.
 template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
                                                    int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work, const Acc... acc_args) {
@@ -108,19 +110,27 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	const uint32_t pblk = chunked ? blockIdx.x % a.px_blocks : blockIdx.x;
 	const uint32_t chunk = chunked ? blockIdx.x / a.px_blocks : 0u;
 	const uint32_t kr0 = SPLIT ? pblk * B + tid : pblk * (B * R) + tid;
+	constexpr bool adapt = IsAdapt<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
 		const uint32_t k = kr0 + r * kstep;
 		const uint32_t kk = k < a.n_rays ? k : a.n_rays - 1;
-		pixel[r] = (uint32_t)shard_pixel(a, kk);
+		const uint32_t pk = local_px(kk, acc_args...);
+		pixel[r] = (uint32_t)shard_pixel(a, pk);
 #pragma unroll
 		for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = 0.0f;
+		if constexpr (adapt) { adapt_args(acc_args...).wst[k0 + r * B] = 0.0; adapt_args(acc_args...).wst[(size_t)n_work + k0 + r * B] = 0.0; }
 		if constexpr (sizeof...(Acc) > 0) {
 			const AccumArgs& q = accum_args(acc_args...);
+			const size_t ks = adapt ? pk : k;                    // index of the running sum
 			if (q.sample_base && !chunked && (!SPLIT || r == 0) && k < a.n_rays) {
 #pragma unroll
-				for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = q.sum[(size_t)k * 3 + c];
+				for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = q.sum[ks * 3 + c];
+				if constexpr (adapt) {
+					const AdaptArgs& d = adapt_args(acc_args...);
+					d.wst[k0 + r * B] = d.s12[ks * 2]; d.wst[(size_t)n_work + k0 + r * B] = d.s12[ks * 2 + 1];
+				}
 			}
 		}
 	}
@@ -219,6 +229,12 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					float* p = acc + (size_t)c * n_work + ka;
 					*p = *p + (c == 0 ? rec.x : c == 1 ? rec.y : rec.z);
 				}
+				if constexpr (adapt) {                           // S1, S2 beside the accumulator, in the same order
+					double* w = adapt_args(acc_args...).wst + ka;
+					const double y = lum_proxy(rec.x, rec.y, rec.z);
+					w[0] = w[0] + y;
+					w[n_work] = w[n_work] + y * y;
+				}
 			}
 		}
 	}
@@ -229,8 +245,14 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		if (k < a.n_rays && !chunked) {
 			if constexpr (sizeof...(Acc) > 0) {
 				const AccumArgs& q = accum_args(acc_args...);
+				const size_t ks = adapt ? local_px(k, acc_args...) : k;
 #pragma unroll
-				for (int c = 0; c < 3; ++c) q.sum[(size_t)k * 3 + c] = acc[(size_t)c * n_work + kw];
+				for (int c = 0; c < 3; ++c) q.sum[ks * 3 + c] = acc[(size_t)c * n_work + kw];
+				if constexpr (adapt) {
+					const AdaptArgs& d = adapt_args(acc_args...);
+					d.s12[ks * 2] = d.wst[kw]; d.s12[ks * 2 + 1] = d.wst[(size_t)n_work + kw];
+					continue;                                    // the frame is resolved from sums and counts (k_adapt_resolve)
+				}
 			}
 			const f3 av = scale3(mk3(acc[kw], acc[(size_t)n_work + kw], acc[(size_t)2 * n_work + kw]), a.inv_n);
 			a.out_rgba[k] = vec3_rgba(mk3(clamp01(av.x), clamp01(av.y), clamp01(av.z)));

@@ -11,6 +11,7 @@
 #include "sp_scan_kernels.h"
 #include "sp_bvh.h"
 #include "sp_bvh_build.h"
+#include "sp_adaptive.h"
 
 #include <hip/hip_runtime.h>
 
@@ -71,6 +72,16 @@ struct sphip_ctx {
 	size_t acc_w = 0, acc_h = 0;
 	uint64_t acc_seed = 0, acc_total = 0;         // acc_total: samples accumulated so far
 	int acc_flags = 0;
+	// ---- adaptive sampling (sphip_accum_begin_adaptive) on top of that accumulation; per local pixel: S1/S2 (16 B), the sample
+	// count, two active lists (the step's and the next), the active rays gathered in list order, a keep byte; per 256 pixels one
+	// block total.  adp_nact: pixels still active (host copy, read back with each step's image); on a multi-device context the
+	// sum over the devices, the rule being the parent's
+	DevBuf adp_s12, adp_cnt, adp_list[2], adp_rays, adp_keep, adp_blk, adp_nact_d, adp_wst;
+	bool adp_on = false;
+	int adp_cur = 0;                              // adp_list[adp_cur] is the current list
+	uint32_t adp_nact = 0, adp_nact_rb = 0;       // adp_nact_rb: the step's readback, valid once the stream has drained
+	double adp_t = 0.0, adp_floor = 0.0;
+	uint32_t adp_min = 0;
 };
 
 namespace {
@@ -297,7 +308,8 @@ constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 // [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
 int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
                   size_t n_samples, uint64_t seed, int mode, int flags, void* d_rgba, void* d_accum, hipStream_t st,
-                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr) {
+                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr, const sp::AdaptArgs* adapt = nullptr) {
+	if (adapt) prog = adapt;                        // an adaptive launch is a progressive one over the active list (sp_kernels.h)
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
 	if (!d_rays || !d_rgba) return fail(c, SPHIP_E_INVALID, "null ray or output pointer");
 	if (n_rays == 0 || n_rays > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n_rays);
@@ -369,7 +381,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			if (samp_bytes > kChunkMaxBytes) chunks = 1;
 			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
 			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * 52;
+				const uint64_t work_bytes = lanes * chunks * (adapt ? 68 : 52);
 				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
@@ -395,10 +407,14 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		return fail(c, SPHIP_E_INVALID, "n_rays %zu too large for one launch of this kernel variant; shard the frame", n_rays);
 	const uint32_t n_work = (uint32_t)n_work64;
 	int2* hist = nullptr; float* acc = nullptr;
+	sp::AdaptArgs ad{};
+	if (adapt) ad = *adapt;
 	if (mode == SPHIP_MODE_PT && is_ts) {
 		if ((rc = ensure(c, c->work, (size_t)n_work * 52))) return rc;
 		hist = (int2*)c->work.p;
 		acc = (float*)((char*)c->work.p + (size_t)n_work * 40);
+		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * 16))) return rc;   // S1, S2 per work slot
+		ad.wst = (double*)c->adp_wst.p;
 	}
 	sp::ScanSrc src2{};
 	if (is_ts && (ts.scan == 1 || ts.scan == 2) && (rc = ensure_cyl(c, st))) return rc;
@@ -443,6 +459,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (variant == kVariantAccel) {
 		if (mode == kModeHits)           hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
 		else if (mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
+		else if (adapt)                   hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad);
 		else if (prog)                    hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog);
 		else                              hipLaunchKernelGGL(sp::k_accel<1>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
 	} else if (mode == kModeHits) {
@@ -476,7 +493,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		else                   hipLaunchKernelGGL(sp::k_flat<1>, grid, block, 0, st, a);
 	} else {
 		if (is_ts) {
-#define SP_PT(R_, SPLIT_, S_) do { if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
+#define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad); \
+                                   else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work); } while (0)
 			if (ts.scan == 3) SP_PT(1, false, 3);
 			else if (ts.scan == 4) SP_PT(1, false, 4);
@@ -493,12 +511,15 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #endif
 #undef SP_PT
 		}
+		else if (adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs>), grid, block, 0, st, a, ad);
+		else if (adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs>), grid, block, 0, st, a, ad);
 		else if (prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs>), grid, block, 0, st, a, *prog);
 		else if (prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs>), grid, block, 0, st, a, *prog);
 		else if (variant == 2) hipLaunchKernelGGL(sp::k_pt<2>, grid, block, 0, st, a);
 		else                   hipLaunchKernelGGL(sp::k_pt<1>, grid, block, 0, st, a);
 	}
-	if (chunks > 1 && prog) hipLaunchKernelGGL((sp::k_resolve<sp::AccumArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, *prog);
+	if (chunks > 1 && adapt) hipLaunchKernelGGL((sp::k_resolve<sp::AdaptArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, ad);
+	else if (chunks > 1 && prog) hipLaunchKernelGGL((sp::k_resolve<sp::AccumArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, *prog);
 	else if (chunks > 1) hipLaunchKernelGGL(sp::k_resolve<>, dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
@@ -776,20 +797,85 @@ int multi_render(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_
 	});
 }
 
+// ---- adaptive sampling (sp_adaptive.h) on one device: a single-device context, or a child of a multi-device one for the n pixels
+// of its shard.  Every pixel starts active, with count 0; the first list is every local pixel in order.
+int adapt_begin_dev(sphip_ctx* k, size_t n, hipStream_t st) {
+	int rc;
+	const size_t nb = (n + 255) / 256;
+	if ((rc = ensure(k, k->adp_s12, n * 16)) || (rc = ensure(k, k->adp_cnt, n * 4)) || (rc = ensure(k, k->adp_list[0], n * 4)) ||
+	    (rc = ensure(k, k->adp_list[1], n * 4)) || (rc = ensure(k, k->adp_rays, n * 24)) || (rc = ensure(k, k->adp_keep, n)) ||
+	    (rc = ensure(k, k->adp_blk, nb * 4)) || (rc = ensure(k, k->adp_nact_d, 4))) return rc;
+	HIP_TRY(k, hipMemsetAsync(k->adp_cnt.p, 0, n * 4, st));
+	hipLaunchKernelGGL(sp::k_adapt_iota, dim3((unsigned)nb), dim3(256), 0, st, (uint32_t*)k->adp_list[0].p, (uint32_t)n);
+	HIP_TRY(k, hipGetLastError());
+	k->adp_cur = 0;
+	k->adp_nact = k->adp_nact_rb = (uint32_t)n;
+	return SPHIP_OK;
+}
+
+// One adaptive step on device context k (par: the context holding the accumulation's parameters, k itself on a single device):
+// the still-active pixels get global samples [total, total + n_samples), the rule and the compaction run on them, and the whole
+// shard is resolved into k->rgba (and d_mean).  The new active count goes to k->adp_nact_rb in stream order.  With no active
+// pixel nothing is traced: the resolve alone runs (same image), and the stats report 0 scans.
+int adapt_step_dev(sphip_ctx* k, const sphip_ctx* par, size_t n, const sphip_shard& sh, size_t n_samples, float* d_mean, hipStream_t st) {
+	const uint32_t na = k->adp_nact;
+	int rc;
+	if (na > 0) {
+		const int cur = k->adp_cur;
+		sp::AdaptArgs q{};
+		q.sum = (float*)k->acc_sum.p;
+		q.sample_base = (uint32_t)par->acc_total;
+		q.list = (const uint32_t*)k->adp_list[cur].p;
+		q.s12 = (double*)k->adp_s12.p;
+		// every pixel active: the list is the identity, the gathered rays would be the accumulation's own
+		const void* rays = na == n ? k->acc_rays.p : k->adp_rays.p;
+		if ((rc = launch_render(k, rays, na, &sh, par->acc_w, n_samples, par->acc_seed, SPHIP_MODE_PT, par->acc_flags, k->rgba.p, nullptr, st,
+		                        nullptr, nullptr, &q))) return rc;
+		const sp::AdaptRule rule{ par->adp_t, par->adp_floor, par->adp_min, (uint32_t)n_samples };
+		const dim3 nb((unsigned)((na + 255) / 256));
+		hipLaunchKernelGGL(sp::k_adapt_decide, nb, dim3(256), 0, st, q.list, na, (uint32_t*)k->adp_cnt.p, (const double*)q.s12, rule,
+		                   (uint8_t*)k->adp_keep.p, (uint32_t*)k->adp_blk.p);
+		hipLaunchKernelGGL(sp::k_adapt_scan, dim3(1), dim3(1024), 0, st, (uint32_t*)k->adp_blk.p, (uint32_t)nb.x, (uint32_t*)k->adp_nact_d.p);
+		hipLaunchKernelGGL(sp::k_adapt_scatter, nb, dim3(256), 0, st, q.list, na, (const uint8_t*)k->adp_keep.p, (const uint32_t*)k->adp_blk.p,
+		                   (const float*)k->acc_rays.p, (uint32_t*)k->adp_list[cur ^ 1].p, (float*)k->adp_rays.p);
+		k->adp_cur = cur ^ 1;
+		k->stats.n_launches += 4;
+	} else {
+		if ((rc = ensure(k, k->counter, 16 * sizeof(unsigned long long)))) return rc;
+		HIP_TRY(k, hipMemsetAsync(k->counter.p, 0, 16 * sizeof(unsigned long long), st));
+		HIP_TRY(k, hipEventRecord(k->ev_k0, st));
+		k->stats.n_launches = 1;
+		k->stats.kernel_variant = (uint32_t)pick_variant(par->acc_flags, k->n_tris);
+		k->stats.n_tris = k->n_tris;
+		k->have_render = true;
+		k->last_stream = st;
+	}
+	hipLaunchKernelGGL(sp::k_adapt_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)k->acc_sum.p,
+	                   (const uint32_t*)k->adp_cnt.p, (uint32_t)n, (uint32_t*)k->rgba.p, d_mean);
+	HIP_TRY(k, hipGetLastError());
+	HIP_TRY(k, hipEventRecord(k->ev_k1, st));        // kernel_ms covers the path kernels, the rule, the compaction and the resolve
+	if (na > 0) HIP_TRY(k, hipMemcpyAsync(&k->adp_nact_rb, k->adp_nact_d.p, 4, hipMemcpyDeviceToHost, st));
+	else k->adp_nact_rb = 0;
+	k->stats.n_pixels = n;
+	return SPHIP_OK;
+}
+
 // sphip_accum_begin on a multi-device context: device r keeps the rays of its shard (the row-tile plan of the frame) and its
 // shard's running sum resident
-int multi_accum_begin(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h) {
+int multi_accum_begin(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, bool adaptive) {
 	const int g = (int)c->kids.size();
 	const RowPlan plan(w, h, g, (size_t)plan_tile_rows(h, g));
 	for (int r = 0; r < g; ++r) {
 		sphip_ctx* k = c->kids[(size_t)r];
 		const size_t n = plan.n_rays(r);
+		k->adp_nact = k->adp_nact_rb = 0;
 		if (n == 0) continue;
 		auto body = [&]() -> int {
 			HIP_TRY(k, hipSetDevice(k->device));
 			int rc;
 			if ((rc = ensure(k, k->acc_rays, n * 24)) || (rc = ensure(k, k->acc_sum, n * 12)) ||
 			    (rc = deal_rays(k, plan, r, rays, cam, k->acc_rays.p, k->own_stream))) return rc;
+			if (adaptive && (rc = adapt_begin_dev(k, n, k->own_stream))) return rc;
 			HIP_TRY(k, hipStreamSynchronize(k->own_stream));       // the rays are borrowed
 			return SPHIP_OK;
 		};
@@ -804,6 +890,16 @@ int multi_accum_begin(sphip_ctx* c, const float* rays, const sphip_camera* cam, 
 }
 
 int multi_accum_step(sphip_ctx* c, size_t n_samples, uint8_t* out_rgba, float* out_mean) {
+	if (c->adp_on) {                                  // every device runs the rule on its own row tiles
+		const int rc = multi_frame(c, c->acc_w, c->acc_h, out_rgba, out_mean, [&](sphip_ctx* k, int, size_t n, const sphip_shard& sh) -> int {
+			return adapt_step_dev(k, c, n, sh, n_samples, out_mean ? (float*)k->accum.p : nullptr, k->own_stream);
+		});
+		if (rc) return rc;
+		uint64_t na = 0;                              // every stream has drained (multi_frame)
+		for (sphip_ctx* k : c->kids) { k->adp_nact = k->adp_nact_rb; na += k->adp_nact; }
+		c->adp_nact = (uint32_t)na;
+		return SPHIP_OK;
+	}
 	return multi_frame(c, c->acc_w, c->acc_h, out_rgba, out_mean, [&](sphip_ctx* k, int, size_t n, const sphip_shard& sh) -> int {
 		const sp::AccumArgs p{ (float*)k->acc_sum.p, (uint32_t)c->acc_total };
 		return launch_render(k, k->acc_rays.p, n, &sh, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, k->rgba.p,
@@ -836,6 +932,42 @@ int multi_get_stats(sphip_ctx* c, sphip_stats* out) {
 	s.n_pixels = c->stats.n_pixels;
 	c->stats = s;
 	*out = s;
+	return SPHIP_OK;
+}
+
+// sphip_accum_begin, and with adaptive != nullptr sphip_accum_begin_adaptive (the rule checked by the caller)
+int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, uint64_t seed, int flags, const sphip_adaptive* adaptive) {
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_accum_begin called before a scene was set");
+	if ((rays == nullptr) == (cam == nullptr)) return fail(c, SPHIP_E_INVALID, "sphip_accum_begin takes exactly one of rays and cam");
+	if (w == 0 || h == 0 || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad viewport size (w=%zu h=%zu)", w, h);
+	if (cam && (cam->res_x != w || cam->res_y != h))
+		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the camera's %ux%u", w, h, cam->res_x, cam->res_y);
+	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
+	c->adp_on = false;
+	if (!c->kids.empty()) {
+		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
+		if (rc) return rc;
+	} else {
+		HIP_TRY(c, hipSetDevice(c->device));
+		const size_t n = w * h;
+		hipStream_t st = c->own_stream;
+		int rc;
+		if ((rc = ensure(c, c->acc_rays, n * 24)) || (rc = ensure(c, c->acc_sum, n * 12))) return rc;
+		if (rays) HIP_TRY(c, hipMemcpyAsync(c->acc_rays.p, rays, n * 24, hipMemcpyHostToDevice, st));      // once per accumulation
+		else if ((rc = launch_viewport(c, cam, c->acc_rays.p, st))) return rc;
+		if (adaptive && (rc = adapt_begin_dev(c, n, st))) return rc;
+		HIP_TRY(c, hipStreamSynchronize(st));        // rays are borrowed
+	}
+	if (adaptive) {
+		c->adp_on = true;
+		c->adp_t = adaptive->rel_error; c->adp_floor = adaptive->floor; c->adp_min = adaptive->min_samples;
+		c->adp_nact = (uint32_t)(w * h);
+	}
+	c->acc_on = true;
+	c->acc_stale = false;
+	c->acc_w = w; c->acc_h = h;
+	c->acc_seed = seed; c->acc_flags = flags;
+	c->acc_total = 0;                              // the first step's sample_base: the sum buffer's contents are not read
 	return SPHIP_OK;
 }
 
@@ -994,7 +1126,8 @@ void sphip_destroy(sphip_t* c) {
 	if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
 	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
-	                   &c->acc_rays, &c->acc_sum };
+	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
+	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
@@ -1060,32 +1193,53 @@ int sphip_render_device_accum(sphip_t* c, const void* d_rays, size_t n_rays, con
 	                     nullptr, &p);
 }
 
+
 int sphip_accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, uint64_t seed, int flags) {
 	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_accum_begin called before a scene was set");
-	if ((rays == nullptr) == (cam == nullptr)) return fail(c, SPHIP_E_INVALID, "sphip_accum_begin takes exactly one of rays and cam");
-	if (w == 0 || h == 0 || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad viewport size (w=%zu h=%zu)", w, h);
-	if (cam && (cam->res_x != w || cam->res_y != h))
-		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the camera's %ux%u", w, h, cam->res_x, cam->res_y);
-	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
-	if (!c->kids.empty()) {
-		const int rc = multi_accum_begin(c, rays, cam, w, h);
-		if (rc) return rc;
-	} else {
-		HIP_TRY(c, hipSetDevice(c->device));
-		const size_t n = w * h;
-		hipStream_t st = c->own_stream;
-		int rc;
-		if ((rc = ensure(c, c->acc_rays, n * 24)) || (rc = ensure(c, c->acc_sum, n * 12))) return rc;
-		if (rays) HIP_TRY(c, hipMemcpyAsync(c->acc_rays.p, rays, n * 24, hipMemcpyHostToDevice, st));      // once per accumulation
-		else if ((rc = launch_viewport(c, cam, c->acc_rays.p, st))) return rc;
-		HIP_TRY(c, hipStreamSynchronize(st));        // rays are borrowed
+	return accum_begin(c, rays, cam, w, h, seed, flags, nullptr);
+}
+
+int sphip_accum_begin_adaptive(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w, size_t h, uint64_t seed, int flags,
+                               const sphip_adaptive* a) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!a) return fail(c, SPHIP_E_INVALID, "null sphip_adaptive");
+	if (!std::isfinite(a->rel_error) || a->rel_error < 0.0 || !std::isfinite(a->floor) || a->floor < 0.0 || a->min_samples < 2 || a->reserved != 0)
+		return fail(c, SPHIP_E_INVALID, "bad sphip_adaptive {rel_error %g, floor %g, min_samples %u, reserved %u}: t and floor finite and >= 0, "
+		            "min_samples >= 2, reserved 0", a->rel_error, a->floor, a->min_samples, a->reserved);
+	return accum_begin(c, rays, cam, w, h, seed, flags, a);
+}
+
+int sphip_accum_counts(sphip_t* c, uint32_t* out_counts, uint64_t* n_active_out) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->acc_on) return fail(c, SPHIP_E_STATE, "sphip_accum_counts called with no accumulation begun");
+	const size_t npix = c->acc_w * c->acc_h;
+	if (n_active_out) *n_active_out = c->adp_on ? c->adp_nact : npix;
+	if (!out_counts) return SPHIP_OK;
+	if (!c->adp_on) {
+		std::fill(out_counts, out_counts + npix, (uint32_t)c->acc_total);
+		return SPHIP_OK;
 	}
-	c->acc_on = true;
-	c->acc_stale = false;
-	c->acc_w = w; c->acc_h = h;
-	c->acc_seed = seed; c->acc_flags = flags;
-	c->acc_total = 0;                              // the first step's sample_base: the sum buffer's contents are not read
+	if (c->kids.empty()) {
+		HIP_TRY(c, hipSetDevice(c->device));
+		HIP_TRY(c, hipMemcpyAsync(out_counts, c->adp_cnt.p, npix * 4, hipMemcpyDeviceToHost, c->own_stream));
+		HIP_TRY(c, hipStreamSynchronize(c->own_stream));
+		return SPHIP_OK;
+	}
+	// a query, not the hot path: each device's counts in its shard's order, put in image order here
+	const int g = (int)c->kids.size();
+	const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
+	std::vector<uint32_t> loc;
+	for (int r = 0; r < g; ++r) {
+		sphip_ctx* k = c->kids[(size_t)r];
+		const size_t n = plan.n_rays(r);
+		if (n == 0) continue;
+		loc.resize(n);
+		HIP_TRY(c, hipSetDevice(k->device));
+		HIP_TRY(c, hipMemcpyAsync(loc.data(), k->adp_cnt.p, n * 4, hipMemcpyDeviceToHost, k->own_stream));
+		HIP_TRY(c, hipStreamSynchronize(k->own_stream));
+		const sphip_shard sh = plan.shard(r);
+		for (size_t i = 0; i < n; ++i) out_counts[sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px] = loc[i];
+	}
 	return SPHIP_OK;
 }
 
@@ -1097,6 +1251,7 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 	if (n_samples == 0 || c->acc_total + n_samples > 0x7fffffffull)
 		return fail(c, SPHIP_E_INVALID, "n_samples = %zu after %llu: each step renders at least one sample, and the total must stay below 2^31",
 		            n_samples, (unsigned long long)c->acc_total);
+	const bool traced = !c->adp_on || c->adp_nact > 0;   // an adaptive step with no active pixel renders nothing
 	int rc;
 	if (!c->kids.empty()) {
 		rc = multi_accum_step(c, n_samples, out_rgba, out_mean);
@@ -1109,13 +1264,17 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 			if ((rc2 = ensure(c, c->rgba, n * 4))) return rc2;
 			if (out_mean && (rc2 = ensure(c, c->accum, n * 12))) return rc2;
 			const sp::AccumArgs p{ (float*)c->acc_sum.p, (uint32_t)c->acc_total };
-			if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
-			                         out_mean ? c->accum.p : nullptr, st, nullptr, &p))) return rc2;
+			const sphip_shard whole{ 0, n, 0 };
+			if (c->adp_on) {
+				if ((rc2 = adapt_step_dev(c, c, n, whole, n_samples, out_mean ? (float*)c->accum.p : nullptr, st))) return rc2;
+			} else if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
+			                                out_mean ? c->accum.p : nullptr, st, nullptr, &p))) return rc2;
 			HIP_TRY(c, hipEventRecord(c->ev_d0, st));
 			HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
 			if (out_mean) HIP_TRY(c, hipMemcpyAsync(out_mean, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
 			HIP_TRY(c, hipEventRecord(c->ev_d1, st));
 			HIP_TRY(c, hipStreamSynchronize(st));
+			c->adp_nact = c->adp_nact_rb;
 			c->timed_upload = false;
 			c->timed_download = true;
 			return SPHIP_OK;
@@ -1127,7 +1286,7 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 		c->acc_on = false;
 		return rc;
 	}
-	c->acc_total += n_samples;
+	if (traced) c->acc_total += n_samples;
 	if (total_out) *total_out = c->acc_total;
 	return SPHIP_OK;
 }

@@ -41,6 +41,8 @@ struct hip_r : public basic_renderer {
 	size_t acc_w, acc_h, acc_scene_n;
 	unsigned long long acc_scene_hash, acc_seed;
 	int acc_flags;
+	// adaptive sampling (set_adaptive) of the progressive mode: adp.rel_error < 0 is off
+	sphip_adaptive adp;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
@@ -48,6 +50,8 @@ struct hip_r : public basic_renderer {
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
+		std::memset(&adp, 0, sizeof adp);
+		adp.rel_error = -1.0;
 		if (sphip_create_multi(ids, n_ids, &ctx) != SPHIP_OK)
 			throw std::runtime_error(std::string("hip_renderer: ") + sphip_last_error(0));
 		desc = sphip_description(ctx);
@@ -93,6 +97,11 @@ struct hip_r : public basic_renderer {
 		return acc_live && acc_w == w && acc_h == h && acc_scene_hash == scene_hash && acc_scene_n == scene_n && acc_seed == seed && acc_flags == flags;
 	}
 
+	void begin(const float* rays, const sphip_camera* cam, size_t w, size_t h) {
+		if (adp.rel_error < 0.0) check(sphip_accum_begin(ctx, rays, cam, w, h, seed, flags), "accum_begin");
+		else check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &adp), "accum_begin_adaptive");
+	}
+
 	// one progressive step of n_samples (the accumulation begun or continued by the caller) into out
 	void accum_step(const size_t n_samples, scene::bitmap& out) {
 		acc_live = false;                  // a failed step ends the accumulation on the library's side too
@@ -111,7 +120,7 @@ struct hip_r : public basic_renderer {
 		if (progressive && mode == SPHIP_MODE_PT) {
 			if (!(same_accumulation(c.res_x, c.res_y) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0)) {
 				acc_live = false;
-				check(sphip_accum_begin(ctx, 0, &c, c.res_x, c.res_y, seed, flags), "accum_begin");
+				begin(0, &c, c.res_x, c.res_y);
 				begun(c.res_x, c.res_y, true);
 				acc_camera = c;
 				acc_rays.clear();
@@ -136,7 +145,7 @@ struct hip_r : public basic_renderer {
 			if (!(same_accumulation(vp.res_x, vp.res_y) && !acc_cam && acc_rays.size() == vp.rays.size() &&
 			      std::memcmp(acc_rays.data(), vp.rays.data(), vp.rays.size() * sizeof(geom::ray)) == 0)) {
 				acc_live = false;
-				check(sphip_accum_begin(ctx, (const float*)vp.rays.data(), 0, vp.res_x, vp.res_y, seed, flags), "accum_begin");
+				begin((const float*)vp.rays.data(), 0, vp.res_x, vp.res_y);
 				begun(vp.res_x, vp.res_y, false);
 				acc_rays.assign(vp.rays.begin(), vp.rays.end());
 			}
@@ -198,6 +207,25 @@ namespace hip_renderer {
 
 	void set_progressive(scene::renderer* r, bool on) {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) { p->progressive = on; p->acc_live = false; }
+	}
+
+	void set_adaptive(scene::renderer* r, double t, double floor, unsigned min_samples) {
+		if (hip_r* p = dynamic_cast<hip_r*>(r)) {
+			p->adp.rel_error = t < 0.0 ? -1.0 : t;
+			p->adp.floor = floor;
+			p->adp.min_samples = min_samples;
+			p->adp.reserved = 0;
+			p->acc_live = false;
+		}
+	}
+
+	bool accum_counts(scene::renderer* r, uint32_t* counts, unsigned long long* n_active) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p || !p->acc_live) return false;
+		uint64_t na = 0;
+		p->check(sphip_accum_counts(p->ctx, counts, &na), "accum_counts");
+		if (n_active) *n_active = na;
+		return true;
 	}
 
 	bool render_own_viewport(scene::renderer* r, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,

@@ -4,6 +4,8 @@
 
 #include "spath_iface.h"
 
+#include <stdint.h>
+
 namespace hip_renderer {
 	// Returns a new renderer owned by the caller (the reference wraps it in std::unique_ptr,
 	// src/main.cpp:242-244).  Throws std::runtime_error when no usable HIP device exists, like the
@@ -26,6 +28,13 @@ namespace hip_renderer {
 	// render of their sum; any change begins a new accumulation.  render_own_viewport does the same, keyed on the camera.
 	// render_flat is not accumulated.  Switching the mode (on or off) also begins anew.
 	extern void set_progressive(scene::renderer* r, bool on);
+	// Adaptive sampling of the progressive mode (include/spath_hip.h: sphip_accum_begin_adaptive): converged pixels stop, each
+	// keeping exactly the image of its own sample count.  t < 0 turns it off (the default).  Switching on or off, or changing the
+	// rule, begins anew.
+	extern void set_adaptive(scene::renderer* r, double t, double floor, unsigned min_samples);
+	// per-pixel sample counts (w*h, image order) and active pixels of the current accumulation; false if r is not a hip renderer
+	// or no accumulation is live
+	extern bool accum_counts(scene::renderer* r, uint32_t* counts, unsigned long long* n_active);
 	// get_viewport + render (or render_flat) with the viewport generated on the device from the renderer's own
 	// camera (bit-identical rays, no 24 B/pixel upload).  Returns false if r is not a hip renderer.
 	extern bool render_own_viewport(scene::renderer* r, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,

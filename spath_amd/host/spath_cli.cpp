@@ -5,9 +5,12 @@
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
 //             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--out image.ppm|image.rgba] [--frames n]
-//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n]
+//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
 //   a viewer refines a still view; prints every step, and the final image is byte-identical to the one rendered in one go
+// --adaptive T[,FLOOR[,MIN]]: with --progressive, stop converged pixels after each step (include/spath_hip.h: sphip_adaptive;
+//   relative error T, FLOOR default 0.1, MIN default 8 samples); every pixel's image is that of its own sample count.
+//   --counts-out: the per-pixel sample counts of the last frame as a 16-bit binary PGM (clamped to 65535)
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
@@ -131,6 +134,9 @@ int main(int argc, char** argv) {
 		int w = 640, h = 480, frames = 1, flags = 0;                 // window default of the reference (main.cpp:238-239)
 		size_t spp = 128;                                            // main.cpp:44
 		size_t progressive = 0;
+		double adp_t = -1.0, adp_floor = 0.1;                        // --adaptive defaults: FLOOR 0.1, MIN 8
+		unsigned adp_min = 8;
+		std::string counts_path;
 		unsigned long long seed = 1;
 		std::vector<std::pair<char, geom::vec3> > moves;
 		for (int i = 1; i < argc; ++i) {
@@ -145,6 +151,17 @@ int main(int argc, char** argv) {
 			else if (k == "--flags") { need(1); flags = std::atoi(argv[++i]); }
 			else if (k == "--primary-reuse") flags |= SPHIP_FLAG_PRIMARY_REUSE;   // one primary scan per pixel (identical image)
 			else if (k == "--progressive") { need(1); progressive = (size_t)std::atoll(argv[++i]); }
+			else if (k == "--adaptive") {
+				need(1);
+				const char* p = argv[++i];
+				char* e = 0;
+				adp_t = std::strtod(p, &e);
+				if (e == p || adp_t < 0.0) throw std::runtime_error("bad --adaptive value (T[,FLOOR[,MIN]], T >= 0)");
+				if (*e == ',') { p = e + 1; adp_floor = std::strtod(p, &e); if (e == p) throw std::runtime_error("bad --adaptive FLOOR"); }
+				if (*e == ',') { p = e + 1; adp_min = (unsigned)std::strtoul(p, &e, 10); if (e == p) throw std::runtime_error("bad --adaptive MIN"); }
+				if (*e) throw std::runtime_error("bad --adaptive value (T[,FLOOR[,MIN]])");
+			}
+			else if (k == "--counts-out") { need(1); counts_path = argv[++i]; }
 			else if (k == "--frames") { need(1); frames = std::atoi(argv[++i]); }
 			else if (k == "--out") { need(1); out_path = argv[++i]; }
 			else if (k == "--device-viewport") device_viewport = true;
@@ -164,6 +181,9 @@ int main(int argc, char** argv) {
 		                                   : all_gpus ? hip_renderer::get_all_devices(w, h) : hip_renderer::get(w, h));
 		hip_renderer::set_seed(r.get(), seed);
 		hip_renderer::set_flags(r.get(), flags);
+		if (adp_t >= 0.0 && !(progressive && mode == "pt")) throw std::runtime_error("--adaptive needs --progressive n and --mode pt");
+		if (!counts_path.empty() && !(progressive && mode == "pt")) throw std::runtime_error("--counts-out needs --progressive n and --mode pt");
+		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);
 		std::printf("Current renderer: %s [%d device(s)]\n", r->get_description(), hip_renderer::device_count(r.get()));     // main.cpp:30-32
 		for (size_t k = 0; k < moves.size(); ++k) {
 			if (moves[k].first == 'm') r->set_delta_mov(moves[k].second);
@@ -184,7 +204,10 @@ int main(int argc, char** argv) {
 					done += n;
 					double kms = 0;
 					hip_renderer::last_stats(r.get(), &kms, 0);
-					std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms\n", step, n, done, kms);
+					unsigned long long active = 0;
+					if (adp_t >= 0.0 && hip_renderer::accum_counts(r.get(), 0, &active))
+						std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms, %llu pixels active\n", step, n, done, kms, active);
+					else std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms\n", step, n, done, kms);
 				}
 			} else if (device_viewport) {                                       // rays generated on the GPU, never uploaded
 				hip_renderer::render_own_viewport(r.get(), tris.data(), mats.data(), tris.size(), spp, bmp, mode != "pt");
@@ -209,6 +232,19 @@ int main(int argc, char** argv) {
 				write_png(o, bmp);
 			} else {
 				std::fwrite(bmp.values.data(), sizeof(scene::RGBA), bmp.values.size(), o);
+			}
+			std::fclose(o);
+		}
+		if (!counts_path.empty()) {
+			std::vector<uint32_t> counts(bmp.values.size());
+			if (!hip_renderer::accum_counts(r.get(), counts.data(), 0)) throw std::runtime_error("no accumulation to read the counts of");
+			FILE* o = std::fopen(counts_path.c_str(), "wb");
+			if (!o) throw std::runtime_error("cannot write " + counts_path);
+			std::fprintf(o, "P5\n%zu %zu\n65535\n", bmp.res_x, bmp.res_y);
+			for (size_t i = 0; i < counts.size(); ++i) {                 // 16-bit PGM: big-endian samples
+				const unsigned v = counts[i] < 65535u ? counts[i] : 65535u;
+				const unsigned char b[2] = { (unsigned char)(v >> 8), (unsigned char)(v & 0xff) };
+				std::fwrite(b, 1, 2, o);
 			}
 			std::fclose(o);
 		}

@@ -71,7 +71,7 @@ class BasicRenderer(Renderer):
 class HipRenderer(BasicRenderer):
     """The MI355X backend behind the reference's plugin interface."""
 
-    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0, progressive: bool = False):
+    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0, progressive: bool = False, adaptive=None):
         super().__init__(x, y)
         self.ctx = capi.Context(device)      # raises like cl_r/vk_r constructors do on init failure
         self.seed = seed
@@ -80,6 +80,11 @@ class HipRenderer(BasicRenderer):
         # viewport rays (bit for bit) or the camera, the scene, the seed and the flags stay the same, and return the image of all
         # of them (bit-identical to one render of the sum); any change begins a new accumulation.  render_flat is not accumulated.
         self.progressive = progressive
+        # adaptive=(t, floor, min_samples) with progressive=True: converged pixels stop (capi.Context.accum_begin); part of the
+        # accumulation's key, so changing it begins anew.  adaptive_counts() gives the per-pixel sample counts.
+        if adaptive is not None and not progressive:
+            raise ValueError("adaptive sampling needs progressive=True")
+        self.adaptive = tuple(adaptive) if adaptive is not None else None
         self._scene_key = None
         self._accum_key = None
         self.last_stats = None
@@ -113,8 +118,9 @@ class HipRenderer(BasicRenderer):
         out.res_x, out.res_y = vp.res_x, vp.res_y          # cpu_renderer.cpp:120-122
         if self.progressive and mode == capi.MODE_PT:
             rays = np.ascontiguousarray(vp.rays, dtype=np.float32).reshape(-1, 6)
-            key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, self.flags)
-            self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=self.flags),
+            key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, self.flags, self.adaptive)
+            self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=self.flags,
+                                                               adaptive=self.adaptive),
                              n_samples, out)
             return
         out.values = self.ctx.render(vp.rays, vp.res_x, vp.res_y, n_samples, seed=self.seed, mode=mode, flags=self.flags)
@@ -133,12 +139,17 @@ class HipRenderer(BasicRenderer):
         out.res_x, out.res_y = self.vc.res_x, self.vc.res_y
         if self.progressive and not flat:
             ca = capi.CameraArgs.from_camera(self.vc)
-            key = ("cam", bytes(ca), self._scene_key, self.seed, self.flags)
-            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags), max(int(n_samples), 1), out)
+            key = ("cam", bytes(ca), self._scene_key, self.seed, self.flags, self.adaptive)
+            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags, adaptive=self.adaptive),
+                             max(int(n_samples), 1), out)
             return
         out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed,
                                             mode=capi.MODE_FLAT if flat else capi.MODE_PT, flags=self.flags)
         self.last_stats = self.ctx.stats()
+
+    def adaptive_counts(self):
+        """(counts[h, w], n_active) of the current accumulation (capi.Context.accum_counts)."""
+        return self.ctx.accum_counts()
 
     def close(self):
         self.ctx.close()
