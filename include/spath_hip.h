@@ -113,7 +113,7 @@ int  sphip_create(int device_id, sphip_t** out);
  *   A device may be listed more than once (several shards on one GPU: how a one-GPU box exercises this path).
  *   SPATH_HIP_GATHER=rccl|peer overrides the choice of exchange.
  * The host-pointer entry points (sphip_set_scene, sphip_render, sphip_render_camera, sphip_accum_begin, sphip_accum_step,
- * sphip_get_stats, sphip_description, sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
+ * sphip_accum_gbuffer, sphip_accum_denoise, sphip_get_stats, sphip_description, sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
 int  sphip_create_multi(const int* device_ids, int n_devices, sphip_t** out);
 int  sphip_device_count(const sphip_t* ctx);        /* devices behind ctx (1 for sphip_create) */
 void sphip_destroy(sphip_t* ctx);
@@ -268,6 +268,57 @@ int sphip_accum_begin_adaptive(sphip_t* ctx, const float* rays /* w*h*6 f32 or N
  * pixels (may be NULL).  A plain accumulation reports `total` for every pixel, all of them active.  Blocking; SPHIP_E_STATE
  * when no accumulation has been begun. */
 int sphip_accum_counts(sphip_t* ctx, uint32_t* out_counts /* w*h or NULL */, uint64_t* n_active_out /* or NULL */);
+
+/* ---- denoising: an edge-aware a-trous wavelet filter (Dammertz et al. 2010) with SVGF-style variance guidance, guided by a
+ * noise-free G-buffer of the primary hits.  A post-process: it leaves the scans, the sums and the raw
+ * image as they are.  Every operation is an f32 + - * / (IEEE division), a comparison or a select in the order below, so the
+ * output is reproducible bit for bit; max(0, x) means x > 0 ? x : 0.
+ *
+ * G-buffer: 32 B per pixel {f32 nx, ny, nz, dist; f32 ar, ag, ab; i32 mat}, from the pixel's primary ray (idx_source = -1) and
+ * the closest hit sphip_closest_hit_device returns for the same rays and flags (SPHIP_FLAG_ACCEL included).  Hit: n = the
+ * triangle's normal, negated when dot3(n, dir) > 0; dist = the hit distance; a = the triangle's reflectance; mat = the smallest
+ * triangle index whose 6 material floats are bitwise equal to the hit triangle's (derived once per scene).  Miss: n = 0,
+ * dist = 1e12f, a = 0, mat = -1.
+ *
+ * Filter: iterations i = 0 .. K-1 with step s = 2^i, each on an f32 {r, g, b, var} per pixel.  A miss pixel (mat_p = -1)
+ * passes through.  For any other pixel p the taps q = p + s * (dx, dy) are visited dy, then dx, over -2 .. 2; taps outside the
+ * image are skipped.  The centre tap has w = 9/64.  Any other tap with mat_q != mat_p is skipped; else
+ *     d  = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z;  wn = max(0, d), then normal_log2 times wn = wn * wn
+ *     dd = |dist_p - dist_q|;  zd = (sigma_depth * s) * dist_p;  wz = zd == 0 ? (dd == 0) : max(0, 1 - dd / zd)
+ *     l  = (r + g) + b of this iteration's input;  dl = l_p - l_q;  ld = (sigma_lum * sigma_lum) * var_p
+ *     wl = 1 without variance or when var_p = +inf;  else ld == 0 ? (dl == 0) : max(0, 1 - (dl * dl) / ld)
+ *     w  = (((h[dx] * h[dy]) * wn) * wz) * wl,  h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ * A tap counts only when ww = w * w > 0: W += w; C.rgb += w * c_q.rgb (per channel); V += ww * var_q (sums start at 0).
+ * Output of the iteration: rgb = C / W per channel, var = V / (W * W).  Final output: the rgb of the last iteration and its
+ * RGBA8 through vec3::clamp and scene::vec3_RGBA (as the render's).  K = 0: the input itself. */
+typedef struct {
+	uint32_t iterations;   /* K, 0..8 */
+	uint32_t normal_log2;  /* 0..8 */
+	float    sigma_depth;  /* > 0, finite */
+	float    sigma_lum;    /* > 0, finite */
+	uint32_t reserved[2];  /* must be 0 */
+} sphip_denoise;
+
+/* the calibrated defaults */
+void sphip_denoise_defaults(sphip_denoise* out);
+/* G-buffer of n_rays primary rays (device pointers, d_out_gbuf n_rays * 32 B); asynchronous like sphip_closest_hit_device, single-device
+ * contexts (SPHIP_E_STATE otherwise).  The first call after a scene change reads the materials back once (material classes). */
+int  sphip_gbuffer_device(sphip_t* ctx, const void* d_rays, size_t n_rays, int flags, void* d_out_gbuf, void* stream);
+/* The filter on a w*h image: d_mean w*h*3 f32, d_var w*h f32 or NULL (no luminance weight), d_gbuf from sphip_gbuffer_device of the
+ * image's rays; d_out_rgba w*h*4 u8, d_out_rgb w*h*3 f32 or NULL.  Asynchronous; single-device contexts (SPHIP_E_STATE otherwise). */
+int  sphip_denoise_device(sphip_t* ctx, const sphip_denoise* p, size_t w, size_t h, const void* d_mean, const void* d_var, const void* d_gbuf,
+                          void* d_out_rgba, void* d_out_rgb, void* stream);
+/* The current accumulation's G-buffer (host output, w*h*32 B), built with the accumulation's flags and cached until the next begin.
+ * Blocking; SPHIP_E_STATE with no accumulation or after a set_scene since the begin. */
+int  sphip_accum_gbuffer(sphip_t* ctx, void* out_gbuf);
+/* Denoises the current accumulation without altering it: the mean of every pixel (its sum times float(1.0 / count)) and, for an
+ * adaptive accumulation, the variance of that mean: per pixel, in double, with the rule's m and v, (float)max(0, v / n), +inf
+ * when n < 2.  A plain accumulation has no statistics and is filtered without wl.  Builds and caches the G-buffer on first use.
+ * Blocking; host outputs (out_rgb may be NULL).  sphip_get_stats then describes the call: the filter's kernels, plus the G-buffer
+ * scan (scans_executed = w*h) when the call built it.  SPHIP_E_STATE before the first step or after a set_scene since the begin.
+ * Multi-device contexts are accepted and give the single-device bytes: every device prepares its row tiles, the frame is
+ * filtered on the first device. */
+int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba, float* out_rgb /* or NULL */);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

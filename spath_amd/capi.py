@@ -33,6 +33,7 @@ SYMBOLS = (
     "sphip_kernel_available", "sphip_selftest_stage1", "sphip_build_info",
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
+    "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -56,6 +57,40 @@ class CameraArgs(C.Structure):
 class Adaptive(C.Structure):
     """sphip_adaptive: the convergence rule of an adaptive accumulation (include/spath_hip.h)."""
     _fields_ = [("rel_error", C.c_double), ("floor", C.c_double), ("min_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Denoise(C.Structure):
+    """sphip_denoise: parameters of the a-trous denoiser (include/spath_hip.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_log2", C.c_uint32), ("sigma_depth", C.c_float), ("sigma_lum", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def defaults(cls):
+        d = cls()
+        load().sphip_denoise_defaults(C.byref(d))
+        return d
+
+    @classmethod
+    def make(cls, params=None):
+        """None: the library's defaults; a Denoise as is; a dict overrides some of the defaults
+        (iterations, normal_log2, sigma_depth, sigma_lum)."""
+        if isinstance(params, cls):
+            return params
+        d = cls.defaults()
+        for k, v in (params or {}).items():
+            if k not in ("iterations", "normal_log2", "sigma_depth", "sigma_lum"):
+                raise ValueError(f"unknown denoise parameter {k!r}")
+            setattr(d, k, v)
+        return d
+
+    def as_dict(self):
+        return {"iterations": self.iterations, "normal_log2": self.normal_log2, "sigma_depth": self.sigma_depth, "sigma_lum": self.sigma_lum}
+
+
+def gbuffer_dtype():
+    """numpy dtype of one 32-byte G-buffer entry {nx, ny, nz, dist, ar, ag, ab, mat}."""
+    import numpy as np
+    return np.dtype([("n", "<f4", 3), ("dist", "<f4"), ("a", "<f4", 3), ("mat", "<i4")])
 
 
 class Stats(C.Structure):
@@ -134,6 +169,16 @@ def load():
     L.sphip_accum_begin_adaptive.argtypes = [vp, vp, C.POINTER(CameraArgs), sz, sz, C.c_uint64, C.c_int, C.POINTER(Adaptive)]
     L.sphip_accum_counts.restype = C.c_int
     L.sphip_accum_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.sphip_denoise_defaults.restype = None
+    L.sphip_denoise_defaults.argtypes = [C.POINTER(Denoise)]
+    L.sphip_gbuffer_device.restype = C.c_int
+    L.sphip_gbuffer_device.argtypes = [vp, vp, sz, C.c_int, vp, vp]
+    L.sphip_denoise_device.restype = C.c_int
+    L.sphip_denoise_device.argtypes = [vp, C.POINTER(Denoise), sz, sz, vp, vp, vp, vp, vp, vp]
+    L.sphip_accum_gbuffer.restype = C.c_int
+    L.sphip_accum_gbuffer.argtypes = [vp, vp]
+    L.sphip_accum_denoise.restype = C.c_int
+    L.sphip_accum_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -358,6 +403,37 @@ class Context:
         self._check(self._L.sphip_accum_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)) if w * h else None, C.byref(n_active)),
                     "sphip_accum_counts")
         return counts, n_active.value
+
+    # denoising -------------------------------------------------------------------------------
+    def gbuffer_device(self, d_rays: int, n_rays: int, d_out_gbuf: int, *, flags=0, stream: int = 0):
+        """G-buffer of n_rays primary rays into d_out_gbuf (n_rays * 32 B, see gbuffer_dtype()); asynchronous."""
+        self._check(self._L.sphip_gbuffer_device(self._h, d_rays, n_rays, flags, d_out_gbuf, stream or None), "sphip_gbuffer_device")
+
+    def denoise_device(self, w: int, h: int, d_mean: int, d_gbuf: int, d_out_rgba: int, *, d_var: int = 0, d_out_rgb: int = 0,
+                       params=None, stream: int = 0):
+        """The a-trous filter on device pointers (d_var 0: no luminance weight); params as for Denoise.make."""
+        p = Denoise.make(params)
+        self._check(self._L.sphip_denoise_device(self._h, C.byref(p), w, h, d_mean, d_var or None, d_gbuf, d_out_rgba, d_out_rgb or None,
+                                                 stream or None), "sphip_denoise_device")
+
+    def accum_gbuffer(self):
+        """-> the current accumulation's G-buffer, a structured array [w*h] of gbuffer_dtype()."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        out = np.zeros(w * h, dtype=gbuffer_dtype())
+        self._check(self._L.sphip_accum_gbuffer(self._h, out.ctypes.data if w * h else None), "sphip_accum_gbuffer")
+        return out
+
+    def accum_denoise(self, params=None, want_rgb=False):
+        """The current accumulation denoised (it is not altered) -> img, or (img, rgb) with want_rgb."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        p = Denoise.make(params)
+        out = np.zeros((w * h, 4), dtype=np.uint8)
+        rgb = np.zeros((w * h, 3), dtype=np.float32) if want_rgb else None
+        self._check(self._L.sphip_accum_denoise(self._h, C.byref(p), out.ctypes.data if w * h else None,
+                                                rgb.ctypes.data if want_rgb and w * h else None), "sphip_accum_denoise")
+        return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2)}
 

@@ -12,6 +12,7 @@
 #include "sp_bvh.h"
 #include "sp_bvh_build.h"
 #include "sp_adaptive.h"
+#include "sp_denoise.h"
 
 #include <hip/hip_runtime.h>
 
@@ -82,6 +83,12 @@ struct sphip_ctx {
 	uint32_t adp_nact = 0, adp_nact_rb = 0;       // adp_nact_rb: the step's readback, valid once the stream has drained
 	double adp_t = 0.0, adp_floor = 0.0;
 	uint32_t adp_min = 0;
+	// ---- denoising (sp_denoise.h): material classes of the scene's triangles (derived on first use), the closest hits of a
+	// G-buffer build, the accumulation's cached G-buffer, the filter's ping-pong buffers.  On a multi-device context the parent's
+	// buffers live on the first device, with the whole frame's rays gathered there for the G-buffer.
+	DevBuf dn_cls, dn_hit, dn_gbuf, dn_a, dn_b, dn_rays;
+	bool dn_cls_valid = false;                    // dropped by every set_scene
+	bool dn_gbuf_ok = false;                      // dropped by every accumulation begin
 };
 
 namespace {
@@ -944,6 +951,7 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the camera's %ux%u", w, h, cam->res_x, cam->res_y);
 	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
 	c->adp_on = false;
+	c->dn_gbuf_ok = false;
 	if (!c->kids.empty()) {
 		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
 		if (rc) return rc;
@@ -969,6 +977,212 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	c->acc_seed = seed; c->acc_flags = flags;
 	c->acc_total = 0;                              // the first step's sample_base: the sum buffer's contents are not read
 	return SPHIP_OK;
+}
+
+// =====================================================================================================================
+// Denoising (sp_denoise.h; include/spath_hip.h: sphip_denoise): a G-buffer of the primary hits and an edge-aware a-trous
+// filter, a post-process that leaves the scans, the sums and the raw image as they are.
+// =====================================================================================================================
+
+int check_denoise(sphip_ctx* c, const sphip_denoise* P) {
+	if (!P) return fail(c, SPHIP_E_INVALID, "null sphip_denoise");
+	if (P->iterations > 8 || P->normal_log2 > 8 || !std::isfinite(P->sigma_depth) || !(P->sigma_depth > 0.0f) ||
+	    !std::isfinite(P->sigma_lum) || !(P->sigma_lum > 0.0f) || P->reserved[0] || P->reserved[1])
+		return fail(c, SPHIP_E_INVALID, "bad sphip_denoise {iterations %u, normal_log2 %u, sigma_depth %g, sigma_lum %g, reserved %u %u}: "
+		            "iterations and normal_log2 in 0..8, sigmas finite and > 0, reserved 0", P->iterations, P->normal_log2,
+		            (double)P->sigma_depth, (double)P->sigma_lum, P->reserved[0], P->reserved[1]);
+	return SPHIP_OK;
+}
+
+// material class of every triangle: the smallest index whose 6 material floats are bitwise equal.  Derived on the host once per
+// scene (the materials are read back: the one wait on the stream this path has)
+int ensure_classes(sphip_ctx* c, hipStream_t st) {
+	if (c->dn_cls_valid) return SPHIP_OK;
+	const size_t n = c->n_tris;
+	std::vector<uint32_t> m(n * 6);
+	std::vector<int> cls(n);
+	HIP_TRY(c, hipMemcpyAsync(m.data(), c->mats.p, n * 24, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	// triangle indices sorted by (material bits, index): in each run of equal materials the first is the smallest index
+	std::vector<uint32_t> ord(n);
+	for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
+	std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+		const int d = std::memcmp(&m[(size_t)a * 6], &m[(size_t)b * 6], 24);
+		return d != 0 ? d < 0 : a < b;
+	});
+	for (size_t k = 0; k < n; ++k)
+		cls[ord[k]] = (k > 0 && std::memcmp(&m[(size_t)ord[k] * 6], &m[(size_t)ord[k - 1] * 6], 24) == 0) ? cls[ord[k - 1]] : (int)ord[k];
+	int rc;
+	if ((rc = ensure(c, c->dn_cls, n * 4))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->dn_cls.p, cls.data(), n * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));             // cls is a local
+	c->dn_cls_valid = true;
+	return SPHIP_OK;
+}
+
+// G-buffer of n rays on a single-device context: the closest hits of sphip_closest_hit_device (same launch, same flags), then
+// one entry per ray.  The stats describe both launches.
+int gbuffer_dev(sphip_ctx* c, const void* d_rays, size_t n, int flags, void* d_out, hipStream_t st) {
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "G-buffer requested before a scene was set");
+	if (!d_rays || !d_out) return fail(c, SPHIP_E_INVALID, "null ray or G-buffer pointer");
+	if (n == 0 || n > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n);
+	int rc;
+	if ((rc = ensure_classes(c, st)) || (rc = ensure(c, c->dn_hit, n * 8))) return rc;
+	int* idx = (int*)c->dn_hit.p;
+	float* dist = (float*)((char*)c->dn_hit.p + n * 4);
+	if ((rc = launch_render(c, d_rays, n, nullptr, 0, 1, 0, kModeHits, flags, idx, dist, st))) return rc;
+	hipLaunchKernelGGL(sp::k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
+	                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
+	c->stats.n_launches += 1;
+	return SPHIP_OK;
+}
+
+// the K iterations on the w*h float4 image in buffer a (written by the caller), ping-ponging with b (both of at least w*h*16 B,
+// on c's device); the last one writes the outputs.  Adds the launches to *launches.
+int atrous_run(sphip_ctx* c, const DevBuf& a, const DevBuf& b, const sphip_denoise* P, size_t w, size_t h, bool use_var, const void* gbuf,
+               uint32_t* rgba, float* rgb, hipStream_t st, uint32_t* launches) {
+	// SPATH_HIP_ATROUS=l2|lds picks the kernel for A/B runs (both give the same bytes); the default is the faster one measured
+	// 
+	const char* kenv = std::getenv("SPATH_HIP_ATROUS");
+	const bool lds = !(kenv && std::strcmp(kenv, "l2") == 0);
+	for (uint32_t i = 0; i < P->iterations; ++i) {
+		const bool last = i + 1 == P->iterations;
+		sp::AtrousArgs A{};
+		A.in = (const float4*)(i % 2 ? b.p : a.p);
+		A.out = (float4*)(i % 2 ? a.p : b.p);
+		A.gbuf = (const float4*)gbuf;
+		A.w = (uint32_t)w; A.h = (uint32_t)h;
+		A.s = 1 << i;
+		A.zs = P->sigma_depth * (float)A.s;
+		A.sl2 = P->sigma_lum * P->sigma_lum;
+		A.normal_log2 = P->normal_log2;
+		A.use_var = use_var ? 1u : 0u;
+		A.rgba = last ? rgba : nullptr;
+		A.rgb = last ? rgb : nullptr;
+		if (lds) {           // 16 x 16 blocks of each of the s x s sub-lattices
+			const size_t su = (w + (size_t)A.s - 1) / (size_t)A.s, sv = (h + (size_t)A.s - 1) / (size_t)A.s;
+			const dim3 grid((unsigned)((su + 15) / 16 * (size_t)A.s), (unsigned)((sv + 15) / 16 * (size_t)A.s));
+			hipLaunchKernelGGL(sp::k_atrous_lds, grid, dim3(256), 0, st, A);
+		} else {
+			const dim3 grid((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
+			hipLaunchKernelGGL(sp::k_atrous, grid, dim3(256), 0, st, A);
+		}
+	}
+	HIP_TRY(c, hipGetLastError());
+	*launches += P->iterations;
+	return SPHIP_OK;
+}
+
+// start of a call's kernel time when no G-buffer is built: 0 scans
+int dn_clock_start(sphip_ctx* c, hipStream_t st) {
+	int rc;
+	if ((rc = ensure(c, c->counter, 16 * sizeof(unsigned long long)))) return rc;
+	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
+	HIP_TRY(c, hipEventRecord(c->ev_k0, st));
+	c->stats.n_launches = 0;
+	return SPHIP_OK;
+}
+
+// sphip_accum_denoise on a single-device context (k == c), or on the first device of a multi-device one with the frame's
+// mean/variance (image order) already in c->dn_a.  d_rays: the frame's rays (for a G-buffer build).  Leaves the outputs in
+// k->rgba / k->accum.
+int accum_denoise_dev(sphip_ctx* c, sphip_ctx* k, const sphip_denoise* P, const void* d_rays, bool have4, bool use_var, bool want_rgb,
+                      hipStream_t st) {
+	const size_t w = c->acc_w, h = c->acc_h, n = w * h;
+	int rc;
+	if ((rc = ensure(c, c->dn_gbuf, n * 32)) || (rc = ensure(c, c->dn_a, n * 16)) || (rc = ensure(c, c->dn_b, n * 16)) ||
+	    (rc = ensure(k, k->rgba, n * 4)) || (want_rgb && (rc = ensure(k, k->accum, n * 12)))) return rc;
+	const bool build = !c->dn_gbuf_ok;
+	if (build) {
+		if ((rc = gbuffer_dev(k, d_rays, n, c->acc_flags, c->dn_gbuf.p, st))) return rc;
+	} else if ((rc = dn_clock_start(k, st))) return rc;
+	uint32_t* rgba = (uint32_t*)k->rgba.p;
+	float* rgb = want_rgb ? (float*)k->accum.p : nullptr;
+	const bool k0 = P->iterations == 0;
+	if (!have4) {
+		hipLaunchKernelGGL(sp::k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->acc_sum.p,
+		                   c->adp_on ? (const uint32_t*)c->adp_cnt.p : nullptr, (uint32_t)c->acc_total, c->adp_on ? (const double*)c->adp_s12.p : nullptr,
+		                   (uint32_t)n, (float4*)c->dn_a.p, k0 ? rgba : nullptr, k0 ? rgb : nullptr);
+		k->stats.n_launches += 1;
+	} else if (k0) {
+		hipLaunchKernelGGL(sp::k_dn_emit4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4*)c->dn_a.p, (uint32_t)n, rgba, rgb);
+		k->stats.n_launches += 1;
+	}
+	HIP_TRY(k, hipGetLastError());
+	if ((rc = atrous_run(k, c->dn_a, c->dn_b, P, w, h, use_var, c->dn_gbuf.p, rgba, rgb, st, &k->stats.n_launches))) return rc;
+	HIP_TRY(k, hipEventRecord(k->ev_k1, st));
+	if (build) c->dn_gbuf_ok = true;
+	k->have_render = true;
+	k->last_stream = st;
+	k->stats.n_pixels = n;
+	k->stats.n_tris = k->n_tris;
+	k->stats.kernel_variant = (uint32_t)pick_variant(c->acc_flags, k->n_tris);
+	return SPHIP_OK;
+}
+
+// sphip_accum_denoise on a multi-device context: every device turns its shard's state into {mean, var}; the frame is put together in
+// image order on the host (and, for a G-buffer build, the rays with it), uploaded to the first device and filtered there -- the
+// per-pixel values do not depend on the sharding, so the bytes are those of a single-device context
+int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba, float* out_rgb) {
+	const int g = (int)c->kids.size();
+	const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
+	const size_t npix = plan.npix;
+	const bool need_rays = !c->dn_gbuf_ok;
+	sphip_ctx* root = c->kids[0];
+	auto body = [&]() -> int {
+		std::vector<float4> img4(npix), loc;
+		std::vector<float> rays(need_rays ? npix * 6 : 0), lrays;
+		int rc;
+		for (int r = 0; r < g; ++r) {
+			sphip_ctx* k = c->kids[(size_t)r];
+			k->have_render = false;
+			const size_t n = plan.n_rays(r);
+			if (n == 0) continue;
+			HIP_TRY(c, hipSetDevice(k->device));
+			hipStream_t st = k->own_stream;
+			if ((rc = ensure(k, k->dn_a, n * 16))) return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+			hipLaunchKernelGGL(sp::k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)k->acc_sum.p,
+			                   c->adp_on ? (const uint32_t*)k->adp_cnt.p : nullptr, (uint32_t)c->acc_total, c->adp_on ? (const double*)k->adp_s12.p : nullptr,
+			                   (uint32_t)n, (float4*)k->dn_a.p, (uint32_t*)nullptr, (float*)nullptr);
+			HIP_TRY(c, hipGetLastError());
+			loc.resize(n);
+			HIP_TRY(c, hipMemcpyAsync(loc.data(), k->dn_a.p, n * 16, hipMemcpyDeviceToHost, st));
+			if (need_rays) { lrays.resize(n * 6); HIP_TRY(c, hipMemcpyAsync(lrays.data(), k->acc_rays.p, n * 24, hipMemcpyDeviceToHost, st)); }
+			HIP_TRY(c, hipStreamSynchronize(st));
+			const sphip_shard sh = plan.shard(r);
+			for (size_t i = 0; i < n; ++i) {
+				const size_t p = sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px;
+				img4[p] = loc[i];
+				if (need_rays) std::memcpy(&rays[p * 6], &lrays[i * 6], 24);
+			}
+		}
+		HIP_TRY(c, hipSetDevice(root->device));
+		hipStream_t rs = root->own_stream;
+		if ((rc = ensure(c, c->dn_a, npix * 16)) || (need_rays && (rc = ensure(c, c->dn_rays, npix * 24)))) return rc;
+		HIP_TRY(c, hipEventRecord(c->ev_g0, rs));
+		HIP_TRY(c, hipMemcpyAsync(c->dn_a.p, img4.data(), npix * 16, hipMemcpyHostToDevice, rs));
+		if (need_rays) HIP_TRY(c, hipMemcpyAsync(c->dn_rays.p, rays.data(), npix * 24, hipMemcpyHostToDevice, rs));
+		if ((rc = accum_denoise_dev(c, root, P, c->dn_rays.p, true, c->adp_on, out_rgb != nullptr, rs)))
+			return fail(c, rc, "device %d: %s", root->device, root->err.c_str());
+		HIP_TRY(c, hipEventRecord(c->ev_g1, rs));
+		HIP_TRY(c, hipMemcpyAsync(out_rgba, root->rgba.p, npix * 4, hipMemcpyDeviceToHost, rs));
+		if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, root->accum.p, npix * 12, hipMemcpyDeviceToHost, rs));
+		HIP_TRY(c, hipStreamSynchronize(rs));          // img4 and rays are locals
+		root->timed_upload = root->timed_download = false;
+		c->have_render = true;
+		c->stats.n_pixels = npix;
+		c->stats.n_tris = c->n_tris;
+		return SPHIP_OK;
+	};
+	const int rc = body();
+	if (rc) {
+		for (sphip_ctx* k : c->kids)
+			if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
+		(void)hipGetLastError();
+	}
+	return rc;
 }
 
 } // namespace
@@ -1113,7 +1327,7 @@ void sphip_destroy(sphip_t* c) {
 		for (void* comm : c->comms) if (comm) (void)g_rccl.destroy(comm);
 		(void)hipSetDevice(c->kids[0]->device);
 		(void)hipDeviceSynchronize();
-		DevBuf* mb[4] = { &c->gath, &c->gath_acc, &c->img, &c->img_acc };
+		DevBuf* mb[9] = { &c->gath, &c->gath_acc, &c->img, &c->img_acc, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays };
 		for (auto b : mb) if (b->p) (void)hipFree(b->p);
 		if (c->ev_g0) (void)hipEventDestroy(c->ev_g0);
 		if (c->ev_g1) (void)hipEventDestroy(c->ev_g1);
@@ -1127,7 +1341,7 @@ void sphip_destroy(sphip_t* c) {
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
 	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
 	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
-	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst };
+	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
@@ -1143,6 +1357,7 @@ int sphip_set_scene(sphip_t* c, const float* tris, const float* mats, size_t n_t
 	if (!c) return SPHIP_E_INVALID;
 	if (!tris || !mats || n_tris == 0 || n_tris > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad scene arguments (n_tris=%zu)", n_tris);
 	c->acc_stale = c->acc_on;                      // the running sum belongs to the old scene
+	c->dn_cls_valid = false;
 	if (!c->kids.empty()) return multi_set_scene(c, tris, mats, n_tris);
 	HIP_TRY(c, hipSetDevice(c->device));
 	int rc;
@@ -1160,6 +1375,7 @@ int sphip_set_scene_device(sphip_t* c, const void* d_tris, const void* d_mats, s
 	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
 	if (!d_tris || !d_mats || n_tris == 0 || n_tris > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad scene arguments (n_tris=%zu)", n_tris);
 	c->acc_stale = c->acc_on;
+	c->dn_cls_valid = false;
 	HIP_TRY(c, hipSetDevice(c->device));
 	hipStream_t st = (hipStream_t)stream;
 	int rc;
@@ -1422,6 +1638,120 @@ int sphip_selftest_stage1(sphip_t* c, const float* rays, size_t n_rays, uint32_t
 	if (d_order) (void)hipFree(d_order);
 	if (d_tri) (void)hipFree(d_tri);
 	if (e != hipSuccess) return fail(c, SPHIP_E_DEVICE, "stage-1 selftest failed: %s", hipGetErrorString(e));
+	return SPHIP_OK;
+}
+
+void sphip_denoise_defaults(sphip_denoise* out) {
+	if (!out) return;
+	std::memset(out, 0, sizeof *out);
+	out->iterations = 5;           // calibrated with tools/denoise_time.py
+	out->normal_log2 = 7;
+	out->sigma_depth = 0.1f;
+	out->sigma_lum = 4.0f;
+}
+
+int sphip_gbuffer_device(sphip_t* c, const void* d_rays, size_t n_rays, int flags, void* d_out_gbuf, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	HIP_TRY(c, hipSetDevice(c->device));
+	c->timed_upload = c->timed_download = false;
+	return gbuffer_dev(c, d_rays, n_rays, flags, d_out_gbuf, (hipStream_t)stream);
+}
+
+int sphip_denoise_device(sphip_t* c, const sphip_denoise* P, size_t w, size_t h, const void* d_mean, const void* d_var, const void* d_gbuf,
+                         void* d_out_rgba, void* d_out_rgb, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if ((rc = check_denoise(c, P))) return rc;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (!d_mean || !d_gbuf || !d_out_rgba) return fail(c, SPHIP_E_INVALID, "null mean, G-buffer or output pointer");
+	if (w == 0 || h == 0 || w >= (1u << 30) || h >= (1u << 30) || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad image size (w=%zu h=%zu)", w, h);
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = (hipStream_t)stream;
+	const size_t n = w * h;
+	if ((rc = ensure(c, c->dn_a, n * 16)) || (rc = ensure(c, c->dn_b, n * 16)) || (rc = dn_clock_start(c, st))) return rc;
+	const bool k0 = P->iterations == 0;
+	hipLaunchKernelGGL(sp::k_dn_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_mean, (const float*)d_var, (uint32_t)n,
+	                   k0 ? (float4*)nullptr : (float4*)c->dn_a.p, k0 ? (uint32_t*)d_out_rgba : nullptr, k0 ? (float*)d_out_rgb : nullptr);
+	HIP_TRY(c, hipGetLastError());
+	c->stats.n_launches = 1;
+	if ((rc = atrous_run(c, c->dn_a, c->dn_b, P, w, h, d_var != nullptr, d_gbuf, (uint32_t*)d_out_rgba, (float*)d_out_rgb, st, &c->stats.n_launches))) return rc;
+	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
+	c->timed_upload = c->timed_download = false;
+	c->have_render = true;
+	c->last_stream = st;
+	c->stats.n_pixels = n;
+	c->stats.n_tris = c->n_tris;
+	return SPHIP_OK;
+}
+
+int sphip_accum_gbuffer(sphip_t* c, void* out_gbuf) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!out_gbuf) return fail(c, SPHIP_E_INVALID, "null G-buffer output");
+	if (!c->acc_on) return fail(c, SPHIP_E_STATE, "sphip_accum_gbuffer called with no accumulation begun");
+	if (c->acc_stale) return fail(c, SPHIP_E_STATE, "the scene changed since sphip_accum_begin: begin a new accumulation");
+	const size_t n = c->acc_w * c->acc_h;
+	if (!c->kids.empty()) {
+		// the whole frame's rays on the first device, as the denoiser builds it there
+		const int g = (int)c->kids.size();
+		const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
+		std::vector<float> rays(n * 6), lrays;
+		for (int r = 0; r < g; ++r) {
+			sphip_ctx* k = c->kids[(size_t)r];
+			const size_t nr = plan.n_rays(r);
+			if (nr == 0) continue;
+			HIP_TRY(c, hipSetDevice(k->device));
+			lrays.resize(nr * 6);
+			HIP_TRY(c, hipMemcpyAsync(lrays.data(), k->acc_rays.p, nr * 24, hipMemcpyDeviceToHost, k->own_stream));
+			HIP_TRY(c, hipStreamSynchronize(k->own_stream));
+			const sphip_shard sh = plan.shard(r);
+			for (size_t i = 0; i < nr; ++i) std::memcpy(&rays[(sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px) * 6], &lrays[i * 6], 24);
+		}
+		sphip_ctx* root = c->kids[0];
+		HIP_TRY(c, hipSetDevice(root->device));
+		int rc;
+		if ((rc = ensure(c, c->dn_rays, n * 24)) || (rc = ensure(c, c->dn_gbuf, n * 32))) return rc;
+		HIP_TRY(c, hipMemcpyAsync(c->dn_rays.p, rays.data(), n * 24, hipMemcpyHostToDevice, root->own_stream));
+		if (!c->dn_gbuf_ok && (rc = gbuffer_dev(root, c->dn_rays.p, n, c->acc_flags, c->dn_gbuf.p, root->own_stream))) {
+			(void)hipStreamSynchronize(root->own_stream);
+			return fail(c, rc, "device %d: %s", root->device, root->err.c_str());
+		}
+		c->dn_gbuf_ok = true;
+		HIP_TRY(c, hipMemcpyAsync(out_gbuf, c->dn_gbuf.p, n * 32, hipMemcpyDeviceToHost, root->own_stream));
+		HIP_TRY(c, hipStreamSynchronize(root->own_stream));
+		return SPHIP_OK;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	int rc;
+	if ((rc = ensure(c, c->dn_gbuf, n * 32))) return rc;
+	if (!c->dn_gbuf_ok && (rc = gbuffer_dev(c, c->acc_rays.p, n, c->acc_flags, c->dn_gbuf.p, st))) { (void)hipStreamSynchronize(st); return rc; }
+	c->dn_gbuf_ok = true;
+	HIP_TRY(c, hipMemcpyAsync(out_gbuf, c->dn_gbuf.p, n * 32, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	return SPHIP_OK;
+}
+
+int sphip_accum_denoise(sphip_t* c, const sphip_denoise* P, uint8_t* out_rgba, float* out_rgb) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if ((rc = check_denoise(c, P))) return rc;
+	if (!out_rgba) return fail(c, SPHIP_E_INVALID, "null output pointer");
+	if (!c->acc_on || c->acc_total == 0) return fail(c, SPHIP_E_STATE, "sphip_accum_denoise needs an accumulation with at least one step");
+	if (c->acc_stale) return fail(c, SPHIP_E_STATE, "the scene changed since sphip_accum_begin: begin a new accumulation");
+	if (c->acc_w >= (1u << 30) || c->acc_h >= (1u << 30)) return fail(c, SPHIP_E_INVALID, "image too wide or tall for the filter");
+	if (!c->kids.empty()) return multi_accum_denoise(c, P, out_rgba, out_rgb);
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	const size_t n = c->acc_w * c->acc_h;
+	rc = accum_denoise_dev(c, c, P, c->acc_rays.p, false, c->adp_on, out_rgb != nullptr, st);
+	if (!rc) {
+		if (hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+		    (out_rgb && hipMemcpyAsync(out_rgb, c->accum.p, n * 12, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+		    hipStreamSynchronize(st) != hipSuccess) rc = fail(c, SPHIP_E_DEVICE, "denoise readback failed: %s", hipGetErrorString(hipGetLastError()));
+	}
+	if (rc) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return rc; }
+	c->timed_upload = c->timed_download = false;
 	return SPHIP_OK;
 }
 

@@ -43,13 +43,19 @@ struct hip_r : public basic_renderer {
 	int acc_flags;
 	// adaptive sampling (set_adaptive) of the progressive mode: adp.rel_error < 0 is off
 	sphip_adaptive adp;
+	// denoising (set_denoise) of the progressive mode; raw: the last step's image before the filter
+	bool dn_on;
+	sphip_denoise dn;
+	scene::bitmap raw;
+	bool have_raw;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
-	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0) {
+	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
+		std::memset(&dn, 0, sizeof dn);
 		std::memset(&adp, 0, sizeof adp);
 		adp.rel_error = -1.0;
 		if (sphip_create_multi(ids, n_ids, &ctx) != SPHIP_OK)
@@ -98,8 +104,14 @@ struct hip_r : public basic_renderer {
 	}
 
 	void begin(const float* rays, const sphip_camera* cam, size_t w, size_t h) {
-		if (adp.rel_error < 0.0) check(sphip_accum_begin(ctx, rays, cam, w, h, seed, flags), "accum_begin");
-		else check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &adp), "accum_begin_adaptive");
+		have_raw = false;
+		if (adp.rel_error >= 0.0) check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &adp), "accum_begin_adaptive");
+		else if (dn_on) {
+			sphip_adaptive never;                 // the variance for the filter, the image of a plain accumulation
+			std::memset(&never, 0, sizeof never);
+			never.min_samples = 0xffffffffu;
+			check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &never), "accum_begin_adaptive");
+		} else check(sphip_accum_begin(ctx, rays, cam, w, h, seed, flags), "accum_begin");
 	}
 
 	// one progressive step of n_samples (the accumulation begun or continued by the caller) into out
@@ -108,6 +120,11 @@ struct hip_r : public basic_renderer {
 		check(sphip_accum_step(ctx, n_samples, (uint8_t*)out.values.data(), 0, 0), "accum_step");
 		acc_live = true;
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
+		if (dn_on) {
+			raw = out;
+			have_raw = true;
+			check(sphip_accum_denoise(ctx, &dn, (uint8_t*)out.values.data(), 0), "accum_denoise");
+		}
 	}
 
 	void frame_own_viewport(const geom::triangle* tris, const scene::material* mats, const size_t n_tris, const size_t n_samples,
@@ -217,6 +234,20 @@ namespace hip_renderer {
 			p->adp.reserved = 0;
 			p->acc_live = false;
 		}
+	}
+
+	void set_denoise(scene::renderer* r, const sphip_denoise* p) {
+		if (hip_r* q = dynamic_cast<hip_r*>(r)) {
+			if (q->dn_on != (p != 0)) q->acc_live = false;       // the rule the accumulation begins with changes
+			q->dn_on = p != 0;
+			if (p) q->dn = *p;
+			q->have_raw = false;
+		}
+	}
+
+	const scene::bitmap* raw_bitmap(scene::renderer* r) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		return p && p->have_raw ? &p->raw : 0;
 	}
 
 	bool accum_counts(scene::renderer* r, uint32_t* counts, unsigned long long* n_active) {

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "spath_iface.h"
+#include "spath_hip.h"
 
 #include <stdint.h>
 
@@ -32,6 +33,13 @@ namespace hip_renderer {
 	// keeping exactly the image of its own sample count.  t < 0 turns it off (the default).  Switching on or off, or changing the
 	// rule, begins anew.
 	extern void set_adaptive(scene::renderer* r, double t, double floor, unsigned min_samples);
+	// Denoising of the progressive mode (include/spath_hip.h: sphip_accum_denoise): with p != NULL the bitmap of every progressive
+	// step is the accumulation denoised with *p (copied), and the raw image stays reachable through raw_bitmap.  Without an
+	// adaptive rule the accumulation is begun with one that never stops a pixel (min_samples = UINT32_MAX), so that the filter has
+	// the variance; the raw image is bit-identical to a plain accumulation's.  NULL turns it off (the default).
+	extern void set_denoise(scene::renderer* r, const sphip_denoise* p);
+	// the raw (not denoised) image of the last progressive step with denoising on; NULL if r is not a hip renderer or there is none
+	extern const scene::bitmap* raw_bitmap(scene::renderer* r);
 	// per-pixel sample counts (w*h, image order) and active pixels of the current accumulation; false if r is not a hip renderer
 	// or no accumulation is live
 	extern bool accum_counts(scene::renderer* r, uint32_t* counts, unsigned long long* n_active);

@@ -5,12 +5,16 @@
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
 //             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--out image.ppm|image.rgba] [--frames n]
-//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]]
+//             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
+//              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
 //   a viewer refines a still view; prints every step, and the final image is byte-identical to the one rendered in one go
 // --adaptive T[,FLOOR[,MIN]]: with --progressive, stop converged pixels after each step (include/spath_hip.h: sphip_adaptive;
 //   relative error T, FLOOR default 0.1, MIN default 8 samples); every pixel's image is that of its own sample count.
 //   --counts-out: the per-pixel sample counts of the last frame as a 16-bit binary PGM (clamped to 65535)
+// --denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]]: with --progressive, the image of every step is the accumulation denoised
+//   (include/spath_hip.h: sphip_accum_denoise; the library's defaults for what is left out); --raw-out FILE: the last raw image, in
+//   the format --out would use for that name
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
@@ -136,7 +140,10 @@ int main(int argc, char** argv) {
 		size_t progressive = 0;
 		double adp_t = -1.0, adp_floor = 0.1;                        // --adaptive defaults: FLOOR 0.1, MIN 8
 		unsigned adp_min = 8;
-		std::string counts_path;
+		std::string counts_path, raw_path;
+		bool denoise = false;
+		sphip_denoise dn;
+		sphip_denoise_defaults(&dn);
 		unsigned long long seed = 1;
 		std::vector<std::pair<char, geom::vec3> > moves;
 		for (int i = 1; i < argc; ++i) {
@@ -162,6 +169,21 @@ int main(int argc, char** argv) {
 				if (*e) throw std::runtime_error("bad --adaptive value (T[,FLOOR[,MIN]])");
 			}
 			else if (k == "--counts-out") { need(1); counts_path = argv[++i]; }
+			else if (k == "--denoise") {
+				denoise = true;
+				if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {     // optional ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]
+					const char* p = argv[++i];
+					char* e = 0;
+					const unsigned long it = std::strtoul(p, &e, 10);
+					if (e == p || it > 8) throw std::runtime_error("bad --denoise value (ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]], ITER 0..8)");
+					dn.iterations = (uint32_t)it;
+					if (*e == ',') { p = e + 1; dn.sigma_lum = std::strtof(p, &e); if (e == p) throw std::runtime_error("bad --denoise SIGMA_L"); }
+					if (*e == ',') { p = e + 1; dn.sigma_depth = std::strtof(p, &e); if (e == p) throw std::runtime_error("bad --denoise SIGMA_Z"); }
+					if (*e == ',') { p = e + 1; dn.normal_log2 = (uint32_t)std::strtoul(p, &e, 10); if (e == p) throw std::runtime_error("bad --denoise NLOG2"); }
+					if (*e) throw std::runtime_error("bad --denoise value (ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]])");
+				}
+			}
+			else if (k == "--raw-out") { need(1); raw_path = argv[++i]; }
 			else if (k == "--frames") { need(1); frames = std::atoi(argv[++i]); }
 			else if (k == "--out") { need(1); out_path = argv[++i]; }
 			else if (k == "--device-viewport") device_viewport = true;
@@ -172,6 +194,8 @@ int main(int argc, char** argv) {
 			else if (k == "--focal") { need(1); moves.push_back(std::make_pair('f', geom::vec3(std::atof(argv[++i]), 0, 0))); }
 			else throw std::runtime_error("unknown argument " + k);
 		}
+		if (denoise && !(progressive && mode == "pt")) throw std::runtime_error("--denoise needs --progressive n and --mode pt");
+		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
 		std::vector<geom::triangle> tris;
 		std::vector<scene::material> mats;
 		if (scene_arg == "default") default_scene(tris, mats);
@@ -184,6 +208,7 @@ int main(int argc, char** argv) {
 		if (adp_t >= 0.0 && !(progressive && mode == "pt")) throw std::runtime_error("--adaptive needs --progressive n and --mode pt");
 		if (!counts_path.empty() && !(progressive && mode == "pt")) throw std::runtime_error("--counts-out needs --progressive n and --mode pt");
 		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);
+		hip_renderer::set_denoise(r.get(), denoise ? &dn : 0);
 		std::printf("Current renderer: %s [%d device(s)]\n", r->get_description(), hip_renderer::device_count(r.get()));     // main.cpp:30-32
 		for (size_t k = 0; k < moves.size(); ++k) {
 			if (moves[k].first == 'm') r->set_delta_mov(moves[k].second);
@@ -222,18 +247,24 @@ int main(int argc, char** argv) {
 			std::printf("Done (%.3fs) frame %d: %dx%d, %zu spp, %zu triangles, kernel %.3f ms, %llu scans, %.1f Mray/s nominal\n", s, f, w, h,
 			            spp, tris.size(), kms, scans, mode == "pt" ? (double)w * h * spp * 5 / s / 1e6 : (double)w * h / s / 1e6);
 		}
-		if (!out_path.empty()) {
-			FILE* o = std::fopen(out_path.c_str(), "wb");
-			if (!o) throw std::runtime_error("cannot write " + out_path);
-			if (out_path.size() > 4 && out_path.substr(out_path.size() - 4) == ".ppm") {
-				std::fprintf(o, "P6\n%zu %zu\n255\n", bmp.res_x, bmp.res_y);
-				for (size_t i = 0; i < bmp.values.size(); ++i) std::fwrite(&bmp.values[i], 1, 3, o);   // row 0 = top, as stored
-			} else if (out_path.size() > 4 && out_path.substr(out_path.size() - 4) == ".png") {
-				write_png(o, bmp);
+		auto write_image = [](const std::string& path, const scene::bitmap& b) {
+			FILE* o = std::fopen(path.c_str(), "wb");
+			if (!o) throw std::runtime_error("cannot write " + path);
+			if (path.size() > 4 && path.substr(path.size() - 4) == ".ppm") {
+				std::fprintf(o, "P6\n%zu %zu\n255\n", b.res_x, b.res_y);
+				for (size_t i = 0; i < b.values.size(); ++i) std::fwrite(&b.values[i], 1, 3, o);   // row 0 = top, as stored
+			} else if (path.size() > 4 && path.substr(path.size() - 4) == ".png") {
+				write_png(o, b);
 			} else {
-				std::fwrite(bmp.values.data(), sizeof(scene::RGBA), bmp.values.size(), o);
+				std::fwrite(b.values.data(), sizeof(scene::RGBA), b.values.size(), o);
 			}
 			std::fclose(o);
+		};
+		if (!out_path.empty()) write_image(out_path, bmp);
+		if (!raw_path.empty()) {
+			const scene::bitmap* raw = hip_renderer::raw_bitmap(r.get());
+			if (!raw) throw std::runtime_error("no raw image to write");
+			write_image(raw_path, *raw);
 		}
 		if (!counts_path.empty()) {
 			std::vector<uint32_t> counts(bmp.values.size());

@@ -19,6 +19,9 @@ from . import capi
 from .view import Camera
 
 
+NEVER_STOP = (0.0, 0.0, 0xFFFFFFFF)    # an adaptive rule that never stops a pixel (min_samples = UINT32_MAX)
+
+
 class Bitmap:
     """scene::bitmap (reference src/scene.h:41-45): res_x, res_y, values[res_x*res_y] RGBA8."""
 
@@ -71,7 +74,8 @@ class BasicRenderer(Renderer):
 class HipRenderer(BasicRenderer):
     """The MI355X backend behind the reference's plugin interface."""
 
-    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0, progressive: bool = False, adaptive=None):
+    def __init__(self, x: int, y: int, device: int = 0, seed: int = 1, flags: int = 0, progressive: bool = False, adaptive=None,
+                 denoise=False):
         super().__init__(x, y)
         self.ctx = capi.Context(device)      # raises like cl_r/vk_r constructors do on init failure
         self.seed = seed
@@ -85,6 +89,14 @@ class HipRenderer(BasicRenderer):
         if adaptive is not None and not progressive:
             raise ValueError("adaptive sampling needs progressive=True")
         self.adaptive = tuple(adaptive) if adaptive is not None else None
+        # denoise=True (the library's defaults) or a dict of capi.Denoise fields, with progressive=True: the bitmap of every
+        # progressive step is the accumulation denoised (capi.Context.accum_denoise); the raw image stays in raw_bitmap.  Without
+        # an adaptive rule the accumulation is begun with one that never stops a pixel, so that the filter has the variance; its
+        # raw image is bit-identical to a plain accumulation's.
+        if denoise is not False and denoise is not None and not progressive:
+            raise ValueError("denoising needs progressive=True")
+        self.denoise = None if denoise is False or denoise is None else capi.Denoise.make(None if denoise is True else denoise)
+        self.raw_bitmap = Bitmap()
         self._scene_key = None
         self._accum_key = None
         self.last_stats = None
@@ -101,7 +113,14 @@ class HipRenderer(BasicRenderer):
             self.ctx.set_scene(tris, mats)
             self._scene_key = key
 
+    def _begin_rule(self):
+        if self.adaptive is None and self.denoise is not None:
+            return NEVER_STOP
+        return self.adaptive
+
     def _accum_step(self, key, begin, n_samples, out):
+        if self.denoise is not None:
+            key = key + ("denoise",)                           # the rule it begins with; the parameters apply to any step
         if key != self._accum_key:
             self._accum_key = None
             begin()
@@ -112,6 +131,9 @@ class HipRenderer(BasicRenderer):
             self._accum_key = None                             # a failed step ends the accumulation in the library too
             raise
         self.last_stats = self.ctx.stats()
+        if self.denoise is not None:
+            self.raw_bitmap.res_x, self.raw_bitmap.res_y, self.raw_bitmap.values = out.res_x, out.res_y, out.values
+            out.values = self.ctx.accum_denoise(self.denoise)
 
     def _render(self, vp, tris, mats, n_tris, n_samples, out, mode):
         self._upload_scene(tris, mats, n_tris)
@@ -120,7 +142,7 @@ class HipRenderer(BasicRenderer):
             rays = np.ascontiguousarray(vp.rays, dtype=np.float32).reshape(-1, 6)
             key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, self.flags, self.adaptive)
             self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=self.flags,
-                                                               adaptive=self.adaptive),
+                                                               adaptive=self._begin_rule()),
                              n_samples, out)
             return
         out.values = self.ctx.render(vp.rays, vp.res_x, vp.res_y, n_samples, seed=self.seed, mode=mode, flags=self.flags)
@@ -140,7 +162,7 @@ class HipRenderer(BasicRenderer):
         if self.progressive and not flat:
             ca = capi.CameraArgs.from_camera(self.vc)
             key = ("cam", bytes(ca), self._scene_key, self.seed, self.flags, self.adaptive)
-            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags, adaptive=self.adaptive),
+            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags, adaptive=self._begin_rule()),
                              max(int(n_samples), 1), out)
             return
         out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed,
