@@ -60,11 +60,13 @@ enum {
 	                                   and a second kernel adds them up per pixel in sample order (src/cpu_renderer.cpp:74-76),
 	                                   so the image is bit-identical whatever the number of chunks.  1 = never split. */
 	SPHIP_FLAG_CHUNKS_MASK = 0xff0000,
-	SPHIP_FLAG_ACCEL = 0x200         /* OPT-IN acceleration structure (linear BVH).  Changes the work
+	SPHIP_FLAG_ACCEL = 0x200,        /* OPT-IN acceleration structure (linear BVH).  Changes the work
 	                                   definition: the reference tests every triangle (README.md:23).  Same strict triangle
 	                                   test and tie rule, so every geometric hit is reproduced bit for bit; what it cannot
 	                                   reproduce are the reference's rounding-noise accepts on rays almost coplanar with a
 	                                   far-away triangle.  Never used by bench.py's headline figure. */
+	SPHIP_FLAG_NEE = 0x400           /* OPT-IN next-event estimation (light sampling with shadow rays) for SPHIP_MODE_PT; see
+	                                   "next-event estimation" below.  Changes the estimator, not its expectation. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -319,6 +321,39 @@ int  sphip_accum_gbuffer(sphip_t* ctx, void* out_gbuf);
  * Multi-device contexts are accepted and give the single-device bytes: every device prepares its row tiles, the frame is
  * filtered on the first device. */
 int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba, float* out_rgb /* or NULL */);
+
+/* ---- next-event estimation (SPHIP_FLAG_NEE): at each of the first four surface hits of a path, one light
+ * sample and one shadow ray.  Valid for SPHIP_MODE_PT on every render and accumulation entry point and with the shipped variants 1,
+ * 2, 8 (SPHIP_FLAG_ACCEL), 15 and 16 (SPHIP_E_INVALID with a variant of -DSP_ALL_VARIANTS builds); flat and hit queries ignore it.
+ * Every operation below is f32 unless marked double; dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
+ *
+ * Paths: the same closest hits and BSDF directions as without the flag (philox_uniforms(seed, pixel, sample, depth)), but at most
+ * four hits: the fifth would carry nothing.  Radiance, unwound from the last hit (rec = 0 beyond it):
+ *     rec_d = (e_d + L_d) + (((brdf_d * rec_{d+1}) * ct_d) * (1/p)),   e_0 = the first hit's emittance, e_d = 0 for d >= 1
+ * (brdf_d = reflectance * (1/pi) and ct_d as without the flag; per channel, in this order).
+ *
+ * Light table (once per scene, on the first NEE render after a set_scene; a negative or non-finite emittance component anywhere in
+ * the scene makes every NEE render fail with SPHIP_E_INVALID): the triangles with Esum = ((double)Er + Eg) + Eb > 0 and
+ * w = A * Esum > 0, in ascending index, A = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz) in double of c = e1 x e2, e1 = (double)v1 -
+ * (double)v0, e2 = (double)v2 - (double)v0; cdf = their running double sum, W = its last entry, ipdf = (float)(W / Esum).
+ * No entry: L_d = 0 everywhere.
+ *
+ * Light sample at hit d (point x = o + dir * dist of the hit, triangle src, normal n turned against dir as the path uses it):
+ *     (r3, r4) = philox_uniforms(seed, pixel, sample, 8 + d);  r5 = the first draw of philox_uniforms(seed, pixel, sample, 16 + d)
+ *     e = the first entry with cdf > r5 * W (double), the last entry if none;  i = its triangle
+ *     a = (float)sqrt(r3) (double sqrt);  b = (float)r4;  y = (v0 + e1 * (a * (1 - b))) + e2 * (a * b)   (e1 = v1 - v0, e2 = v2 - v0)
+ *     w = y - x;  dist2 = dot3(w, w);  dist = sqrtf(dist2);  wd = w / dist (per component)
+ *     cos_x = dot3(wd, n);  cos_y = |dot3(wd, n_i)|   (n_i: triangle i's normal; emitters are two-sided);  sxz = sqrtf(wd.x * wd.x + wd.z * wd.z)
+ *     L_d = 0 without a shadow ray when i == src, !(dist2 > 0), !(cos_x > 0), !(cos_y > 0) or !(sxz > 0);  else the shadow ray
+ *     (x, wd) skips src with tmax = dist * (1 - 2^-10), and L_d = 0 when it is occluded, else
+ *     L_d = (reflectance_src * (1/pi)) * (Le_i * ((((cos_x * cos_y) / dist2) * ipdf_e) * ((float)(2/pi) / sxz)))   (per channel)
+ * The last factor is 2 pi times the density per solid angle of the reference's BSDF directions (geom.h:164-177 draws the elevation
+ * above the world y plane uniformly in angle: 1 / (pi^2 sqrt(x^2 + z^2))), so that NEE estimates the plain estimator's image.
+ * Occluded: some triangle other than src gives 0 < d < tmax under the reference's strict triangle test, i.e. the closest hit that
+ * skips src (sphip_closest_hit_device) lies below tmax.  Every scan variant agrees on it bit for bit.
+ * sphip_stats.scans_executed counts the path scans plus the shadow rays traced (one each, whether the scan left early or not).
+ * Progressive and adaptive accumulation (the luminance proxy of the NEE sample), primary-hit reuse, sample chunks, denoising,
+ * shards and multi-device contexts work as without the flag, bit for bit. */
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

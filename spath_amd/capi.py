@@ -16,6 +16,7 @@ MODE_PT = 1
 KERNEL_AUTO = 0
 FLAG_PRIMARY_REUSE = 0x100
 FLAG_ACCEL = 0x200          # opt-in linear BVH; not the brute-force path
+FLAG_NEE = 0x400            # opt-in next-event estimation: light sampling with shadow rays
 
 
 def flag_chunks(n: int) -> int:

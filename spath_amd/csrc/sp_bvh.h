@@ -44,9 +44,11 @@ SP_DEV bool box_hit(const float4 a, const float4 b, f3 o, f3 inv, float tbest, f
 	return (a.x <= a.w) && (tmin <= tmax * 1.00001f + 1e-30f);
 }
 
-SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int& best_i, uint32_t* steps_out = nullptr, uint32_t* leaves_out = nullptr) {
+// tmax < kMaxDist, any_hit: the shadow form -- only hits with d < tmax count, and the walk stops at the first one
+SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int& best_i, uint32_t* steps_out = nullptr, uint32_t* leaves_out = nullptr,
+                     float tmax = kMaxDist, bool any_hit = false) {
 	uint32_t n_steps = 0, n_leaves = 0;
-	float bd = kMaxDist;
+	float bd = tmax;
 	int bi = -1;
 	const f3 inv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
 	for (uint32_t j = 4u * B.n_leaves, e = 4u * B.n_leaves + B.meta[8]; j < e; ++j) {       // wave-uniform loop: scalar loads
@@ -57,6 +59,7 @@ SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int
 		bd = take ? d : bd;
 		bi = take ? orig : bi;
 	}
+	if (any_hit && bi >= 0) { best_d = bd; best_i = bi; return; }
 	uint32_t node = 1, trail = 0;
 	// Every step either descends one level or retires one pending sibling, so the walk visits each node at most once;
 	// the explicit bound is a belt-and-braces exit condition (a wave that never finishes can take the whole GPU down).
@@ -90,6 +93,7 @@ SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int
 				bd = take ? d : bd;
 				bi = take ? orig : bi;
 			}
+			if (any_hit && bi >= 0) break;
 		}
 		if (!descended) {
 			// pop: climb to the deepest level whose far child is still pending and go to that sibling -- unless the best
@@ -145,6 +149,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		return;
 	}
 	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_kernels.h AdaptArgs)
+	constexpr bool nee = IsNee<Acc...>::value;         // next-event estimation (sp_kernels.h NeeArgs)
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
@@ -158,7 +163,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 			accum = mk3(q.sum[(size_t)pk * 3 + 0], q.sum[(size_t)pk * 3 + 1], q.sum[(size_t)pk * 3 + 2]);
 			s1 = q.s12[(size_t)pk * 2]; s2 = q.s12[(size_t)pk * 2 + 1];
 		}
-	} else if constexpr (sizeof...(Acc) > 0) {
+	} else if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		s0 = q.sample_base;
 		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
@@ -167,10 +172,11 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		f3 o = po, dir = pdir;
 		int src = -1, hidx[5];
 		float hcos[5];
+		f3 hL[kNeeDepths];
 		int nh = 0;
 		bool alive = valid;
 #pragma unroll
-		for (int depth = 0; depth < 5; ++depth) {
+		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {
 			if (alive) {
 				float bd; int bi;
 				scan_bvh(B, o, dir, src, bd, bi);
@@ -179,6 +185,17 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					const float* tn = a.tris + (size_t)bi * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);
+					if constexpr (nee) {
+						f3 wd, Lc; float tm;
+						const f3 x = add3(o, scale3(dir, bd));
+						hL[depth] = mk3(0.0f, 0.0f, 0.0f);
+						if (nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, x, n, bi, wd, tm, Lc)) {
+							float sd; int si;
+							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
+							my_scans++;
+							if (si < 0) hL[depth] = Lc;
+						}
+					}
 					double r1, r2;
 					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
 					const f3 nd = rand_unit_vec(n, r1, r2);
@@ -199,7 +216,9 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 			if (depth < nh) {
 				const float* m = a.mats + (size_t)hidx[depth] * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
-				rec = add3(mk3(m[3], m[4], m[5]), scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
+				f3 e = mk3(m[3], m[4], m[5]);
+				if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
+				rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
 			}
 		}
 		accum = add3(accum, rec);
@@ -214,7 +233,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		wave_add_scans(a.scans, my_scans);
 		return;
 	}
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		if (valid) { q.sum[(size_t)k * 3 + 0] = accum.x; q.sum[(size_t)k * 3 + 1] = accum.y; q.sum[(size_t)k * 3 + 2] = accum.z; }
 	}

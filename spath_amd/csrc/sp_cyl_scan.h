@@ -427,8 +427,10 @@ SP_DEV void scan_cyl(const KArgs& a, const CylStream cs, float rv, const RaySlot
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kCylCap = 64u * 12u;      // list entries per wave and pass (16 bits each): 12 per lane on average
 
-template <int R>
-SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R]) {
+// Bounded / shadow form (tmax, shadow): as scan_cylm's (sp_cylm_scan.h), per slot.
+template <int R, bool BOUNDED = false>
+SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R],
+                      const float* tmax = nullptr, bool shadow = false) {
 	__shared__ float4 sm[2 * kCylTileQ];
 	__shared__ unsigned short lst[4 * kCylCap];               // per wave: (donor lane << 7) | group within the tile
 	__shared__ uint32_t lcnt[4];                              // per wave: entries listed in the current pass
@@ -443,7 +445,10 @@ SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlo
 	cyl_setup<R>(rv, s, f);
 	const unsigned long long kNone = ((unsigned long long)__float_as_uint(kMaxDist) << 32) | 0xffffffffull;
 #pragma unroll
-	for (int r = 0; r < R; ++r) cell[r * 256 + tid] = kNone;
+	for (int r = 0; r < R; ++r) {
+		cell[r * 256 + tid] = tmax ? (((unsigned long long)__float_as_uint(tmax[r]) << 32) | 0xffffffffull) : kNone;
+		if (BOUNDED && shadow && !s.act[r]) cell[r * 256 + tid] = 0ull;     // no shadow ray: done from the start
+	}
 
 	const uint32_t total_tiles = cs.hdr[6];
 	uint32_t cls = 0;
@@ -483,6 +488,14 @@ SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlo
 			const uint32_t done = g - g0;                             // bits appended; left-align (wave-uniform shift)
 #pragma unroll
 			for (int r = 0; r < R; ++r) word[r][wi] = done == 0u ? 0u : (wv[r] << (32u - done));
+		}
+		if (BOUNDED && shadow) {                                      // any-hit: occluded rays list nothing more
+#pragma unroll
+			for (int r = 0; r < R; ++r) {
+				const bool fin = (uint32_t)cell[r * 256 + tid] != 0xffffffffu;
+#pragma unroll
+				for (int wi = 0; wi < kW; ++wi) word[r][wi] = fin ? 0u : word[r][wi];
+			}
 		}
 		// the next tile streams in while the survivors are resolved
 		if (gt + 1u < total_tiles) cyl_tile_dma(cs.rec + (size_t)(gt + 1u) * kCylTileQ, sm + ((gt + 1u) & 1u) * kCylTileQ, tid, wbase);
@@ -528,6 +541,9 @@ SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlo
 					const int src = __shfl(s.src[r], L, 64);
 					const float Pa = __shfl(f.Pa[r], L, 64), Pb = __shfl(f.Pb[r], L, 64), Pc = __shfl(f.Pc[r], L, 64);
 					const float D = __shfl(f.D[r], L, 64), Dq = __shfl(f.Dq[r], L, 64);
+					float tmx = kMaxDist;                                         // the donor's bound (bounded form)
+					if constexpr (BOUNDED) tmx = __shfl(tmax ? tmax[r] : kMaxDist, L, 64);
+
 					// (a ray whose filter is off has a zero moment and Dq = +inf: it survives whatever x comes out, so -dir serves for all)
 					// the group's four records and their x again: which of the four survive
 					uint32_t cand = 0;
@@ -554,7 +570,7 @@ SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlo
 							const float4 x0 = a.scan[3 * (size_t)idx + 0], x1 = a.scan[3 * (size_t)idx + 1], x2 = a.scan[3 * (size_t)idx + 2];
 							const float d = ray_tri_strict(mk3(ox, oy, oz), mk3(dx, dy, dz), mk3(x0.x, x0.y, x0.z), mk3(x0.w, x1.x, x1.y), mk3(x1.z, x1.w, x2.x));
 							// cpu_renderer.cpp:44: cur_d > 0 && cur_d < d, d starting at MAX_VALUE_DIST; ties -> lowest index: the key's low word
-							if ((d > 0.0f) && (d < kMaxDist) && (idx != src))
+							if ((d > 0.0f) && (d < tmx) && (idx != src))
 								atomicMin(&cell[r * 256 + (int)wbase + L], ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(uint32_t)idx);
 						}
 					}
@@ -564,6 +580,14 @@ SP_DEV void scan_cylw(const KArgs& a, const CylStream cs, float rv, const RaySlo
 #ifdef SP_FILTER_STATS
 		if (lane == 0) atomicAdd(a.scans + 3, 1ull);
 #endif
+		if (BOUNDED && shadow) {
+			// the next tile's LDS-DMA has landed before anyone leaves; the barrier decides whether an active ray is still unoccluded
+			__asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			bool open = false;
+#pragma unroll
+			for (int r = 0; r < R; ++r) open |= (uint32_t)cell[r * 256 + tid] == 0xffffffffu;
+			if (!__syncthreads_or(open ? 1 : 0)) break;
+		} else
 		__syncthreads();                        // next tile landed (vmcnt(0) in the fence) and this one is free again
 	}
 #pragma unroll

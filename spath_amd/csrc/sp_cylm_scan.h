@@ -554,7 +554,17 @@ SP_DEV uint32_t wave_incl_scan(uint32_t x) {
 //       full batches of 64 (and on what is left at the end of the scan): every lane busy in every exact turn, where one turn
 //       per round and its stragglers' turns used half of them (profiles/filter_stats.json).
 // Results meet in the 64-bit LDS atomicMin on (d, index) keys, so no order matters (sp_cyl_scan.h, scan_cylw).
-SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlots<1>& s, float (&bd)[1], int (&bi)[1]) {
+//
+// Bounded (shadow) form, tmax != nullptr: a hit counts only when d < tmax[0] -- the lane's key cell starts at (tmax bits, -1) in place of
+// kMaxDist and the exact test's bound is the lane's tmax -- so the cell ends as (tmax, -1) iff no triangle other than src lies in
+// (0, tmax).  With `shadow` (block-uniform; NEE) the scan is an ANY-hit query: a ray whose cell holds a hit, or an
+// inactive one, lists no more groups, and the workgroup leaves the stream at a tile end once no active ray is unoccluded.  The
+// hit it reports is then just some occluder.
+// BOUNDED = false is the plain scan, unchanged; the NEE kernels run both their path and their shadow scans through BOUNDED = true
+// (one instantiation: one set of LDS buffers).
+template <bool BOUNDED = false>
+SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlots<1>& s, float (&bd)[1], int (&bi)[1],
+                      const float* tmax = nullptr, bool shadow = false) {
 	// Two tile buffers as two separate LDS objects, the tile loop unrolled over them: the LDS-DMA of the next tile is issued BEFORE
 	// stage 1 of the current one, and hipcc, which orders every LDS read it cannot tell apart from an outstanding LDS-DMA behind
 	// s_waitcnt vmcnt(0), can tell these apart -- the transfer has the whole tile to land in, not just stage 2
@@ -574,8 +584,9 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 	CylRay<1>& f = R.f;
 
 	// ---- the big class first: every lane, its own ray, records through the scalar cache (wave-uniform addresses)
+	const float tm = tmax ? tmax[0] : kMaxDist;
 	{
-		float bd0 = kMaxDist; int bi0 = -1;
+		float bd0 = tm; int bi0 = -1;
 		typedef float f4v __attribute__((ext_vector_type(4)));
 		typedef __attribute__((address_space(4))) const f4v* cptr_t;             // constant address space: a uniform load is a scalar load
 		const cptr_t big = (cptr_t)(uintptr_t)cs.big;
@@ -589,6 +600,7 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 			bi0 = take ? idx : bi0;
 		}
 		cell[tid] = ((unsigned long long)__float_as_uint(bd0) << 32) | (unsigned long long)(uint32_t)bi0;     // bi0 = -1: the "no hit" key
+		if (BOUNDED && shadow && !s.act[0]) cell[tid] = 0ull;        // no shadow ray: done from the start
 	}
 	R.build(0u, lane);
 
@@ -610,9 +622,10 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 		const float ox = wave_fetch(la, s.o[0].x), oy = wave_fetch(la, s.o[0].y), oz = wave_fetch(la, s.o[0].z);
 		const float dx = wave_fetch(la, s.dir[0].x), dy = wave_fetch(la, s.dir[0].y), dz = wave_fetch(la, s.dir[0].z);
 		const int src = wave_fetch(la, s.src[0]);
+		const float tmx = tmax ? wave_fetch(la, tm) : kMaxDist;
 		const float d = ray_tri_strict(mk3(ox, oy, oz), mk3(dx, dy, dz), mk3(x0.x, x0.y, x0.z), mk3(x0.w, x1.x, x1.y), mk3(x1.z, x1.w, x2.x));
 		// cpu_renderer.cpp:44: cur_d > 0 && cur_d < d, d starting at MAX_VALUE_DIST; ties -> lowest index: the key's low word
-		if (ok && (d > 0.0f) && (d < kMaxDist) && (idx != src))
+		if (ok && (d > 0.0f) && (d < tmx) && (idx != src))
 			atomicMin(&cell[wbase + (la >> 2)], ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(uint32_t)idx);
 		q2n -= n;
 #ifdef SP_FILTER_STATS
@@ -666,6 +679,16 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 #ifdef SP_DBG_ALLBITS
 			word[w][0] = word[w][1] = done == 0u ? 0u : (0xffffffffu << (32u - done));
 #endif
+		}
+		if (BOUNDED && shadow) {
+			// any-hit: the rays already known to be occluded (or without a shadow ray) list nothing more.  Word rb of a lane holds
+			// bits of ray (lane & 31) + 32 rb of the wave, whose cell only this wave's atomics touch
+#pragma unroll
+			for (int rb = 0; rb < 2; ++rb) {
+				const bool fin = (uint32_t)cell[wbase + (lane & 31u) + 32u * (uint32_t)rb] != 0xffffffffu;
+#pragma unroll
+				for (int w = 0; w < (int)kMWords; ++w) word[w][rb] = fin ? 0u : word[w][rb];
+			}
 		}
 		SP_PH_STAMP(ph_t1); SP_PH_ADD(ph_s1, ph_t0, ph_t1);
 #ifdef SP_CYLM_LATE_DMA
@@ -787,14 +810,30 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 		if (lane == 0) atomicAdd(a.scans + 3, 1ull);
 #endif
 		SP_PH_STAMP(ph_t0); SP_PH_ADD(ph_list, ph_t1, ph_t0);
+		if (BOUNDED && shadow) {
+			// the LDS-DMA of the next tile has landed before anyone leaves (no transfer stays in flight into a buffer the next scan
+			// reuses), then the same barrier decides whether any active ray is still unoccluded
+			__asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			if (!__syncthreads_or((uint32_t)cell[tid] == 0xffffffffu ? 1 : 0)) return false;
+		} else
 		__syncthreads();                        // next tile landed (vmcnt(0) in the fence) and this one is free again
 		SP_PH_STAMP(ph_t1); SP_PH_ADD(ph_bar, ph_t0, ph_t1);
+		return true;
 	};
-	for (uint32_t gt = 0; gt < total_tiles; gt += 2u) {
-		tile_body(std::integral_constant<int, 0>{}, gt);
-		if (gt + 1u < total_tiles) tile_body(std::integral_constant<int, 1>{}, gt + 1u);
+	if constexpr (BOUNDED) {
+		bool all_done = false;                  // shadow form: every ray of the workgroup is resolved, the stream was left early
+		for (uint32_t gt = 0; gt < total_tiles; gt += 2u) {
+			if (!tile_body(std::integral_constant<int, 0>{}, gt)) { all_done = true; break; }
+			if (gt + 1u < total_tiles && !tile_body(std::integral_constant<int, 1>{}, gt + 1u)) { all_done = true; break; }
+		}
+		if (q2n && !all_done) exact_batch(q2n); // (q2n < 64 here)
+	} else {
+		for (uint32_t gt = 0; gt < total_tiles; gt += 2u) {
+			tile_body(std::integral_constant<int, 0>{}, gt);
+			if (gt + 1u < total_tiles) tile_body(std::integral_constant<int, 1>{}, gt + 1u);
+		}
+		if (q2n) exact_batch(q2n);              // (q2n < 64 here)
 	}
-	if (q2n) exact_batch(q2n);                  // (q2n < 64 here)
 #ifdef SP_PHASE_TIMERS
 	if (lane == 0) {
 		atomicAdd(a.scans + 8, ph_s1); atomicAdd(a.scans + 9, ph_list); atomicAdd(a.scans + 10, ph_retest); atomicAdd(a.scans + 11, ph_exact);

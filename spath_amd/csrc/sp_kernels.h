@@ -59,9 +59,37 @@ struct AdaptArgs : AccumArgs {
 	double* s12;               // n_local * 2
 	double* wst;               // 2 * n_work (two-stage kernels only)
 };
+// next-event estimation (SPHIP_FLAG_NEE): the scene's light table, built on the host once per scene.
+// Emitter e of the table is triangle tri[e]; cdf is the running double sum of the weights A * Esum; ipdf = (float)(W / Esum).
+// It rides as the LAST element of the trailing pack: k_pt<V, NeeArgs>, k_pt_filter<R, S, SCAN, AccumArgs, NeeArgs>, ...  L: the
+// two-stage kernels park the direct light of depth d there, L[(d * 3 + c) * n_work + slot] (12 B per depth and slot).
+struct NeeArgs {
+	const double* cdf;         // n ascending
+	const int*    tri;         // n emitter triangle indices, ascending
+	const float*  ipdf;        // n
+	uint32_t n;                // emitters of positive weight (0: no direct light)
+	double W;                  // cdf[n - 1]
+	float* L;                  // two-stage kernels only
+};
+constexpr int kNeeDepths = 4;                                    // light samples at hits 0..3; the 5th hit would carry nothing
+constexpr float kShadowMargin = 1.0f - 0x1p-10f;                  // tmax = dist * (1 - 2^-10)
+constexpr float kTwoOverPi = (float)(2.0 / kPi);                  // 2 pi x the reference's direction density (nee_light)
+
 template <typename... Acc> struct IsAdapt { static constexpr bool value = false; };
 template <> struct IsAdapt<AdaptArgs> { static constexpr bool value = true; };
+template <> struct IsAdapt<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
+template <typename... Acc> struct IsNee { static constexpr bool value = false; };
+template <> struct IsNee<NeeArgs> { static constexpr bool value = true; };
+template <> struct IsNee<AccumArgs, NeeArgs> { static constexpr bool value = true; };
+template <> struct IsNee<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
+// a running sum rides in the pack (progressive or adaptive)
+template <typename... Acc> struct HasAccum { static constexpr bool value = sizeof...(Acc) > (IsNee<Acc...>::value ? 1u : 0u); };
 SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p) { return p; }
+SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p, const NeeArgs&) { return p; }
+SP_DEV const AccumArgs& accum_args(const AccumArgs& p, const NeeArgs&) { return p; }
+SP_DEV const NeeArgs& nee_args(const NeeArgs& n) { return n; }
+SP_DEV const NeeArgs& nee_args(const AccumArgs&, const NeeArgs& n) { return n; }
+SP_DEV const NeeArgs& nee_args(const AdaptArgs&, const NeeArgs& n) { return n; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
 template <typename... Acc>
 SP_DEV uint32_t local_px(uint32_t k, const Acc&... acc_args) {
@@ -81,7 +109,7 @@ __global__ void __launch_bounds__(256) k_resolve(const KArgs a, const Acc... acc
 	const uint32_t pk = local_px(k, acc_args...);             // where the pixel's running sum lives
 	float ax = 0.0f, ay = 0.0f, az = 0.0f;
 	double s1 = 0.0, s2 = 0.0;
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		if (q.sample_base) { ax = q.sum[(size_t)pk * 3 + 0]; ay = q.sum[(size_t)pk * 3 + 1]; az = q.sum[(size_t)pk * 3 + 2]; }
 		if constexpr (adapt) if (q.sample_base) { s1 = adapt_args(acc_args...).s12[(size_t)pk * 2]; s2 = adapt_args(acc_args...).s12[(size_t)pk * 2 + 1]; }
@@ -94,7 +122,7 @@ __global__ void __launch_bounds__(256) k_resolve(const KArgs a, const Acc... acc
 		az = az + rz;
 		if constexpr (adapt) { const double y = lum_proxy(rx, ry, rz); s1 = s1 + y; s2 = s2 + y * y; }
 	}
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		q.sum[(size_t)pk * 3 + 0] = ax; q.sum[(size_t)pk * 3 + 1] = ay; q.sum[(size_t)pk * 3 + 2] = az;
 	}
@@ -221,12 +249,57 @@ SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
 }
 
+// ---- next-event estimation: one light sample at the hit x of a path (include/spath_hip.h).
+// n: the hit triangle's normal as the path uses it (turned against the incoming ray); src: the hit triangle.  Returns whether a
+// shadow ray (x, wd) with the bound tmax is to be traced, and then L = the direct light it carries when nothing occludes it.
+SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_t sample, int depth, f3 x, f3 n, int src,
+                      f3& wd, float& tmax, f3& L) {
+	if (ne.n == 0) return false;
+	double r3, r4, r5, r6;
+	philox_uniforms(a.seed, pixel, sample, 8u + (uint32_t)depth, &r3, &r4);
+	philox_uniforms(a.seed, pixel, sample, 16u + (uint32_t)depth, &r5, &r6);
+	// the first emitter whose cdf exceeds r5 W, the last one when rounding leaves none
+	const double t = r5 * ne.W;
+	uint32_t lo = 0, hi = ne.n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (ne.cdf[mid] > t) hi = mid; else lo = mid + 1u;
+	}
+	const int li = ne.tri[lo];
+	if (li == src) return false;
+	const float* tv = a.tris + (size_t)li * 12;
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);
+	const float ua = (float)__builtin_sqrt(r3), ub = (float)r4;
+	const f3 y = add3(add3(v0, scale3(e1, ua * (1.0f - ub))), scale3(e2, ua * ub));
+	const f3 w = sub3(y, x);
+	const float dist2 = dot3(w, w);
+	if (!(dist2 > 0.0f)) return false;
+	const float dist = __builtin_sqrtf(dist2);
+	wd = mk3(w.x / dist, w.y / dist, w.z / dist);
+	const float cos_x = dot3(wd, n);
+	const float cos_y = fabsf(dot3(wd, mk3(tv[9], tv[10], tv[11])));      // emitters are two-sided
+	// the reference's direction sampler (rand_unit_vec, geom.h:164-177) draws the elevation from the world y plane uniformly in ANGLE:
+	// density q = 1 / (pi^2 sqrt(x^2 + z^2)) per solid angle, while the path weight assumes 1/p = 2 pi.  The plain estimator's
+	// expectation therefore carries 2 pi q(w) per bounce; the light sample carries the same factor, 2 / (pi sxz), so that both
+	// estimate the same image
+	const float sxz = __builtin_sqrtf(wd.x * wd.x + wd.z * wd.z);
+	if (!(cos_x > 0.0f) || !(cos_y > 0.0f) || !(sxz > 0.0f)) return false;
+	tmax = dist * kShadowMargin;
+	const float* me = a.mats + (size_t)li * 6;
+	const float* ms = a.mats + (size_t)src * 6;
+	const float g = (((cos_x * cos_y) / dist2) * ne.ipdf[lo]) * (kTwoOverPi / sxz);
+	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
+	return true;
+}
+
 // ---- closest-hit scan, variant "rpl_sload": ray per lane, triangle index wave-uniform so the
 // records arrive through the scalar data path (s_load_dwordx4) and every VALU op reads them as
 // SGPR operands.  Semantics of cpu_renderer.cpp:36-49: ascending index, strict '<', skip idx_source.
+// tmax < kMaxDist: the bounded (shadow) form of the same scan -- only hits with d < tmax count (sp_cylm_scan.h, scan_cylm)
 SP_DEV void scan_rpl_sload(const float4* __restrict__ scan, uint32_t n_tris, f3 o, f3 dir, int src,
-                           float& best_d, int& best_i) {
-	float bd = kMaxDist;
+                           float& best_d, int& best_i, float tmax = kMaxDist) {
+	float bd = tmax;
 	int bi = -1;
 	for (uint32_t j = 0; j < n_tris; ++j) {
 		const float4 q0 = scan[3 * j + 0], q1 = scan[3 * j + 1], q2 = scan[3 * j + 2];
@@ -250,7 +323,7 @@ constexpr int kTileQ = kTile * 3;               // float4 per tile
 static_assert(kTileQ % 256 == 0, "tile must split evenly over the 256 threads");
 
 SP_DEV void scan_rpl_lds(const float4* __restrict__ scan, uint32_t n_tris, f3 o, f3 dir, int src,
-                         float& best_d, int& best_i) {
+                         float& best_d, int& best_i, float tmax = kMaxDist) {
 	__shared__ float4 sm[2 * kTileQ];
 	static_assert(kTileQ == 3 * 256, "three float4 per thread per tile");
 	const uint32_t tid = threadIdx.x;
@@ -259,7 +332,7 @@ SP_DEV void scan_rpl_lds(const float4* __restrict__ scan, uint32_t n_tris, f3 o,
 	__syncthreads();                            // readers of the previous scan are done with sm
 	sm[tid] = p0; sm[256 + tid] = p1; sm[512 + tid] = p2;
 	__syncthreads();
-	float bd = kMaxDist;
+	float bd = tmax;
 	int bi = -1;
 	for (uint32_t t = 0; t < ntiles; ++t) {
 		const float4* cur = sm + (t & 1u) * kTileQ;
@@ -289,9 +362,9 @@ SP_DEV void scan_rpl_lds(const float4* __restrict__ scan, uint32_t n_tris, f3 o,
 
 // VARIANT 1 = rpl_sload, 2 = rpl_lds.  Every variant must be called block-uniformly.
 template <int VARIANT>
-SP_DEV void closest_hit(const KArgs& a, f3 o, f3 dir, int src, float& best_d, int& best_i) {
-	if (VARIANT == 2) scan_rpl_lds(a.scan, a.n_tris, o, dir, src, best_d, best_i);
-	else scan_rpl_sload(a.scan, a.n_tris, o, dir, src, best_d, best_i);
+SP_DEV void closest_hit(const KArgs& a, f3 o, f3 dir, int src, float& best_d, int& best_i, float tmax = kMaxDist) {
+	if (VARIANT == 2) scan_rpl_lds(a.scan, a.n_tris, o, dir, src, best_d, best_i, tmax);
+	else scan_rpl_sload(a.scan, a.n_tris, o, dir, src, best_d, best_i, tmax);
 }
 
 SP_DEV void wave_add_scans(unsigned long long* ctr, uint32_t mine) {
@@ -346,6 +419,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	const float* r = a.rays + (size_t)kk * 6;
 	const f3 po = mk3(r[0], r[1], r[2]), pdir = mk3(r[3], r[4], r[5]);
 	constexpr bool adapt = IsAdapt<Acc...>::value;
+	constexpr bool nee = IsNee<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = (a.flags & 0x100u) != 0;
@@ -365,7 +439,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			accum = mk3(q.sum[(size_t)pk * 3 + 0], q.sum[(size_t)pk * 3 + 1], q.sum[(size_t)pk * 3 + 2]);
 			s1 = q.s12[(size_t)pk * 2]; s2 = q.s12[(size_t)pk * 2 + 1];
 		}
-	} else if constexpr (sizeof...(Acc) > 0) {
+	} else if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		s0 = q.sample_base;
 		if (s0 && valid) accum = mk3(q.sum[(size_t)k * 3 + 0], q.sum[(size_t)k * 3 + 1], q.sum[(size_t)k * 3 + 2]);
@@ -376,17 +450,22 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		int idx0 = -1, idx1 = -1, idx2 = -1, idx3 = -1, idx4 = -1;
 		float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f;
 		bool alive = valid;
+		f3 L0 = mk3(0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0, L3 = L0;   // NEE: direct light sampled at hits 0..3
 #pragma unroll 1
-		for (int depth = 0; depth < 5; ++depth) {                // :33 depth >= 5 -> black
+		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {   // :33 depth >= 5 -> black (NEE: the 5th hit carries nothing)
 			if (!__syncthreads_or(alive ? 1 : 0)) break;   // block-uniform: the LDS scan has barriers
 			float bd; int bi;
 			if (depth == 0 && reuse) { bd = pd; bi = pi; }
 			else { closest_hit<VARIANT>(a, o, dir, src, bd, bi); my_scans += alive ? 1u : 0u; }
 			const bool hit = alive && (bi >= 0);                  // :51 miss -> black
+			bool sh = false;                                      // NEE: this lane traces a shadow ray
+			f3 wd = dir, Lc = mk3(0.0f, 0.0f, 0.0f);
+			float tm = kMaxDist;
 			if (hit) {
 				const float* tn = a.tris + (size_t)bi * 12 + 9;
 				f3 n = mk3(tn[0], tn[1], tn[2]);                  // :55
 				if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);    // :56-57
+				if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
 				double r1, r2;
 				philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
 				const f3 nd = rand_unit_vec(n, r1, r2);           // :58
@@ -401,6 +480,17 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				else { idx4 = bi; c4 = ct; }
 			}
 			alive = hit;
+			if constexpr (nee) {
+				// the shadow rays of the block: (x, wd), skipping the hit triangle, bounded by tmax; any hit occludes
+				if (__syncthreads_or(sh ? 1 : 0)) {
+					float sd; int si;
+					closest_hit<VARIANT>(a, o, wd, src, sd, si, tm);
+					my_scans += sh ? 1u : 0u;
+					sh = sh && si < 0;
+				}
+				const f3 Ld = sh ? Lc : mk3(0.0f, 0.0f, 0.0f);
+				if (depth == 0) L0 = Ld; else if (depth == 1) L1 = Ld; else if (depth == 2) L2 = Ld; else L3 = Ld;
+			}
 		}
 		// unwind: rec(depth) = E + (((BRDF * rec(depth+1)) * cos) * (1/p)), rec beyond the last hit = 0
 		f3 rec = mk3(0.0f, 0.0f, 0.0f);
@@ -411,7 +501,11 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			if (id >= 0) {
 				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                     // :63
-				const f3 e = mk3(m[3], m[4], m[5]);
+				f3 e = mk3(m[3], m[4], m[5]);
+				if constexpr (nee) {                                                        // (e_0 or 0) + L_d
+					if (depth > 0) e = mk3(0.0f, 0.0f, 0.0f);
+					e = add3(e, depth == 0 ? L0 : depth == 1 ? L1 : depth == 2 ? L2 : L3);
+				}
 				rec = add3(e, scale3(scale3(mul3(brdf, rec), ct), kInvP));                 // :67
 			}
 		}
@@ -427,7 +521,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		wave_add_scans(a.scans, my_scans);
 		return;
 	}
-	if constexpr (sizeof...(Acc) > 0) {
+	if constexpr (HasAccum<Acc...>::value) {
 		const AccumArgs& q = accum_args(acc_args...);
 		if (valid) { q.sum[(size_t)k * 3 + 0] = accum.x; q.sum[(size_t)k * 3 + 1] = accum.y; q.sum[(size_t)k * 3 + 2] = accum.z; }
 	}

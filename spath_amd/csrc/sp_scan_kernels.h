@@ -20,11 +20,13 @@ struct ScanSrc {
 // threads per workgroup of the kernels below: the matrix-pipe scan shares its (larger) tiles between 8 waves
 template <int SCAN> constexpr uint32_t scan_block() { return SCAN == 4 ? cylm512::kMThreads : 256u; }
 
-template <int R, int SCAN>
-SP_DEV void two_stage_scan(const KArgs& a, const ScanSrc& src, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R]) {
-	if constexpr (SCAN == 4) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm512::scan_cylm(a, src.cylm, rv, s, bd, bi); }
-	else if constexpr (SCAN == 3) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm256::scan_cylm(a, src.cylm, rv, s, bd, bi); }
-	else if constexpr (SCAN == 2) scan_cylw<R>(a, src.cyl, rv, s, bd, bi);
+// tmax / shadow: the bounded and the any-hit (shadow ray) forms of scans 2-4 (sp_cylm_scan.h, scan_cylm); scans 0 and 1 have none
+template <int R, int SCAN, bool BOUNDED = false>
+SP_DEV void two_stage_scan(const KArgs& a, const ScanSrc& src, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R],
+                           const float* tmax = nullptr, bool shadow = false) {
+	if constexpr (SCAN == 4) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm512::scan_cylm<BOUNDED>(a, src.cylm, rv, s, bd, bi, tmax, shadow); }
+	else if constexpr (SCAN == 3) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm256::scan_cylm<BOUNDED>(a, src.cylm, rv, s, bd, bi, tmax, shadow); }
+	else if constexpr (SCAN == 2) scan_cylw<R, BOUNDED>(a, src.cyl, rv, s, bd, bi, tmax, shadow);
 	else if constexpr (SCAN == 1) scan_cyl<R>(a, src.cyl, rv, s, bd, bi);
 	else scan_filter<R>(a, src.filt, rv, s, bd, bi);
 }
@@ -111,6 +113,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	const uint32_t chunk = chunked ? blockIdx.x / a.px_blocks : 0u;
 	const uint32_t kr0 = SPLIT ? pblk * B + tid : pblk * (B * R) + tid;
 	constexpr bool adapt = IsAdapt<Acc...>::value;
+	constexpr bool nee = IsNee<Acc...>::value;               // next-event estimation: L_d parked in NeeArgs::L (sp_kernels.h)
+	static_assert(!nee || SCAN >= 2, "NEE needs the bounded form of the scan");
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -121,7 +125,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 #pragma unroll
 		for (int c = 0; c < 3; ++c) acc[(size_t)c * n_work + k0 + r * B] = 0.0f;
 		if constexpr (adapt) { adapt_args(acc_args...).wst[k0 + r * B] = 0.0; adapt_args(acc_args...).wst[(size_t)n_work + k0 + r * B] = 0.0; }
-		if constexpr (sizeof...(Acc) > 0) {
+		if constexpr (HasAccum<Acc...>::value) {
 			const AccumArgs& q = accum_args(acc_args...);
 			const size_t ks = adapt ? pk : k;                    // index of the running sum
 			if (q.sample_base && !chunked && (!SPLIT || r == 0) && k < a.n_rays) {
@@ -148,7 +152,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	}
 
 	uint32_t s0 = 0;                                         // global index of the launch's first sample
-	if constexpr (sizeof...(Acc) > 0) s0 = accum_args(acc_args...).sample_base;
+	if constexpr (HasAccum<Acc...>::value) s0 = accum_args(acc_args...).sample_base;
 	const uint32_t n_iter = SPLIT ? (a.n_samples + R - 1) / R : a.n_samples;
 	uint32_t it0 = 0, it1 = n_iter;
 	if (chunked) {
@@ -172,7 +176,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			nh[r] = 0;
 		}
 #pragma unroll 1
-		for (int depth = 0; depth < 5; ++depth) {
+		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {   // NEE: the 5th hit would carry nothing
 			bool any_alive = false;
 #pragma unroll
 			for (int r = 0; r < R; ++r) any_alive |= s.act[r];
@@ -182,9 +186,66 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 #pragma unroll
 				for (int r = 0; r < R; ++r) { bd[r] = pd[r]; bi[r] = pi[r]; }
 			} else {
-				two_stage_scan<R, SCAN>(a, src2, rv, s, bd, bi);
+				two_stage_scan<R, SCAN, nee>(a, src2, rv, s, bd, bi);
 #pragma unroll
 				for (int r = 0; r < R; ++r) my_scans += s.act[r] ? 1u : 0u;
+			}
+			if constexpr (nee) {
+				// one light sample per hit, then ONE block-uniform shadow scan for the slots that have a shadow ray (none: skipped)
+				const NeeArgs& ne = nee_args(acc_args...);
+				RaySlots<R> sh;
+				float tmx[R];
+				f3 nadj[R];
+				bool hitr[R], any_sh = false;
+#pragma unroll
+				for (int r = 0; r < R; ++r) {
+					hitr[r] = s.act[r] && (bi[r] >= 0);
+					sh.o[r] = s.o[r]; sh.dir[r] = s.dir[r]; sh.src[r] = s.src[r]; sh.act[r] = false; tmx[r] = kMaxDist;
+					nadj[r] = s.dir[r];
+					if (hitr[r]) {
+						const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
+						f3 n = mk3(tn[0], tn[1], tn[2]);
+						if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
+						nadj[r] = n;
+						const f3 x = add3(s.o[r], scale3(s.dir[r], bd[r]));
+						f3 wd = s.dir[r], Lc = mk3(0.0f, 0.0f, 0.0f);
+						float tm = kMaxDist;
+						sh.act[r] = nee_light(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+						sh.o[r] = x; sh.dir[r] = wd; sh.src[r] = bi[r]; tmx[r] = tm;
+						float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
+						Lp[0] = sh.act[r] ? Lc.x : 0.0f; Lp[n_work] = sh.act[r] ? Lc.y : 0.0f; Lp[(size_t)2 * n_work] = sh.act[r] ? Lc.z : 0.0f;
+					}
+					any_sh |= sh.act[r];
+				}
+				if (__syncthreads_or(any_sh ? 1 : 0)) {
+					float sbd[R]; int sbi[R];
+					two_stage_scan<R, SCAN, true>(a, src2, rv, sh, sbd, sbi, tmx, true);
+#pragma unroll
+					for (int r = 0; r < R; ++r) {
+						my_scans += sh.act[r] ? 1u : 0u;
+						if (sh.act[r] && sbi[r] >= 0) {                 // occluded
+							float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
+							Lp[0] = 0.0f; Lp[n_work] = 0.0f; Lp[(size_t)2 * n_work] = 0.0f;
+						}
+					}
+				}
+				// the bounce, exactly as without NEE
+#pragma unroll
+				for (int r = 0; r < R; ++r) {
+					if (hitr[r]) {
+						double r1, r2;
+						philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
+						const f3 nd = rand_unit_vec(nadj[r], r1, r2);
+						const float ct = dot3(nd, nadj[r]);
+						s.o[r] = sh.o[r];
+						s.dir[r] = nd;
+						s.src[r] = sh.src[r];
+						hist[(size_t)depth * n_work + k0 + r * B] = make_int2(sh.src[r], (int)__float_as_uint(ct));
+						nh[r] = depth + 1;
+					}
+					s.act[r] = hitr[r];
+				}
+				continue;
 			}
 #pragma unroll
 			for (int r = 0; r < R; ++r) {
@@ -214,7 +275,12 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				const int2 hc = hist[(size_t)d * n_work + kw];
 				const float* m = a.mats + (size_t)hc.x * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
-				const f3 e = mk3(m[3], m[4], m[5]);
+				f3 e = mk3(m[3], m[4], m[5]);
+				if constexpr (nee) {                         // (e_0 or 0) + L_d
+					const float* Lp = nee_args(acc_args...).L + (size_t)d * 3 * n_work + kw;
+					if (d > 0) e = mk3(0.0f, 0.0f, 0.0f);
+					e = add3(e, mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]));
+				}
 				rec = add3(e, scale3(scale3(mul3(brdf, rec), __uint_as_float((uint32_t)hc.y)), kInvP));
 			}
 			// cpu_renderer.cpp:75 accum += sample, in sample order: with SPLIT the slots are consecutive samples of one
@@ -243,7 +309,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		const uint32_t k = kr0 + r * kstep;
 		const uint32_t kw = k0 + r * B;
 		if (k < a.n_rays && !chunked) {
-			if constexpr (sizeof...(Acc) > 0) {
+			if constexpr (HasAccum<Acc...>::value) {
 				const AccumArgs& q = accum_args(acc_args...);
 				const size_t ks = adapt ? local_px(k, acc_args...) : k;
 #pragma unroll

@@ -88,6 +88,13 @@ struct sphip_ctx {
 	// buffers live on the first device, with the whole frame's rays gathered there for the G-buffer.
 	DevBuf dn_cls, dn_hit, dn_gbuf, dn_a, dn_b, dn_rays;
 	bool dn_cls_valid = false;                    // dropped by every set_scene
+	// ---- next-event estimation (SPHIP_FLAG_NEE): the scene's light table {double cdf[n]; int tri[n]; float ipdf[n]}, built on the host
+	// from a read-back on the first NEE render after a scene change; nee_bad: the scene has an invalid emittance (nee_msg says which)
+	DevBuf nee_tab;
+	bool nee_valid = false, nee_bad = false;      // nee_valid dropped by every set_scene
+	uint32_t nee_n = 0;
+	double nee_W = 0.0;
+	std::string nee_msg;
 	bool dn_gbuf_ok = false;                      // dropped by every accumulation begin
 };
 
@@ -173,6 +180,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	HIP_TRY(c, hipGetLastError());
 	c->have_scene = true;
 	c->bvh_valid = c->filt_valid = c->cyl_valid = c->cylm_valid = false;
+	c->nee_valid = false;
 	return SPHIP_OK;
 }
 
@@ -309,6 +317,62 @@ int ensure_bvh(sphip_ctx* c, hipStream_t st) {
 	return SPHIP_OK;
 }
 
+// ---- the light table of next-event estimation (include/spath_hip.h), built on the host once per scene:
+// emitters are the triangles with Esum = ((double)Er + Eg) + Eb > 0, weighted by w = A * Esum (A in double from the f32 vertices); the
+// table lists those with w > 0 in ascending index with their running double sum cdf and ipdf = (float)(W / Esum), W = the total
+int ensure_lights(sphip_ctx* c, hipStream_t st) {
+	if (c->nee_valid) return c->nee_bad ? fail(c, SPHIP_E_INVALID, "%s", c->nee_msg.c_str()) : SPHIP_OK;
+	const size_t n = c->n_tris;
+	std::vector<float> t(n * 12), m(n * 6);
+	HIP_TRY(c, hipMemcpyAsync(t.data(), c->tris.p, n * 48, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(m.data(), c->mats.p, n * 24, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	std::vector<double> cdf;
+	std::vector<int> tri;
+	std::vector<float> ipdf;
+	std::vector<double> esum;
+	double W = 0.0;
+	c->nee_bad = false;
+	for (size_t i = 0; i < n; ++i) {
+		const float* e = &m[i * 6 + 3];
+		for (int k = 0; k < 3; ++k)
+			if (!(e[k] >= 0.0f) || !std::isfinite(e[k])) {
+				char buf[160];
+				snprintf(buf, sizeof buf, "SPHIP_FLAG_NEE: triangle %zu has emittance component %d = %g (must be finite and >= 0)", i, k, (double)e[k]);
+				c->nee_msg = buf;
+				c->nee_bad = true;
+				c->nee_valid = true;
+				return fail(c, SPHIP_E_INVALID, "%s", buf);
+			}
+		const double es = ((double)e[0] + (double)e[1]) + (double)e[2];
+		if (!(es > 0.0)) continue;
+		const float* v = &t[i * 12];
+		const double e1[3] = { (double)v[3] - (double)v[0], (double)v[4] - (double)v[1], (double)v[5] - (double)v[2] };
+		const double e2[3] = { (double)v[6] - (double)v[0], (double)v[7] - (double)v[1], (double)v[8] - (double)v[2] };
+		const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+		const double w = (0.5 * std::sqrt((cx * cx + cy * cy) + cz * cz)) * es;
+		if (!(w > 0.0) || !std::isfinite(w)) continue;
+		W = W + w;
+		cdf.push_back(W); tri.push_back((int)i); esum.push_back(es);
+	}
+	const size_t ne = cdf.size();
+	for (size_t k = 0; k < ne; ++k) ipdf.push_back((float)(W / esum[k]));
+	int rc;
+	if ((rc = ensure(c, c->nee_tab, ne * 16 + 16))) return rc;
+	if (ne) {
+		std::vector<char> blob(ne * 16);
+		memcpy(blob.data(), cdf.data(), ne * 8);
+		memcpy(blob.data() + ne * 8, tri.data(), ne * 4);
+		memcpy(blob.data() + ne * 12, ipdf.data(), ne * 4);
+		HIP_TRY(c, hipMemcpyAsync(c->nee_tab.p, blob.data(), ne * 16, hipMemcpyHostToDevice, st));
+		HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
+	}
+	c->nee_n = (uint32_t)ne;
+	c->nee_W = W;
+	c->nee_valid = true;
+	return SPHIP_OK;
+}
+
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
 // prog != nullptr: progressive accumulation (path tracing only): the launch renders global samples
@@ -357,6 +421,19 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		return fail(c, SPHIP_E_INVALID, "rpl_cylm handles scenes of fewer than 2^%u triangles (this one has %zu); use rpl_cylw4s", sp::kMIdxBits, c->n_tris);
 	if (!variant_built(variant))
 		return fail(c, SPHIP_E_INVALID, "kernel variant %d (%s) is not compiled into this build of libspath_hip (rebuild with -DSP_ALL_VARIANTS)", variant, kVariantNames[variant]);
+	// next-event estimation: path tracing with the shipped variants only (the bounded scans); flat and hit queries ignore the flag
+	const bool nee = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_NEE);
+	sp::NeeArgs ne{};
+	if (nee) {
+		if (!(variant == 1 || variant == 2 || variant == kVariantAccel || variant == 15 || variant == 16))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_NEE is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+		if ((rc = ensure_lights(c, st))) return rc;
+		ne.cdf = (const double*)c->nee_tab.p;
+		ne.tri = (const int*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 8);
+		ne.ipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 12);
+		ne.n = c->nee_n;
+		ne.W = c->nee_W;
+	}
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -388,7 +465,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			if (samp_bytes > kChunkMaxBytes) chunks = 1;
 			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
 			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * (adapt ? 68 : 52);
+				const uint64_t work_bytes = lanes * chunks * ((adapt ? 68 : 52) + (nee ? 48 : 0));
 				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
@@ -417,9 +494,10 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	sp::AdaptArgs ad{};
 	if (adapt) ad = *adapt;
 	if (mode == SPHIP_MODE_PT && is_ts) {
-		if ((rc = ensure(c, c->work, (size_t)n_work * 52))) return rc;
+		if ((rc = ensure(c, c->work, (size_t)n_work * (nee ? 100 : 52)))) return rc;
 		hist = (int2*)c->work.p;
 		acc = (float*)((char*)c->work.p + (size_t)n_work * 40);
+		ne.L = (float*)((char*)c->work.p + (size_t)n_work * 52);          // NEE: L[4][3][n_work]
 		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * 16))) return rc;   // S1, S2 per work slot
 		ad.wst = (double*)c->adp_wst.p;
 	}
@@ -466,6 +544,9 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (variant == kVariantAccel) {
 		if (mode == kModeHits)           hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
 		else if (mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
+		else if (nee && adapt)            hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad, ne);
+		else if (nee && prog)             hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog, ne);
+		else if (nee)                     hipLaunchKernelGGL((sp::k_accel<1, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ne);
 		else if (adapt)                   hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad);
 		else if (prog)                    hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog);
 		else                              hipLaunchKernelGGL(sp::k_accel<1>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
@@ -503,7 +584,14 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad); \
                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work); } while (0)
-			if (ts.scan == 3) SP_PT(1, false, 3);
+#define SP_PTN(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, ne); \
+                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, ne); \
+                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ne); } while (0)
+			if (nee && ts.scan == 3) SP_PTN(1, false, 3);
+			else if (nee && ts.scan == 4) SP_PTN(1, false, 4);
+			else if (nee) SP_PTN(4, true, 2);                                // variant 15 (checked above)
+#undef SP_PTN
+			else if (ts.scan == 3) SP_PT(1, false, 3);
 			else if (ts.scan == 4) SP_PT(1, false, 4);
 			else if (ts.scan == 2 && ts.split) SP_PT(4, true, 2);
 #ifdef SP_ALL_VARIANTS
@@ -518,6 +606,12 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #endif
 #undef SP_PT
 		}
+		else if (nee && adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
+		else if (nee && adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
+		else if (nee && prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, *prog, ne);
+		else if (nee && prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, *prog, ne);
+		else if (nee && variant == 2)         hipLaunchKernelGGL((sp::k_pt<2, sp::NeeArgs>), grid, block, 0, st, a, ne);
+		else if (nee)                         hipLaunchKernelGGL((sp::k_pt<1, sp::NeeArgs>), grid, block, 0, st, a, ne);
 		else if (adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs>), grid, block, 0, st, a, ad);
 		else if (adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs>), grid, block, 0, st, a, ad);
 		else if (prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs>), grid, block, 0, st, a, *prog);
@@ -1341,7 +1435,7 @@ void sphip_destroy(sphip_t* c) {
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
 	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
 	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
-	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays };
+	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);

@@ -222,6 +222,10 @@ namespace hip_renderer {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = flags;
 	}
 
+	void set_nee(scene::renderer* r, bool on) {
+		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = on ? (p->flags | SPHIP_FLAG_NEE) : (p->flags & ~SPHIP_FLAG_NEE);
+	}
+
 	void set_progressive(scene::renderer* r, bool on) {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) { p->progressive = on; p->acc_live = false; }
 	}

@@ -23,6 +23,9 @@ namespace hip_renderer {
 	// frames and the C-ABI flags word (kernel variant, primary-hit reuse; see include/spath_hip.h).
 	extern void set_seed(scene::renderer* r, unsigned long long seed);
 	extern void set_flags(scene::renderer* r, int flags);
+	// next-event estimation on or off (SPHIP_FLAG_NEE in the flags word; include/spath_hip.h): light sampling with shadow rays,
+	// a less noisy estimate of the same image
+	extern void set_nee(scene::renderer* r, bool on);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one
