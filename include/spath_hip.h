@@ -65,8 +65,10 @@ enum {
 	                                   test and tie rule, so every geometric hit is reproduced bit for bit; what it cannot
 	                                   reproduce are the reference's rounding-noise accepts on rays almost coplanar with a
 	                                   far-away triangle.  Never used by bench.py's headline figure. */
-	SPHIP_FLAG_NEE = 0x400           /* OPT-IN next-event estimation (light sampling with shadow rays) for SPHIP_MODE_PT; see
+	SPHIP_FLAG_NEE = 0x400,          /* OPT-IN next-event estimation (light sampling with shadow rays) for SPHIP_MODE_PT; see
 	                                   "next-event estimation" below.  Changes the estimator, not its expectation. */
+	SPHIP_FLAG_MIS = 0x800           /* OPT-IN multiple importance sampling of next-event estimation: valid only together with
+	                                   SPHIP_FLAG_NEE; see "multiple importance sampling" below.  Same expectation again. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -354,6 +356,26 @@ int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba
  * sphip_stats.scans_executed counts the path scans plus the shadow rays traced (one each, whether the scan left early or not).
  * Progressive and adaptive accumulation (the luminance proxy of the NEE sample), primary-hit reuse, sample chunks, denoising,
  * shards and multi-device contexts work as without the flag, bit for bit. */
+
+/* ---- multiple importance sampling (SPHIP_FLAG_MIS | SPHIP_FLAG_NEE): next-event estimation's light samples at
+ * hits 0..3 and the emission that BSDF directions find at hits 1..4, combined by the balance heuristic.  Valid wherever
+ * SPHIP_FLAG_NEE is; SPHIP_FLAG_MIS without SPHIP_FLAG_NEE makes a path-traced render fail with SPHIP_E_INVALID (flat and hit queries
+ * ignore both).  Notation, light table, draws and shadow rays as for next-event estimation above.
+ *
+ * Paths: the same closest hits and BSDF directions, up to five hits (the fifth is traced again: its emission counts).  Radiance:
+ *     rec_d = D_d + (((brdf_d * rec_{d+1}) * ct_d) * (1/p)),   D_d = Ew_d + L_d (d = 0..3),  D_4 = Ew_4   (per channel)
+ * u (both densities per solid angle: p_l = dist2 / (cos_y * ipdf) of the light table, q = 1 / (pi^2 sxz) of the BSDF directions):
+ *     u(sxz, dist2, cos_y, ipdf) = (((float)(pi^2) * sxz) * dist2) / (cos_y * ipdf),   0 where that quotient is NaN (0/0, inf/inf)
+ * Ew_d, the emission e_d = Le of the triangle j hit at depth d:  Ew_0 = e_0;  for d >= 1, with tipdf[j] = ipdf of j's table entry or
+ * 0 when j is not in the table (no emittance, zero area, empty table):  Ew_d = e_d when !(tipdf[j] > 0), else Ew_d = e_d / (1 + u_b)
+ * per channel, u_b = u(sqrtf(dir.x * dir.x + dir.z * dir.z), bd * bd, |dot3(dir, n_j)|, tipdf[j]), where dir is the BSDF direction
+ * (the ray of depth d), bd its closest-hit distance and n_j triangle j's stored normal.
+ * Light sample at hit d (d = 0..3): as for next-event estimation except that sxz = 0 is no early-out (the term stays finite), and
+ *     L_d = (reflectance_src * (1/pi)) * (Le_i * (((float)(2 pi) * cos_x) / (1 + u(sxz, dist2, cos_y, ipdf_e))))   (per channel)
+ * -- NEE's term times u / (1 + u), with the 1/dist2 and 1/sxz factors cancelled, so it never exceeds 2 * reflectance * Le.
+ * L_d = 0 where NEE's would be (no sample, or occluded).  A sample's radiance is therefore at most
+ * sum_{d=0..4} (2 rho_max)^d (Le_max + 2 rho_max Le_max) per channel.  scans_executed: path scans plus shadow rays.  The image and
+ * every composition are bit-for-bit as for next-event estimation (the luminance proxy is that of the MIS sample). */
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

@@ -17,6 +17,7 @@ KERNEL_AUTO = 0
 FLAG_PRIMARY_REUSE = 0x100
 FLAG_ACCEL = 0x200          # opt-in linear BVH; not the brute-force path
 FLAG_NEE = 0x400            # opt-in next-event estimation: light sampling with shadow rays
+FLAG_MIS = 0x800            # with FLAG_NEE: multiple importance sampling of its light samples
 
 
 def flag_chunks(n: int) -> int:

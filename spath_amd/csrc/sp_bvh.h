@@ -150,6 +150,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	}
 	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_kernels.h AdaptArgs)
 	constexpr bool nee = IsNee<Acc...>::value;         // next-event estimation (sp_kernels.h NeeArgs)
+	constexpr bool mis = IsMis<Acc...>::value;         // MIS on top of it (sp_kernels.h MisArgs): the folded terms D_0..D_4
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
@@ -173,10 +174,11 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		int src = -1, hidx[5];
 		float hcos[5];
 		f3 hL[kNeeDepths];
+		f3 hD[kMisDepths];
 		int nh = 0;
 		bool alive = valid;
 #pragma unroll
-		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {
+		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {
 			if (alive) {
 				float bd; int bi;
 				scan_bvh(B, o, dir, src, bd, bi);
@@ -185,7 +187,20 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					const float* tn = a.tris + (size_t)bi * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);
-					if constexpr (nee) {
+					if constexpr (mis) {
+						f3 wd, Lc; float tm;
+						const f3 x = add3(o, scale3(dir, bd));
+						const float* m = a.mats + (size_t)bi * 6;
+						const f3 De = depth == 0 ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
+						f3 Ld = mk3(0.0f, 0.0f, 0.0f);
+						if (depth < kNeeDepths && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, n, bi, wd, tm, Lc)) {
+							float sd; int si;
+							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
+							my_scans++;
+							if (si < 0) Ld = Lc;
+						}
+						hD[depth] = depth < kNeeDepths ? add3(De, Ld) : De;
+					} else if constexpr (nee) {
 						f3 wd, Lc; float tm;
 						const f3 x = add3(o, scale3(dir, bd));
 						hL[depth] = mk3(0.0f, 0.0f, 0.0f);
@@ -217,7 +232,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 				const float* m = a.mats + (size_t)hidx[depth] * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
-				if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
+				if constexpr (mis) e = hD[depth];
+				else if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
 				rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
 			}
 		}

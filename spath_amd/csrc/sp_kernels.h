@@ -74,14 +74,32 @@ struct NeeArgs {
 constexpr int kNeeDepths = 4;                                    // light samples at hits 0..3; the 5th hit would carry nothing
 constexpr float kShadowMargin = 1.0f - 0x1p-10f;                  // tmax = dist * (1 - 2^-10)
 constexpr float kTwoOverPi = (float)(2.0 / kPi);                  // 2 pi x the reference's direction density (nee_light)
+// multiple importance sampling (SPHIP_FLAG_MIS with SPHIP_FLAG_NEE): NeeArgs plus the light table's pdf by
+// triangle, tipdf[i] = ipdf of triangle i's table entry, 0 for a triangle not in the table.  It rides in NeeArgs' place:
+// k_pt<V, MisArgs>, k_pt_filter<R, S, SCAN, AccumArgs, MisArgs>, ...  L: the two-stage kernels park the folded direct term D_d of
+// depths 0..4 there (15 floats per slot instead of 12).
+struct MisArgs : NeeArgs {
+	const float* tipdf;        // n_tris
+};
+constexpr int kMisDepths = 5;                                     // MIS traces the 5th hit again: its emission counts
+constexpr float kTwoPi = (float)(2.0 * kPi);
+constexpr float kPiSq = (float)(kPi * kPi);
 
 template <typename... Acc> struct IsAdapt { static constexpr bool value = false; };
 template <> struct IsAdapt<AdaptArgs> { static constexpr bool value = true; };
 template <> struct IsAdapt<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
+template <> struct IsAdapt<AdaptArgs, MisArgs> { static constexpr bool value = true; };
 template <typename... Acc> struct IsNee { static constexpr bool value = false; };
 template <> struct IsNee<NeeArgs> { static constexpr bool value = true; };
 template <> struct IsNee<AccumArgs, NeeArgs> { static constexpr bool value = true; };
 template <> struct IsNee<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
+template <> struct IsNee<MisArgs> { static constexpr bool value = true; };
+template <> struct IsNee<AccumArgs, MisArgs> { static constexpr bool value = true; };
+template <> struct IsNee<AdaptArgs, MisArgs> { static constexpr bool value = true; };
+template <typename... Acc> struct IsMis { static constexpr bool value = false; };
+template <> struct IsMis<MisArgs> { static constexpr bool value = true; };
+template <> struct IsMis<AccumArgs, MisArgs> { static constexpr bool value = true; };
+template <> struct IsMis<AdaptArgs, MisArgs> { static constexpr bool value = true; };
 // a running sum rides in the pack (progressive or adaptive)
 template <typename... Acc> struct HasAccum { static constexpr bool value = sizeof...(Acc) > (IsNee<Acc...>::value ? 1u : 0u); };
 SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p) { return p; }
@@ -90,6 +108,8 @@ SP_DEV const AccumArgs& accum_args(const AccumArgs& p, const NeeArgs&) { return 
 SP_DEV const NeeArgs& nee_args(const NeeArgs& n) { return n; }
 SP_DEV const NeeArgs& nee_args(const AccumArgs&, const NeeArgs& n) { return n; }
 SP_DEV const NeeArgs& nee_args(const AdaptArgs&, const NeeArgs& n) { return n; }
+SP_DEV const float* mis_tipdf(const MisArgs& m) { return m.tipdf; }
+SP_DEV const float* mis_tipdf(const AccumArgs&, const MisArgs& m) { return m.tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
 template <typename... Acc>
 SP_DEV uint32_t local_px(uint32_t k, const Acc&... acc_args) {
@@ -249,9 +269,32 @@ SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
 }
 
+// ---- MIS (include/spath_hip.h): u = p_l / q, the light table's density over the reference's BSDF density,
+// both per solid angle, for a direction w that reaches emitter j at distance sqrt(dist2) under cos_y.  A NaN quotient (0/0 or
+// inf/inf) counts as 0, so 1 / (1 + u) is a weight in [0, 1] for every input.
+SP_DEV float mis_u(float sxz, float dist2, float cos_y, float ipdf) {
+	const float u = ((kPiSq * sxz) * dist2) / (cos_y * ipdf);
+	return u == u ? u : 0.0f;
+}
+// the emission e_d of the triangle bi that the BSDF direction dir found at distance bd (d >= 1), weighted by the balance heuristic:
+// e_d / (1 + u_b), or e_d itself when bi is not in the light table (tipdf[bi] = 0: the light sample never picks it)
+SP_DEV f3 mis_emit(const KArgs& a, const float* tipdf, f3 dir, float bd, int bi) {
+	const float* m = a.mats + (size_t)bi * 6;
+	const f3 e = mk3(m[3], m[4], m[5]);
+	const float ip = tipdf[bi];
+	if (!(ip > 0.0f)) return e;
+	const float* tn = a.tris + (size_t)bi * 12 + 9;
+	const float cos_y = fabsf(dot3(dir, mk3(tn[0], tn[1], tn[2])));
+	const float sxz = __builtin_sqrtf(dir.x * dir.x + dir.z * dir.z);
+	const float opu = 1.0f + mis_u(sxz, bd * bd, cos_y, ip);
+	return mk3(e.x / opu, e.y / opu, e.z / opu);
+}
+
 // ---- next-event estimation: one light sample at the hit x of a path (include/spath_hip.h).
 // n: the hit triangle's normal as the path uses it (turned against the incoming ray); src: the hit triangle.  Returns whether a
 // shadow ray (x, wd) with the bound tmax is to be traced, and then L = the direct light it carries when nothing occludes it.
+// MIS: L carries the balance heuristic's weight u / (1 + u), and sxz = 0 is no early-out (L is finite).
+template <bool MIS = false>
 SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_t sample, int depth, f3 x, f3 n, int src,
                       f3& wd, float& tmax, f3& L) {
 	if (ne.n == 0) return false;
@@ -284,11 +327,18 @@ SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_
 	// expectation therefore carries 2 pi q(w) per bounce; the light sample carries the same factor, 2 / (pi sxz), so that both
 	// estimate the same image
 	const float sxz = __builtin_sqrtf(wd.x * wd.x + wd.z * wd.z);
-	if (!(cos_x > 0.0f) || !(cos_y > 0.0f) || !(sxz > 0.0f)) return false;
+	if constexpr (MIS) {
+		if (!(cos_x > 0.0f) || !(cos_y > 0.0f)) return false;
+	} else {
+		if (!(cos_x > 0.0f) || !(cos_y > 0.0f) || !(sxz > 0.0f)) return false;
+	}
 	tmax = dist * kShadowMargin;
 	const float* me = a.mats + (size_t)li * 6;
 	const float* ms = a.mats + (size_t)src * 6;
-	const float g = (((cos_x * cos_y) / dist2) * ne.ipdf[lo]) * (kTwoOverPi / sxz);
+	float g;
+	// MIS: g (u / (1 + u)) with u = ((pi^2 sxz) dist2) / (cos_y ipdf): the 1 / dist2 and 1 / sxz factors cancel, g <= 2 pi
+	if constexpr (MIS) g = (kTwoPi * cos_x) / (1.0f + mis_u(sxz, dist2, cos_y, ne.ipdf[lo]));
+	else g = (((cos_x * cos_y) / dist2) * ne.ipdf[lo]) * (kTwoOverPi / sxz);
 	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
 	return true;
 }
@@ -420,6 +470,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	const f3 po = mk3(r[0], r[1], r[2]), pdir = mk3(r[3], r[4], r[5]);
 	constexpr bool adapt = IsAdapt<Acc...>::value;
 	constexpr bool nee = IsNee<Acc...>::value;
+	constexpr bool mis = IsMis<Acc...>::value;                   // MIS: nee too; the folded terms D_0..D_4
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = (a.flags & 0x100u) != 0;
@@ -451,8 +502,9 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f;
 		bool alive = valid;
 		f3 L0 = mk3(0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0, L3 = L0;   // NEE: direct light sampled at hits 0..3
+		f3 D0 = L0, D1 = L0, D2 = L0, D3 = L0, D4 = L0;             // MIS: D_d = e_d w_b + L_d
 #pragma unroll 1
-		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {   // :33 depth >= 5 -> black (NEE: the 5th hit carries nothing)
+		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {   // :33 depth >= 5 -> black (NEE: the 5th hit carries nothing)
 			if (!__syncthreads_or(alive ? 1 : 0)) break;   // block-uniform: the LDS scan has barriers
 			float bd; int bi;
 			if (depth == 0 && reuse) { bd = pd; bi = pi; }
@@ -461,11 +513,16 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			bool sh = false;                                      // NEE: this lane traces a shadow ray
 			f3 wd = dir, Lc = mk3(0.0f, 0.0f, 0.0f);
 			float tm = kMaxDist;
+			f3 De = Lc;                                           // MIS: e_d w_b
 			if (hit) {
 				const float* tn = a.tris + (size_t)bi * 12 + 9;
 				f3 n = mk3(tn[0], tn[1], tn[2]);                  // :55
 				if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);    // :56-57
-				if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
+				if constexpr (mis) {
+					if (depth == 0) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
+					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
+					if (depth < kNeeDepths) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
+				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
 				double r1, r2;
 				philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
 				const f3 nd = rand_unit_vec(n, r1, r2);           // :58
@@ -489,7 +546,12 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 					sh = sh && si < 0;
 				}
 				const f3 Ld = sh ? Lc : mk3(0.0f, 0.0f, 0.0f);
-				if (depth == 0) L0 = Ld; else if (depth == 1) L1 = Ld; else if (depth == 2) L2 = Ld; else L3 = Ld;
+				if constexpr (mis) {
+					const f3 Dd = depth < kNeeDepths ? add3(De, Ld) : De;
+					if (depth == 0) D0 = Dd; else if (depth == 1) D1 = Dd; else if (depth == 2) D2 = Dd; else if (depth == 3) D3 = Dd; else D4 = Dd;
+				} else {
+					if (depth == 0) L0 = Ld; else if (depth == 1) L1 = Ld; else if (depth == 2) L2 = Ld; else L3 = Ld;
+				}
 			}
 		}
 		// unwind: rec(depth) = E + (((BRDF * rec(depth+1)) * cos) * (1/p)), rec beyond the last hit = 0
@@ -502,7 +564,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                     // :63
 				f3 e = mk3(m[3], m[4], m[5]);
-				if constexpr (nee) {                                                        // (e_0 or 0) + L_d
+				if constexpr (mis) e = depth == 0 ? D0 : depth == 1 ? D1 : depth == 2 ? D2 : depth == 3 ? D3 : D4;   // D_d
+				else if constexpr (nee) {                                                   // (e_0 or 0) + L_d
 					if (depth > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, depth == 0 ? L0 : depth == 1 ? L1 : depth == 2 ? L2 : L3);
 				}

@@ -115,6 +115,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	constexpr bool adapt = IsAdapt<Acc...>::value;
 	constexpr bool nee = IsNee<Acc...>::value;               // next-event estimation: L_d parked in NeeArgs::L (sp_kernels.h)
 	static_assert(!nee || SCAN >= 2, "NEE needs the bounded form of the scan");
+	constexpr bool mis = IsMis<Acc...>::value;               // MIS: D_d parked in NeeArgs::L for d = 0..4 (sp_kernels.h MisArgs)
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -176,7 +177,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			nh[r] = 0;
 		}
 #pragma unroll 1
-		for (int depth = 0; depth < (nee ? kNeeDepths : 5); ++depth) {   // NEE: the 5th hit would carry nothing
+		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {   // NEE: the 5th hit would carry nothing
 			bool any_alive = false;
 #pragma unroll
 			for (int r = 0; r < R; ++r) any_alive |= s.act[r];
@@ -210,10 +211,26 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						const f3 x = add3(s.o[r], scale3(s.dir[r], bd[r]));
 						f3 wd = s.dir[r], Lc = mk3(0.0f, 0.0f, 0.0f);
 						float tm = kMaxDist;
-						sh.act[r] = nee_light(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
-						sh.o[r] = x; sh.dir[r] = wd; sh.src[r] = bi[r]; tmx[r] = tm;
-						float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
-						Lp[0] = sh.act[r] ? Lc.x : 0.0f; Lp[n_work] = sh.act[r] ? Lc.y : 0.0f; Lp[(size_t)2 * n_work] = sh.act[r] ? Lc.z : 0.0f;
+						if constexpr (mis) {
+							float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
+							// D_d = e_d w_b + L_d, assuming the shadow ray gets through; e_d w_b waits in depth 4's cells (written at
+							// depth 4 only) in case it does not
+							const float* m = a.mats + (size_t)bi[r] * 6;
+							const f3 De = depth == 0 ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), s.dir[r], bd[r], bi[r]);
+							sh.act[r] = depth < kNeeDepths && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+							const f3 Dd = depth < kNeeDepths ? add3(De, sh.act[r] ? Lc : mk3(0.0f, 0.0f, 0.0f)) : De;
+							Lp[0] = Dd.x; Lp[n_work] = Dd.y; Lp[(size_t)2 * n_work] = Dd.z;
+							if (sh.act[r]) {
+								float* Lq = ne.L + (size_t)kNeeDepths * 3 * n_work + k0 + r * B;
+								Lq[0] = De.x; Lq[n_work] = De.y; Lq[(size_t)2 * n_work] = De.z;
+							}
+							sh.o[r] = x; sh.dir[r] = wd; sh.src[r] = bi[r]; tmx[r] = tm;
+						} else {
+							sh.act[r] = nee_light(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+							sh.o[r] = x; sh.dir[r] = wd; sh.src[r] = bi[r]; tmx[r] = tm;
+							float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
+							Lp[0] = sh.act[r] ? Lc.x : 0.0f; Lp[n_work] = sh.act[r] ? Lc.y : 0.0f; Lp[(size_t)2 * n_work] = sh.act[r] ? Lc.z : 0.0f;
+						}
 					}
 					any_sh |= sh.act[r];
 				}
@@ -225,7 +242,12 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						my_scans += sh.act[r] ? 1u : 0u;
 						if (sh.act[r] && sbi[r] >= 0) {                 // occluded
 							float* Lp = ne.L + (size_t)depth * 3 * n_work + k0 + r * B;
-							Lp[0] = 0.0f; Lp[n_work] = 0.0f; Lp[(size_t)2 * n_work] = 0.0f;
+							if constexpr (mis) {                       // D_d = e_d w_b
+								const float* Lq = ne.L + (size_t)kNeeDepths * 3 * n_work + k0 + r * B;
+								Lp[0] = Lq[0]; Lp[n_work] = Lq[n_work]; Lp[(size_t)2 * n_work] = Lq[(size_t)2 * n_work];
+							} else {
+								Lp[0] = 0.0f; Lp[n_work] = 0.0f; Lp[(size_t)2 * n_work] = 0.0f;
+							}
 						}
 					}
 				}
@@ -276,7 +298,10 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				const float* m = a.mats + (size_t)hc.x * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
-				if constexpr (nee) {                         // (e_0 or 0) + L_d
+				if constexpr (mis) {                         // D_d
+					const float* Lp = nee_args(acc_args...).L + (size_t)d * 3 * n_work + kw;
+					e = mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]);
+				} else if constexpr (nee) {                  // (e_0 or 0) + L_d
 					const float* Lp = nee_args(acc_args...).L + (size_t)d * 3 * n_work + kw;
 					if (d > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]));

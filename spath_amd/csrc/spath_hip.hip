@@ -88,7 +88,8 @@ struct sphip_ctx {
 	// buffers live on the first device, with the whole frame's rays gathered there for the G-buffer.
 	DevBuf dn_cls, dn_hit, dn_gbuf, dn_a, dn_b, dn_rays;
 	bool dn_cls_valid = false;                    // dropped by every set_scene
-	// ---- next-event estimation (SPHIP_FLAG_NEE): the scene's light table {double cdf[n]; int tri[n]; float ipdf[n]}, built on the host
+	// ---- next-event estimation (SPHIP_FLAG_NEE): the scene's light table {double cdf[n]; int tri[n]; float ipdf[n]}, followed by
+	// MIS's pdf by triangle {float tipdf[n_tris]} (ipdf of the triangle's entry, 0 for a triangle not in the table), built on the host
 	// from a read-back on the first NEE render after a scene change; nee_bad: the scene has an invalid emittance (nee_msg says which)
 	DevBuf nee_tab;
 	bool nee_valid = false, nee_bad = false;      // nee_valid dropped by every set_scene
@@ -357,14 +358,17 @@ int ensure_lights(sphip_ctx* c, hipStream_t st) {
 	}
 	const size_t ne = cdf.size();
 	for (size_t k = 0; k < ne; ++k) ipdf.push_back((float)(W / esum[k]));
+	std::vector<float> tipdf(n, 0.0f);                    // MIS: the table's ipdf by triangle, 0 = not in the table
+	for (size_t k = 0; k < ne; ++k) tipdf[(size_t)tri[k]] = ipdf[k];
 	int rc;
-	if ((rc = ensure(c, c->nee_tab, ne * 16 + 16))) return rc;
-	if (ne) {
-		std::vector<char> blob(ne * 16);
-		memcpy(blob.data(), cdf.data(), ne * 8);
-		memcpy(blob.data() + ne * 8, tri.data(), ne * 4);
-		memcpy(blob.data() + ne * 12, ipdf.data(), ne * 4);
-		HIP_TRY(c, hipMemcpyAsync(c->nee_tab.p, blob.data(), ne * 16, hipMemcpyHostToDevice, st));
+	if ((rc = ensure(c, c->nee_tab, ne * 16 + n * 4 + 16))) return rc;
+	std::vector<char> blob(ne * 16 + n * 4);
+	memcpy(blob.data(), cdf.data(), ne * 8);
+	memcpy(blob.data() + ne * 8, tri.data(), ne * 4);
+	memcpy(blob.data() + ne * 12, ipdf.data(), ne * 4);
+	memcpy(blob.data() + ne * 16, tipdf.data(), n * 4);
+	if (!blob.empty()) {
+		HIP_TRY(c, hipMemcpyAsync(c->nee_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
 		HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
 	}
 	c->nee_n = (uint32_t)ne;
@@ -421,8 +425,11 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		return fail(c, SPHIP_E_INVALID, "rpl_cylm handles scenes of fewer than 2^%u triangles (this one has %zu); use rpl_cylw4s", sp::kMIdxBits, c->n_tris);
 	if (!variant_built(variant))
 		return fail(c, SPHIP_E_INVALID, "kernel variant %d (%s) is not compiled into this build of libspath_hip (rebuild with -DSP_ALL_VARIANTS)", variant, kVariantNames[variant]);
-	// next-event estimation: path tracing with the shipped variants only (the bounded scans); flat and hit queries ignore the flag
+	// next-event estimation: path tracing with the shipped variants only (the bounded scans); flat and hit queries ignore the flag.
+	// MIS is a form of it: without SPHIP_FLAG_NEE the flag is an error
 	const bool nee = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_NEE);
+	const bool mis = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_MIS);
+	if (mis && !nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	sp::NeeArgs ne{};
 	if (nee) {
 		if (!(variant == 1 || variant == 2 || variant == kVariantAccel || variant == 15 || variant == 16))
@@ -465,7 +472,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			if (samp_bytes > kChunkMaxBytes) chunks = 1;
 			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
 			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * ((adapt ? 68 : 52) + (nee ? 48 : 0));
+				const uint64_t work_bytes = lanes * chunks * ((adapt ? 68 : 52) + (mis ? 60 : nee ? 48 : 0));
 				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
@@ -494,10 +501,10 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	sp::AdaptArgs ad{};
 	if (adapt) ad = *adapt;
 	if (mode == SPHIP_MODE_PT && is_ts) {
-		if ((rc = ensure(c, c->work, (size_t)n_work * (nee ? 100 : 52)))) return rc;
+		if ((rc = ensure(c, c->work, (size_t)n_work * (mis ? 112 : nee ? 100 : 52)))) return rc;
 		hist = (int2*)c->work.p;
 		acc = (float*)((char*)c->work.p + (size_t)n_work * 40);
-		ne.L = (float*)((char*)c->work.p + (size_t)n_work * 52);          // NEE: L[4][3][n_work]
+		ne.L = (float*)((char*)c->work.p + (size_t)n_work * 52);          // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
 		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * 16))) return rc;   // S1, S2 per work slot
 		ad.wst = (double*)c->adp_wst.p;
 	}
@@ -541,9 +548,17 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		a.prim_idx = oi; a.prim_d = od;
 		prim_pass = true;
 	}
+	sp::MisArgs me{};
+	if (mis) {
+		static_cast<sp::NeeArgs&>(me) = ne;
+		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
+	}
 	if (variant == kVariantAccel) {
 		if (mode == kModeHits)           hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
 		else if (mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
+		else if (mis && adapt)            hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad, me);
+		else if (mis && prog)             hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog, me);
+		else if (mis)                     hipLaunchKernelGGL((sp::k_accel<1, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, me);
 		else if (nee && adapt)            hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad, ne);
 		else if (nee && prog)             hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog, ne);
 		else if (nee)                     hipLaunchKernelGGL((sp::k_accel<1, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ne);
@@ -584,12 +599,15 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad); \
                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work); } while (0)
-#define SP_PTN(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, ne); \
-                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, ne); \
-                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::NeeArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ne); } while (0)
-			if (nee && ts.scan == 3) SP_PTN(1, false, 3);
-			else if (nee && ts.scan == 4) SP_PTN(1, false, 4);
-			else if (nee) SP_PTN(4, true, 2);                                // variant 15 (checked above)
+#define SP_PTN(R_, SPLIT_, S_, T_, V_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, V_); \
+                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, V_); \
+                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, V_); } while (0)
+			if (mis && ts.scan == 3) SP_PTN(1, false, 3, sp::MisArgs, me);
+			else if (mis && ts.scan == 4) SP_PTN(1, false, 4, sp::MisArgs, me);
+			else if (mis) SP_PTN(4, true, 2, sp::MisArgs, me);               // variant 15 (checked above)
+			else if (nee && ts.scan == 3) SP_PTN(1, false, 3, sp::NeeArgs, ne);
+			else if (nee && ts.scan == 4) SP_PTN(1, false, 4, sp::NeeArgs, ne);
+			else if (nee) SP_PTN(4, true, 2, sp::NeeArgs, ne);               // variant 15 (checked above)
 #undef SP_PTN
 			else if (ts.scan == 3) SP_PT(1, false, 3);
 			else if (ts.scan == 4) SP_PT(1, false, 4);
@@ -606,6 +624,12 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 #endif
 #undef SP_PT
 		}
+		else if (mis && adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, ad, me);
+		else if (mis && adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, ad, me);
+		else if (mis && prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, *prog, me);
+		else if (mis && prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, *prog, me);
+		else if (mis && variant == 2)         hipLaunchKernelGGL((sp::k_pt<2, sp::MisArgs>), grid, block, 0, st, a, me);
+		else if (mis)                         hipLaunchKernelGGL((sp::k_pt<1, sp::MisArgs>), grid, block, 0, st, a, me);
 		else if (nee && adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
 		else if (nee && adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
 		else if (nee && prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, *prog, ne);

@@ -226,6 +226,11 @@ namespace hip_renderer {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = on ? (p->flags | SPHIP_FLAG_NEE) : (p->flags & ~SPHIP_FLAG_NEE);
 	}
 
+	void set_mis(scene::renderer* r, bool on) {
+		const int f = SPHIP_FLAG_NEE | SPHIP_FLAG_MIS;
+		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = on ? (p->flags | f) : (p->flags & ~SPHIP_FLAG_MIS);
+	}
+
 	void set_progressive(scene::renderer* r, bool on) {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) { p->progressive = on; p->acc_live = false; }
 	}

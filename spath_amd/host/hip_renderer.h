@@ -26,6 +26,9 @@ namespace hip_renderer {
 	// next-event estimation on or off (SPHIP_FLAG_NEE in the flags word; include/spath_hip.h): light sampling with shadow rays,
 	// a less noisy estimate of the same image
 	extern void set_nee(scene::renderer* r, bool on);
+	// next-event estimation with multiple importance sampling (SPHIP_FLAG_NEE | SPHIP_FLAG_MIS): on sets both flags, off clears
+	// SPHIP_FLAG_MIS only (NEE stays as set_nee left it); the same image again, without NEE's fireflies
+	extern void set_mis(scene::renderer* r, bool on);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

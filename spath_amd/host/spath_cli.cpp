@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -16,6 +16,7 @@
 //   (include/spath_hip.h: sphip_accum_denoise; the library's defaults for what is left out); --raw-out FILE: the last raw image, in
 //   the format --out would use for that name
 // --nee: next-event estimation (include/spath_hip.h: SPHIP_FLAG_NEE); combines with --progressive, --adaptive and --denoise
+// --mis: next-event estimation with multiple importance sampling (SPHIP_FLAG_NEE | SPHIP_FLAG_MIS); implies --nee
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
@@ -137,7 +138,7 @@ int main(int argc, char** argv) {
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
 		int w = 640, h = 480, frames = 1, flags = 0;                 // window default of the reference (main.cpp:238-239)
-		bool nee = false;
+		bool nee = false, mis = false;
 		size_t spp = 128;                                            // main.cpp:44
 		size_t progressive = 0;
 		double adp_t = -1.0, adp_floor = 0.1;                        // --adaptive defaults: FLOOR 0.1, MIN 8
@@ -160,6 +161,7 @@ int main(int argc, char** argv) {
 			else if (k == "--flags") { need(1); flags = std::atoi(argv[++i]); }
 			else if (k == "--primary-reuse") flags |= SPHIP_FLAG_PRIMARY_REUSE;   // one primary scan per pixel (identical image)
 			else if (k == "--nee") nee = true;                                   // next-event estimation (SPHIP_FLAG_NEE)
+			else if (k == "--mis") mis = true;                                   // ... with MIS (SPHIP_FLAG_MIS, implies --nee)
 			else if (k == "--progressive") { need(1); progressive = (size_t)std::atoll(argv[++i]); }
 			else if (k == "--adaptive") {
 				need(1);
@@ -209,6 +211,7 @@ int main(int argc, char** argv) {
 		hip_renderer::set_seed(r.get(), seed);
 		hip_renderer::set_flags(r.get(), flags);
 		hip_renderer::set_nee(r.get(), nee);
+		if (mis) hip_renderer::set_mis(r.get(), true);
 		if (adp_t >= 0.0 && !(progressive && mode == "pt")) throw std::runtime_error("--adaptive needs --progressive n and --mode pt");
 		if (!counts_path.empty() && !(progressive && mode == "pt")) throw std::runtime_error("--counts-out needs --progressive n and --mode pt");
 		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);

@@ -152,6 +152,38 @@ def open_clutter(n_tris: int, seed: int = 7):
     return tris, mats
 
 
+def light_table(tris: np.ndarray, mats: np.ndarray):
+    """The light table of next-event estimation and MIS as the library builds it once per scene (include/spath_hip.h), in numpy:
+    -> (tri, cdf, ipdf, W, tipdf).  The emitters are the triangles with Esum = ((double)Er + Eg) + Eb > 0 and a positive, finite
+    weight A * Esum (A in double from the f32 vertices), in ascending index; cdf is the running double sum of the weights, W its
+    last entry, ipdf = float32(W / Esum).  tipdf is MIS's pdf by triangle: float32 [N], the ipdf of the triangle's entry and 0 for
+    a triangle not in the table (no emittance, zero area).  The emittances must be finite and >= 0 (the library's contract)."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    m = np.asarray(mats, F).reshape(-1, 6)
+    tri, cdf, es_l = [], [], []
+    W = 0.0
+    for i in range(t.shape[0]):
+        e = m[i, 3:6].astype(np.float64)
+        es = (e[0] + e[1]) + e[2]
+        if not es > 0.0:
+            continue
+        v = t[i, :9].astype(np.float64)
+        e1, e2 = v[3:6] - v[0:3], v[6:9] - v[0:3]
+        cx = e1[1] * e2[2] - e1[2] * e2[1]
+        cy = e1[2] * e2[0] - e1[0] * e2[2]
+        cz = e1[0] * e2[1] - e1[1] * e2[0]
+        w = (0.5 * np.sqrt((cx * cx + cy * cy) + cz * cz)) * es
+        if not (w > 0.0 and np.isfinite(w)):
+            continue
+        W = W + w
+        tri.append(i), cdf.append(W), es_l.append(es)
+    ipdf = np.array([W / e for e in es_l], np.float64).astype(F)
+    tri = np.array(tri, np.int64)
+    tipdf = np.zeros(t.shape[0], F)
+    tipdf[tri] = ipdf
+    return tri, np.array(cdf, np.float64), ipdf, W, tipdf
+
+
 def write_scene(path, tris: np.ndarray, mats: np.ndarray) -> None:
     """Scene file read by oracle/ref_driver.cpp and the headless CLI: 'SPSC', n, tris, mats."""
     tris = np.ascontiguousarray(tris, dtype=F).reshape(-1, 12)
