@@ -67,8 +67,10 @@ enum {
 	                                   far-away triangle.  Never used by bench.py's headline figure. */
 	SPHIP_FLAG_NEE = 0x400,          /* OPT-IN next-event estimation (light sampling with shadow rays) for SPHIP_MODE_PT; see
 	                                   "next-event estimation" below.  Changes the estimator, not its expectation. */
-	SPHIP_FLAG_MIS = 0x800           /* OPT-IN multiple importance sampling of next-event estimation: valid only together with
+	SPHIP_FLAG_MIS = 0x800,          /* OPT-IN multiple importance sampling of next-event estimation: valid only together with
 	                                   SPHIP_FLAG_NEE; see "multiple importance sampling" below.  Same expectation again. */
+	SPHIP_FLAG_CAMERA_SAMPLES = 0x1000 /* OPT-IN per-sample camera rays (pixel antialiasing, thin-lens depth of field) for the camera paths
+	                                   of SPHIP_MODE_PT; see "camera samples" below.  Changes the image: it is no longer the reference's. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -376,6 +378,43 @@ int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba
  * L_d = 0 where NEE's would be (no sample, or occluded).  A sample's radiance is therefore at most
  * sum_{d=0..4} (2 rho_max)^d (Le_max + 2 rho_max Le_max) per channel.  scans_executed: path scans plus shadow rays.  The image and
  * every composition are bit-for-bit as for next-event estimation (the luminance proxy is that of the MIS sample). */
+
+/* ---- camera samples (SPHIP_FLAG_CAMERA_SAMPLES): every (pixel, sample) of a path-traced render that has a camera
+ * starts from a primary ray of its own, generated on the device inside the path-tracing kernels: a box-filtered position in the pixel
+ * and, when the lens has a nonzero aperture, a point on a thin lens.  Without the flag every sample starts from the pixel-centre ray of
+ * sphip_viewport_device (src/cpu_renderer.cpp:74-76 with src/view.h:111).
+ *
+ * Valid on sphip_render_camera and on sphip_accum_begin / sphip_accum_begin_adaptive with `cam` (multi-device contexts included), with
+ * sample chunks, SPHIP_FLAG_NEE and SPHIP_FLAG_MIS, and with the shipped variants 1, 2, 8 (SPHIP_FLAG_ACCEL), 15 and 16.
+ * SPHIP_E_INVALID: on a path that takes rays (sphip_render, sphip_render_device, sphip_render_device_accum, sphip_accum_begin with
+ * rays), together with SPHIP_FLAG_PRIMARY_REUSE, with any other variant.  Flat mode and hit queries ignore the flag; the G-buffer of
+ * an accumulation stays that of the pixel-centre rays.  sphip_stats.scans_executed keeps its meaning.
+ *
+ * Arithmetic, with the constants x_max, x_step, y_max, y_step, focal, the rotation and pos of sphip_viewport_device (src/view.h:101-108),
+ * global pixel p, i = p % res_x, j = p / res_x, global sample s; f32 unless marked double, nothing fused, dot3 as for NEE below:
+ *     (r1, r2) = philox_uniforms(seed, p, s, 24)
+ *     cur = ((x_max - x_step * (float)i) - x_step * (float)r1, (y_max - y_step * (float)j) - y_step * (float)r2, 0);  t = cur + (0, 0, focal)
+ *     aperture == 0:  o = cur;  g = t
+ *     aperture  > 0:  (r3, r4) = philox_uniforms(seed, p, s, 25);  rho = aperture * (float)sqrt(r3) (double sqrt);
+ *                     phi = (float)((r4 * pi) * 2.0) (double, as geom.h:167);  (sn, cs) = sincos_glibc(phi) (selftest what 0)
+ *                     o = (cur.x + rho * cs, cur.y + rho * sn, 0);  k = focus_dist / focal;  F = cur + t * k (per component);  g = F - o
+ *     l = sqrtf(dot3(g, g));  dir = rel_move(g / l per component);  pos = rel_move(o) + cam.pos   (rel_move: src/view.h:83-85)
+ * i.e. the reference camera with its lens on the image plane; the plane in focus is local z = focus_dist.  With aperture 0 the ray is
+ * sphip_viewport_device's pinhole ray at the jittered position.  Draw keys 24 and 25 are disjoint from the path's (0..4, 8..11, 16..19). */
+typedef struct {
+	float    aperture;     /* >= 0, finite: radius of the lens disk on the image plane (the image is 1 unit high); 0 = pinhole */
+	float    focus_dist;   /* > 0, finite when aperture > 0: local z of the plane in focus */
+	uint32_t reserved;     /* must be 0 */
+} sphip_lens;
+
+/* The context's lens (NULL = aperture 0), for its later camera-sample renders.  An accumulation captures the lens at its begin: a later
+ * sphip_set_lens applies from the next begin.  SPHIP_E_INVALID for a negative or non-finite aperture, a focus_dist that is not finite and
+ * positive when aperture > 0, reserved != 0.  Accepted by multi-device contexts. */
+int sphip_set_lens(sphip_t* ctx, const sphip_lens* lens);
+/* The res_x*res_y primary rays of global sample `sample` with the context's lens (d_rays_out: res_x*res_y*6 f32, ray k = pixel k), from
+ * the device function the kernels call; asynchronous, single-device contexts (SPHIP_E_STATE otherwise).  A chain of one-sample
+ * sphip_render_device_accum calls (sample_base = s) over these rays gives a flagged render's image bit for bit. */
+int sphip_camera_rays_device(sphip_t* ctx, const sphip_camera* cam, uint64_t seed, uint32_t sample, void* d_rays_out, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

@@ -18,6 +18,7 @@ FLAG_PRIMARY_REUSE = 0x100
 FLAG_ACCEL = 0x200          # opt-in linear BVH; not the brute-force path
 FLAG_NEE = 0x400            # opt-in next-event estimation: light sampling with shadow rays
 FLAG_MIS = 0x800            # with FLAG_NEE: multiple importance sampling of its light samples
+FLAG_CAMERA_SAMPLES = 0x1000  # per-sample camera rays on the camera paths: pixel antialiasing, thin lens
 
 
 def flag_chunks(n: int) -> int:
@@ -36,6 +37,7 @@ SYMBOLS = (
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
+    "sphip_set_lens", "sphip_camera_rays_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -54,6 +56,11 @@ class CameraArgs(C.Structure):
         """cam: spath_amd.view.Camera"""
         return cls((C.c_float * 3)(*[float(x) for x in cam.pos]), float(cam.cosY), float(cam.sinY), float(cam.cosX), float(cam.sinX),
                    float(cam.focal), int(cam.res_x), int(cam.res_y))
+
+
+class Lens(C.Structure):
+    """sphip_lens: the thin lens of camera samples (include/spath_hip.h)."""
+    _fields_ = [("aperture", C.c_float), ("focus_dist", C.c_float), ("reserved", C.c_uint32)]
 
 
 class Adaptive(C.Structure):
@@ -181,6 +188,10 @@ def load():
     L.sphip_accum_gbuffer.argtypes = [vp, vp]
     L.sphip_accum_denoise.restype = C.c_int
     L.sphip_accum_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp]
+    L.sphip_set_lens.restype = C.c_int
+    L.sphip_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.sphip_camera_rays_device.restype = C.c_int
+    L.sphip_camera_rays_device.argtypes = [vp, C.POINTER(CameraArgs), C.c_uint64, C.c_uint32, vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -343,6 +354,18 @@ class Context:
         """camera::get_viewport on the device (cam: spath_amd.view.Camera); writes res_x*res_y*6 floats."""
         ca = CameraArgs.from_camera(cam)
         self._check(self._L.sphip_viewport_device(self._h, C.byref(ca), d_rays_out, stream or None), "sphip_viewport_device")
+
+    def set_lens(self, aperture=0.0, focus_dist=0.0, reserved=0):
+        """sphip_set_lens: the thin lens of later FLAG_CAMERA_SAMPLES renders (aperture 0 = pinhole); an accumulation keeps the lens of
+        its begin."""
+        lens = Lens(float(aperture), float(focus_dist), int(reserved))
+        self._check(self._L.sphip_set_lens(self._h, C.byref(lens)), "sphip_set_lens")
+
+    def camera_rays_device(self, cam, sample: int, d_rays_out: int, *, seed=1, stream: int = 0):
+        """sphip_camera_rays_device: the res_x*res_y primary rays of global sample `sample` with the context's lens (6 floats each)."""
+        ca = CameraArgs.from_camera(cam)
+        self._check(self._L.sphip_camera_rays_device(self._h, C.byref(ca), seed, sample, d_rays_out, stream or None),
+                    "sphip_camera_rays_device")
 
     def render_camera(self, cam, n_samples, seed=1, mode=MODE_PT, flags=0, want_accum=False):
         """get_viewport + render in one call; the rays never leave the device."""

@@ -124,8 +124,12 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = k < a.n_rays;
 	const uint32_t kk = valid ? k : a.n_rays - 1;
-	const float* r = a.rays + (size_t)kk * 6;
-	const f3 po = mk3(r[0], r[1], r[2]), pdir = mk3(r[3], r[4], r[5]);
+	constexpr bool cam = IsCam<Acc...>::value;         // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
+	f3 po = mk3(0.0f, 0.0f, 0.0f), pdir = po;
+	if constexpr (!cam) {
+		const float* r = a.rays + (size_t)kk * 6;
+		po = mk3(r[0], r[1], r[2]); pdir = mk3(r[3], r[4], r[5]);
+	}
 	if (MODE == 2) {
 		float bd; int bi;
 #ifdef SP_BVH_STATS
@@ -171,6 +175,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		f3 o = po, dir = pdir;
+		if constexpr (cam) camera_ray(cam_args(acc_args...), a.seed, pixel, s0 + s, o, dir);
 		int src = -1, hidx[5];
 		float hcos[5];
 		f3 hL[kNeeDepths];

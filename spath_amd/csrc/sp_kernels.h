@@ -9,6 +9,8 @@
 
 #include "sp_device_math.h"
 
+#include <type_traits>
+
 namespace sp {
 
 // scan record: 48 B = 3 x float4, produced by k_repack
@@ -46,7 +48,6 @@ struct AccumArgs {
 	float* sum;                // n_rays * 3, AoS like out_accum
 	uint32_t sample_base;
 };
-SP_DEV const AccumArgs& accum_args(const AccumArgs& p) { return p; }
 
 // adaptive sampling (sphip_accum_begin_adaptive, sp_adaptive.h): a progressive launch over the still-active pixels only.  Ray k
 // of the launch is local pixel list[k]: the host gathers the active rays into a dense buffer in list order, so the ray reads
@@ -85,31 +86,47 @@ constexpr int kMisDepths = 5;                                     // MIS traces 
 constexpr float kTwoPi = (float)(2.0 * kPi);
 constexpr float kPiSq = (float)(kPi * kPi);
 
-template <typename... Acc> struct IsAdapt { static constexpr bool value = false; };
-template <> struct IsAdapt<AdaptArgs> { static constexpr bool value = true; };
-template <> struct IsAdapt<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
-template <> struct IsAdapt<AdaptArgs, MisArgs> { static constexpr bool value = true; };
-template <typename... Acc> struct IsNee { static constexpr bool value = false; };
-template <> struct IsNee<NeeArgs> { static constexpr bool value = true; };
-template <> struct IsNee<AccumArgs, NeeArgs> { static constexpr bool value = true; };
-template <> struct IsNee<AdaptArgs, NeeArgs> { static constexpr bool value = true; };
-template <> struct IsNee<MisArgs> { static constexpr bool value = true; };
-template <> struct IsNee<AccumArgs, MisArgs> { static constexpr bool value = true; };
-template <> struct IsNee<AdaptArgs, MisArgs> { static constexpr bool value = true; };
-template <typename... Acc> struct IsMis { static constexpr bool value = false; };
-template <> struct IsMis<MisArgs> { static constexpr bool value = true; };
-template <> struct IsMis<AccumArgs, MisArgs> { static constexpr bool value = true; };
-template <> struct IsMis<AdaptArgs, MisArgs> { static constexpr bool value = true; };
+// ---- view::camera::get_viewport (view.h:94-132) on the device: one thread per pixel.
+// The eight step constants are computed on the host in the reference's mixed double/float way (view.h:101-108).
+struct ViewArgs {
+	float x_max, x_step, h_x_step, y_max, y_step, h_y_step;
+	float focal, cos_y, sin_y, cos_x, sin_x;
+	float px, py, pz;
+	uint32_t res_x, res_y;
+	// which pixels: ray k of the output is global pixel pixel_base + (k / tile_px) * tile_stride_px + k % tile_px (sphip_shard);
+	// the whole image is {0, res_x*res_y, 0} with n_local = res_x*res_y
+	uint64_t pixel_base, tile_px, tile_stride_px;
+	uint32_t n_local;
+};
+// per-sample camera rays (SPHIP_FLAG_CAMERA_SAMPLES): the viewport constants (the shard fields unused: the
+// kernels key the ray by the global pixel they already know) and the lens.  It rides as the LAST element of the trailing pack:
+// k_pt<V, CamArgs>, k_pt_filter<R, S, SCAN, AccumArgs, NeeArgs, CamArgs>, ...  Every sample's primary ray is then generated from
+// (seed, global pixel, global sample) instead of being read from KArgs::rays.
+struct CamArgs {
+	ViewArgs v;
+	float aperture;            // lens radius on the image plane, 0 = pinhole
+	float focus_dist;          // local z of the plane in focus (aperture > 0)
+};
+
+// the pack's optional elements, found by type wherever they sit (MisArgs is a NeeArgs, AdaptArgs an AccumArgs)
+template <typename T, typename... P> struct PackHas { static constexpr bool value = (std::is_same<T, P>::value || ...); };
+template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHas<AdaptArgs, Acc...>::value; };
+template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
+template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
+template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
 // a running sum rides in the pack (progressive or adaptive)
-template <typename... Acc> struct HasAccum { static constexpr bool value = sizeof...(Acc) > (IsNee<Acc...>::value ? 1u : 0u); };
-SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p) { return p; }
-SP_DEV const AdaptArgs& adapt_args(const AdaptArgs& p, const NeeArgs&) { return p; }
-SP_DEV const AccumArgs& accum_args(const AccumArgs& p, const NeeArgs&) { return p; }
-SP_DEV const NeeArgs& nee_args(const NeeArgs& n) { return n; }
-SP_DEV const NeeArgs& nee_args(const AccumArgs&, const NeeArgs& n) { return n; }
-SP_DEV const NeeArgs& nee_args(const AdaptArgs&, const NeeArgs& n) { return n; }
-SP_DEV const float* mis_tipdf(const MisArgs& m) { return m.tipdf; }
-SP_DEV const float* mis_tipdf(const AccumArgs&, const MisArgs& m) { return m.tipdf; }
+template <typename... Acc> struct HasAccum { static constexpr bool value = PackHas<AccumArgs, Acc...>::value || IsAdapt<Acc...>::value; };
+// the first element of the pack that is a T
+template <typename T, typename H, typename... R>
+SP_DEV const T& pack_get(const H& h, const R&... r) {
+	if constexpr (std::is_base_of<T, H>::value) return h;
+	else return pack_get<T>(r...);
+}
+template <typename... P> SP_DEV const AdaptArgs& adapt_args(const P&... p) { return pack_get<AdaptArgs>(p...); }
+template <typename... P> SP_DEV const AccumArgs& accum_args(const P&... p) { return pack_get<AccumArgs>(p...); }
+template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return pack_get<NeeArgs>(p...); }
+template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
+template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
 template <typename... Acc>
 SP_DEV uint32_t local_px(uint32_t k, const Acc&... acc_args) {
@@ -188,19 +205,6 @@ __global__ void __launch_bounds__(256) k_repack(const float* __restrict__ tris, 
 	atomicMax(bounds, __float_as_uint(r) & 0x7fffffffu);
 }
 
-// ---- view::camera::get_viewport (view.h:94-132) on the device: one thread per pixel.
-// The eight step constants are computed on the host in the reference's mixed double/float way (view.h:101-108).
-struct ViewArgs {
-	float x_max, x_step, h_x_step, y_max, y_step, h_y_step;
-	float focal, cos_y, sin_y, cos_x, sin_x;
-	float px, py, pz;
-	uint32_t res_x, res_y;
-	// which pixels: ray k of the output is global pixel pixel_base + (k / tile_px) * tile_stride_px + k % tile_px (sphip_shard);
-	// the whole image is {0, res_x*res_y, 0} with n_local = res_x*res_y
-	uint64_t pixel_base, tile_px, tile_stride_px;
-	uint32_t n_local;
-};
-
 SP_DEV f3 cam_rel_move(const ViewArgs& v, f3 in) {                               // view.h:83-85 = rY(rX(in))
 	const f3 a = mk3(in.x, in.y * v.cos_x + in.z * -v.sin_x, in.y * v.sin_x + in.z * v.cos_x);   // :62-68
 	return mk3(a.x * v.cos_y + a.z * v.sin_y, a.y, a.x * -v.sin_y + a.z * v.cos_y);              // :54-60
@@ -217,6 +221,43 @@ __global__ void __launch_bounds__(256) k_viewport(const ViewArgs v, float* __res
 	const float l = __builtin_sqrtf(t.x * t.x + t.y * t.y + t.z * t.z);           // geom.h:130-136 (IEEE sqrt)
 	const f3 dir = cam_rel_move(v, mk3(t.x / l, t.y / l, t.z / l));               // :138-141 then view.h:127
 	const f3 pos = add3(cam_rel_move(v, cur), mk3(v.px, v.py, v.pz));             // view.h:126,131
+	float* o = rays + (size_t)k * 6;
+	o[0] = pos.x; o[1] = pos.y; o[2] = pos.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z;
+}
+
+// ---- the primary ray of (global pixel p, global sample) with SPHIP_FLAG_CAMERA_SAMPLES (include/spath_hip.h):
+// k_viewport's pinhole ray at a box-filtered position in the pixel and, with a lens, from a point of the lens disk (on the image
+// plane) through the point in focus at local z = focus_dist.  f32 throughout except where the reference's own draws are double.
+SP_DEV void camera_ray(const CamArgs& c, uint64_t seed, uint32_t p, uint32_t sample, f3& pos, f3& dir) {
+	const ViewArgs& v = c.v;
+	const uint32_t i = p % v.res_x, j = p / v.res_x;
+	double r1, r2;
+	philox_uniforms(seed, p, sample, 24u, &r1, &r2);
+	const f3 cur = mk3((v.x_max - v.x_step * (float)i) - v.x_step * (float)r1, (v.y_max - v.y_step * (float)j) - v.y_step * (float)r2, 0.0f);
+	const f3 t = add3(cur, mk3(0.0f, 0.0f, v.focal));
+	f3 o = cur, g = t;
+	if (c.aperture > 0.0f) {
+		double r3, r4;
+		philox_uniforms(seed, p, sample, 25u, &r3, &r4);
+		const float rho = c.aperture * (float)__builtin_sqrt(r3);
+		const float phi = (float)((r4 * kPi) * 2.0);                 // as geom.h:167
+		float sn, cs;
+		sincos_glibc(phi, &sn, &cs);
+		o = mk3(cur.x + rho * cs, cur.y + rho * sn, 0.0f);
+		const float kf = c.focus_dist / v.focal;
+		g = sub3(add3(cur, scale3(t, kf)), o);                          // F - o, F = cur + t * k
+	}
+	const float l = __builtin_sqrtf(dot3(g, g));
+	dir = cam_rel_move(v, mk3(g.x / l, g.y / l, g.z / l));
+	pos = add3(cam_rel_move(v, o), mk3(v.px, v.py, v.pz));
+}
+
+// sphip_camera_rays_device: the rays of one sample for the whole image, ray k = global pixel k
+__global__ void __launch_bounds__(256) k_camera_rays(const CamArgs c, uint64_t seed, uint32_t sample, float* __restrict__ rays) {
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	if (k >= c.v.n_local) return;
+	f3 pos, dir;
+	camera_ray(c, seed, k, sample, pos, dir);
 	float* o = rays + (size_t)k * 6;
 	o[0] = pos.x; o[1] = pos.y; o[2] = pos.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z;
 }
@@ -466,14 +507,18 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = k < a.n_rays;
 	const uint32_t kk = valid ? k : a.n_rays - 1;
-	const float* r = a.rays + (size_t)kk * 6;
-	const f3 po = mk3(r[0], r[1], r[2]), pdir = mk3(r[3], r[4], r[5]);
+	constexpr bool cam = IsCam<Acc...>::value;                   // per-sample camera rays (CamArgs): KArgs::rays is not read
+	f3 po = mk3(0.0f, 0.0f, 0.0f), pdir = po;
+	if constexpr (!cam) {
+		const float* r = a.rays + (size_t)kk * 6;
+		po = mk3(r[0], r[1], r[2]); pdir = mk3(r[3], r[4], r[5]);
+	}
 	constexpr bool adapt = IsAdapt<Acc...>::value;
 	constexpr bool nee = IsNee<Acc...>::value;
 	constexpr bool mis = IsMis<Acc...>::value;                   // MIS: nee too; the folded terms D_0..D_4
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
-	const bool reuse = (a.flags & 0x100u) != 0;
+	const bool reuse = !cam && (a.flags & 0x100u) != 0;          // the host rejects reuse with camera samples
 
 	uint32_t my_scans = 0;
 	// optional primary-hit reuse: the primary ray is the same for every sample (:74-76)
@@ -497,6 +542,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	}
 	for (uint32_t s = 0; s < a.n_samples; ++s) {
 		f3 o = po, dir = pdir;
+		if constexpr (cam) camera_ray(cam_args(acc_args...), a.seed, pixel, s0 + s, o, dir);
 		int src = -1;
 		int idx0 = -1, idx1 = -1, idx2 = -1, idx3 = -1, idx4 = -1;
 		float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f;

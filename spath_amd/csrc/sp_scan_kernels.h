@@ -116,6 +116,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	constexpr bool nee = IsNee<Acc...>::value;               // next-event estimation: L_d parked in NeeArgs::L (sp_kernels.h)
 	static_assert(!nee || SCAN >= 2, "NEE needs the bounded form of the scan");
 	constexpr bool mis = IsMis<Acc...>::value;               // MIS: D_d parked in NeeArgs::L for d = 0..4 (sp_kernels.h MisArgs)
+	constexpr bool cam = IsCam<Acc...>::value;               // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -141,7 +142,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	}
 	// primary-hit reuse: cpu_renderer.cpp:74-76 starts every sample from the same vp.rays[idx], so the first
 	// scan of all samples of a pixel has one result; the host ran it once per pixel (k_hit_filter) before this launch
-	const bool reuse = a.prim_idx != nullptr;
+	const bool reuse = !cam && a.prim_idx != nullptr;           // the host rejects reuse with camera samples
 	uint32_t my_scans = 0;
 	float pd[R]; int pi[R];
 #pragma unroll
@@ -171,8 +172,11 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			const uint32_t k = kr0 + r * kstep;
 			smp[r] = SPLIT ? it * R + r : it;
 			live[r] = (k < a.n_rays) && (smp[r] < a.n_samples);
-			const float* pr = a.rays + (size_t)(k < a.n_rays ? k : a.n_rays - 1) * 6;
-			s.o[r] = mk3(pr[0], pr[1], pr[2]); s.dir[r] = mk3(pr[3], pr[4], pr[5]);
+			if constexpr (cam) camera_ray(cam_args(acc_args...), a.seed, pixel[r], s0 + smp[r], s.o[r], s.dir[r]);
+			else {
+				const float* pr = a.rays + (size_t)(k < a.n_rays ? k : a.n_rays - 1) * 6;
+				s.o[r] = mk3(pr[0], pr[1], pr[2]); s.dir[r] = mk3(pr[3], pr[4], pr[5]);
+			}
 			s.src[r] = -1; s.act[r] = live[r];
 			nh[r] = 0;
 		}

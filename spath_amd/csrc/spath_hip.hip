@@ -97,6 +97,12 @@ struct sphip_ctx {
 	double nee_W = 0.0;
 	std::string nee_msg;
 	bool dn_gbuf_ok = false;                      // dropped by every accumulation begin
+	// ---- camera samples (SPHIP_FLAG_CAMERA_SAMPLES): the lens of later renders (sphip_set_lens; the parent's on a multi-device context),
+	// and what an accumulation begun with a camera captured: the camera and the lens of its begin
+	sphip_lens lens{};
+	sphip_lens acc_lens{};
+	sphip_camera acc_cam{};
+	bool acc_has_cam = false;
 };
 
 namespace {
@@ -383,7 +389,8 @@ constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 // [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
 int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
                   size_t n_samples, uint64_t seed, int mode, int flags, void* d_rgba, void* d_accum, hipStream_t st,
-                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr, const sp::AdaptArgs* adapt = nullptr) {
+                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr, const sp::AdaptArgs* adapt = nullptr,
+                  const sp::CamArgs* cams = nullptr) {
 	if (adapt) prog = adapt;                        // an adaptive launch is a progressive one over the active list (sp_kernels.h)
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
 	if (!d_rays || !d_rgba) return fail(c, SPHIP_E_INVALID, "null ray or output pointer");
@@ -441,6 +448,16 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ne.n = c->nee_n;
 		ne.W = c->nee_W;
 	}
+	// per-sample camera rays: path tracing behind a camera, with the shipped variants, without primary-hit reuse (the
+	// primary ray is no longer shared by the samples); flat and hit queries ignore the flag
+	const bool camf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_CAMERA_SAMPLES);
+	if (camf && !cams)
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (sphip_render_camera, sphip_accum_begin[_adaptive] with cam), not rays");
+	if (camf && (flags & SPHIP_FLAG_PRIMARY_REUSE))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
+	if (camf && !(variant == 1 || variant == 2 || variant == kVariantAccel || variant == 15 || variant == 16))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+	if (!camf) cams = nullptr;
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -553,19 +570,77 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		static_cast<sp::NeeArgs&>(me) = ne;
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
 	}
-	if (variant == kVariantAccel) {
-		if (mode == kModeHits)           hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
-		else if (mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
-		else if (mis && adapt)            hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad, me);
-		else if (mis && prog)             hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog, me);
-		else if (mis)                     hipLaunchKernelGGL((sp::k_accel<1, sp::MisArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, me);
-		else if (nee && adapt)            hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad, ne);
-		else if (nee && prog)             hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog, ne);
-		else if (nee)                     hipLaunchKernelGGL((sp::k_accel<1, sp::NeeArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ne);
-		else if (adapt)                   hipLaunchKernelGGL((sp::k_accel<1, sp::AdaptArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, ad);
-		else if (prog)                    hipLaunchKernelGGL((sp::k_accel<1, sp::AccumArgs>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr, *prog);
-		else                              hipLaunchKernelGGL(sp::k_accel<1>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
-	} else if (mode == kModeHits) {
+	// path tracing; cam_tail: nothing, or the CamArgs of per-sample camera rays as the pack's last element (sp_kernels.h)
+	auto launch_pt = [&](const auto&... cam_tail) {
+		constexpr bool with_cam = sizeof...(cam_tail) > 0;
+		if (variant == kVariantAccel) {
+#define SP_ACC(...) hipLaunchKernelGGL((sp::k_accel<1, ##__VA_ARGS__, std::decay_t<decltype(cam_tail)>...>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr
+			if (mis && adapt)       SP_ACC(sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
+			else if (mis && prog)   SP_ACC(sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
+			else if (mis)           SP_ACC(sp::MisArgs), me, cam_tail...);
+			else if (nee && adapt)  SP_ACC(sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
+			else if (nee && prog)   SP_ACC(sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
+			else if (nee)           SP_ACC(sp::NeeArgs), ne, cam_tail...);
+			else if (adapt)         SP_ACC(sp::AdaptArgs), ad, cam_tail...);
+			else if (prog)          SP_ACC(sp::AccumArgs), *prog, cam_tail...);
+			else                    SP_ACC(), cam_tail...);
+#undef SP_ACC
+		} else if (is_ts) {
+#define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, cam_tail...); \
+                                   else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, cam_tail...); \
+                                   else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, cam_tail...); } while (0)
+#define SP_PTN(R_, SPLIT_, S_, T_, V_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, V_, cam_tail...); \
+                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, V_, cam_tail...); \
+                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, V_, cam_tail...); } while (0)
+			if (mis && ts.scan == 3) SP_PTN(1, false, 3, sp::MisArgs, me);
+			else if (mis && ts.scan == 4) SP_PTN(1, false, 4, sp::MisArgs, me);
+			else if (mis) SP_PTN(4, true, 2, sp::MisArgs, me);               // variant 15 (checked above)
+			else if (nee && ts.scan == 3) SP_PTN(1, false, 3, sp::NeeArgs, ne);
+			else if (nee && ts.scan == 4) SP_PTN(1, false, 4, sp::NeeArgs, ne);
+			else if (nee) SP_PTN(4, true, 2, sp::NeeArgs, ne);               // variant 15 (checked above)
+#undef SP_PTN
+			else if (ts.scan == 3) SP_PT(1, false, 3);
+			else if (ts.scan == 4) SP_PT(1, false, 4);
+			else if (ts.scan == 2 && ts.split) SP_PT(4, true, 2);
+#ifdef SP_ALL_VARIANTS
+			else if constexpr (!with_cam) {                                 // camera samples: the shipped variants only (checked above)
+				if (ts.scan == 2) SP_PT(4, false, 2);
+				else if (ts.scan == 0) {
+					if (ts.split) { if (ts.R == 4) SP_PT(4, true, 0); else SP_PT(2, true, 0); }
+					else          { if (ts.R == 4) SP_PT(4, false, 0); else if (ts.R == 2) SP_PT(2, false, 0); else SP_PT(1, false, 0); }
+				} else {
+					if (ts.split) { if (ts.R == 4) SP_PT(4, true, 1); else SP_PT(2, true, 1); }
+					else          { if (ts.R == 4) SP_PT(4, false, 1); else if (ts.R == 2) SP_PT(2, false, 1); else SP_PT(1, false, 1); }
+				}
+			}
+#endif
+#undef SP_PT
+		} else {
+#define SP_KPT(V_, ...) hipLaunchKernelGGL((sp::k_pt<V_, ##__VA_ARGS__, std::decay_t<decltype(cam_tail)>...>), grid, block, 0, st, a
+			if (mis && adapt && variant == 2)      SP_KPT(2, sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
+			else if (mis && adapt)                SP_KPT(1, sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
+			else if (mis && prog && variant == 2) SP_KPT(2, sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
+			else if (mis && prog)                 SP_KPT(1, sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
+			else if (mis && variant == 2)         SP_KPT(2, sp::MisArgs), me, cam_tail...);
+			else if (mis)                         SP_KPT(1, sp::MisArgs), me, cam_tail...);
+			else if (nee && adapt && variant == 2) SP_KPT(2, sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
+			else if (nee && adapt)                SP_KPT(1, sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
+			else if (nee && prog && variant == 2) SP_KPT(2, sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
+			else if (nee && prog)                 SP_KPT(1, sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
+			else if (nee && variant == 2)         SP_KPT(2, sp::NeeArgs), ne, cam_tail...);
+			else if (nee)                         SP_KPT(1, sp::NeeArgs), ne, cam_tail...);
+			else if (adapt && variant == 2)       SP_KPT(2, sp::AdaptArgs), ad, cam_tail...);
+			else if (adapt)                       SP_KPT(1, sp::AdaptArgs), ad, cam_tail...);
+			else if (prog && variant == 2)        SP_KPT(2, sp::AccumArgs), *prog, cam_tail...);
+			else if (prog)                        SP_KPT(1, sp::AccumArgs), *prog, cam_tail...);
+			else if (variant == 2)                SP_KPT(2), cam_tail...);
+			else                                  SP_KPT(1), cam_tail...);
+#undef SP_KPT
+		}
+	};
+	if (variant == kVariantAccel && mode == kModeHits) hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
+	else if (variant == kVariantAccel && mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
+	else if (mode == kModeHits) {
 		int* oi = (int*)d_rgba; float* od = (float*)d_accum;
 		if (is_ts) {
 #define SP_HIT(R_, S_) hipLaunchKernelGGL((sp::k_hit_filter<R_, S_>), grid_px, block_ts, 0, st, a, src2, bnd, d_src, oi, od)
@@ -594,55 +669,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		}
 		else if (variant == 2) hipLaunchKernelGGL(sp::k_flat<2>, grid, block, 0, st, a);
 		else                   hipLaunchKernelGGL(sp::k_flat<1>, grid, block, 0, st, a);
-	} else {
-		if (is_ts) {
-#define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad); \
-                                   else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog); \
-                                   else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work); } while (0)
-#define SP_PTN(R_, SPLIT_, S_, T_, V_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, V_); \
-                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, V_); \
-                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, T_>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, V_); } while (0)
-			if (mis && ts.scan == 3) SP_PTN(1, false, 3, sp::MisArgs, me);
-			else if (mis && ts.scan == 4) SP_PTN(1, false, 4, sp::MisArgs, me);
-			else if (mis) SP_PTN(4, true, 2, sp::MisArgs, me);               // variant 15 (checked above)
-			else if (nee && ts.scan == 3) SP_PTN(1, false, 3, sp::NeeArgs, ne);
-			else if (nee && ts.scan == 4) SP_PTN(1, false, 4, sp::NeeArgs, ne);
-			else if (nee) SP_PTN(4, true, 2, sp::NeeArgs, ne);               // variant 15 (checked above)
-#undef SP_PTN
-			else if (ts.scan == 3) SP_PT(1, false, 3);
-			else if (ts.scan == 4) SP_PT(1, false, 4);
-			else if (ts.scan == 2 && ts.split) SP_PT(4, true, 2);
-#ifdef SP_ALL_VARIANTS
-			else if (ts.scan == 2) SP_PT(4, false, 2);
-			else if (ts.scan == 0) {
-				if (ts.split) { if (ts.R == 4) SP_PT(4, true, 0); else SP_PT(2, true, 0); }
-				else          { if (ts.R == 4) SP_PT(4, false, 0); else if (ts.R == 2) SP_PT(2, false, 0); else SP_PT(1, false, 0); }
-			} else {
-				if (ts.split) { if (ts.R == 4) SP_PT(4, true, 1); else SP_PT(2, true, 1); }
-				else          { if (ts.R == 4) SP_PT(4, false, 1); else if (ts.R == 2) SP_PT(2, false, 1); else SP_PT(1, false, 1); }
-			}
-#endif
-#undef SP_PT
-		}
-		else if (mis && adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, ad, me);
-		else if (mis && adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs, sp::MisArgs>), grid, block, 0, st, a, ad, me);
-		else if (mis && prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, *prog, me);
-		else if (mis && prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs, sp::MisArgs>), grid, block, 0, st, a, *prog, me);
-		else if (mis && variant == 2)         hipLaunchKernelGGL((sp::k_pt<2, sp::MisArgs>), grid, block, 0, st, a, me);
-		else if (mis)                         hipLaunchKernelGGL((sp::k_pt<1, sp::MisArgs>), grid, block, 0, st, a, me);
-		else if (nee && adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
-		else if (nee && adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs, sp::NeeArgs>), grid, block, 0, st, a, ad, ne);
-		else if (nee && prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, *prog, ne);
-		else if (nee && prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs, sp::NeeArgs>), grid, block, 0, st, a, *prog, ne);
-		else if (nee && variant == 2)         hipLaunchKernelGGL((sp::k_pt<2, sp::NeeArgs>), grid, block, 0, st, a, ne);
-		else if (nee)                         hipLaunchKernelGGL((sp::k_pt<1, sp::NeeArgs>), grid, block, 0, st, a, ne);
-		else if (adapt && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AdaptArgs>), grid, block, 0, st, a, ad);
-		else if (adapt)                hipLaunchKernelGGL((sp::k_pt<1, sp::AdaptArgs>), grid, block, 0, st, a, ad);
-		else if (prog && variant == 2) hipLaunchKernelGGL((sp::k_pt<2, sp::AccumArgs>), grid, block, 0, st, a, *prog);
-		else if (prog)                 hipLaunchKernelGGL((sp::k_pt<1, sp::AccumArgs>), grid, block, 0, st, a, *prog);
-		else if (variant == 2) hipLaunchKernelGGL(sp::k_pt<2>, grid, block, 0, st, a);
-		else                   hipLaunchKernelGGL(sp::k_pt<1>, grid, block, 0, st, a);
-	}
+	} else if (cams) launch_pt(*cams);
+	else launch_pt();
 	if (chunks > 1 && adapt) hipLaunchKernelGGL((sp::k_resolve<sp::AdaptArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, ad);
 	else if (chunks > 1 && prog) hipLaunchKernelGGL((sp::k_resolve<sp::AccumArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, *prog);
 	else if (chunks > 1) hipLaunchKernelGGL(sp::k_resolve<>, dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a);
@@ -658,13 +686,10 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 }
 
 
-// ---- view::camera::get_viewport on the device for the pixels of a shard (sp_kernels.h: k_viewport)
-int launch_viewport(sphip_ctx* c, const sphip_camera* cam, void* d_rays, hipStream_t st, const sphip_shard* shard = nullptr, size_t n_local = 0) {
-	if (!cam || !d_rays) return fail(c, SPHIP_E_INVALID, "null camera or ray pointer");
-	if (cam->res_x == 0 || cam->res_y == 0 || (uint64_t)cam->res_x * cam->res_y > 0xffffffffull)
-		return fail(c, SPHIP_E_INVALID, "bad viewport size %ux%u", cam->res_x, cam->res_y);
+// the viewport constants of view::camera::get_viewport (view.h:101-108: `real` (float) variables initialised from double expressions);
+// the shard fields are the whole image
+sp::ViewArgs view_args(const sphip_camera* cam) {
 	sp::ViewArgs v{};
-	// view.h:101-108: `real` (float) variables initialised from double expressions
 	const float x_size = (float)(1.0 * (double)cam->res_x / (double)cam->res_y), y_size = 1.0f;
 	v.x_max = (float)((double)x_size / 2.0);
 	v.x_step = x_size / (float)cam->res_x;
@@ -675,6 +700,26 @@ int launch_viewport(sphip_ctx* c, const sphip_camera* cam, void* d_rays, hipStre
 	v.focal = cam->focal; v.cos_y = cam->cos_y; v.sin_y = cam->sin_y; v.cos_x = cam->cos_x; v.sin_x = cam->sin_x;
 	v.px = cam->pos[0]; v.py = cam->pos[1]; v.pz = cam->pos[2];
 	v.res_x = cam->res_x; v.res_y = cam->res_y;
+	v.n_local = cam->res_x * cam->res_y;
+	v.pixel_base = 0; v.tile_px = v.n_local; v.tile_stride_px = 0;
+	return v;
+}
+
+// the trailing kernel argument of per-sample camera rays (sp_kernels.h CamArgs): the camera's viewport constants and a lens
+sp::CamArgs cam_args_of(const sphip_camera* cam, const sphip_lens& lens) {
+	sp::CamArgs ca{};
+	ca.v = view_args(cam);
+	ca.aperture = lens.aperture;
+	ca.focus_dist = lens.focus_dist;
+	return ca;
+}
+
+// ---- view::camera::get_viewport on the device for the pixels of a shard (sp_kernels.h: k_viewport)
+int launch_viewport(sphip_ctx* c, const sphip_camera* cam, void* d_rays, hipStream_t st, const sphip_shard* shard = nullptr, size_t n_local = 0) {
+	if (!cam || !d_rays) return fail(c, SPHIP_E_INVALID, "null camera or ray pointer");
+	if (cam->res_x == 0 || cam->res_y == 0 || (uint64_t)cam->res_x * cam->res_y > 0xffffffffull)
+		return fail(c, SPHIP_E_INVALID, "bad viewport size %ux%u", cam->res_x, cam->res_y);
+	sp::ViewArgs v = view_args(cam);
 	const uint32_t n = shard ? (uint32_t)n_local : cam->res_x * cam->res_y;
 	v.n_local = n;
 	if (shard) { v.pixel_base = shard->pixel_base; v.tile_px = shard->tile_px; v.tile_stride_px = shard->tile_stride_px; }
@@ -915,10 +960,13 @@ int multi_render(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_
 	if (mode == SPHIP_MODE_PT && (n_samples == 0 || n_samples > 0x7fffffffull))
 		return fail(c, SPHIP_E_INVALID, "n_samples must be in [1, 2^31) (the reference divides by it, cpu_renderer.cpp:77)");
 	const RowPlan plan(w, h, (int)c->kids.size(), (size_t)plan_tile_rows(h, (int)c->kids.size()));
+	sp::CamArgs ca{};
+	if (cam) ca = cam_args_of(cam, c->lens);
 	return multi_frame(c, w, h, out_rgba, out_accum, [&](sphip_ctx* k, int r, size_t n, const sphip_shard& sh) -> int {
 		int rc2;
 		if ((rc2 = ensure(k, k->rays, n * 24)) || (rc2 = deal_rays(k, plan, r, rays, cam, k->rays.p, k->own_stream))) return rc2;
-		return launch_render(k, k->rays.p, n, &sh, w, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, k->own_stream);
+		return launch_render(k, k->rays.p, n, &sh, w, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, k->own_stream,
+		                     nullptr, nullptr, nullptr, cam ? &ca : nullptr);
 	});
 }
 
@@ -954,8 +1002,9 @@ int adapt_step_dev(sphip_ctx* k, const sphip_ctx* par, size_t n, const sphip_sha
 		q.s12 = (double*)k->adp_s12.p;
 		// every pixel active: the list is the identity, the gathered rays would be the accumulation's own
 		const void* rays = na == n ? k->acc_rays.p : k->adp_rays.p;
+		const sp::CamArgs ca = cam_args_of(&par->acc_cam, par->acc_lens);
 		if ((rc = launch_render(k, rays, na, &sh, par->acc_w, n_samples, par->acc_seed, SPHIP_MODE_PT, par->acc_flags, k->rgba.p, nullptr, st,
-		                        nullptr, nullptr, &q))) return rc;
+		                        nullptr, nullptr, &q, par->acc_has_cam ? &ca : nullptr))) return rc;
 		const sp::AdaptRule rule{ par->adp_t, par->adp_floor, par->adp_min, (uint32_t)n_samples };
 		const dim3 nb((unsigned)((na + 255) / 256));
 		hipLaunchKernelGGL(sp::k_adapt_decide, nb, dim3(256), 0, st, q.list, na, (uint32_t*)k->adp_cnt.p, (const double*)q.s12, rule,
@@ -1025,10 +1074,11 @@ int multi_accum_step(sphip_ctx* c, size_t n_samples, uint8_t* out_rgba, float* o
 		c->adp_nact = (uint32_t)na;
 		return SPHIP_OK;
 	}
+	const sp::CamArgs ca = cam_args_of(&c->acc_cam, c->acc_lens);
 	return multi_frame(c, c->acc_w, c->acc_h, out_rgba, out_mean, [&](sphip_ctx* k, int, size_t n, const sphip_shard& sh) -> int {
 		const sp::AccumArgs p{ (float*)k->acc_sum.p, (uint32_t)c->acc_total };
 		return launch_render(k, k->acc_rays.p, n, &sh, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, k->rgba.p,
-		                     out_mean ? k->accum.p : nullptr, k->own_stream, nullptr, &p);
+		                     out_mean ? k->accum.p : nullptr, k->own_stream, nullptr, &p, nullptr, c->acc_has_cam ? &ca : nullptr);
 	});
 }
 
@@ -1070,6 +1120,14 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
 	c->adp_on = false;
 	c->dn_gbuf_ok = false;
+	if (flags & SPHIP_FLAG_CAMERA_SAMPLES) {       // the step would refuse them as well: say so at the begin
+		if (!cam) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (accum_begin with cam), not rays");
+		if (flags & SPHIP_FLAG_PRIMARY_REUSE)
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
+		const int v = pick_variant(flags, c->n_tris);
+		if (!(v == 1 || v == 2 || v == kVariantAccel || v == 15 || v == 16))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", v, kVariantNames[v]);
+	}
 	if (!c->kids.empty()) {
 		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
 		if (rc) return rc;
@@ -1093,6 +1151,9 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	c->acc_stale = false;
 	c->acc_w = w; c->acc_h = h;
 	c->acc_seed = seed; c->acc_flags = flags;
+	c->acc_has_cam = cam != nullptr;               // the camera and the lens of camera samples, as they are at the begin
+	if (cam) c->acc_cam = *cam;
+	c->acc_lens = c->lens;
 	c->acc_total = 0;                              // the first step's sample_base: the sum buffer's contents are not read
 	return SPHIP_OK;
 }
@@ -1601,8 +1662,11 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 			const sphip_shard whole{ 0, n, 0 };
 			if (c->adp_on) {
 				if ((rc2 = adapt_step_dev(c, c, n, whole, n_samples, out_mean ? (float*)c->accum.p : nullptr, st))) return rc2;
-			} else if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
-			                                out_mean ? c->accum.p : nullptr, st, nullptr, &p))) return rc2;
+			} else {
+				const sp::CamArgs ca = cam_args_of(&c->acc_cam, c->acc_lens);
+				if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
+				                         out_mean ? c->accum.p : nullptr, st, nullptr, &p, nullptr, c->acc_has_cam ? &ca : nullptr))) return rc2;
+			}
 			HIP_TRY(c, hipEventRecord(c->ev_d0, st));
 			HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
 			if (out_mean) HIP_TRY(c, hipMemcpyAsync(out_mean, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
@@ -1632,6 +1696,29 @@ int sphip_viewport_device(sphip_t* c, const sphip_camera* cam, void* d_rays_out,
 	return launch_viewport(c, cam, d_rays_out, (hipStream_t)stream);
 }
 
+int sphip_set_lens(sphip_t* c, const sphip_lens* lens) {
+	if (!c) return SPHIP_E_INVALID;
+	const sphip_lens l = lens ? *lens : sphip_lens{ 0.0f, 0.0f, 0 };
+	if (!std::isfinite(l.aperture) || l.aperture < 0.0f || (l.aperture > 0.0f && !(std::isfinite(l.focus_dist) && l.focus_dist > 0.0f)) || l.reserved != 0)
+		return fail(c, SPHIP_E_INVALID, "bad sphip_lens {aperture %g, focus_dist %g, reserved %u}: aperture finite and >= 0, focus_dist finite and > 0 "
+		            "when aperture > 0, reserved 0", (double)l.aperture, (double)l.focus_dist, l.reserved);
+	c->lens = l;
+	return SPHIP_OK;
+}
+
+int sphip_camera_rays_device(sphip_t* c, const sphip_camera* cam, uint64_t seed, uint32_t sample, void* d_rays_out, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (!cam || !d_rays_out) return fail(c, SPHIP_E_INVALID, "null camera or ray pointer");
+	if (cam->res_x == 0 || cam->res_y == 0 || (uint64_t)cam->res_x * cam->res_y > 0xffffffffull)
+		return fail(c, SPHIP_E_INVALID, "bad viewport size %ux%u", cam->res_x, cam->res_y);
+	HIP_TRY(c, hipSetDevice(c->device));
+	const sp::CamArgs ca = cam_args_of(cam, c->lens);
+	hipLaunchKernelGGL(sp::k_camera_rays, dim3((ca.v.n_local + 255) / 256), dim3(256), 0, (hipStream_t)stream, ca, seed, sample, (float*)d_rays_out);
+	HIP_TRY(c, hipGetLastError());
+	return SPHIP_OK;
+}
+
 int sphip_render_camera(sphip_t* c, const sphip_camera* cam, size_t n_samples, uint64_t seed, int mode, int flags,
                         uint8_t* out_rgba, float* out_accum) {
 	if (!c) return SPHIP_E_INVALID;
@@ -1644,7 +1731,9 @@ int sphip_render_camera(sphip_t* c, const sphip_camera* cam, size_t n_samples, u
 	if ((rc = ensure(c, c->rays, (n ? n : 1) * 24)) || (rc = ensure(c, c->rgba, (n ? n : 1) * 4))) return rc;
 	if (out_accum && (rc = ensure(c, c->accum, n * 12))) return rc;
 	if ((rc = launch_viewport(c, cam, c->rays.p, st))) return rc;
-	if ((rc = launch_render(c, c->rays.p, n, nullptr, cam->res_x, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st))) return rc;
+	const sp::CamArgs ca = cam_args_of(cam, c->lens);
+	if ((rc = launch_render(c, c->rays.p, n, nullptr, cam->res_x, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st,
+	                        nullptr, nullptr, nullptr, &ca))) return rc;
 	HIP_TRY(c, hipEventRecord(c->ev_d0, st));
 	HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
 	if (out_accum) HIP_TRY(c, hipMemcpyAsync(out_accum, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));

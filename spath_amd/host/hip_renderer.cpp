@@ -48,13 +48,20 @@ struct hip_r : public basic_renderer {
 	sphip_denoise dn;
 	scene::bitmap raw;
 	bool have_raw;
+	// per-sample camera rays (set_camera_samples, set_lens): SPHIP_FLAG_CAMERA_SAMPLES on the camera path (render_own_viewport) only;
+	// the lens is the context's, and the one an accumulation was begun with joins its key
+	bool cam_samples;
+	sphip_lens lens, acc_lens;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
-	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false) {
+	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
+	                                                                   cam_samples(false) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
+		std::memset(&lens, 0, sizeof lens);
+		std::memset(&acc_lens, 0, sizeof acc_lens);
 		std::memset(&dn, 0, sizeof dn);
 		std::memset(&adp, 0, sizeof adp);
 		adp.rel_error = -1.0;
@@ -99,11 +106,11 @@ struct hip_r : public basic_renderer {
 		return c;
 	}
 
-	bool same_accumulation(size_t w, size_t h) const {
-		return acc_live && acc_w == w && acc_h == h && acc_scene_hash == scene_hash && acc_scene_n == scene_n && acc_seed == seed && acc_flags == flags;
+	bool same_accumulation(size_t w, size_t h, int f) const {
+		return acc_live && acc_w == w && acc_h == h && acc_scene_hash == scene_hash && acc_scene_n == scene_n && acc_seed == seed && acc_flags == f;
 	}
 
-	void begin(const float* rays, const sphip_camera* cam, size_t w, size_t h) {
+	void begin(const float* rays, const sphip_camera* cam, size_t w, size_t h, int flags) {
 		have_raw = false;
 		if (adp.rel_error >= 0.0) check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &adp), "accum_begin_adaptive");
 		else if (dn_on) {
@@ -134,18 +141,21 @@ struct hip_r : public basic_renderer {
 		out.res_y = vc.res_y;
 		out.values.resize(out.res_x * out.res_y);
 		const sphip_camera c = camera_args();
+		const int f = cam_samples ? (flags | SPHIP_FLAG_CAMERA_SAMPLES) : flags;
 		if (progressive && mode == SPHIP_MODE_PT) {
-			if (!(same_accumulation(c.res_x, c.res_y) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0)) {
+			if (!(same_accumulation(c.res_x, c.res_y, f) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0 &&
+			      std::memcmp(&lens, &acc_lens, sizeof lens) == 0)) {
 				acc_live = false;
-				begin(0, &c, c.res_x, c.res_y);
-				begun(c.res_x, c.res_y, true);
+				begin(0, &c, c.res_x, c.res_y, f);
+				begun(c.res_x, c.res_y, true, f);
 				acc_camera = c;
+				acc_lens = lens;
 				acc_rays.clear();
 			}
 			accum_step(n_samples, out);
 			return;
 		}
-		check(sphip_render_camera(ctx, &c, n_samples, seed, mode, flags, (uint8_t*)out.values.data(), 0), "render_camera");
+		check(sphip_render_camera(ctx, &c, n_samples, seed, mode, f, (uint8_t*)out.values.data(), 0), "render_camera");
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
 	}
 
@@ -159,11 +169,11 @@ struct hip_r : public basic_renderer {
 		if (vp.rays.size() != out.values.size()) throw std::runtime_error("hip_renderer: viewport size and ray count disagree");
 		if (progressive && mode == SPHIP_MODE_PT) {
 			// the rays are compared bit for bit with those the accumulation was begun with
-			if (!(same_accumulation(vp.res_x, vp.res_y) && !acc_cam && acc_rays.size() == vp.rays.size() &&
+			if (!(same_accumulation(vp.res_x, vp.res_y, flags) && !acc_cam && acc_rays.size() == vp.rays.size() &&
 			      std::memcmp(acc_rays.data(), vp.rays.data(), vp.rays.size() * sizeof(geom::ray)) == 0)) {
 				acc_live = false;
-				begin((const float*)vp.rays.data(), 0, vp.res_x, vp.res_y);
-				begun(vp.res_x, vp.res_y, false);
+				begin((const float*)vp.rays.data(), 0, vp.res_x, vp.res_y, flags);
+				begun(vp.res_x, vp.res_y, false, flags);
 				acc_rays.assign(vp.rays.begin(), vp.rays.end());
 			}
 			accum_step(n_samples, out);
@@ -174,11 +184,11 @@ struct hip_r : public basic_renderer {
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
 	}
 
-	void begun(size_t w, size_t h, bool cam) {
+	void begun(size_t w, size_t h, bool cam, int f) {
 		acc_live = true; acc_cam = cam;
 		acc_w = w; acc_h = h;
 		acc_scene_hash = scene_hash; acc_scene_n = scene_n;
-		acc_seed = seed; acc_flags = flags;
+		acc_seed = seed; acc_flags = f;
 	}
 
 	virtual void render_flat(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris, const size_t n_samples, scene::bitmap& out) {
@@ -229,6 +239,21 @@ namespace hip_renderer {
 	void set_mis(scene::renderer* r, bool on) {
 		const int f = SPHIP_FLAG_NEE | SPHIP_FLAG_MIS;
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->flags = on ? (p->flags | f) : (p->flags & ~SPHIP_FLAG_MIS);
+	}
+
+	void set_camera_samples(scene::renderer* r, bool on) {
+		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->cam_samples = on;
+	}
+
+	void set_lens(scene::renderer* r, float aperture, float focus_dist) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		sphip_lens l;
+		std::memset(&l, 0, sizeof l);
+		l.aperture = aperture;
+		l.focus_dist = focus_dist;
+		p->check(sphip_set_lens(p->ctx, &l), "set_lens");
+		p->lens = l;
 	}
 
 	void set_progressive(scene::renderer* r, bool on) {

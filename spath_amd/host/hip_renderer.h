@@ -29,6 +29,12 @@ namespace hip_renderer {
 	// next-event estimation with multiple importance sampling (SPHIP_FLAG_NEE | SPHIP_FLAG_MIS): on sets both flags, off clears
 	// SPHIP_FLAG_MIS only (NEE stays as set_nee left it); the same image again, without NEE's fireflies
 	extern void set_mis(scene::renderer* r, bool on);
+	// per-sample camera rays (SPHIP_FLAG_CAMERA_SAMPLES; include/spath_hip.h "camera samples"): pixel antialiasing and, with a lens,
+	// depth of field.  Honoured by render_own_viewport only: render() takes the caller's rays and renders exactly as without it.
+	extern void set_camera_samples(scene::renderer* r, bool on);
+	// the thin lens of camera samples (sphip_set_lens): aperture 0 = pinhole; throws std::runtime_error on values the library refuses.
+	// The lens joins the key of a progressive accumulation on the camera path
+	extern void set_lens(scene::renderer* r, float aperture, float focus_dist);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

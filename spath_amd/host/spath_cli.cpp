@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -17,11 +17,14 @@
 //   the format --out would use for that name
 // --nee: next-event estimation (include/spath_hip.h: SPHIP_FLAG_NEE); combines with --progressive, --adaptive and --denoise
 // --mis: next-event estimation with multiple importance sampling (SPHIP_FLAG_NEE | SPHIP_FLAG_MIS); implies --nee
+// --aa: per-sample camera rays, box-filtered in the pixel (SPHIP_FLAG_CAMERA_SAMPLES); --lens A,F: a thin lens of aperture A focused at
+//   F (sphip_lens; implies --aa).  Both render through the device-generated viewport (as --device-viewport)
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -138,7 +141,8 @@ int main(int argc, char** argv) {
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
 		int w = 640, h = 480, frames = 1, flags = 0;                 // window default of the reference (main.cpp:238-239)
-		bool nee = false, mis = false;
+		bool nee = false, mis = false, aa = false;
+		float lens_a = 0.0f, lens_f = 0.0f;
 		size_t spp = 128;                                            // main.cpp:44
 		size_t progressive = 0;
 		double adp_t = -1.0, adp_floor = 0.1;                        // --adaptive defaults: FLOOR 0.1, MIN 8
@@ -162,6 +166,18 @@ int main(int argc, char** argv) {
 			else if (k == "--primary-reuse") flags |= SPHIP_FLAG_PRIMARY_REUSE;   // one primary scan per pixel (identical image)
 			else if (k == "--nee") nee = true;                                   // next-event estimation (SPHIP_FLAG_NEE)
 			else if (k == "--mis") mis = true;                                   // ... with MIS (SPHIP_FLAG_MIS, implies --nee)
+			else if (k == "--aa") aa = true;                                     // per-sample camera rays (SPHIP_FLAG_CAMERA_SAMPLES)
+			else if (k == "--lens") {                                            // A,F: thin lens (implies --aa)
+				need(1);
+				const char* p = argv[++i];
+				char* e = 0;
+				lens_a = std::strtof(p, &e);
+				if (e == p || *e != ',' || !std::isfinite(lens_a) || lens_a < 0.0f) throw std::runtime_error("bad --lens value (A,F: aperture A >= 0, focus distance F > 0)");
+				p = e + 1;
+				lens_f = std::strtof(p, &e);
+				if (e == p || *e || !std::isfinite(lens_f) || !(lens_f > 0.0f)) throw std::runtime_error("bad --lens value (A,F: aperture A >= 0, focus distance F > 0)");
+				aa = true;
+			}
 			else if (k == "--progressive") { need(1); progressive = (size_t)std::atoll(argv[++i]); }
 			else if (k == "--adaptive") {
 				need(1);
@@ -212,6 +228,9 @@ int main(int argc, char** argv) {
 		hip_renderer::set_flags(r.get(), flags);
 		hip_renderer::set_nee(r.get(), nee);
 		if (mis) hip_renderer::set_mis(r.get(), true);
+		hip_renderer::set_camera_samples(r.get(), aa);
+		hip_renderer::set_lens(r.get(), lens_a, lens_f);
+		if (aa) device_viewport = true;                                  // camera samples live on the camera path
 		if (adp_t >= 0.0 && !(progressive && mode == "pt")) throw std::runtime_error("--adaptive needs --progressive n and --mode pt");
 		if (!counts_path.empty() && !(progressive && mode == "pt")) throw std::runtime_error("--counts-out needs --progressive n and --mode pt");
 		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);
