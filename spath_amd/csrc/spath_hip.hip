@@ -153,16 +153,26 @@ bool two_stage(int variant, TwoStage* out) {
 	return true;
 }
 
-// The shipped library carries the exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15) and the
-// default (16).  The slab-filter generation and the per-lane cylinder variants are compiled only with -DSP_ALL_VARIANTS (soak and
-// experiment builds: tools/).
+// The shipped library carries the exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15: <4, split, 2>)
+// and the default (16: <1, -, 3>, with its 512-thread shape <1, -, 4>).  The slab-filter generation and the per-lane cylinder variants
+// are compiled only with -DSP_ALL_VARIANTS (soak and experiment builds: tools/), and only without NEE, MIS and camera samples.
+constexpr bool shape_shipped(int R, bool split, int scan) { return scan >= 3 || (scan == 2 && R == 4 && split); }
+bool variant_shipped(int v) {
+	TwoStage ts;
+	return v == 1 || v == 2 || v == kVariantAccel || (two_stage(v, &ts) && shape_shipped(ts.R, ts.split, ts.scan));
+}
 bool variant_built(int v) {
 #ifdef SP_ALL_VARIANTS
 	return v >= 1 && v <= kVariantLast;
 #else
-	return v == 1 || v == 2 || v == kVariantAccel || v == 15 || v == 16;
+	return variant_shipped(v);
 #endif
 }
+
+// the two-stage path-tracing kernels' work buffer, per work slot (sp_scan_kernels.h): the path history (5 x int2), the accumulator
+// (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adaptive sampling parks S1, S2 (2 doubles) in a buffer of its own (adp_wst)
+constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16;
+constexpr size_t work_slot_bytes(bool nee, bool mis) { return kSlotHist + kSlotAcc + (mis ? kSlotMisD : nee ? kSlotNeeL : 0); }
 
 int pick_variant(int flags, size_t n_tris) {
 	if (flags & SPHIP_FLAG_ACCEL) return kVariantAccel;
@@ -385,6 +395,53 @@ int ensure_lights(sphip_ctx* c, hipStream_t st) {
 
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
+// f(args...) with the trailing pack of a path-tracing kernel for the run-time choices, always in the kernels' order: the running
+// sum (nothing, AccumArgs or AdaptArgs), the estimator (nothing, NeeArgs or MisArgs), the camera (nothing or CamArgs).  Each
+// combination is a kernel of its own; f prunes the ones that are not built with if constexpr on the pack traits (sp_kernels.h).
+template <typename F>
+void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
+	if (ad) f(*ad);
+	else if (prog) f(*prog);
+	else f();
+}
+template <typename F>
+void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::CamArgs* cam, F&& f) {
+	with_accum(prog, ad, [&](const auto&... acc) {
+		auto est = [&](const auto&... e) {
+			if (cam) f(acc..., e..., *cam);
+			else f(acc..., e...);
+		};
+		if (me) est(*me);
+		else if (ne) est(*ne);
+		else est();
+	});
+}
+
+// f(Shape<R, SPLIT, SCAN>{}) for a two-stage variant's scan shape (scan 4: the 512-thread shape of scan 3, set by launch_render).
+// The one-scan kernels (k_hit_filter, k_flat_filter) take <R, SCAN> of the same shape.
+template <int R_, bool SPLIT_, int SCAN_> struct Shape {
+	static constexpr int R = R_, SCAN = SCAN_;
+	static constexpr bool SPLIT = SPLIT_, shipped = shape_shipped(R_, SPLIT_, SCAN_);
+};
+template <int SCAN, typename F>
+void with_lane_shape(const TwoStage& ts, F&& f) {
+	if (ts.split) { if (ts.R == 4) f(Shape<4, true, SCAN>{}); else f(Shape<2, true, SCAN>{}); }
+	else if (ts.R == 4) f(Shape<4, false, SCAN>{});
+	else if (ts.R == 2) f(Shape<2, false, SCAN>{});
+	else f(Shape<1, false, SCAN>{});
+}
+template <typename F>
+void with_scan_shape(const TwoStage& ts, F&& f) {
+	if (ts.scan == 3) f(Shape<1, false, 3>{});
+	else if (ts.scan == 4) f(Shape<1, false, 4>{});
+	else if (ts.scan == 2 && ts.split) f(Shape<4, true, 2>{});
+#ifdef SP_ALL_VARIANTS
+	else if (ts.scan == 2) f(Shape<4, false, 2>{});
+	else if (ts.scan == 1) with_lane_shape<1>(ts, f);
+	else with_lane_shape<0>(ts, f);
+#endif
+}
+
 // prog != nullptr: progressive accumulation (path tracing only): the launch renders global samples
 // [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
 int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
@@ -439,7 +496,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (mis && !nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	sp::NeeArgs ne{};
 	if (nee) {
-		if (!(variant == 1 || variant == 2 || variant == kVariantAccel || variant == 15 || variant == 16))
+		if (!variant_shipped(variant))
 			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_NEE is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
 		if ((rc = ensure_lights(c, st))) return rc;
 		ne.cdf = (const double*)c->nee_tab.p;
@@ -455,7 +512,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (sphip_render_camera, sphip_accum_begin[_adaptive] with cam), not rays");
 	if (camf && (flags & SPHIP_FLAG_PRIMARY_REUSE))
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
-	if (camf && !(variant == 1 || variant == 2 || variant == kVariantAccel || variant == 15 || variant == 16))
+	if (camf && !variant_shipped(variant))
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
 	if (!camf) cams = nullptr;
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
@@ -489,7 +546,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			if (samp_bytes > kChunkMaxBytes) chunks = 1;
 			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
 			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * ((adapt ? 68 : 52) + (mis ? 60 : nee ? 48 : 0));
+				const uint64_t work_bytes = lanes * chunks * (work_slot_bytes(nee, mis) + (adapt ? kSlotAdaptWst : 0));
 				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
@@ -518,11 +575,11 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	sp::AdaptArgs ad{};
 	if (adapt) ad = *adapt;
 	if (mode == SPHIP_MODE_PT && is_ts) {
-		if ((rc = ensure(c, c->work, (size_t)n_work * (mis ? 112 : nee ? 100 : 52)))) return rc;
+		if ((rc = ensure(c, c->work, (size_t)n_work * work_slot_bytes(nee, mis)))) return rc;
 		hist = (int2*)c->work.p;
-		acc = (float*)((char*)c->work.p + (size_t)n_work * 40);
-		ne.L = (float*)((char*)c->work.p + (size_t)n_work * 52);          // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
-		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * 16))) return rc;   // S1, S2 per work slot
+		acc = (float*)((char*)c->work.p + (size_t)n_work * kSlotHist);
+		ne.L = (float*)((char*)c->work.p + (size_t)n_work * (kSlotHist + kSlotAcc));     // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
+		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * kSlotAdaptWst))) return rc;   // S1, S2 per work slot
 		ad.wst = (double*)c->adp_wst.p;
 	}
 	sp::ScanSrc src2{};
@@ -544,6 +601,13 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		B.n_leaves = c->bvh_leaves; B.first_leaf = c->bvh_leaves; B.meta = (const uint32_t*)c->bvh_meta.p;
 	}
 	HIP_TRY(c, hipEventRecord(c->ev_k0, st));
+	// the closest-hit scan alone with a two-stage variant, R pixels per lane: hit queries and the primary-hit pre-pass
+	auto hit_filter = [&](const sp::KArgs& ka, const int* src_idx, int* oi, float* od) {
+		with_scan_shape(ts, [&](auto shape) {
+			using S = decltype(shape);
+			hipLaunchKernelGGL((sp::k_hit_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, ka, src2, bnd, src_idx, oi, od);
+		});
+	};
 	// primary-hit reuse with a two-stage kernel: one closest-hit scan per PIXEL first (R pixels per lane, the same scan family),
 	// whatever the number of samples and sample chunks; the path-tracing launch then starts every sample from that hit
 	bool prim_pass = false;
@@ -552,16 +616,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		int* oi = (int*)c->prim.p; float* od = (float*)((char*)c->prim.p + n_rays * 4);
 		sp::KArgs h = a;
 		h.n_chunks = 0; h.samp = nullptr;
-		const int* no_src = nullptr;
-#define SP_PRIM(R_, S_) hipLaunchKernelGGL((sp::k_hit_filter<R_, S_>), grid_px, block_ts, 0, st, h, src2, bnd, no_src, oi, od)
-		if (ts.scan == 3) SP_PRIM(1, 3);
-		else if (ts.scan == 4) SP_PRIM(1, 4);
-		else if (ts.scan == 2) SP_PRIM(4, 2);
-#ifdef SP_ALL_VARIANTS
-		else if (ts.scan == 0) { if (ts.R == 4) SP_PRIM(4, 0); else if (ts.R == 2) SP_PRIM(2, 0); else SP_PRIM(1, 0); }
-		else              { if (ts.R == 4) SP_PRIM(4, 1); else if (ts.R == 2) SP_PRIM(2, 1); else SP_PRIM(1, 1); }
-#endif
-#undef SP_PRIM
+		hit_filter(h, nullptr, oi, od);
 		a.prim_idx = oi; a.prim_d = od;
 		prim_pass = true;
 	}
@@ -570,110 +625,49 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		static_cast<sp::NeeArgs&>(me) = ne;
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
 	}
-	// path tracing; cam_tail: nothing, or the CamArgs of per-sample camera rays as the pack's last element (sp_kernels.h)
-	auto launch_pt = [&](const auto&... cam_tail) {
-		constexpr bool with_cam = sizeof...(cam_tail) > 0;
-		if (variant == kVariantAccel) {
-#define SP_ACC(...) hipLaunchKernelGGL((sp::k_accel<1, ##__VA_ARGS__, std::decay_t<decltype(cam_tail)>...>), grid, block, 0, st, a, B, nullptr, nullptr, nullptr
-			if (mis && adapt)       SP_ACC(sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
-			else if (mis && prog)   SP_ACC(sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
-			else if (mis)           SP_ACC(sp::MisArgs), me, cam_tail...);
-			else if (nee && adapt)  SP_ACC(sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
-			else if (nee && prog)   SP_ACC(sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
-			else if (nee)           SP_ACC(sp::NeeArgs), ne, cam_tail...);
-			else if (adapt)         SP_ACC(sp::AdaptArgs), ad, cam_tail...);
-			else if (prog)          SP_ACC(sp::AccumArgs), *prog, cam_tail...);
-			else                    SP_ACC(), cam_tail...);
-#undef SP_ACC
-		} else if (is_ts) {
-#define SP_PT(R_, SPLIT_, S_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, cam_tail...); \
-                                   else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, cam_tail...); \
-                                   else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, cam_tail...); } while (0)
-#define SP_PTN(R_, SPLIT_, S_, T_, V_) do { if (adapt) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AdaptArgs, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, ad, V_, cam_tail...); \
-                                    else if (prog) hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, sp::AccumArgs, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, *prog, V_, cam_tail...); \
-                                    else hipLaunchKernelGGL((sp::k_pt_filter<R_, SPLIT_, S_, T_, std::decay_t<decltype(cam_tail)>...>), grid_pt, block_ts, 0, st, a, src2, bnd, hist, acc, n_work, V_, cam_tail...); } while (0)
-			if (mis && ts.scan == 3) SP_PTN(1, false, 3, sp::MisArgs, me);
-			else if (mis && ts.scan == 4) SP_PTN(1, false, 4, sp::MisArgs, me);
-			else if (mis) SP_PTN(4, true, 2, sp::MisArgs, me);               // variant 15 (checked above)
-			else if (nee && ts.scan == 3) SP_PTN(1, false, 3, sp::NeeArgs, ne);
-			else if (nee && ts.scan == 4) SP_PTN(1, false, 4, sp::NeeArgs, ne);
-			else if (nee) SP_PTN(4, true, 2, sp::NeeArgs, ne);               // variant 15 (checked above)
-#undef SP_PTN
-			else if (ts.scan == 3) SP_PT(1, false, 3);
-			else if (ts.scan == 4) SP_PT(1, false, 4);
-			else if (ts.scan == 2 && ts.split) SP_PT(4, true, 2);
-#ifdef SP_ALL_VARIANTS
-			else if constexpr (!with_cam) {                                 // camera samples: the shipped variants only (checked above)
-				if (ts.scan == 2) SP_PT(4, false, 2);
-				else if (ts.scan == 0) {
-					if (ts.split) { if (ts.R == 4) SP_PT(4, true, 0); else SP_PT(2, true, 0); }
-					else          { if (ts.R == 4) SP_PT(4, false, 0); else if (ts.R == 2) SP_PT(2, false, 0); else SP_PT(1, false, 0); }
-				} else {
-					if (ts.split) { if (ts.R == 4) SP_PT(4, true, 1); else SP_PT(2, true, 1); }
-					else          { if (ts.R == 4) SP_PT(4, false, 1); else if (ts.R == 2) SP_PT(2, false, 1); else SP_PT(1, false, 1); }
-				}
-			}
-#endif
-#undef SP_PT
-		} else {
-#define SP_KPT(V_, ...) hipLaunchKernelGGL((sp::k_pt<V_, ##__VA_ARGS__, std::decay_t<decltype(cam_tail)>...>), grid, block, 0, st, a
-			if (mis && adapt && variant == 2)      SP_KPT(2, sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
-			else if (mis && adapt)                SP_KPT(1, sp::AdaptArgs, sp::MisArgs), ad, me, cam_tail...);
-			else if (mis && prog && variant == 2) SP_KPT(2, sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
-			else if (mis && prog)                 SP_KPT(1, sp::AccumArgs, sp::MisArgs), *prog, me, cam_tail...);
-			else if (mis && variant == 2)         SP_KPT(2, sp::MisArgs), me, cam_tail...);
-			else if (mis)                         SP_KPT(1, sp::MisArgs), me, cam_tail...);
-			else if (nee && adapt && variant == 2) SP_KPT(2, sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
-			else if (nee && adapt)                SP_KPT(1, sp::AdaptArgs, sp::NeeArgs), ad, ne, cam_tail...);
-			else if (nee && prog && variant == 2) SP_KPT(2, sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
-			else if (nee && prog)                 SP_KPT(1, sp::AccumArgs, sp::NeeArgs), *prog, ne, cam_tail...);
-			else if (nee && variant == 2)         SP_KPT(2, sp::NeeArgs), ne, cam_tail...);
-			else if (nee)                         SP_KPT(1, sp::NeeArgs), ne, cam_tail...);
-			else if (adapt && variant == 2)       SP_KPT(2, sp::AdaptArgs), ad, cam_tail...);
-			else if (adapt)                       SP_KPT(1, sp::AdaptArgs), ad, cam_tail...);
-			else if (prog && variant == 2)        SP_KPT(2, sp::AccumArgs), *prog, cam_tail...);
-			else if (prog)                        SP_KPT(1, sp::AccumArgs), *prog, cam_tail...);
-			else if (variant == 2)                SP_KPT(2), cam_tail...);
-			else                                  SP_KPT(1), cam_tail...);
-#undef SP_KPT
-		}
+	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
+	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, cams, f); };
+	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
+	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
+		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
 	};
-	if (variant == kVariantAccel && mode == kModeHits) hipLaunchKernelGGL(sp::k_accel<2>, grid, block, 0, st, a, B, d_src, (int*)d_rgba, (float*)d_accum);
-	else if (variant == kVariantAccel && mode == SPHIP_MODE_FLAT) hipLaunchKernelGGL(sp::k_accel<0>, grid, block, 0, st, a, B, nullptr, nullptr, nullptr);
-	else if (mode == kModeHits) {
+	auto with_exact = [&](auto&& f) {
+		if (variant == 2) f(std::integral_constant<int, 2>{});
+		else f(std::integral_constant<int, 1>{});
+	};
+	if (mode == kModeHits) {
 		int* oi = (int*)d_rgba; float* od = (float*)d_accum;
-		if (is_ts) {
-#define SP_HIT(R_, S_) hipLaunchKernelGGL((sp::k_hit_filter<R_, S_>), grid_px, block_ts, 0, st, a, src2, bnd, d_src, oi, od)
-			if (ts.scan == 3) SP_HIT(1, 3);
-			else if (ts.scan == 4) SP_HIT(1, 4);
-			else if (ts.scan == 2) SP_HIT(4, 2);
-#ifdef SP_ALL_VARIANTS
-			else if (ts.scan == 0) { if (ts.R == 4) SP_HIT(4, 0); else if (ts.R == 2) SP_HIT(2, 0); else SP_HIT(1, 0); }
-			else              { if (ts.R == 4) SP_HIT(4, 1); else if (ts.R == 2) SP_HIT(2, 1); else SP_HIT(1, 1); }
-#endif
-#undef SP_HIT
-		}
-		else if (variant == 2) hipLaunchKernelGGL(sp::k_hit<2>, grid, block, 0, st, a, d_src, oi, od);
-		else                   hipLaunchKernelGGL(sp::k_hit<1>, grid, block, 0, st, a, d_src, oi, od);
+		if (variant == kVariantAccel) accel(std::integral_constant<int, 2>{}, d_src, oi, od);
+		else if (is_ts) hit_filter(a, d_src, oi, od);
+		else with_exact([&](auto v) { hipLaunchKernelGGL((sp::k_hit<decltype(v)::value>), grid, block, 0, st, a, d_src, oi, od); });
 	} else if (mode == SPHIP_MODE_FLAT) {
-		if (is_ts) {
-#define SP_FLAT(R_, S_) hipLaunchKernelGGL((sp::k_flat_filter<R_, S_>), grid_px, block_ts, 0, st, a, src2, bnd)
-			if (ts.scan == 3) SP_FLAT(1, 3);
-			else if (ts.scan == 4) SP_FLAT(1, 4);
-			else if (ts.scan == 2) SP_FLAT(4, 2);
-#ifdef SP_ALL_VARIANTS
-			else if (ts.scan == 0) { if (ts.R == 4) SP_FLAT(4, 0); else if (ts.R == 2) SP_FLAT(2, 0); else SP_FLAT(1, 0); }
-			else              { if (ts.R == 4) SP_FLAT(4, 1); else if (ts.R == 2) SP_FLAT(2, 1); else SP_FLAT(1, 1); }
-#endif
-#undef SP_FLAT
-		}
-		else if (variant == 2) hipLaunchKernelGGL(sp::k_flat<2>, grid, block, 0, st, a);
-		else                   hipLaunchKernelGGL(sp::k_flat<1>, grid, block, 0, st, a);
-	} else if (cams) launch_pt(*cams);
-	else launch_pt();
-	if (chunks > 1 && adapt) hipLaunchKernelGGL((sp::k_resolve<sp::AdaptArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, ad);
-	else if (chunks > 1 && prog) hipLaunchKernelGGL((sp::k_resolve<sp::AccumArgs>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, *prog);
-	else if (chunks > 1) hipLaunchKernelGGL(sp::k_resolve<>, dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a);
+		if (variant == kVariantAccel) accel(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr);
+		else if (is_ts) with_scan_shape(ts, [&](auto shape) {
+			using S = decltype(shape);
+			hipLaunchKernelGGL((sp::k_flat_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, a, src2, bnd);
+		});
+		else with_exact([&](auto v) { hipLaunchKernelGGL((sp::k_flat<decltype(v)::value>), grid, block, 0, st, a); });
+	} else if (variant == kVariantAccel) {
+		pt_pack([&](const auto&... p) { accel(std::integral_constant<int, 1>{}, nullptr, nullptr, nullptr, p...); });
+	} else if (is_ts) {
+		with_scan_shape(ts, [&](auto shape) {
+			using S = decltype(shape);
+			pt_pack([&](const auto&... p) {
+				// NEE (the bounded scans), MIS and camera samples are built for the shipped shapes only (checked above)
+				if constexpr (S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value))
+					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
+					                   a, src2, bnd, hist, acc, n_work, p...);
+			});
+		});
+	} else {
+		with_exact([&](auto v) {
+			pt_pack([&](const auto&... p) { hipLaunchKernelGGL((sp::k_pt<decltype(v)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, p...); });
+		});
+	}
+	if (chunks > 1)
+		with_accum(prog, adp, [&](const auto&... q) {
+			hipLaunchKernelGGL((sp::k_resolve<std::decay_t<decltype(q)>...>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, q...);
+		});
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
 	c->have_render = true;
@@ -1125,7 +1119,7 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 		if (flags & SPHIP_FLAG_PRIMARY_REUSE)
 			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
 		const int v = pick_variant(flags, c->n_tris);
-		if (!(v == 1 || v == 2 || v == kVariantAccel || v == 15 || v == 16))
+		if (!variant_shipped(v))
 			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", v, kVariantNames[v]);
 	}
 	if (!c->kids.empty()) {
