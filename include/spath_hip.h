@@ -69,8 +69,11 @@ enum {
 	                                   "next-event estimation" below.  Changes the estimator, not its expectation. */
 	SPHIP_FLAG_MIS = 0x800,          /* OPT-IN multiple importance sampling of next-event estimation: valid only together with
 	                                   SPHIP_FLAG_NEE; see "multiple importance sampling" below.  Same expectation again. */
-	SPHIP_FLAG_CAMERA_SAMPLES = 0x1000 /* OPT-IN per-sample camera rays (pixel antialiasing, thin-lens depth of field) for the camera paths
+	SPHIP_FLAG_CAMERA_SAMPLES = 0x1000, /* OPT-IN per-sample camera rays (pixel antialiasing, thin-lens depth of field) for the camera paths
 	                                   of SPHIP_MODE_PT; see "camera samples" below.  Changes the image: it is no longer the reference's. */
+	SPHIP_FLAG_SPECULAR = 0x2000     /* OPT-IN mirror and mixed diffuse/mirror materials from the context's specular table
+	                                   (sphip_set_specular) for SPHIP_MODE_PT; see "specular reflection" below.  Without the flag the
+	                                   table is ignored. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -415,6 +418,49 @@ int sphip_set_lens(sphip_t* ctx, const sphip_lens* lens);
  * the device function the kernels call; asynchronous, single-device contexts (SPHIP_E_STATE otherwise).  A chain of one-sample
  * sphip_render_device_accum calls (sample_base = s) over these rays gives a flagged render's image bit for bit. */
 int sphip_camera_rays_device(sphip_t* ctx, const sphip_camera* cam, uint64_t seed, uint32_t sample, void* d_rays_out, void* stream);
+
+/* ---- specular reflection (SPHIP_FLAG_SPECULAR): a per-triangle specular table beside the scene's materials,
+ * 4 f32 per triangle: ks.r, ks.g, ks.b, p.  ks is the mirror reflectance per channel, p the probability that a hit on the triangle
+ * takes the mirror lobe: p = 0 leaves the triangle as it is without the table, p = 1 makes it a pure mirror, in between one sample
+ * takes one lobe.  The 6-float material and sphip_set_scene are unchanged.
+ *
+ * Valid for SPHIP_MODE_PT with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with the shipped variants 1, 2, 8
+ * (SPHIP_FLAG_ACCEL), 15 and 16, with progressive and adaptive accumulation, sphip_accum_denoise (the G-buffer is unchanged: the lobe
+ * is chosen per sample), sample chunks, primary-hit reuse (the shared primary hit stays valid), SPHIP_FLAG_CAMERA_SAMPLES and
+ * multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT; with any other variant; with SPHIP_FLAG_NEE without SPHIP_FLAG_MIS
+ * (plain NEE stops after four hits because the fifth carries nothing, which a mirror at hit 3 breaks, and it is the firefly-prone
+ * estimator MIS replaced: leaving it out saves a third of the specular kernels).  SPHIP_E_STATE: the flag without a table.  Hit queries
+ * ignore the flag.  Without the flag every render is bit for bit what it is without a table; with the flag and a table of zeros too.
+ *
+ * The estimator, at hit d (d = 0..4) of the path of (seed, global pixel, global sample) on triangle i, (ks, p) = spec[i], n the
+ * triangle's normal turned against dir as always, (r1, r2) the direction draws of Philox stream d as always; f32, every operation
+ * rounded on its own, nothing fused, dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z:
+ *   lobe:      (r7, _) = philox_uniforms(seed, pixel, sample, 32 + d)  (streams 0-4, 8-11, 16-19, 24, 25 are taken);
+ *              the hit is specular iff r7 < (double)p
+ *   specular:  c = dot3(dir, n);  t = c + c;  nd = dir - n * t per component (not renormalised);  origin and source triangle as always
+ *   diffuse:   unchanged: nd = rand_unit_vec(n, r1, r2), ct = dot3(nd, n)
+ *   weights:   wS = 1.0f / p,  wD = 1.0f / (1.0f - p)  (IEEE f32 divisions), each used only when its lobe was taken
+ *   unwind:    diffuse hit   rec_d = E_d + ((((brdf_d * rec_{d+1}) * ct_d) * (1/p_ref)) * wD)   (today's expression, 1/p_ref its 2 pi,
+ *                            with one more scale; wD = 1.0f when p = 0)
+ *              specular hit  rec_d = E_d + ((ks * rec_{d+1}) * wS)                               (per channel)
+ *   E_d is the emission e_d of the plain estimator, D_d with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS:
+ *              a specular hit draws no light sample and traces no shadow ray: L_d = 0
+ *              Ew_d = e_d in full when d = 0 or hit d-1 was specular, else multiple importance sampling's e_d / (1 + u_b)
+ *              D_d = Ew_d + L_d * wD (d = 0..3, per channel, L_d the light sample of multiple importance sampling),  D_4 = Ew_4
+ *   so both strategies estimate the diffuse lobe's direct light given that lobe was chosen, and the mirror lobe carries everything
+ *   it sees divided by p.  scans_executed counts what ran: no shadow scan for a specular hit. */
+
+/* The context's specular table: n_tris * 4 f32 on the host for the scene last set (NULL clears the table); blocking, the array is
+ * borrowed for the call; accepted by multi-device contexts (every device keeps the whole table, like the scene).  Every set_scene
+ * clears the table.  During an accumulation it ends the accumulation as a set_scene does (the next step: SPHIP_E_STATE).
+ * SPHIP_E_STATE without a scene; SPHIP_E_INVALID when a value is not finite, a ks < 0, p outside [0, 1] (the message names the first
+ * such triangle; the table stays as it was) or the scene has 2^30 triangles or more (bit 30 of a triangle index marks a mirror bounce
+ * in the kernels' path history). */
+int sphip_set_specular(sphip_t* ctx, const float* spec);
+/* The same from a device pointer, by the rules of sphip_set_scene_device: single-device contexts (SPHIP_E_STATE otherwise), ordered by
+ * `stream` alone, and copied, so the caller may free d_spec once the stream has passed the call.  It does NOT validate the values:
+ * a table that breaks the rules above gives undefined images (never out-of-bounds accesses). */
+int sphip_set_specular_device(sphip_t* ctx, const void* d_spec, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

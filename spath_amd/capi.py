@@ -19,6 +19,7 @@ FLAG_ACCEL = 0x200          # opt-in linear BVH; not the brute-fo
 FLAG_NEE = 0x400            # opt-in next-event estimation: light sampling with shadow rays
 FLAG_MIS = 0x800            # with FLAG_NEE: multiple importance sampling of its light samples
 FLAG_CAMERA_SAMPLES = 0x1000  # per-sample camera rays on the camera paths: pixel antialiasing, thin lens
+FLAG_SPECULAR = 0x2000      # mirror and mixed diffuse/mirror materials from the context's specular table
 
 
 def flag_chunks(n: int) -> int:
@@ -38,6 +39,7 @@ SYMBOLS = (
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
     "sphip_set_lens", "sphip_camera_rays_device",
+    "sphip_set_specular", "sphip_set_specular_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -192,6 +194,10 @@ def load():
     L.sphip_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.sphip_camera_rays_device.restype = C.c_int
     L.sphip_camera_rays_device.argtypes = [vp, C.POINTER(CameraArgs), C.c_uint64, C.c_uint32, vp, vp]
+    L.sphip_set_specular.restype = C.c_int
+    L.sphip_set_specular.argtypes = [vp, vp]
+    L.sphip_set_specular_device.restype = C.c_int
+    L.sphip_set_specular_device.argtypes = [vp, vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -310,6 +316,19 @@ class Context:
         if tris.shape[0] != mats.shape[0]:
             raise ValueError("one material per triangle")
         self._check(self._L.sphip_set_scene(self._h, tris.ctypes.data, mats.ctypes.data, tris.shape[0]), "sphip_set_scene")
+        self._n_tris = tris.shape[0]
+
+    def set_specular(self, spec):
+        """sphip_set_specular: the specular table of FLAG_SPECULAR renders, (n_tris, 4) f32 rows ks.r, ks.g, ks.b, p for the scene last
+        set (scene.specular_table builds one); None clears it.  Every set_scene clears it too."""
+        import numpy as np
+        if spec is None:
+            self._check(self._L.sphip_set_specular(self._h, None), "sphip_set_specular")
+            return
+        spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1, 4)
+        if spec.shape[0] != getattr(self, "_n_tris", spec.shape[0]):
+            raise ValueError("one specular row per triangle of the scene")
+        self._check(self._L.sphip_set_specular(self._h, spec.ctypes.data), "sphip_set_specular")
 
     def render(self, rays, w, h, n_samples, seed=1, mode=MODE_PT, flags=0, want_accum=False):
         import numpy as np
@@ -325,6 +344,11 @@ class Context:
     # device-resident path ----------------------------------------------------------------------
     def set_scene_device(self, d_tris: int, d_mats: int, n_tris: int, stream: int = 0):
         self._check(self._L.sphip_set_scene_device(self._h, d_tris, d_mats, n_tris, stream), "sphip_set_scene_device")
+        self._n_tris = n_tris
+
+    def set_specular_device(self, d_spec: int, stream: int = 0):
+        """sphip_set_specular_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_specular_device(self._h, d_spec, stream), "sphip_set_specular_device")
 
     def render_device(self, d_rays: int, n_rays: int, n_samples: int, d_out_rgba: int, *, seed=1, mode=MODE_PT,
                       flags=0, shard=None, image_width=0, d_out_accum: int = 0, stream: int = 0):

@@ -155,6 +155,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_kernels.h AdaptArgs)
 	constexpr bool nee = IsNee<Acc...>::value;         // next-event estimation (sp_kernels.h NeeArgs)
 	constexpr bool mis = IsMis<Acc...>::value;         // MIS on top of it (sp_kernels.h MisArgs): the folded terms D_0..D_4
+	constexpr bool spc = IsSpec<Acc...>::value;        // specular reflection (sp_kernels.h SpecArgs): kSpecBit in hidx marks a mirror bounce
+	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
@@ -192,17 +194,22 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					const float* tn = a.tris + (size_t)bi * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);
+					bool sl = false;                              // specular: this hit takes the mirror lobe
+					float pm = 0.0f;
+					if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
 					if constexpr (mis) {
 						f3 wd, Lc; float tm;
 						const f3 x = add3(o, scale3(dir, bd));
 						const float* m = a.mats + (size_t)bi * 6;
-						const f3 De = depth == 0 ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
+						const bool full = depth == 0 || (spc && (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);   // after a mirror bounce e_d counts in full
+						const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
 						f3 Ld = mk3(0.0f, 0.0f, 0.0f);
-						if (depth < kNeeDepths && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, n, bi, wd, tm, Lc)) {
+						if (depth < kNeeDepths && !sl && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, n, bi, wd, tm, Lc)) {
 							float sd; int si;
 							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
 							my_scans++;
 							if (si < 0) Ld = Lc;
+							if constexpr (spc) Ld = scale3(Ld, 1.0f / (1.0f - pm));   // L_d wD
 						}
 						hD[depth] = depth < kNeeDepths ? add3(De, Ld) : De;
 					} else if constexpr (nee) {
@@ -216,11 +223,15 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 							if (si < 0) hL[depth] = Lc;
 						}
 					}
-					double r1, r2;
-					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
-					const f3 nd = rand_unit_vec(n, r1, r2);
-					hcos[depth] = dot3(nd, n);
-					hidx[depth] = bi;
+					f3 nd;
+					if (spc && sl) { nd = spec_reflect(dir, n); hcos[depth] = 0.0f; }
+					else {
+						double r1, r2;
+						philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
+						nd = rand_unit_vec(n, r1, r2);
+						hcos[depth] = dot3(nd, n);
+					}
+					hidx[depth] = spc && sl ? bi | kSpecBit : bi;
 					o = add3(o, scale3(dir, bd));
 					dir = nd;
 					src = bi;
@@ -234,12 +245,14 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 #pragma unroll
 		for (int depth = 4; depth >= 0; --depth) {
 			if (depth < nh) {
-				const float* m = a.mats + (size_t)hidx[depth] * 6;
+				const int id = spc ? hidx[depth] & ~kSpecBit : hidx[depth];
+				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = hD[depth];
 				else if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
-				rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
+				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hidx[depth] & kSpecBit) != 0, e, brdf, rec, hcos[depth]);
+				else rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
 			}
 		}
 		accum = add3(accum, rec);

@@ -108,12 +108,23 @@ struct CamArgs {
 	float focus_dist;          // local z of the plane in focus (aperture > 0)
 };
 
+// specular reflection (SPHIP_FLAG_SPECULAR, include/spath_hip.h): the scene's specular table, one float4 per
+// triangle: ks.r ks.g ks.b p.  It rides between the estimator and the camera: k_pt<V, MisArgs, SpecArgs, CamArgs>, ...  A hit of
+// depth d takes the mirror lobe iff the first uniform of Philox stream kSpecStream + d is below p; the path history marks such a
+// hit with kSpecBit in its triangle index (triangle indices stay below 2^30: sphip_set_specular checks it).
+struct SpecArgs {
+	const float4* spec;        // n_tris
+};
+constexpr uint32_t kSpecStream = 32u;
+constexpr int kSpecBit = 0x40000000;
+
 // the pack's optional elements, found by type wherever they sit (MisArgs is a NeeArgs, AdaptArgs an AccumArgs)
 template <typename T, typename... P> struct PackHas { static constexpr bool value = (std::is_same<T, P>::value || ...); };
 template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHas<AdaptArgs, Acc...>::value; };
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
+template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value; };
 // a running sum rides in the pack (progressive or adaptive)
 template <typename... Acc> struct HasAccum { static constexpr bool value = PackHas<AccumArgs, Acc...>::value || IsAdapt<Acc...>::value; };
 // the first element of the pack that is a T
@@ -126,6 +137,7 @@ template <typename... P> SP_DEV const AdaptArgs& adapt_args(const P&... p) { ret
 template <typename... P> SP_DEV const AccumArgs& accum_args(const P&... p) { return pack_get<AccumArgs>(p...); }
 template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return pack_get<NeeArgs>(p...); }
 template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
+template <typename... P> SP_DEV const float4* spec_table(const P&... p) { return pack_get<SpecArgs>(p...).spec; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
 template <typename... Acc>
@@ -384,6 +396,25 @@ SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_
 	return true;
 }
 
+// ---- specular reflection (include/spath_hip.h).  The lobe of the hit of depth d on a triangle of mirror
+// probability p: specular iff r7 < (double)p, r7 the first uniform of stream kSpecStream + d
+SP_DEV bool spec_lobe(uint64_t seed, uint32_t pixel, uint32_t sample, int depth, float p) {
+	double r7, r8;
+	philox_uniforms(seed, pixel, sample, kSpecStream + (uint32_t)depth, &r7, &r8);
+	return r7 < (double)p;
+}
+// the mirror direction of dir about n: dir - n * (c + c), c = dot3(dir, n); not renormalised
+SP_DEV f3 spec_reflect(f3 dir, f3 n) {
+	const float c = dot3(dir, n);
+	return sub3(dir, scale3(n, c + c));
+}
+// one step of the unwind at a hit on triangle id whose lobe was specular (sl) or diffuse: E + ((ks * rec) * (1 / p)), or today's
+// expression scaled once more, by 1 / (1 - p)
+SP_DEV f3 spec_unwind(const float4 q, bool sl, f3 e, f3 brdf, f3 rec, float ct) {
+	if (sl) return add3(e, scale3(mul3(mk3(q.x, q.y, q.z), rec), 1.0f / q.w));
+	return add3(e, scale3(scale3(scale3(mul3(brdf, rec), ct), kInvP), 1.0f / (1.0f - q.w)));
+}
+
 // ---- closest-hit scan, variant "rpl_sload": ray per lane, triangle index wave-uniform so the
 // records arrive through the scalar data path (s_load_dwordx4) and every VALU op reads them as
 // SGPR operands.  Semantics of cpu_renderer.cpp:36-49: ascending index, strict '<', skip idx_source.
@@ -516,6 +547,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	constexpr bool adapt = IsAdapt<Acc...>::value;
 	constexpr bool nee = IsNee<Acc...>::value;
 	constexpr bool mis = IsMis<Acc...>::value;                   // MIS: nee too; the folded terms D_0..D_4
+	constexpr bool spc = IsSpec<Acc...>::value;                  // specular reflection (SpecArgs): a mirror lobe per hit, marked by kSpecBit in idx0..4
+	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = !cam && (a.flags & 0x100u) != 0;          // the host rejects reuse with camera samples
@@ -547,6 +580,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		int idx0 = -1, idx1 = -1, idx2 = -1, idx3 = -1, idx4 = -1;
 		float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f, c4 = 0.0f;
 		bool alive = valid;
+		bool pspec = false;                                          // specular: the previous hit took the mirror lobe
 		f3 L0 = mk3(0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0, L3 = L0;   // NEE: direct light sampled at hits 0..3
 		f3 D0 = L0, D1 = L0, D2 = L0, D3 = L0, D4 = L0;             // MIS: D_d = e_d w_b + L_d
 #pragma unroll 1
@@ -564,18 +598,28 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				const float* tn = a.tris + (size_t)bi * 12 + 9;
 				f3 n = mk3(tn[0], tn[1], tn[2]);                  // :55
 				if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);    // :56-57
+				bool sl = false;                                  // specular: this hit takes the mirror lobe
+				float pm = 0.0f;
+				if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
 				if constexpr (mis) {
-					if (depth == 0) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
+					if (depth == 0 || (spc && pspec)) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
 					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
-					if (depth < kNeeDepths) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
+					if (depth < kNeeDepths && !sl) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
+					if constexpr (spc) if (sh) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
-				double r1, r2;
-				philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
-				const f3 nd = rand_unit_vec(n, r1, r2);           // :58
-				const float ct = dot3(nd, n);                     // :62
+				f3 nd;
+				float ct = 0.0f;
+				if (spc && sl) nd = spec_reflect(dir, n);
+				else {
+					double r1, r2;
+					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
+					nd = rand_unit_vec(n, r1, r2);                // :58
+					ct = dot3(nd, n);                             // :62
+				}
 				o = add3(o, scale3(dir, bd));                     // geom.h:218 point = pos + dir*d
 				dir = nd;
 				src = bi;
+				if constexpr (spc) { pspec = sl; if (sl) bi |= kSpecBit; }
 				if (depth == 0) { idx0 = bi; c0 = ct; }
 				else if (depth == 1) { idx1 = bi; c1 = ct; }
 				else if (depth == 2) { idx2 = bi; c2 = ct; }
@@ -607,7 +651,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			const int id = depth == 0 ? idx0 : depth == 1 ? idx1 : depth == 2 ? idx2 : depth == 3 ? idx3 : idx4;
 			const float ct = depth == 0 ? c0 : depth == 1 ? c1 : depth == 2 ? c2 : depth == 3 ? c3 : c4;
 			if (id >= 0) {
-				const float* m = a.mats + (size_t)id * 6;
+				const float* m = a.mats + (size_t)(spc ? id & ~kSpecBit : id) * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                     // :63
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = depth == 0 ? D0 : depth == 1 ? D1 : depth == 2 ? D2 : depth == 3 ? D3 : D4;   // D_d
@@ -615,7 +659,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 					if (depth > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, depth == 0 ? L0 : depth == 1 ? L1 : depth == 2 ? L2 : L3);
 				}
-				rec = add3(e, scale3(scale3(mul3(brdf, rec), ct), kInvP));                 // :67
+				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id & ~kSpecBit], (id & kSpecBit) != 0, e, brdf, rec, ct);
+				else rec = add3(e, scale3(scale3(mul3(brdf, rec), ct), kInvP));            // :67
 			}
 		}
 		accum = add3(accum, rec);                                // :75

@@ -100,6 +100,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 // and leaves it at the end -- with SPLIT only slot 0 carries it; a sample-chunked launch leaves both to k_resolve.
 // With a trailing AdaptArgs (adaptive sampling) the same holds for S1, S2, parked in AdaptArgs::wst[2][n_work] (16 B per slot,
 // touched once per sample, never inside the scan), and ray k is local pixel list[k] for the RNG and the running sums.
+// With a SpecArgs (specular reflection, sp_kernels.h) a hit that took the mirror lobe carries kSpecBit in its history index: the
+// slot stays 8 B per depth, and the unwind (and the next hit's MIS weight) reads the lobe back from there.
 template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
                                                    int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work, const Acc... acc_args) {
@@ -117,6 +119,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	static_assert(!nee || SCAN >= 2, "NEE needs the bounded form of the scan");
 	constexpr bool mis = IsMis<Acc...>::value;               // MIS: D_d parked in NeeArgs::L for d = 0..4 (sp_kernels.h MisArgs)
 	constexpr bool cam = IsCam<Acc...>::value;               // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
+	constexpr bool spc = IsSpec<Acc...>::value;              // specular reflection (sp_kernels.h SpecArgs)
+	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -202,11 +206,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				float tmx[R];
 				f3 nadj[R];
 				bool hitr[R], any_sh = false;
+				bool slr[R];                                     // specular: the hit takes the mirror lobe (no light sample)
 #pragma unroll
 				for (int r = 0; r < R; ++r) {
 					hitr[r] = s.act[r] && (bi[r] >= 0);
 					sh.o[r] = s.o[r]; sh.dir[r] = s.dir[r]; sh.src[r] = s.src[r]; sh.act[r] = false; tmx[r] = kMaxDist;
 					nadj[r] = s.dir[r];
+					slr[r] = false;
 					if (hitr[r]) {
 						const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
 						f3 n = mk3(tn[0], tn[1], tn[2]);
@@ -220,8 +226,18 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 							// D_d = e_d w_b + L_d, assuming the shadow ray gets through; e_d w_b waits in depth 4's cells (written at
 							// depth 4 only) in case it does not
 							const float* m = a.mats + (size_t)bi[r] * 6;
-							const f3 De = depth == 0 ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), s.dir[r], bd[r], bi[r]);
-							sh.act[r] = depth < kNeeDepths && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+							bool full = depth == 0;                    // e_d counts in full: the camera's hit, or the hit after a mirror bounce
+							// the light sample is drawn in one of two places: before De with a table, after it without one.  Keep both: the
+							// kernels without SpecArgs then hold the instructions they held before the element existed (tools/listing_diff.py)
+							if constexpr (spc) {
+								if (depth > 0) full = (hist[(size_t)(depth - 1) * n_work + k0 + r * B].x & kSpecBit) != 0;
+								const float pm = spec_table(acc_args...)[bi[r]].w;
+								slr[r] = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, pm);
+								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+								if (sh.act[r]) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
+							}
+							const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), s.dir[r], bd[r], bi[r]);
+							if constexpr (!spc) sh.act[r] = depth < kNeeDepths && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
 							const f3 Dd = depth < kNeeDepths ? add3(De, sh.act[r] ? Lc : mk3(0.0f, 0.0f, 0.0f)) : De;
 							Lp[0] = Dd.x; Lp[n_work] = Dd.y; Lp[(size_t)2 * n_work] = Dd.z;
 							if (sh.act[r]) {
@@ -259,14 +275,19 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 #pragma unroll
 				for (int r = 0; r < R; ++r) {
 					if (hitr[r]) {
-						double r1, r2;
-						philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
-						const f3 nd = rand_unit_vec(nadj[r], r1, r2);
-						const float ct = dot3(nd, nadj[r]);
+						f3 nd;
+						float ct = 0.0f;
+						if (spc && slr[r]) nd = spec_reflect(s.dir[r], nadj[r]);
+						else {
+							double r1, r2;
+							philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
+							nd = rand_unit_vec(nadj[r], r1, r2);
+							ct = dot3(nd, nadj[r]);
+						}
 						s.o[r] = sh.o[r];
 						s.dir[r] = nd;
 						s.src[r] = sh.src[r];
-						hist[(size_t)depth * n_work + k0 + r * B] = make_int2(sh.src[r], (int)__float_as_uint(ct));
+						hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && slr[r] ? sh.src[r] | kSpecBit : sh.src[r], (int)__float_as_uint(ct));
 						nh[r] = depth + 1;
 					}
 					s.act[r] = hitr[r];
@@ -280,14 +301,21 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
-					double r1, r2;
-					philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
-					const f3 nd = rand_unit_vec(n, r1, r2);
-					const float ct = dot3(nd, n);
+					bool sl = false;
+					if constexpr (spc) sl = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, spec_table(acc_args...)[bi[r]].w);
+					f3 nd;
+					float ct = 0.0f;
+					if (spc && sl) nd = spec_reflect(s.dir[r], n);
+					else {
+						double r1, r2;
+						philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
+						nd = rand_unit_vec(n, r1, r2);
+						ct = dot3(nd, n);
+					}
 					s.o[r] = add3(s.o[r], scale3(s.dir[r], bd[r]));
 					s.dir[r] = nd;
 					s.src[r] = bi[r];
-					hist[(size_t)depth * n_work + k0 + r * B] = make_int2(bi[r], (int)__float_as_uint(ct));
+					hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && sl ? bi[r] | kSpecBit : bi[r], (int)__float_as_uint(ct));
 					nh[r] = depth + 1;
 				}
 				s.act[r] = hit;
@@ -299,7 +327,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			f3 rec = mk3(0.0f, 0.0f, 0.0f);
 			for (int d = nh[r] - 1; d >= 0; --d) {
 				const int2 hc = hist[(size_t)d * n_work + kw];
-				const float* m = a.mats + (size_t)hc.x * 6;
+				const int id = spc ? hc.x & ~kSpecBit : hc.x;
+				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) {                         // D_d
@@ -310,7 +339,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					if (d > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]));
 				}
-				rec = add3(e, scale3(scale3(mul3(brdf, rec), __uint_as_float((uint32_t)hc.y)), kInvP));
+				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hc.x & kSpecBit) != 0, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
+				else rec = add3(e, scale3(scale3(mul3(brdf, rec), __uint_as_float((uint32_t)hc.y)), kInvP));
 			}
 			// cpu_renderer.cpp:75 accum += sample, in sample order: with SPLIT the slots are consecutive samples of one
 			// pixel and are added to slot 0's accumulator one after the other (this loop is unrolled in order)

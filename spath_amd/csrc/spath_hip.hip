@@ -103,6 +103,10 @@ struct sphip_ctx {
 	sphip_lens acc_lens{};
 	sphip_camera acc_cam{};
 	bool acc_has_cam = false;
+	// ---- specular reflection (SPHIP_FLAG_SPECULAR): the scene's specular table, 4 floats per triangle (every device of a multi-device
+	// context keeps the whole table, like the scene); dropped by every set_scene
+	DevBuf spec;
+	bool have_spec = false;
 };
 
 namespace {
@@ -198,6 +202,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->have_scene = true;
 	c->bvh_valid = c->filt_valid = c->cyl_valid = c->cylm_valid = false;
 	c->nee_valid = false;
+	c->have_spec = false;                          // the specular table belongs to the old scene
 	return SPHIP_OK;
 }
 
@@ -396,8 +401,10 @@ int ensure_lights(sphip_ctx* c, hipStream_t st) {
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
 // f(args...) with the trailing pack of a path-tracing kernel for the run-time choices, always in the kernels' order: the running
-// sum (nothing, AccumArgs or AdaptArgs), the estimator (nothing, NeeArgs or MisArgs), the camera (nothing or CamArgs).  Each
-// combination is a kernel of its own; f prunes the ones that are not built with if constexpr on the pack traits (sp_kernels.h).
+// sum (nothing, AccumArgs or AdaptArgs), the estimator (nothing, NeeArgs or MisArgs), the specular table (nothing or SpecArgs), the
+// camera (nothing or CamArgs).  Each combination is a kernel of its own; the table is composed with the plain estimator and with
+// MIS only (launch_render rejects it with NEE alone), and f prunes the other ones that are not built with if constexpr on the
+// pack traits (sp_kernels.h).
 template <typename F>
 void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 	if (ad) f(*ad);
@@ -405,11 +412,16 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 	else f();
 }
 template <typename F>
-void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::CamArgs* cam, F&& f) {
+void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
+               const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
-			if (cam) f(acc..., e..., *cam);
-			else f(acc..., e...);
+			auto tail = [&](const auto&... t) {
+				if (cam) f(acc..., e..., t..., *cam);
+				else f(acc..., e..., t...);
+			};
+			if constexpr (sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value) { if (spc) { tail(*spc); return; } }
+			tail();
 		};
 		if (me) est(*me);
 		else if (ne) est(*ne);
@@ -515,6 +527,16 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (camf && !variant_shipped(variant))
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
 	if (!camf) cams = nullptr;
+	// specular reflection: path tracing with the plain estimator or with NEE|MIS, with the shipped variants; the flat
+	// pass has no use for it and says so; hit queries ignore the flag
+	if (mode == SPHIP_MODE_FLAT && (flags & SPHIP_FLAG_SPECULAR)) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is valid for SPHIP_MODE_PT only");
+	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR);
+	if (specf && nee && !mis)
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
+	if (specf && !variant_shipped(variant))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+	if (specf && !c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
+	const sp::SpecArgs spa{ (const float4*)c->spec.p };
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -626,7 +648,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
 	}
 	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
-	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, cams, f); };
+	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf ? &spa : nullptr, cams, f); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
@@ -653,8 +675,9 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		with_scan_shape(ts, [&](auto shape) {
 			using S = decltype(shape);
 			pt_pack([&](const auto&... p) {
-				// NEE (the bounded scans), MIS and camera samples are built for the shipped shapes only (checked above)
-				if constexpr (S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value))
+				// NEE (the bounded scans), MIS, camera samples and specular reflection are built for the shipped shapes only (checked above)
+				if constexpr (S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value ||
+				                              sp::IsSpec<std::decay_t<decltype(p)>...>::value))
 					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
 					                   a, src2, bnd, hist, acc, n_work, p...);
 			});
@@ -800,6 +823,7 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 		if (rcs[(size_t)r]) return fail(c, rcs[(size_t)r], "device %d: %s", c->kids[(size_t)r]->device, c->kids[(size_t)r]->err.c_str());
 	c->n_tris = n_tris;
 	c->have_scene = true;
+	c->have_spec = false;
 	return SPHIP_OK;
 }
 
@@ -1121,6 +1145,14 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 		const int v = pick_variant(flags, c->n_tris);
 		if (!variant_shipped(v))
 			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", v, kVariantNames[v]);
+	}
+	if (flags & SPHIP_FLAG_SPECULAR) {             // likewise
+		if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
+		const int v = pick_variant(flags, c->n_tris);
+		if (!variant_shipped(v))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", v, kVariantNames[v]);
+		if (!c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
 	}
 	if (!c->kids.empty()) {
 		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
@@ -1514,7 +1546,7 @@ void sphip_destroy(sphip_t* c) {
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
 	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
 	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
-	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab };
+	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab, &c->spec };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
@@ -1557,6 +1589,67 @@ int sphip_set_scene_device(sphip_t* c, const void* d_tris, const void* d_mats, s
 	HIP_TRY(c, hipMemcpyAsync(c->tris.p, d_tris, n_tris * 48, hipMemcpyDeviceToDevice, st));
 	HIP_TRY(c, hipMemcpyAsync(c->mats.p, d_mats, n_tris * 24, hipMemcpyDeviceToDevice, st));
 	return repack(c, st);
+}
+
+// the first triangle of a specular table that breaks the rules (finite, ks >= 0, 0 <= p <= 1), or n_tris
+static size_t spec_first_bad(const float* spec, size_t n_tris) {
+	for (size_t i = 0; i < n_tris; ++i) {
+		const float* q = spec + i * 4;
+		for (int k = 0; k < 4; ++k) if (!std::isfinite(q[k]) || !(q[k] >= 0.0f)) return i;
+		if (!(q[3] <= 1.0f)) return i;
+	}
+	return n_tris;
+}
+
+int sphip_set_specular(sphip_t* c, const float* spec) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_specular called before a scene was set");
+	if (spec) {
+		// kSpecBit marks a mirror bounce in the path history: triangle indices must stay below it
+		if (c->n_tris >= (size_t)sp::kSpecBit) return fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris);
+		const size_t bad = spec_first_bad(spec, c->n_tris);
+		if (bad < c->n_tris) {
+			const float* q = spec + bad * 4;
+			return fail(c, SPHIP_E_INVALID, "specular table: triangle %zu has {ks %g %g %g, p %g} (every value finite, ks >= 0, 0 <= p <= 1)", bad,
+			            (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
+		}
+	}
+	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old table
+	if (!c->kids.empty()) {
+		c->have_spec = false;                      // a device that refuses leaves no device with a table: they must never differ
+		for (sphip_ctx* k : c->kids)
+			if (const int rc = sphip_set_specular(k, spec)) {
+				for (sphip_ctx* q : c->kids) q->have_spec = false;
+				return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+			}
+		c->have_spec = spec != nullptr;
+		return SPHIP_OK;
+	}
+	c->have_spec = false;
+	if (!spec) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure(c, c->spec, c->n_tris * 16))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->spec.p, spec, c->n_tris * 16, hipMemcpyHostToDevice, c->own_stream));
+	HIP_TRY(c, hipStreamSynchronize(c->own_stream));   // spec is borrowed: do not outlive the call
+	c->have_spec = true;
+	return SPHIP_OK;
+}
+
+int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_specular_device called before a scene was set");
+	c->acc_stale = c->acc_on;
+	c->have_spec = false;
+	if (!d_spec) return SPHIP_OK;
+	if (c->n_tris >= (size_t)sp::kSpecBit) return fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris);
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure(c, c->spec, c->n_tris * 16))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->spec.p, d_spec, c->n_tris * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+	c->have_spec = true;
+	return SPHIP_OK;
 }
 
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,

@@ -35,6 +35,11 @@ namespace hip_renderer {
 	// the thin lens of camera samples (sphip_set_lens): aperture 0 = pinhole; throws std::runtime_error on values the library refuses.
 	// The lens joins the key of a progressive accumulation on the camera path
 	extern void set_lens(scene::renderer* r, float aperture, float focus_dist);
+	// specular reflection (sphip_set_specular, SPHIP_FLAG_SPECULAR; include/spath_hip.h "specular reflection"): a table of n_tris rows
+	// ks.r ks.g ks.b p (copied) beside the materials of the scenes rendered next; while one is set, path-traced frames mirror by it
+	// (render_flat is unchanged).  NULL or n_tris = 0 removes it.  A table the library refuses makes the next frame throw
+	// std::runtime_error, as does one whose size differs from the scene's.  Changing it begins a new progressive accumulation.
+	extern void set_specular(scene::renderer* r, const float* spec, size_t n_tris);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

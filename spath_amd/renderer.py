@@ -100,6 +100,20 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
         self._accum_key = None
         self.last_stats = None
+        self._spec = None
+
+    def set_specular(self, spec):
+        """The specular table of capi.FLAG_SPECULAR renders ([n_tris, 4] float32, scene.specular_table; None: no table), like
+        hip_renderer::set_specular: it goes to the library with the next scene upload and begins a new accumulation, and while one is
+        set every path-traced frame carries capi.FLAG_SPECULAR (render_flat never does).  Without a table the flags are the caller's."""
+        self._spec = None if spec is None else np.ascontiguousarray(spec, dtype=np.float32).reshape(-1, 4).copy()
+        self._scene_key = None
+
+    def _flags(self, mode):
+        """the flags word of a frame: FLAG_SPECULAR on while a table is set, and never on the flat pass"""
+        if mode == capi.MODE_FLAT:
+            return self.flags & ~capi.FLAG_SPECULAR
+        return self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
 
     def get_description(self) -> str:
         return self.ctx.description
@@ -108,9 +122,11 @@ class HipRenderer(BasicRenderer):
         tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)[:n_tris]
         mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 6)[:n_tris]
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
-        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()))
+        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
+            if self._spec is not None:
+                self.ctx.set_specular(self._spec[:n_tris])
             self._scene_key = key
 
     def _begin_rule(self):
@@ -140,12 +156,14 @@ class HipRenderer(BasicRenderer):
         out.res_x, out.res_y = vp.res_x, vp.res_y          # cpu_renderer.cpp:120-122
         if self.progressive and mode == capi.MODE_PT:
             rays = np.ascontiguousarray(vp.rays, dtype=np.float32).reshape(-1, 6)
-            key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, self.flags, self.adaptive)
-            self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=self.flags,
+            flags = self._flags(mode)
+            key = ("rays", vp.res_x, vp.res_y, rays.tobytes(), self._scene_key, self.seed, flags, self.adaptive)
+            self._accum_step(key, lambda: self.ctx.accum_begin(rays=rays, w=vp.res_x, h=vp.res_y, seed=self.seed, flags=flags,
                                                                adaptive=self._begin_rule()),
                              n_samples, out)
             return
-        out.values = self.ctx.render(vp.rays, vp.res_x, vp.res_y, n_samples, seed=self.seed, mode=mode, flags=self.flags)
+        flags = self._flags(mode)                                                               # the flat pass has no materials to mirror
+        out.values = self.ctx.render(vp.rays, vp.res_x, vp.res_y, n_samples, seed=self.seed, mode=mode, flags=flags)
         self.last_stats = self.ctx.stats()
 
     def render_flat(self, vp, tris, mats, n_tris, n_samples, out):
@@ -161,12 +179,13 @@ class HipRenderer(BasicRenderer):
         out.res_x, out.res_y = self.vc.res_x, self.vc.res_y
         if self.progressive and not flat:
             ca = capi.CameraArgs.from_camera(self.vc)
-            key = ("cam", bytes(ca), self._scene_key, self.seed, self.flags, self.adaptive)
-            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=self.flags, adaptive=self._begin_rule()),
+            flags = self._flags(capi.MODE_PT)
+            key = ("cam", bytes(ca), self._scene_key, self.seed, flags, self.adaptive)
+            self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=flags, adaptive=self._begin_rule()),
                              max(int(n_samples), 1), out)
             return
-        out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed,
-                                            mode=capi.MODE_FLAT if flat else capi.MODE_PT, flags=self.flags)
+        out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed, mode=capi.MODE_FLAT if flat else capi.MODE_PT,
+                                            flags=self._flags(capi.MODE_FLAT if flat else capi.MODE_PT))
         self.last_stats = self.ctx.stats()
 
     def adaptive_counts(self):

@@ -17,6 +17,7 @@ import numpy as np
 
 F = np.float32
 SCENE_MAGIC = 0x43535053  # 'SPSC'
+SPEC_MAGIC = 0x50535053   # 'SPSP'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -182,6 +183,47 @@ def light_table(tris: np.ndarray, mats: np.ndarray):
     tipdf = np.zeros(t.shape[0], F)
     tipdf[tri] = ipdf
     return tri, np.array(cdf, np.float64), ipdf, W, tipdf
+
+
+def specular_table(tris: np.ndarray, mats: np.ndarray, ks=0.0, which=None, p=None) -> np.ndarray:
+    """A specular table for capi.Context.set_specular (include/spath_hip.h, "specular reflection"): float32 [N, 4] rows ks.r ks.g ks.b p.
+    ks: the mirror reflectance, a scalar, an rgb triple or an [N, 3] array (finite, >= 0); which: the triangles that get it (an index
+    array or a boolean mask; None = all), every other row is zero (the triangle stays as it is).  p, the probability of the mirror
+    lobe, is the given value (a scalar or [N], in [0, 1]) or, when None, the share of the mirror in what the triangle reflects:
+        s = ((double)ks.r + ks.g) + ks.b,  r = ((double)rho.r + rho.g) + rho.b  (rho: the material's reflectance),
+        p = float32(s / (s + r)) where s > 0, else 0
+    so a triangle with no diffuse reflectance becomes a pure mirror (p = 1) and one with ks = 0 stays diffuse (p = 0).  Any p in
+    (0, 1) gives the same expectation; this one spends the samples where the energy goes."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    m = np.asarray(mats, F).reshape(-1, 6)
+    n = t.shape[0]
+    if m.shape[0] != n:
+        raise ValueError("one material per triangle")
+    sel = np.ones(n, bool) if which is None else np.zeros(n, bool)
+    if which is not None:
+        sel[np.asarray(which)] = True
+    spec = np.zeros((n, 4), F)
+    spec[:, 0:3] = np.broadcast_to(np.asarray(ks, F), (n, 3)) if np.ndim(ks) else F(ks)
+    if p is None:
+        k64, r64 = spec[:, 0:3].astype(np.float64), m[:, 0:3].astype(np.float64)
+        s = (k64[:, 0] + k64[:, 1]) + k64[:, 2]
+        r = (r64[:, 0] + r64[:, 1]) + r64[:, 2]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            spec[:, 3] = np.where(s > 0.0, s / (s + r), 0.0).astype(F)
+    else:
+        spec[:, 3] = np.broadcast_to(np.asarray(p, F), (n,))
+    spec[~sel] = 0.0
+    if not (np.isfinite(spec).all() and (spec >= 0).all() and (spec[:, 3] <= 1).all()):
+        raise ValueError("specular table: every value finite, ks >= 0, 0 <= p <= 1")
+    return spec
+
+
+def write_specular(path, spec: np.ndarray) -> None:
+    """Specular file read by the headless CLI (--spec), beside the scene file: 'SPSP', n, n * 4 float32."""
+    spec = np.ascontiguousarray(spec, dtype=F).reshape(-1, 4)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", SPEC_MAGIC, spec.shape[0]))
+        f.write(spec.tobytes())
 
 
 def write_scene(path, tris: np.ndarray, mats: np.ndarray) -> None:
