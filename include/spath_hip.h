@@ -71,9 +71,11 @@ enum {
 	                                   SPHIP_FLAG_NEE; see "multiple importance sampling" below.  Same expectation again. */
 	SPHIP_FLAG_CAMERA_SAMPLES = 0x1000, /* OPT-IN per-sample camera rays (pixel antialiasing, thin-lens depth of field) for the camera paths
 	                                   of SPHIP_MODE_PT; see "camera samples" below.  Changes the image: it is no longer the reference's. */
-	SPHIP_FLAG_SPECULAR = 0x2000     /* OPT-IN mirror and mixed diffuse/mirror materials from the context's specular table
+	SPHIP_FLAG_SPECULAR = 0x2000,    /* OPT-IN mirror and mixed diffuse/mirror materials from the context's specular table
 	                                   (sphip_set_specular) for SPHIP_MODE_PT; see "specular reflection" below.  Without the flag the
 	                                   table is ignored. */
+	SPHIP_FLAG_SMOOTH = 0x4000       /* OPT-IN smooth shading by the context's per-vertex normals (sphip_set_vertex_normals) for
+	                                   SPHIP_MODE_PT; see "smooth shading" below.  Without the flag the normals are ignored. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -199,7 +201,8 @@ int sphip_plan_shard(size_t width, size_t height, int n_devices, size_t tile_row
  *        4  ray_tri_strict (geom.h:197-222)                        in f32[15n] pos dir v0 v1 v2       out f32[n] distance or -1
  *        5  vec3_rgba      (scene.h:32-39)                         in f32[3n]                         out u32[n]
  *        6  the f16 matrix-pipe side product of sp_cylm_scan.h      in f32[12n] 5 triangle values, 5 ray values, P_a (a half), 0
- *                                                                  out f32[2n] the instruction's result, the same 16 products summed in double */
+ *                                                                  out f32[2n] the instruction's result, the same 16 products summed in double
+ *        7  shade_normal   ("smooth shading" below)                in f32[24n] pos dir v0 v1 v2 n0 n1 n2   out f32[6n] u, v, ns.xyz, sm */
 int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void* out);
 
 /* TEST-ONLY: stage 1 of the default scan ALONE -- the conservative reject that decides which (ray, triangle) pairs ever reach
@@ -461,6 +464,51 @@ int sphip_set_specular(sphip_t* ctx, const float* spec);
  * `stream` alone, and copied, so the caller may free d_spec once the stream has passed the call.  It does NOT validate the values:
  * a table that breaks the rules above gives undefined images (never out-of-bounds accesses). */
 int sphip_set_specular_device(sphip_t* ctx, const void* d_spec, void* stream);
+
+/* ---- smooth shading (SPHIP_FLAG_SMOOTH): per-vertex normals beside the scene, 9 f32 per triangle:
+ * n0.xyz n1.xyz n2.xyz for v0 v1 v2.  Every hit of a path then shades with the normal interpolated at the hit point instead of the
+ * triangle's stored one.  The normals need not be unit length (their lengths weigh the interpolation); a row of nine zeros leaves
+ * that triangle flat.  The 12-float triangle and sphip_set_scene are unchanged.
+ *
+ * Valid for SPHIP_MODE_PT with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with variants 1, 8 (SPHIP_FLAG_ACCEL)
+ * and 16 (both workgroup shapes), with SPHIP_FLAG_SPECULAR, SPHIP_FLAG_CAMERA_SAMPLES, progressive and adaptive accumulation,
+ * denoising, sample chunks, primary-hit reuse, shards and multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT; with
+ * SPHIP_FLAG_NEE without SPHIP_FLAG_MIS; with any other variant (2 and 15 are A/B scans: leaving them out halves the new kernels).
+ * SPHIP_E_STATE: the flag without normals.  sphip_closest_hit_device ignores the flag.  Without the flag every render is bit for
+ * bit what it is without normals; with the flag and a table of zeros too.
+ *
+ * The arithmetic, at hit d of a path on triangle i by the ray (o, dir); n is the triangle's stored normal turned against dir as
+ * always, (n0, n1, n2) = the triangle's row; f32, every operation rounded on its own, nothing fused,
+ * dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z:
+ *   bary:    edge1, edge2, h, a, f = 1.0f / a, s, u = f * dot(s, h), q, v = f * dot(dir, q): exactly as the intersection test computes
+ *            them for (o, dir, triangle i) (the reference's geom.h:200-212); recomputed for the winning triangle only, after the scan
+ *   interp:  w = (1.0f - u) - v;  m = (n0 * w + n1 * u) + n2 * v per component;  l2 = dot3(m, m)
+ *            sm = l2 > 0 and l2 finite.  !sm: ns = n, and the hit is in every respect what it is without the flag.
+ *            sm:  ns = m / sqrtf(l2) per component (IEEE);  if dot3(ns, n) < 0: ns = -ns
+ *   diffuse: nd = rand_unit_vec(ns, r1, r2);  ct = dot3(nd, ns);  sm and dot3(nd, n) < 0: the path ENDS after hit d
+ *            (the hit keeps E_d; rec_{d+1} = 0; nothing more is scanned or counted)
+ *   mirror:  c = dot3(dir, ns);  t = c + c;  nd = dir - ns * t;  sm and (!(c < 0) or dot3(nd, n) < 0): the path ends likewise
+ *   light:   cos_x = dot3(wd, ns);  additionally, when sm, L_d = 0 without a shadow ray when !(dot3(wd, n) > 0)
+ * Emitters keep their stored normal in cos_y, u_b and the light table (area densities are geometric).  Origins, source-triangle
+ * skipping, the draw streams, wS, wD, Ew, D_d and the unwind expressions are unchanged; ct is simply the new value.  Both strategies
+ * of multiple importance sampling integrate over the same set {w . ns > 0, w . n > 0}, so the plain estimator and NEE | MIS keep one
+ * expectation.
+ *
+ * G-buffer: with the flag and normals set, sphip_gbuffer_device and sphip_accum_gbuffer store ns of the primary ray (the same
+ * device function) where they store n otherwise; dist, albedo and mat are unchanged, and so is the filter.
+ * sphip_selftest_device what 7: in f32[24 n] (pos dir v0 v1 v2 n0 n1 n2), out f32[6 n] (u, v, ns.xyz, sm as 0/1), the stored normal
+ * taken as the reference's flat_normal of the vertices: the device function the kernels call. */
+
+/* The context's vertex normals: n_tris * 9 f32 on the host for the scene last set (NULL clears them); blocking, the array is
+ * borrowed for the call; accepted by multi-device contexts (every device keeps the whole table, like the scene).  Every set_scene
+ * clears them.  During an accumulation it ends the accumulation as a set_scene does (the next step: SPHIP_E_STATE).
+ * SPHIP_E_STATE without a scene; SPHIP_E_INVALID when a value is not finite (the message names the first such triangle; the table
+ * stays as it was). */
+int sphip_set_vertex_normals(sphip_t* ctx, const float* vn);
+/* The same from a device pointer, by the rules of sphip_set_scene_device: single-device contexts (SPHIP_E_STATE otherwise), ordered by
+ * `stream` alone, and copied, so the caller may free d_vn once the stream has passed the call.  It does NOT validate the values:
+ * non-finite normals give undefined images (never out-of-bounds accesses: the table is indexed by triangle alone). */
+int sphip_set_vertex_normals_device(sphip_t* ctx, const void* d_vn, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

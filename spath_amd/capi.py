@@ -20,6 +20,7 @@ FLAG_NEE = 0x400            # opt-in next-event estimation: light sampling with 
 FLAG_MIS = 0x800            # with FLAG_NEE: multiple importance sampling of its light samples
 FLAG_CAMERA_SAMPLES = 0x1000  # per-sample camera rays on the camera paths: pixel antialiasing, thin lens
 FLAG_SPECULAR = 0x2000      # mirror and mixed diffuse/mirror materials from the context's specular table
+FLAG_SMOOTH = 0x4000        # smooth shading by the context's per-vertex normals
 
 
 def flag_chunks(n: int) -> int:
@@ -40,6 +41,7 @@ SYMBOLS = (
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
     "sphip_set_lens", "sphip_camera_rays_device",
     "sphip_set_specular", "sphip_set_specular_device",
+    "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -198,6 +200,10 @@ def load():
     L.sphip_set_specular.argtypes = [vp, vp]
     L.sphip_set_specular_device.restype = C.c_int
     L.sphip_set_specular_device.argtypes = [vp, vp, vp]
+    L.sphip_set_vertex_normals.restype = C.c_int
+    L.sphip_set_vertex_normals.argtypes = [vp, vp]
+    L.sphip_set_vertex_normals_device.restype = C.c_int
+    L.sphip_set_vertex_normals_device.argtypes = [vp, vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -330,6 +336,18 @@ class Context:
             raise ValueError("one specular row per triangle of the scene")
         self._check(self._L.sphip_set_specular(self._h, spec.ctypes.data), "sphip_set_specular")
 
+    def set_vertex_normals(self, vn):
+        """sphip_set_vertex_normals: the per-vertex normals of FLAG_SMOOTH renders, (n_tris, 9) f32 rows n0.xyz n1.xyz n2.xyz for the
+        scene last set (scene.vertex_normals builds them); None clears them.  Every set_scene clears them too."""
+        import numpy as np
+        if vn is None:
+            self._check(self._L.sphip_set_vertex_normals(self._h, None), "sphip_set_vertex_normals")
+            return
+        vn = np.ascontiguousarray(vn, dtype=np.float32).reshape(-1, 9)
+        if vn.shape[0] != getattr(self, "_n_tris", vn.shape[0]):
+            raise ValueError("one row of vertex normals per triangle of the scene")
+        self._check(self._L.sphip_set_vertex_normals(self._h, vn.ctypes.data), "sphip_set_vertex_normals")
+
     def render(self, rays, w, h, n_samples, seed=1, mode=MODE_PT, flags=0, want_accum=False):
         import numpy as np
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
@@ -349,6 +367,10 @@ class Context:
     def set_specular_device(self, d_spec: int, stream: int = 0):
         """sphip_set_specular_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_specular_device(self._h, d_spec, stream), "sphip_set_specular_device")
+
+    def set_vertex_normals_device(self, d_vn: int, stream: int = 0):
+        """sphip_set_vertex_normals_device: the normals from a device pointer (n_tris * 9 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_vertex_normals_device(self._h, d_vn, stream), "sphip_set_vertex_normals_device")
 
     def render_device(self, d_rays: int, n_rays: int, n_samples: int, d_out_rgba: int, *, seed=1, mode=MODE_PT,
                       flags=0, shard=None, image_width=0, d_out_accum: int = 0, stream: int = 0):
@@ -484,7 +506,8 @@ class Context:
                                                 rgb.ctypes.data if want_rgb and w * h else None), "sphip_accum_denoise")
         return (out, rgb) if want_rgb else out
 
-    SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2)}
+    SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
+                    7: ("float32", 6)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""

@@ -157,6 +157,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	constexpr bool mis = IsMis<Acc...>::value;         // MIS on top of it (sp_kernels.h MisArgs): the folded terms D_0..D_4
 	constexpr bool spc = IsSpec<Acc...>::value;        // specular reflection (sp_kernels.h SpecArgs): kSpecBit in hidx marks a mirror bounce
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
+	constexpr bool smo = IsNorm<Acc...>::value;        // smooth shading (sp_kernels.h NormArgs): ns of shade_normal shades, n guards
+	static_assert(!smo || mis || !nee, "smooth shading: plain or NEE|MIS (DESIGN.md section 5.8)");
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
@@ -194,6 +196,9 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					const float* tn = a.tris + (size_t)bi * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);
+					f3 ns = n;                                    // the shading normal
+					bool sm = false, ended = false;               // smooth shading: a bounce below the surface ends the path
+					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
 					bool sl = false;                              // specular: this hit takes the mirror lobe
 					float pm = 0.0f;
 					if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
@@ -204,7 +209,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						const bool full = depth == 0 || (spc && (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);   // after a mirror bounce e_d counts in full
 						const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
 						f3 Ld = mk3(0.0f, 0.0f, 0.0f);
-						if (depth < kNeeDepths && !sl && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, n, bi, wd, tm, Lc)) {
+						if (depth < kNeeDepths && !sl && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, ns, bi, wd, tm, Lc) && (!smo || smooth_light_ok(sm, wd, n))) {
 							float sd; int si;
 							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
 							my_scans++;
@@ -224,18 +229,22 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						}
 					}
 					f3 nd;
-					if (spc && sl) { nd = spec_reflect(dir, n); hcos[depth] = 0.0f; }
-					else {
+					if (spc && sl) {
+						nd = spec_reflect(dir, ns); hcos[depth] = 0.0f;
+						if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
+					} else {
 						double r1, r2;
 						philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
-						nd = rand_unit_vec(n, r1, r2);
-						hcos[depth] = dot3(nd, n);
+						nd = rand_unit_vec(ns, r1, r2);
+						hcos[depth] = dot3(nd, ns);
+						if constexpr (smo) ended = sm && dot3(nd, n) < 0.0f;
 					}
 					hidx[depth] = spc && sl ? bi | kSpecBit : bi;
 					o = add3(o, scale3(dir, bd));
 					dir = nd;
 					src = bi;
 					nh = depth + 1;
+					if constexpr (smo) if (ended) alive = false;
 				} else {
 					alive = false;
 				}

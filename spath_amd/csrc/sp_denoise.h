@@ -13,10 +13,12 @@
 
 namespace sp {
 
-// one G-buffer entry per ray from the closest hit (idx, dist) of sphip_closest_hit_device; cls[t] = material class of triangle t
-__global__ void __launch_bounds__(256) k_gbuffer(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
-                                                 const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
-                                                 uint32_t n, float4* __restrict__ out) {
+// one G-buffer entry per ray from the closest hit (idx, dist) of sphip_closest_hit_device; cls[t] = material class of triangle t.
+// With a trailing NormArgs (smooth shading, sp_kernels.h: k_gbuffer_smooth) the normal is the path kernels' shading normal of the primary ray.
+template <typename... Norm>
+SP_DEV void gbuffer_entry(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
+                          const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
+                          uint32_t n, float4* __restrict__ out, const Norm... norm) {
 	const uint32_t p = blockIdx.x * 256u + threadIdx.x;
 	if (p >= n) return;
 	const int i = idx[p];
@@ -26,12 +28,27 @@ __global__ void __launch_bounds__(256) k_gbuffer(const float* __restrict__ rays,
 		f3 nn = mk3(tn[0], tn[1], tn[2]);
 		const f3 dir = mk3(rays[(size_t)p * 6 + 3], rays[(size_t)p * 6 + 4], rays[(size_t)p * 6 + 5]);
 		if (dot3(nn, dir) > 0.0f) nn = scale3(nn, -1.0f);            // as the path kernels orient it (sp_kernels.h)
+		if constexpr (IsNorm<Norm...>::value) {
+			const f3 o = mk3(rays[(size_t)p * 6], rays[(size_t)p * 6 + 1], rays[(size_t)p * 6 + 2]);
+			const f3 ng = nn;
+			(void)shade_normal(tris + (size_t)i * 12, norm_table(norm...) + (size_t)i * 9, o, dir, ng, nn);
+		}
 		const float* m = mats + (size_t)i * 6;
 		g0 = make_float4(nn.x, nn.y, nn.z, dist[p]);
 		g1 = make_float4(m[0], m[1], m[2], __int_as_float(cls[i]));
 	}
 	out[(size_t)p * 2] = g0;
 	out[(size_t)p * 2 + 1] = g1;
+}
+__global__ void __launch_bounds__(256) k_gbuffer(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
+                                                 const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
+                                                 uint32_t n, float4* __restrict__ out) {
+	gbuffer_entry(rays, idx, dist, tris, mats, cls, n, out);
+}
+__global__ void __launch_bounds__(256) k_gbuffer_smooth(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
+                                                        const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
+                                                        uint32_t n, float4* __restrict__ out, const NormArgs norm) {
+	gbuffer_entry(rays, idx, dist, tris, mats, cls, n, out, norm);
 }
 
 SP_DEV void dn_emit(uint32_t p, float r, float g, float b, uint32_t* __restrict__ rgba, float* __restrict__ rgb) {

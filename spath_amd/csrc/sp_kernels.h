@@ -118,6 +118,13 @@ struct SpecArgs {
 constexpr uint32_t kSpecStream = 32u;
 constexpr int kSpecBit = 0x40000000;
 
+// smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
+// n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
+// CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
+struct NormArgs {
+	const float* vnorm;        // n_tris * 9
+};
+
 // the pack's optional elements, found by type wherever they sit (MisArgs is a NeeArgs, AdaptArgs an AccumArgs)
 template <typename T, typename... P> struct PackHas { static constexpr bool value = (std::is_same<T, P>::value || ...); };
 template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHas<AdaptArgs, Acc...>::value; };
@@ -125,6 +132,7 @@ template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
 template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value; };
+template <typename... Acc> struct IsNorm { static constexpr bool value = PackHas<NormArgs, Acc...>::value; };
 // a running sum rides in the pack (progressive or adaptive)
 template <typename... Acc> struct HasAccum { static constexpr bool value = PackHas<AccumArgs, Acc...>::value || IsAdapt<Acc...>::value; };
 // the first element of the pack that is a T
@@ -138,6 +146,7 @@ template <typename... P> SP_DEV const AccumArgs& accum_args(const P&... p) { ret
 template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return pack_get<NeeArgs>(p...); }
 template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
 template <typename... P> SP_DEV const float4* spec_table(const P&... p) { return pack_get<SpecArgs>(p...).spec; }
+template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
 template <typename... Acc>
@@ -286,6 +295,40 @@ __global__ void __launch_bounds__(256) k_assemble(const uint32_t* __restrict__ g
 	for (int c = 0; c < C; ++c) out[(size_t)p * C + c] = gathered[((size_t)r * pad + k) * C + c];
 }
 
+// ---- smooth shading (include/spath_hip.h): the shading normal ns of the hit of ray (o, dir) on the triangle
+// whose vertices are tv[0..8] (v0 v1 v2) and whose vertex normals are vn[0..8]; n is the triangle's stored normal turned against dir.
+//   bary:    u, v exactly as ray_tri_strict computed them for this triangle (geom.h:200-212), once, for the winning triangle
+//   interp:  w = (1 - u) - v;  m = (n0 w + n1 u) + n2 v;  l2 = dot3(m, m);  smooth iff l2 > 0 and finite
+//            ns = m / sqrtf(l2) per component, turned to n's side; otherwise ns = n and the hit is the flat one
+// Returns whether the hit is smooth.  uv: where the selftest wants u, v.
+// The light sample of a smooth hit (nee_light with ns for n) counts only when its direction is above the stored normal as well
+// (smooth_light_ok): both strategies of MIS then integrate over {w . ns > 0, w . n > 0}.
+SP_DEV bool shade_normal(const float* __restrict__ tv, const float* __restrict__ vn, f3 o, f3 dir, f3 n, f3& ns, float* uv = nullptr) {
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);   // geom.h:200-201
+	const f3 h = cross3(dir, e2);                    // :202
+	const float a = dot3(e1, h);                     // :203
+	const float f = recip_ieee(a);                   // :206
+	const f3 s = sub3(o, v0);                        // :207
+	const float u = f * dot3(s, h);                  // :208
+	const f3 q = cross3(s, e1);                      // :211
+	const float v = f * dot3(dir, q);                // :212
+	if (uv) { uv[0] = u; uv[1] = v; }
+	const float w = (1.0f - u) - v;
+	const f3 m = add3(add3(scale3(mk3(vn[0], vn[1], vn[2]), w), scale3(mk3(vn[3], vn[4], vn[5]), u)), scale3(mk3(vn[6], vn[7], vn[8]), v));
+	const float l2 = dot3(m, m);
+	const bool sm = l2 > 0.0f && l2 < __builtin_inff();
+	ns = n;
+	if (sm) {
+		const float l = __builtin_sqrtf(l2);
+		ns = mk3(m.x / l, m.y / l, m.z / l);
+		if (dot3(ns, n) < 0.0f) ns = scale3(ns, -1.0f);
+	}
+	return sm;
+}
+
+SP_DEV bool smooth_light_ok(bool sm, f3 wd, f3 n) { return !sm || dot3(wd, n) > 0.0f; }
+
 // ---- test-only: the device functions of the path on caller-supplied inputs (include/spath_hip.h: sphip_selftest_device)
 __global__ void __launch_bounds__(256) k_selftest(int what, const void* __restrict__ in, uint32_t n, void* __restrict__ out) {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -315,6 +358,23 @@ __global__ void __launch_bounds__(256) k_selftest(int what, const void* __restri
 		const float* q = (const float*)in + 3 * (size_t)i;
 		((uint32_t*)out)[i] = vec3_rgba(mk3(clamp01(q[0]), clamp01(q[1]), clamp01(q[2])));
 	}
+}
+
+// what 7: shade_normal.  pos dir v0 v1 v2 n0 n1 n2 -> u v ns.xyz sm; the stored normal is geom::flat_normal of the vertices (geom.h:192-195)
+__global__ void __launch_bounds__(256) k_selftest_shade(const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const float* q = in + 24 * (size_t)i;
+	const f3 o = mk3(q[0], q[1], q[2]), dir = mk3(q[3], q[4], q[5]), v0 = mk3(q[6], q[7], q[8]);
+	const f3 c = cross3(sub3(mk3(q[9], q[10], q[11]), v0), sub3(mk3(q[12], q[13], q[14]), v0));
+	const float l = __builtin_sqrtf(dot3(c, c));
+	f3 nn = mk3(c.x / l, c.y / l, c.z / l);
+	if (dot3(nn, dir) > 0.0f) nn = scale3(nn, -1.0f);
+	f3 ns;
+	float uv[2];
+	const bool sm = shade_normal(q + 6, q + 15, o, dir, nn, ns, uv);
+	float* w = out + 6 * (size_t)i;
+	w[0] = uv[0]; w[1] = uv[1]; w[2] = ns.x; w[3] = ns.y; w[4] = ns.z; w[5] = sm ? 1.0f : 0.0f;
 }
 
 SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
@@ -549,6 +609,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	constexpr bool mis = IsMis<Acc...>::value;                   // MIS: nee too; the folded terms D_0..D_4
 	constexpr bool spc = IsSpec<Acc...>::value;                  // specular reflection (SpecArgs): a mirror lobe per hit, marked by kSpecBit in idx0..4
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
+	constexpr bool smo = IsNorm<Acc...>::value;                  // smooth shading (NormArgs): ns of shade_normal shades, n guards
+	static_assert(!smo || ((mis || !nee) && VARIANT == 1), "smooth shading: plain or NEE|MIS, variant 1 (DESIGN.md section 5.8)");
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = !cam && (a.flags & 0x100u) != 0;          // the host rejects reuse with camera samples
@@ -594,27 +656,35 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			f3 wd = dir, Lc = mk3(0.0f, 0.0f, 0.0f);
 			float tm = kMaxDist;
 			f3 De = Lc;                                           // MIS: e_d w_b
+			bool ended = false;                                   // smooth shading: the bounce left the surface's upper side, the path ends here
 			if (hit) {
 				const float* tn = a.tris + (size_t)bi * 12 + 9;
 				f3 n = mk3(tn[0], tn[1], tn[2]);                  // :55
 				if (dot3(n, dir) > 0.0f) n = scale3(n, -1.0f);    // :56-57
+				f3 ns = n;                                        // the shading normal
+				bool sm = false;
+				if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
 				bool sl = false;                                  // specular: this hit takes the mirror lobe
 				float pm = 0.0f;
 				if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
 				if constexpr (mis) {
 					if (depth == 0 || (spc && pspec)) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
 					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
-					if (depth < kNeeDepths && !sl) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
+					if (depth < kNeeDepths && !sl) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc);
+					if constexpr (smo) sh = sh && smooth_light_ok(sm, wd, n);
 					if constexpr (spc) if (sh) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
 				f3 nd;
 				float ct = 0.0f;
-				if (spc && sl) nd = spec_reflect(dir, n);
-				else {
+				if (spc && sl) {
+					nd = spec_reflect(dir, ns);
+					if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
+				} else {
 					double r1, r2;
 					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
-					nd = rand_unit_vec(n, r1, r2);                // :58
-					ct = dot3(nd, n);                             // :62
+					nd = rand_unit_vec(ns, r1, r2);               // :58
+					ct = dot3(nd, ns);                            // :62
+					if constexpr (smo) ended = sm && dot3(nd, n) < 0.0f;
 				}
 				o = add3(o, scale3(dir, bd));                     // geom.h:218 point = pos + dir*d
 				dir = nd;
@@ -626,7 +696,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				else if (depth == 3) { idx3 = bi; c3 = ct; }
 				else { idx4 = bi; c4 = ct; }
 			}
-			alive = hit;
+			alive = hit && !ended;
 			if constexpr (nee) {
 				// the shadow rays of the block: (x, wd), skipping the hit triangle, bounded by tmax; any hit occludes
 				if (__syncthreads_or(sh ? 1 : 0)) {

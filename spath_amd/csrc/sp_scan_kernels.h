@@ -102,6 +102,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 // touched once per sample, never inside the scan), and ray k is local pixel list[k] for the RNG and the running sums.
 // With a SpecArgs (specular reflection, sp_kernels.h) a hit that took the mirror lobe carries kSpecBit in its history index: the
 // slot stays 8 B per depth, and the unwind (and the next hit's MIS weight) reads the lobe back from there.
+// With a NormArgs (smooth shading, sp_kernels.h) the barycentric coordinates are recomputed for the winning triangle after the
+// scan (shade_normal), never inside its tile loops; a path whose bounce leaves the surface's upper side stops being active.
 template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
                                                    int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work, const Acc... acc_args) {
@@ -121,6 +123,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	constexpr bool cam = IsCam<Acc...>::value;               // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
 	constexpr bool spc = IsSpec<Acc...>::value;              // specular reflection (sp_kernels.h SpecArgs)
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
+	constexpr bool smo = IsNorm<Acc...>::value;              // smooth shading (sp_kernels.h NormArgs)
+	static_assert(!smo || ((mis || !nee) && SCAN >= 3), "smooth shading: plain or NEE|MIS, the default scan (DESIGN.md section 5.8)");
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -207,17 +211,21 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				f3 nadj[R];
 				bool hitr[R], any_sh = false;
 				bool slr[R];                                     // specular: the hit takes the mirror lobe (no light sample)
+				bool smr[R];                                     // smooth shading: nadj is an interpolated normal
 #pragma unroll
 				for (int r = 0; r < R; ++r) {
 					hitr[r] = s.act[r] && (bi[r] >= 0);
 					sh.o[r] = s.o[r]; sh.dir[r] = s.dir[r]; sh.src[r] = s.src[r]; sh.act[r] = false; tmx[r] = kMaxDist;
 					nadj[r] = s.dir[r];
 					slr[r] = false;
+					smr[r] = false;
 					if (hitr[r]) {
 						const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
 						f3 n = mk3(tn[0], tn[1], tn[2]);
 						if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
-						nadj[r] = n;
+						f3 ns = n;                                 // the shading normal
+						if constexpr (smo) smr[r] = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
+						nadj[r] = ns;
 						const f3 x = add3(s.o[r], scale3(s.dir[r], bd[r]));
 						f3 wd = s.dir[r], Lc = mk3(0.0f, 0.0f, 0.0f);
 						float tm = kMaxDist;
@@ -233,11 +241,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 								if (depth > 0) full = (hist[(size_t)(depth - 1) * n_work + k0 + r * B].x & kSpecBit) != 0;
 								const float pm = spec_table(acc_args...)[bi[r]].w;
 								slr[r] = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, pm);
-								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc);
+								if constexpr (smo) sh.act[r] = sh.act[r] && smooth_light_ok(smr[r], wd, n);
 								if (sh.act[r]) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 							}
 							const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), s.dir[r], bd[r], bi[r]);
-							if constexpr (!spc) sh.act[r] = depth < kNeeDepths && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, n, bi[r], wd, tm, Lc);
+							if constexpr (!spc) sh.act[r] = depth < kNeeDepths && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc);
+							if constexpr (smo && !spc) sh.act[r] = sh.act[r] && smooth_light_ok(smr[r], wd, n);
 							const f3 Dd = depth < kNeeDepths ? add3(De, sh.act[r] ? Lc : mk3(0.0f, 0.0f, 0.0f)) : De;
 							Lp[0] = Dd.x; Lp[n_work] = Dd.y; Lp[(size_t)2 * n_work] = Dd.z;
 							if (sh.act[r]) {
@@ -274,15 +284,25 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				// the bounce, exactly as without NEE
 #pragma unroll
 				for (int r = 0; r < R; ++r) {
+					bool ended = false;                          // smooth shading: the bounce left the surface's upper side
 					if (hitr[r]) {
 						f3 nd;
 						float ct = 0.0f;
-						if (spc && slr[r]) nd = spec_reflect(s.dir[r], nadj[r]);
-						else {
+						f3 ng = nadj[r];                         // smooth shading: the stored normal again, read after the shadow scan
+						if constexpr (smo) {
+							const float* tn = a.tris + (size_t)sh.src[r] * 12 + 9;
+							ng = mk3(tn[0], tn[1], tn[2]);
+							if (dot3(ng, s.dir[r]) > 0.0f) ng = scale3(ng, -1.0f);
+						}
+						if (spc && slr[r]) {
+							nd = spec_reflect(s.dir[r], nadj[r]);
+							if constexpr (smo) ended = smr[r] && (!(dot3(s.dir[r], nadj[r]) < 0.0f) || dot3(nd, ng) < 0.0f);
+						} else {
 							double r1, r2;
 							philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
 							nd = rand_unit_vec(nadj[r], r1, r2);
 							ct = dot3(nd, nadj[r]);
+							if constexpr (smo) ended = smr[r] && dot3(nd, ng) < 0.0f;
 						}
 						s.o[r] = sh.o[r];
 						s.dir[r] = nd;
@@ -290,27 +310,34 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && slr[r] ? sh.src[r] | kSpecBit : sh.src[r], (int)__float_as_uint(ct));
 						nh[r] = depth + 1;
 					}
-					s.act[r] = hitr[r];
+					s.act[r] = hitr[r] && !ended;
 				}
 				continue;
 			}
 #pragma unroll
 			for (int r = 0; r < R; ++r) {
 				const bool hit = s.act[r] && (bi[r] >= 0);
+				bool ended = false;                              // smooth shading: the bounce left the surface's upper side
 				if (hit) {
 					const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
 					f3 n = mk3(tn[0], tn[1], tn[2]);
 					if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
+					f3 ns = n;                                   // the shading normal
+					bool sm = false;
+					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
 					bool sl = false;
 					if constexpr (spc) sl = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, spec_table(acc_args...)[bi[r]].w);
 					f3 nd;
 					float ct = 0.0f;
-					if (spc && sl) nd = spec_reflect(s.dir[r], n);
-					else {
+					if (spc && sl) {
+						nd = spec_reflect(s.dir[r], ns);
+						if constexpr (smo) ended = sm && (!(dot3(s.dir[r], ns) < 0.0f) || dot3(nd, n) < 0.0f);
+					} else {
 						double r1, r2;
 						philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
-						nd = rand_unit_vec(n, r1, r2);
-						ct = dot3(nd, n);
+						nd = rand_unit_vec(ns, r1, r2);
+						ct = dot3(nd, ns);
+						if constexpr (smo) ended = sm && dot3(nd, n) < 0.0f;
 					}
 					s.o[r] = add3(s.o[r], scale3(s.dir[r], bd[r]));
 					s.dir[r] = nd;
@@ -318,7 +345,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && sl ? bi[r] | kSpecBit : bi[r], (int)__float_as_uint(ct));
 					nh[r] = depth + 1;
 				}
-				s.act[r] = hit;
+				s.act[r] = hit && !ended;
 			}
 		}
 #pragma unroll

@@ -107,6 +107,9 @@ struct sphip_ctx {
 	// context keeps the whole table, like the scene); dropped by every set_scene
 	DevBuf spec;
 	bool have_spec = false;
+	// ---- smooth shading (SPHIP_FLAG_SMOOTH): the scene's vertex normals, 9 floats per triangle, kept and dropped like the specular table
+	DevBuf vnorm;
+	bool have_vnorm = false;
 };
 
 namespace {
@@ -165,6 +168,8 @@ bool variant_shipped(int v) {
 	TwoStage ts;
 	return v == 1 || v == 2 || v == kVariantAccel || (two_stage(v, &ts) && shape_shipped(ts.R, ts.split, ts.scan));
 }
+// smooth shading is built for the exact scan, the BVH and the default scan (both shapes)
+bool variant_smooth(int v) { return v == 1 || v == kVariantAccel || v == 16; }
 bool variant_built(int v) {
 #ifdef SP_ALL_VARIANTS
 	return v >= 1 && v <= kVariantLast;
@@ -203,6 +208,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->bvh_valid = c->filt_valid = c->cyl_valid = c->cylm_valid = false;
 	c->nee_valid = false;
 	c->have_spec = false;                          // the specular table belongs to the old scene
+	c->have_vnorm = false;                         // and so do the vertex normals
 	return SPHIP_OK;
 }
 
@@ -402,9 +408,9 @@ constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
 // f(args...) with the trailing pack of a path-tracing kernel for the run-time choices, always in the kernels' order: the running
 // sum (nothing, AccumArgs or AdaptArgs), the estimator (nothing, NeeArgs or MisArgs), the specular table (nothing or SpecArgs), the
-// camera (nothing or CamArgs).  Each combination is a kernel of its own; the table is composed with the plain estimator and with
-// MIS only (launch_render rejects it with NEE alone), and f prunes the other ones that are not built with if constexpr on the
-// pack traits (sp_kernels.h).
+// vertex normals (nothing or NormArgs), the camera (nothing or CamArgs).  Each combination is a kernel of its own; the two tables
+// are composed with the plain estimator and with MIS only (launch_render rejects them with NEE alone), and f prunes the other ones
+// that are not built with if constexpr on the pack traits (sp_kernels.h).
 template <typename F>
 void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 	if (ad) f(*ad);
@@ -413,14 +419,19 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::CamArgs* cam, F&& f) {
+               const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
+			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
 			auto tail = [&](const auto&... t) {
-				if (cam) f(acc..., e..., t..., *cam);
-				else f(acc..., e..., t...);
+				auto last = [&](const auto&... u) {
+					if (cam) f(acc..., e..., t..., u..., *cam);
+					else f(acc..., e..., t..., u...);
+				};
+				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
+				last();
 			};
-			if constexpr (sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value) { if (spc) { tail(*spc); return; } }
+			if constexpr (tables) { if (spc) { tail(*spc); return; } }
 			tail();
 		};
 		if (me) est(*me);
@@ -537,6 +548,15 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
 	if (specf && !c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
 	const sp::SpecArgs spa{ (const float4*)c->spec.p };
+	// smooth shading: by the same rules, with variants 1, 8 and 16 only (2 and 15 are A/B scans)
+	if (mode == SPHIP_MODE_FLAT && (flags & SPHIP_FLAG_SMOOTH)) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is valid for SPHIP_MODE_PT only");
+	const bool smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
+	if (smoothf && nee && !mis)
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
+	if (smoothf && !variant_smooth(variant))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+	if (smoothf && !c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
+	const sp::NormArgs nra{ (const float*)c->vnorm.p };
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -648,7 +668,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
 	}
 	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
-	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf ? &spa : nullptr, cams, f); };
+	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf ? &spa : nullptr, smoothf ? &nra : nullptr, cams, f); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
@@ -675,16 +695,21 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		with_scan_shape(ts, [&](auto shape) {
 			using S = decltype(shape);
 			pt_pack([&](const auto&... p) {
-				// NEE (the bounded scans), MIS, camera samples and specular reflection are built for the shipped shapes only (checked above)
-				if constexpr (S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value ||
-				                              sp::IsSpec<std::decay_t<decltype(p)>...>::value))
+				// NEE (the bounded scans), MIS, camera samples and specular reflection are built for the shipped shapes only (checked above),
+				// smooth shading for the default scan's two shapes
+				if constexpr ((S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value ||
+				                               sp::IsSpec<std::decay_t<decltype(p)>...>::value)) &&
+				              (S::SCAN >= 3 || !sp::IsNorm<std::decay_t<decltype(p)>...>::value))
 					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
 					                   a, src2, bnd, hist, acc, n_work, p...);
 			});
 		});
 	} else {
 		with_exact([&](auto v) {
-			pt_pack([&](const auto&... p) { hipLaunchKernelGGL((sp::k_pt<decltype(v)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, p...); });
+			pt_pack([&](const auto&... p) {
+				if constexpr (decltype(v)::value == 1 || !sp::IsNorm<std::decay_t<decltype(p)>...>::value)   // smooth shading: variant 1 only (checked above)
+					hipLaunchKernelGGL((sp::k_pt<decltype(v)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, p...);
+			});
 		});
 	}
 	if (chunks > 1)
@@ -824,6 +849,7 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	c->n_tris = n_tris;
 	c->have_scene = true;
 	c->have_spec = false;
+	c->have_vnorm = false;
 	return SPHIP_OK;
 }
 
@@ -1154,6 +1180,14 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", v, kVariantNames[v]);
 		if (!c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
 	}
+	if (flags & SPHIP_FLAG_SMOOTH) {               // likewise
+		if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
+		const int v = pick_variant(flags, c->n_tris);
+		if (!variant_smooth(v))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is not available with kernel variant %d (%s)", v, kVariantNames[v]);
+		if (!c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
+	}
 	if (!c->kids.empty()) {
 		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
 		if (rc) return rc;
@@ -1231,13 +1265,20 @@ int gbuffer_dev(sphip_ctx* c, const void* d_rays, size_t n, int flags, void* d_o
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "G-buffer requested before a scene was set");
 	if (!d_rays || !d_out) return fail(c, SPHIP_E_INVALID, "null ray or G-buffer pointer");
 	if (n == 0 || n > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n);
+	const bool smooth = (flags & SPHIP_FLAG_SMOOTH) != 0;  // the normals are the path's shading normals
+	if (smooth && !c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
 	int rc;
 	if ((rc = ensure_classes(c, st)) || (rc = ensure(c, c->dn_hit, n * 8))) return rc;
 	int* idx = (int*)c->dn_hit.p;
 	float* dist = (float*)((char*)c->dn_hit.p + n * 4);
 	if ((rc = launch_render(c, d_rays, n, nullptr, 0, 1, 0, kModeHits, flags, idx, dist, st))) return rc;
-	hipLaunchKernelGGL(sp::k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
-	                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out);
+	if (smooth)
+		hipLaunchKernelGGL(sp::k_gbuffer_smooth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
+		                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out,
+		                   sp::NormArgs{ (const float*)c->vnorm.p });
+	else
+		hipLaunchKernelGGL(sp::k_gbuffer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
+		                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
 	c->stats.n_launches += 1;
@@ -1546,7 +1587,7 @@ void sphip_destroy(sphip_t* c) {
 	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
 	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
 	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
-	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab, &c->spec };
+	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab, &c->spec, &c->vnorm };
 	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
@@ -1649,6 +1690,55 @@ int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) {
 	if ((rc = ensure(c, c->spec, c->n_tris * 16))) return rc;
 	HIP_TRY(c, hipMemcpyAsync(c->spec.p, d_spec, c->n_tris * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
 	c->have_spec = true;
+	return SPHIP_OK;
+}
+
+int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals called before a scene was set");
+	if (vn) {
+		for (size_t i = 0; i < c->n_tris; ++i)
+			for (int k = 0; k < 9; ++k)
+				if (!std::isfinite(vn[i * 9 + k])) {
+					const float* q = vn + i * 9;
+					return fail(c, SPHIP_E_INVALID, "vertex normals: triangle %zu has {%g %g %g, %g %g %g, %g %g %g} (every value finite)", i, (double)q[0],
+					            (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5], (double)q[6], (double)q[7], (double)q[8]);
+				}
+	}
+	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old normals
+	if (!c->kids.empty()) {
+		c->have_vnorm = false;                     // a device that refuses leaves no device with a table: they must never differ
+		for (sphip_ctx* k : c->kids)
+			if (const int rc = sphip_set_vertex_normals(k, vn)) {
+				for (sphip_ctx* q : c->kids) q->have_vnorm = false;
+				return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+			}
+		c->have_vnorm = vn != nullptr;
+		return SPHIP_OK;
+	}
+	c->have_vnorm = false;
+	if (!vn) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure(c, c->vnorm, c->n_tris * 36))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->vnorm.p, vn, c->n_tris * 36, hipMemcpyHostToDevice, c->own_stream));
+	HIP_TRY(c, hipStreamSynchronize(c->own_stream));   // vn is borrowed: do not outlive the call
+	c->have_vnorm = true;
+	return SPHIP_OK;
+}
+
+int sphip_set_vertex_normals_device(sphip_t* c, const void* d_vn, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals_device called before a scene was set");
+	c->acc_stale = c->acc_on;
+	c->have_vnorm = false;
+	if (!d_vn) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure(c, c->vnorm, c->n_tris * 36))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->vnorm.p, d_vn, c->n_tris * 36, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+	c->have_vnorm = true;
 	return SPHIP_OK;
 }
 
@@ -1866,8 +1956,8 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[7] = { 4, 4, 20, 40, 60, 12, 48 }, out_b[7] = { 8, 4, 16, 12, 4, 4, 8 };
-	if (what < 0 || what > 6 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[8] = { 4, 4, 20, 40, 60, 12, 48, 96 }, out_b[8] = { 8, 4, 16, 12, 4, 4, 8, 24 };
+	if (what < 0 || what > 7 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
 	HIP_TRY(c, hipSetDevice(k->device));
 	void *d_in = nullptr, *d_out = nullptr;
@@ -1875,7 +1965,8 @@ int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* 
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 6) hipLaunchKernelGGL(sp::cylm256::k_selftest_cylm, dim3((unsigned)n), dim3(64), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
+		if (what == 7) hipLaunchKernelGGL(sp::k_selftest_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
+		else if (what == 6) hipLaunchKernelGGL(sp::cylm256::k_selftest_cylm, dim3((unsigned)n), dim3(64), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else hipLaunchKernelGGL(sp::k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, what, (const void*)d_in, (uint32_t)n, d_out);
 		e = hipGetLastError();
 	}

@@ -55,6 +55,8 @@ struct hip_r : public basic_renderer {
 	// specular reflection (set_specular): the table goes to the library with every scene upload (sphip_set_scene clears it) and joins
 	// the scene's key; while there is one, path-traced frames carry SPHIP_FLAG_SPECULAR
 	std::vector<float> spec;
+	// smooth shading (set_vertex_normals): likewise, 9 floats per triangle and SPHIP_FLAG_SMOOTH
+	std::vector<float> vnorm;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
@@ -95,9 +97,14 @@ struct hip_r : public basic_renderer {
 			if (spec.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the specular table and the scene differ in size");
 			h = fnv(spec.data(), spec.size() * sizeof(float), h);
 		}
+		if (!vnorm.empty()) {
+			if (vnorm.size() != n_tris * 9) throw std::runtime_error("hip_renderer: the vertex normals and the scene differ in size");
+			h = fnv(vnorm.data(), vnorm.size() * sizeof(float), h);
+		}
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
 			if (!spec.empty()) check(sphip_set_specular(ctx, spec.data()), "set_specular");
+			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
 			scene_hash = h; scene_n = n_tris;
 		}
 	}
@@ -149,7 +156,7 @@ struct hip_r : public basic_renderer {
 		out.res_y = vc.res_y;
 		out.values.resize(out.res_x * out.res_y);
 		const sphip_camera c = camera_args();
-		const int f = (cam_samples ? (flags | SPHIP_FLAG_CAMERA_SAMPLES) : flags) | spec_flag(mode);
+		const int f = (cam_samples ? (flags | SPHIP_FLAG_CAMERA_SAMPLES) : flags) | table_flags(mode);
 		if (progressive && mode == SPHIP_MODE_PT) {
 			if (!(same_accumulation(c.res_x, c.res_y, f) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0 &&
 			      std::memcmp(&lens, &acc_lens, sizeof lens) == 0)) {
@@ -167,12 +174,15 @@ struct hip_r : public basic_renderer {
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
 	}
 
-	int spec_flag(const int mode) const { return !spec.empty() && mode == SPHIP_MODE_PT ? SPHIP_FLAG_SPECULAR : 0; }
+	int table_flags(const int mode) const {              // the flags of the tables that are set
+		if (mode != SPHIP_MODE_PT) return 0;
+		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0);
+	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
 	           const size_t n_samples, scene::bitmap& out, const int mode) {
 		upload_scene(tris, mats, n_tris);
-		const int flags = this->flags | spec_flag(mode);
+		const int flags = this->flags | table_flags(mode);
 		// first ensure that the bitmap is of correct size (src/cpu_renderer.cpp:120-122)
 		out.res_x = vp.res_x;
 		out.res_y = vp.res_y;
@@ -262,6 +272,14 @@ namespace hip_renderer {
 		if (spec && n_tris) p->spec.assign(spec, spec + n_tris * 4);
 		else p->spec.clear();
 		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+	}
+
+	void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (vn && n_tris) p->vnorm.assign(vn, vn + n_tris * 9);
+		else p->vnorm.clear();
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the normals (or none) with it
 	}
 
 	void set_lens(scene::renderer* r, float aperture, float focus_dist) {

@@ -40,6 +40,11 @@ namespace hip_renderer {
 	// (render_flat is unchanged).  NULL or n_tris = 0 removes it.  A table the library refuses makes the next frame throw
 	// std::runtime_error, as does one whose size differs from the scene's.  Changing it begins a new progressive accumulation.
 	extern void set_specular(scene::renderer* r, const float* spec, size_t n_tris);
+	// smooth shading (sphip_set_vertex_normals, SPHIP_FLAG_SMOOTH; include/spath_hip.h "smooth shading"): n_tris rows n0.xyz n1.xyz
+	// n2.xyz (copied) beside the triangles of the scenes rendered next; while they are set, path-traced frames shade by them
+	// (render_flat is unchanged).  NULL or n_tris = 0 removes them.  Normals the library refuses make the next frame throw
+	// std::runtime_error, as do ones whose size differs from the scene's.  Changing them begins a new progressive accumulation.
+	extern void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

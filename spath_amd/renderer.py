@@ -101,6 +101,14 @@ class HipRenderer(BasicRenderer):
         self._accum_key = None
         self.last_stats = None
         self._spec = None
+        self._vnorm = None
+
+    def set_vertex_normals(self, vn):
+        """The per-vertex normals of capi.FLAG_SMOOTH renders ([n_tris, 9] float32, scene.vertex_normals; None: none), like
+        hip_renderer::set_vertex_normals: they go to the library with the next scene upload and begin a new accumulation, and while
+        they are set every path-traced frame carries capi.FLAG_SMOOTH (render_flat never does)."""
+        self._vnorm = None if vn is None else np.ascontiguousarray(vn, dtype=np.float32).reshape(-1, 9).copy()
+        self._scene_key = None
 
     def set_specular(self, spec):
         """The specular table of capi.FLAG_SPECULAR renders ([n_tris, 4] float32, scene.specular_table; None: no table), like
@@ -110,10 +118,11 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR on while a table is set, and never on the flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR and FLAG_SMOOTH on while their tables are set, and never on the flat pass"""
         if mode == capi.MODE_FLAT:
-            return self.flags & ~capi.FLAG_SPECULAR
-        return self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
+            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH)
+        flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
+        return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
 
     def get_description(self) -> str:
         return self.ctx.description
@@ -122,11 +131,14 @@ class HipRenderer(BasicRenderer):
         tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)[:n_tris]
         mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 6)[:n_tris]
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
-        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()))
+        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
+               None if self._vnorm is None else hash(self._vnorm.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
             if self._spec is not None:
                 self.ctx.set_specular(self._spec[:n_tris])
+            if self._vnorm is not None:
+                self.ctx.set_vertex_normals(self._vnorm[:n_tris])
             self._scene_key = key
 
     def _begin_rule(self):

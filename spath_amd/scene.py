@@ -18,6 +18,7 @@ import numpy as np
 F = np.float32
 SCENE_MAGIC = 0x43535053  # 'SPSC'
 SPEC_MAGIC = 0x50535053   # 'SPSP'
+VNORM_MAGIC = 0x4E565053  # 'SPVN'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -224,6 +225,85 @@ def write_specular(path, spec: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(struct.pack("<II", SPEC_MAGIC, spec.shape[0]))
         f.write(spec.tobytes())
+
+
+def vertex_normals(tris: np.ndarray, crease_deg: float = 180.0, which=None) -> np.ndarray:
+    """Per-vertex normals for capi.Context.set_vertex_normals (include/spath_hip.h, "smooth shading"): float32 [N, 9] rows n0.xyz n1.xyz
+    n2.xyz.  The normal of vertex k of triangle i is the double-precision sum of cross(e1, e2) (the area-weighted face normals, from
+    the f32 vertices) over the triangles j that have a vertex at the same position bitwise and whose face normal lies within
+    crease_deg of triangle i's (the cosine of the two unit face normals, in double, >= cos(crease_deg); i itself always counts),
+    normalised and cast to float32.  crease_deg = 0 therefore returns the face normals, 180 smooths everything that touches.
+    which: the triangles that get normals (an index array or a boolean mask; None = all), every other row is zero (the triangle
+    stays flat).  Zero-area triangles get zero rows."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    n = t.shape[0]
+    sel = np.ones(n, bool) if which is None else np.zeros(n, bool)
+    if which is not None:
+        sel[np.asarray(which)] = True
+    v = t[:, :9].astype(np.float64).reshape(n, 3, 3)
+    fn = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    ln = np.sqrt((fn * fn).sum(1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        un = np.where(ln[:, None] > 0.0, fn / ln[:, None], 0.0)
+    share = {}
+    for i in range(n):
+        for k in range(3):
+            share.setdefault(t[i, 3 * k:3 * k + 3].tobytes(), []).append(i)
+    cos_c = np.cos(np.deg2rad(min(max(float(crease_deg), 0.0), 180.0)))
+    out = np.zeros((n, 9), F)
+    for i in np.nonzero(sel & (ln > 0.0))[0]:
+        for k in range(3):
+            js = np.asarray(share[t[i, 3 * k:3 * k + 3].tobytes()])
+            if crease_deg >= 180.0:                               # everything that touches: a dot product of opposite unit normals may round below -1
+                keep = np.ones(js.size, bool)
+            elif crease_deg <= 0.0:
+                keep = js == i
+            else:
+                keep = (un[js] @ un[i] >= cos_c) | (js == i)
+            m = fn[js[keep]].sum(0)
+            l = np.sqrt((m * m).sum())
+            if l > 0.0:
+                out[i, 3 * k:3 * k + 3] = (m / l).astype(F)
+    return out
+
+
+def write_vertex_normals(path, vn: np.ndarray) -> None:
+    """Vertex-normal file read by the headless CLI (--normals), beside the scene file: 'SPVN', n, n * 9 float32."""
+    vn = np.ascontiguousarray(vn, dtype=F).reshape(-1, 9)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", VNORM_MAGIC, vn.shape[0]))
+        f.write(vn.tobytes())
+
+
+def icosphere(subdiv: int, centre=(0.0, 0.0, 0.0), radius: float = 1.0, material=(0.8, 0.8, 0.8, 0.0, 0.0, 0.0)):
+    """A curved test object: an icosahedron subdivided subdiv times (20 * 4^subdiv triangles), every vertex pushed onto the sphere
+    of the given centre and radius.  -> (tris [N, 12], mats [N, 6]) float32 with outward flat_normals; a vertex shared by several
+    triangles has the same bits in each (one vertex table, computed in double and cast once), which is what vertex_normals joins."""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    vs = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    vs = [tuple(np.asarray(p, np.float64) / np.sqrt(1.0 + g * g)) for p in vs]
+    fs = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+          (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(subdiv)):
+        mid, nf = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                p = (np.asarray(vs[a]) + np.asarray(vs[b])) * 0.5
+                vs.append(tuple(p / np.sqrt((p * p).sum())))
+                mid[key] = len(vs) - 1
+            return mid[key]
+        for a, b, c in fs:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        fs = nf
+    pos = (np.asarray(centre, np.float64) + float(radius) * np.asarray(vs, np.float64)).astype(F)
+    tris = np.zeros((len(fs), 12), F)
+    tris[:, :9] = pos[np.asarray(fs)].reshape(-1, 9)
+    tris = flat_normals(tris)
+    mats = np.tile(np.asarray(material, F).reshape(1, 6), (len(fs), 1))
+    return tris, mats
 
 
 def write_scene(path, tris: np.ndarray, mats: np.ndarray) -> None:
