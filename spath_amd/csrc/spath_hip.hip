@@ -35,6 +35,10 @@ thread_local std::string g_create_error;
 struct DevBuf {
 	void* p = nullptr;
 	size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;                // owns p: freed with the context (sphip_destroy makes its device current first)
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 } // namespace
@@ -130,6 +134,12 @@ int fail(sphip_ctx* c, int code, const char* fmt, ...) {
 		if (e_ != hipSuccess)                                                                    \
 			return fail((c), SPHIP_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
 	} while (0)
+
+// the guard of the device-pointer entry points: a context, and a single-device one
+int single_device_entry(sphip_ctx* c) {
+	if (!c) return SPHIP_E_INVALID;
+	return c->kids.empty() ? SPHIP_OK : fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+}
 
 int ensure(sphip_ctx* c, DevBuf& b, size_t bytes) {
 	if (bytes <= b.cap && b.p) return SPHIP_OK;
@@ -253,17 +263,10 @@ int build_cylm(sphip_ctx* c, hipStream_t st) {
 	int half = 0;
 	if ((rc = radix_sort(c, n, 32, st, &half))) return rc;
 	const uint32_t* sorted = vals + (size_t)half * n;
-	if (WIDE) {
-		hipLaunchKernelGGL(sp::cylm512::k_cylm_hdr, dim3(1), dim3(1), 0, st, hdr, bnd);
-		hipLaunchKernelGGL(sp::cylm512::k_cylm_scatter, dim3(nblocks), dim3(256), 0, st, tris, n, sorted, (const uint32_t*)hdr, rec, (const float4*)c->scan.p, (float4*)c->cylm_big.p);
-		hipLaunchKernelGGL(sp::cylm512::k_cylm_pad, dim3(3), dim3(256), 0, st, (const uint32_t*)hdr, n, rec);
-		hipLaunchKernelGGL(sp::cylm512::k_cylm_hmax, dim3(max_tiles), dim3(sp::cylm512::kMGroups), 0, st, (const uint32_t*)hdr, rec);
-	} else {
-		hipLaunchKernelGGL(sp::cylm256::k_cylm_hdr, dim3(1), dim3(1), 0, st, hdr, bnd);
-		hipLaunchKernelGGL(sp::cylm256::k_cylm_scatter, dim3(nblocks), dim3(256), 0, st, tris, n, sorted, (const uint32_t*)hdr, rec, (const float4*)c->scan.p, (float4*)c->cylm_big.p);
-		hipLaunchKernelGGL(sp::cylm256::k_cylm_pad, dim3(3), dim3(256), 0, st, (const uint32_t*)hdr, n, rec);
-		hipLaunchKernelGGL(sp::cylm256::k_cylm_hmax, dim3(max_tiles), dim3(sp::cylm256::kMGroups), 0, st, (const uint32_t*)hdr, rec);
-	}
+	hipLaunchKernelGGL(SP_CM(k_cylm_hdr), dim3(1), dim3(1), 0, st, hdr, bnd);
+	hipLaunchKernelGGL(SP_CM(k_cylm_scatter), dim3(nblocks), dim3(256), 0, st, tris, n, sorted, (const uint32_t*)hdr, rec, (const float4*)c->scan.p, (float4*)c->cylm_big.p);
+	hipLaunchKernelGGL(SP_CM(k_cylm_pad), dim3(3), dim3(256), 0, st, (const uint32_t*)hdr, n, rec);
+	hipLaunchKernelGGL(SP_CM(k_cylm_hmax), dim3(max_tiles), dim3(SP_CM(kMGroups)), 0, st, (const uint32_t*)hdr, rec);
 #undef SP_CM
 	HIP_TRY(c, hipGetLastError());
 	c->cylm_valid = true;
@@ -465,6 +468,46 @@ void with_scan_shape(const TwoStage& ts, F&& f) {
 #endif
 }
 
+// ---- the flag rules that launch_render and accum_begin share (a begin checks as a path-tracing render would: the step would
+// refuse as well, so it says so at once)
+// per-sample camera rays: path tracing behind a camera, with the shipped variants, without primary-hit reuse (the
+// primary ray is no longer shared by the samples); flat and hit queries ignore the flag
+int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_cam) {
+	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) return SPHIP_OK;
+	if (!have_cam)
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (sphip_render_camera, sphip_accum_begin[_adaptive] with cam), not rays");
+	if (flags & SPHIP_FLAG_PRIMARY_REUSE)
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
+	if (!variant_shipped(variant))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+	return SPHIP_OK;
+}
+
+// the per-triangle tables: specular reflection and smooth shading (5.8; variants 1, 8 and 16 only: 2 and 15 are
+// A/B scans).  Path tracing with the plain estimator or with NEE|MIS, with the feature's variants, once its table is set; the flat pass
+// has no use for them and says so; hit queries ignore the flags
+struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; };
+const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_shipped, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
+const TableRule kSmoothRule{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" };
+int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
+	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
+	if (mode == SPHIP_MODE_FLAT) return fail(c, SPHIP_E_INVALID, "%s is valid for SPHIP_MODE_PT only", r.flag);
+	if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
+		return fail(c, SPHIP_E_INVALID, "%s works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone", r.flag);
+	if (!r.variant_ok(variant)) return fail(c, SPHIP_E_INVALID, "%s is not available with kernel variant %d (%s)", r.flag, variant, kVariantNames[variant]);
+	if (!(c->*r.have)) return fail(c, SPHIP_E_STATE, "%s needs %s", r.flag, r.needs);
+	return SPHIP_OK;
+}
+
+// what sphip_get_stats reports of the last launch on c
+void note_render(sphip_ctx* c, hipStream_t st, size_t n_pixels, int variant) {
+	c->have_render = true;
+	c->last_stream = st;
+	c->stats.n_pixels = n_pixels;
+	c->stats.n_tris = c->n_tris;
+	c->stats.kernel_variant = (uint32_t)variant;
+}
+
 // prog != nullptr: progressive accumulation (path tracing only): the launch renders global samples
 // [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
 int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
@@ -528,34 +571,11 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ne.n = c->nee_n;
 		ne.W = c->nee_W;
 	}
-	// per-sample camera rays: path tracing behind a camera, with the shipped variants, without primary-hit reuse (the
-	// primary ray is no longer shared by the samples); flat and hit queries ignore the flag
-	const bool camf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_CAMERA_SAMPLES);
-	if (camf && !cams)
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (sphip_render_camera, sphip_accum_begin[_adaptive] with cam), not rays");
-	if (camf && (flags & SPHIP_FLAG_PRIMARY_REUSE))
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
-	if (camf && !variant_shipped(variant))
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
-	if (!camf) cams = nullptr;
-	// specular reflection: path tracing with the plain estimator or with NEE|MIS, with the shipped variants; the flat
-	// pass has no use for it and says so; hit queries ignore the flag
-	if (mode == SPHIP_MODE_FLAT && (flags & SPHIP_FLAG_SPECULAR)) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is valid for SPHIP_MODE_PT only");
-	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR);
-	if (specf && nee && !mis)
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
-	if (specf && !variant_shipped(variant))
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
-	if (specf && !c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
+	if ((rc = check_camera_rule(c, flags, variant, mode, cams != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, variant, mode)) ||
+	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode))) return rc;
+	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) cams = nullptr;
+	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR), smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
 	const sp::SpecArgs spa{ (const float4*)c->spec.p };
-	// smooth shading: by the same rules, with variants 1, 8 and 16 only (2 and 15 are A/B scans)
-	if (mode == SPHIP_MODE_FLAT && (flags & SPHIP_FLAG_SMOOTH)) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is valid for SPHIP_MODE_PT only");
-	const bool smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
-	if (smoothf && nee && !mis)
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
-	if (smoothf && !variant_smooth(variant))
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
-	if (smoothf && !c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
 	const sp::NormArgs nra{ (const float*)c->vnorm.p };
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
@@ -718,11 +738,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		});
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
-	c->have_render = true;
-	c->last_stream = st;
-	c->stats.n_tris = c->n_tris;
-	c->stats.n_pixels = n_rays;
-	c->stats.kernel_variant = (uint32_t)variant;
+	note_render(c, st, n_rays, variant);
 	c->stats.n_launches = (chunks > 1 ? 2u : 1u) + (prim_pass ? 1u : 0u);
 	return SPHIP_OK;
 }
@@ -797,6 +813,8 @@ struct RowPlan {
 	}
 	size_t max_rays() const { size_t m = 0; for (int r = 0; r < g; ++r) m = std::max(m, n_rays(r)); return m; }
 	sphip_shard shard(int rank) const { return sphip_shard{ (uint64_t)rank * tile_px, (uint64_t)tile_px, (uint64_t)g * tile_px }; }
+	// the image-order pixel of local index i of that shard
+	size_t pixel(int rank, size_t i) const { const sphip_shard sh = shard(rank); return sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px; }
 };
 
 // ---- RCCL, loaded on first use: the single-GPU path (and every process that never creates a multi-device context) does not
@@ -838,6 +856,51 @@ void* load_rccl() {
 	return nullptr;
 }
 
+// Whatever goes wrong on one device, no device is left with work in flight when the call returns: the next call may free or
+// regrow the buffers that work reads and writes.
+void drain_all(sphip_ctx* c) {
+	for (sphip_ctx* k : c->kids)
+		if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
+	(void)hipGetLastError();
+}
+
+// Per-device arrays (a buffer of every child, elem_bytes per pixel in its shard's order) read back and put in image order in the
+// host arrays `out`.  A query, not the hot path: one wait per device for all the arrays.
+struct ShardArray { DevBuf sphip_ctx::*buf; size_t elem_bytes; void* out; };
+int read_shards(sphip_ctx* c, const RowPlan& plan, const std::vector<ShardArray>& arrays) {
+	std::vector<std::vector<char>> loc(arrays.size());
+	for (int r = 0; r < plan.g; ++r) {
+		sphip_ctx* k = c->kids[(size_t)r];
+		const size_t n = plan.n_rays(r);
+		if (n == 0) continue;
+		HIP_TRY(c, hipSetDevice(k->device));
+		for (size_t a = 0; a < arrays.size(); ++a) {
+			loc[a].resize(n * arrays[a].elem_bytes);
+			HIP_TRY(c, hipMemcpyAsync(loc[a].data(), (k->*arrays[a].buf).p, loc[a].size(), hipMemcpyDeviceToHost, k->own_stream));
+		}
+		HIP_TRY(c, hipStreamSynchronize(k->own_stream));
+		for (size_t i = 0; i < n; ++i)
+			for (size_t a = 0, p = plan.pixel(r, i); a < arrays.size(); ++a)
+				std::memcpy((char*)arrays[a].out + p * arrays[a].elem_bytes, &loc[a][i * arrays[a].elem_bytes], arrays[a].elem_bytes);
+	}
+	return SPHIP_OK;
+}
+
+// Device r's n pixels (and float triples) -> slot r of the first device's gather buffers, in stream order behind its kernels;
+// ev_tile[r] marks their arrival.  A device listed twice, or the first device itself, makes it a local copy.  err receives an error.
+int enqueue_peer_tile(sphip_ctx* c, sphip_ctx* err, int r, size_t n, size_t pad, bool with_accum) {
+	sphip_ctx *k = c->kids[(size_t)r], *root = c->kids[0];
+	auto copy = [&](const DevBuf& dst, const DevBuf& src, size_t elem) {
+		char* d = (char*)dst.p + (size_t)r * pad * elem;
+		if (k->device == root->device) return hipMemcpyAsync(d, src.p, n * elem, hipMemcpyDeviceToDevice, k->own_stream);
+		return hipMemcpyPeerAsync(d, root->device, src.p, k->device, n * elem, k->own_stream);
+	};
+	HIP_TRY(err, copy(c->gath, k->rgba, 4));
+	if (with_accum) HIP_TRY(err, copy(c->gath_acc, k->accum, 12));
+	HIP_TRY(err, hipEventRecord(c->ev_tile[(size_t)r], k->own_stream));
+	return SPHIP_OK;
+}
+
 int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n_tris) {
 	const int g = (int)c->kids.size();
 	std::vector<int> rcs((size_t)g, SPHIP_OK);
@@ -850,6 +913,46 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	c->have_scene = true;
 	c->have_spec = false;
 	c->have_vnorm = false;
+	return SPHIP_OK;
+}
+
+// One per-triangle table of the scene (the specular table, the vertex normals) on a single-device context: bytes_per_tri per triangle
+// from src, or no table with src == nullptr.  sync: src is borrowed host memory and must not outlive the call.
+int set_tri_table(sphip_ctx* c, DevBuf& buf, bool& have, const void* src, size_t bytes_per_tri, hipMemcpyKind kind, hipStream_t st, bool sync) {
+	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old table
+	have = false;
+	if (!src) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure(c, buf, c->n_tris * bytes_per_tri))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(buf.p, src, c->n_tris * bytes_per_tri, kind, st));
+	if (sync) HIP_TRY(c, hipStreamSynchronize(st));
+	have = true;
+	return SPHIP_OK;
+}
+
+// ... and on a multi-device context: every device keeps the whole table (child_set: the entry point, for a child).  A device that refuses
+// leaves no device with a table: they must never differ.
+int multi_set_tri_table(sphip_ctx* c, bool sphip_ctx::*have, int (*child_set)(sphip_t*, const float*), const float* src) {
+	c->acc_stale = c->acc_on;
+	c->*have = false;
+	for (sphip_ctx* k : c->kids)
+		if (const int rc = child_set(k, src)) {
+			for (sphip_ctx* q : c->kids) q->*have = false;
+			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+		}
+	c->*have = src != nullptr;
+	return SPHIP_OK;
+}
+
+// The tail of the host-pointer paths: n pixels of c->rgba (and, with out_f, the float triples of c->accum) to the caller, timed for
+// sphip_get_stats; blocking, like every reference backend (main.cpp:70-83)
+int download_frame(sphip_ctx* c, size_t n, uint8_t* out_rgba, float* out_f, hipStream_t st) {
+	HIP_TRY(c, hipEventRecord(c->ev_d0, st));
+	HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
+	if (out_f) HIP_TRY(c, hipMemcpyAsync(out_f, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipEventRecord(c->ev_d1, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
 	return SPHIP_OK;
 }
 
@@ -893,21 +996,12 @@ int multi_frame_impl(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float*
 			k->have_render = false;
 			if (n == 0) return SPHIP_OK;
 			HIP_TRY(k, hipSetDevice(k->device));
-			hipStream_t st = k->own_stream;
 			int rc2;
 			if ((rc2 = ensure(k, k->rgba, pad * 4))) return rc2;
 			if (out_accum && (rc2 = ensure(k, k->accum, pad * 12))) return rc2;
 			if ((rc2 = render_shard(k, r, n, plan.shard(r)))) return rc2;
 			k->timed_upload = k->timed_download = false;
-			if (peer) {           // tiles -> slot r of the first device's gather buffer, in stream order behind the kernels
-				const bool same = k->device == root->device;      // a device listed twice, or the first device itself: a local copy
-				if (same) HIP_TRY(k, hipMemcpyAsync((char*)c->gath.p + (size_t)r * pad * 4, k->rgba.p, n * 4, hipMemcpyDeviceToDevice, st));
-				else HIP_TRY(k, hipMemcpyPeerAsync((char*)c->gath.p + (size_t)r * pad * 4, root->device, k->rgba.p, k->device, n * 4, st));
-				if (out_accum && same) HIP_TRY(k, hipMemcpyAsync((char*)c->gath_acc.p + (size_t)r * pad * 12, k->accum.p, n * 12, hipMemcpyDeviceToDevice, st));
-				else if (out_accum) HIP_TRY(k, hipMemcpyPeerAsync((char*)c->gath_acc.p + (size_t)r * pad * 12, root->device, k->accum.p, k->device, n * 12, st));
-				HIP_TRY(k, hipEventRecord(c->ev_tile[(size_t)r], st));
-			}
-			return SPHIP_OK;
+			return peer ? enqueue_peer_tile(c, k, r, n, pad, out_accum != nullptr) : SPHIP_OK;
 		};
 		rcs[(size_t)r] = body();
 	});
@@ -916,20 +1010,12 @@ int multi_frame_impl(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float*
 		if (rcs[(size_t)r]) return fail(c, rcs[(size_t)r], "device %d: %s", c->kids[(size_t)r]->device, c->kids[(size_t)r]->err.c_str());
 	HIP_TRY(c, hipSetDevice(root->device));
 	hipStream_t rs = root->own_stream;
-	// peer-copy exchange, issued from this thread: device r's tiles -> slot r of the first device's buffer, in stream order behind its
-	// kernels (the host threads do the same themselves when peer copies are the context's exchange from the start)
+	// peer-copy exchange, issued from this thread (the host threads do it themselves when peer copies are the context's exchange from the start)
 	auto gather_peer_now = [&]() -> int {
 		for (int r = 0; r < g; ++r) {
-			const size_t n = plan.n_rays(r);
-			if (!n) continue;
-			sphip_ctx* k = c->kids[(size_t)r];
-			HIP_TRY(c, hipSetDevice(k->device));
-			const bool same = k->device == root->device;
-			if (same) HIP_TRY(c, hipMemcpyAsync((char*)c->gath.p + (size_t)r * pad * 4, k->rgba.p, n * 4, hipMemcpyDeviceToDevice, k->own_stream));
-			else HIP_TRY(c, hipMemcpyPeerAsync((char*)c->gath.p + (size_t)r * pad * 4, root->device, k->rgba.p, k->device, n * 4, k->own_stream));
-			if (out_accum && same) HIP_TRY(c, hipMemcpyAsync((char*)c->gath_acc.p + (size_t)r * pad * 12, k->accum.p, n * 12, hipMemcpyDeviceToDevice, k->own_stream));
-			else if (out_accum) HIP_TRY(c, hipMemcpyPeerAsync((char*)c->gath_acc.p + (size_t)r * pad * 12, root->device, k->accum.p, k->device, n * 12, k->own_stream));
-			HIP_TRY(c, hipEventRecord(c->ev_tile[(size_t)r], k->own_stream));
+			if (!plan.n_rays(r)) continue;
+			HIP_TRY(c, hipSetDevice(c->kids[(size_t)r]->device));
+			if (const int rc2 = enqueue_peer_tile(c, c, r, plan.n_rays(r), pad, out_accum != nullptr)) return rc2;
 		}
 		HIP_TRY(c, hipSetDevice(root->device));
 		return SPHIP_OK;
@@ -983,16 +1069,11 @@ int multi_frame_impl(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float*
 	return SPHIP_OK;
 }
 
-// Whatever goes wrong on one device, no device is left with work in flight when the call returns: the next call may free or
-// regrow the buffers that work reads and writes.
+// (on an error every device is drained: drain_all)
 template <class RenderShard>
 int multi_frame(sphip_ctx* c, size_t w, size_t h, uint8_t* out_rgba, float* out_accum, const RenderShard& render_shard) {
 	const int rc = multi_frame_impl(c, w, h, out_rgba, out_accum, render_shard);
-	if (rc != SPHIP_OK) {
-		for (sphip_ctx* k : c->kids)
-			if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
-		(void)hipGetLastError();
-	}
+	if (rc != SPHIP_OK) drain_all(c);
 	return rc;
 }
 
@@ -1063,10 +1144,7 @@ int adapt_step_dev(sphip_ctx* k, const sphip_ctx* par, size_t n, const sphip_sha
 		HIP_TRY(k, hipMemsetAsync(k->counter.p, 0, 16 * sizeof(unsigned long long), st));
 		HIP_TRY(k, hipEventRecord(k->ev_k0, st));
 		k->stats.n_launches = 1;
-		k->stats.kernel_variant = (uint32_t)pick_variant(par->acc_flags, k->n_tris);
-		k->stats.n_tris = k->n_tris;
-		k->have_render = true;
-		k->last_stream = st;
+		note_render(k, st, n, pick_variant(par->acc_flags, k->n_tris));
 	}
 	hipLaunchKernelGGL(sp::k_adapt_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)k->acc_sum.p,
 	                   (const uint32_t*)k->adp_cnt.p, (uint32_t)n, (uint32_t*)k->rgba.p, d_mean);
@@ -1098,9 +1176,7 @@ int multi_accum_begin(sphip_ctx* c, const float* rays, const sphip_camera* cam, 
 			return SPHIP_OK;
 		};
 		if (const int rc = body()) {
-			for (sphip_ctx* q : c->kids)
-				if (hipSetDevice(q->device) == hipSuccess && q->own_stream) (void)hipStreamSynchronize(q->own_stream);
-			(void)hipGetLastError();
+			drain_all(c);
 			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
 		}
 	}
@@ -1164,38 +1240,16 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
 	c->adp_on = false;
 	c->dn_gbuf_ok = false;
-	if (flags & SPHIP_FLAG_CAMERA_SAMPLES) {       // the step would refuse them as well: say so at the begin
-		if (!cam) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (accum_begin with cam), not rays");
-		if (flags & SPHIP_FLAG_PRIMARY_REUSE)
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
-		const int v = pick_variant(flags, c->n_tris);
-		if (!variant_shipped(v))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", v, kVariantNames[v]);
-	}
-	if (flags & SPHIP_FLAG_SPECULAR) {             // likewise
-		if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
-		const int v = pick_variant(flags, c->n_tris);
-		if (!variant_shipped(v))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SPECULAR is not available with kernel variant %d (%s)", v, kVariantNames[v]);
-		if (!c->have_spec) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SPECULAR needs a specular table (sphip_set_specular)");
-	}
-	if (flags & SPHIP_FLAG_SMOOTH) {               // likewise
-		if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone");
-		const int v = pick_variant(flags, c->n_tris);
-		if (!variant_smooth(v))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_SMOOTH is not available with kernel variant %d (%s)", v, kVariantNames[v]);
-		if (!c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
-	}
+	const int v = pick_variant(flags, c->n_tris);
+	int rc;
+	if ((rc = check_camera_rule(c, flags, v, SPHIP_MODE_PT, cam != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, v, SPHIP_MODE_PT)) ||
+	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT))) return rc;
 	if (!c->kids.empty()) {
-		const int rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr);
-		if (rc) return rc;
+		if ((rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr))) return rc;
 	} else {
 		HIP_TRY(c, hipSetDevice(c->device));
 		const size_t n = w * h;
 		hipStream_t st = c->own_stream;
-		int rc;
 		if ((rc = ensure(c, c->acc_rays, n * 24)) || (rc = ensure(c, c->acc_sum, n * 12))) return rc;
 		if (rays) HIP_TRY(c, hipMemcpyAsync(c->acc_rays.p, rays, n * 24, hipMemcpyHostToDevice, st));      // once per accumulation
 		else if ((rc = launch_viewport(c, cam, c->acc_rays.p, st))) return rc;
@@ -1360,11 +1414,7 @@ int accum_denoise_dev(sphip_ctx* c, sphip_ctx* k, const sphip_denoise* P, const 
 	if ((rc = atrous_run(k, c->dn_a, c->dn_b, P, w, h, use_var, c->dn_gbuf.p, rgba, rgb, st, &k->stats.n_launches))) return rc;
 	HIP_TRY(k, hipEventRecord(k->ev_k1, st));
 	if (build) c->dn_gbuf_ok = true;
-	k->have_render = true;
-	k->last_stream = st;
-	k->stats.n_pixels = n;
-	k->stats.n_tris = k->n_tris;
-	k->stats.kernel_variant = (uint32_t)pick_variant(c->acc_flags, k->n_tris);
+	note_render(k, st, n, pick_variant(c->acc_flags, k->n_tris));
 	return SPHIP_OK;
 }
 
@@ -1378,8 +1428,8 @@ int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba,
 	const bool need_rays = !c->dn_gbuf_ok;
 	sphip_ctx* root = c->kids[0];
 	auto body = [&]() -> int {
-		std::vector<float4> img4(npix), loc;
-		std::vector<float> rays(need_rays ? npix * 6 : 0), lrays;
+		std::vector<float4> img4(npix);
+		std::vector<float> rays(need_rays ? npix * 6 : 0);
 		int rc;
 		for (int r = 0; r < g; ++r) {
 			sphip_ctx* k = c->kids[(size_t)r];
@@ -1387,23 +1437,15 @@ int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba,
 			const size_t n = plan.n_rays(r);
 			if (n == 0) continue;
 			HIP_TRY(c, hipSetDevice(k->device));
-			hipStream_t st = k->own_stream;
 			if ((rc = ensure(k, k->dn_a, n * 16))) return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-			hipLaunchKernelGGL(sp::k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)k->acc_sum.p,
+			hipLaunchKernelGGL(sp::k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)k->acc_sum.p,
 			                   c->adp_on ? (const uint32_t*)k->adp_cnt.p : nullptr, (uint32_t)c->acc_total, c->adp_on ? (const double*)k->adp_s12.p : nullptr,
 			                   (uint32_t)n, (float4*)k->dn_a.p, (uint32_t*)nullptr, (float*)nullptr);
 			HIP_TRY(c, hipGetLastError());
-			loc.resize(n);
-			HIP_TRY(c, hipMemcpyAsync(loc.data(), k->dn_a.p, n * 16, hipMemcpyDeviceToHost, st));
-			if (need_rays) { lrays.resize(n * 6); HIP_TRY(c, hipMemcpyAsync(lrays.data(), k->acc_rays.p, n * 24, hipMemcpyDeviceToHost, st)); }
-			HIP_TRY(c, hipStreamSynchronize(st));
-			const sphip_shard sh = plan.shard(r);
-			for (size_t i = 0; i < n; ++i) {
-				const size_t p = sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px;
-				img4[p] = loc[i];
-				if (need_rays) std::memcpy(&rays[p * 6], &lrays[i * 6], 24);
-			}
 		}
+		std::vector<ShardArray> arrays{ { &sphip_ctx::dn_a, 16, img4.data() } };
+		if (need_rays) arrays.push_back({ &sphip_ctx::acc_rays, 24, rays.data() });
+		if ((rc = read_shards(c, plan, arrays))) return rc;
 		HIP_TRY(c, hipSetDevice(root->device));
 		hipStream_t rs = root->own_stream;
 		if ((rc = ensure(c, c->dn_a, npix * 16)) || (need_rays && (rc = ensure(c, c->dn_rays, npix * 24)))) return rc;
@@ -1423,11 +1465,7 @@ int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba,
 		return SPHIP_OK;
 	};
 	const int rc = body();
-	if (rc) {
-		for (sphip_ctx* k : c->kids)
-			if (hipSetDevice(k->device) == hipSuccess && k->own_stream) (void)hipStreamSynchronize(k->own_stream);
-		(void)hipGetLastError();
-	}
+	if (rc) drain_all(c);
 	return rc;
 }
 
@@ -1571,24 +1609,19 @@ void sphip_destroy(sphip_t* c) {
 	if (!c) return;
 	if (!c->kids.empty()) {
 		for (void* comm : c->comms) if (comm) (void)g_rccl.destroy(comm);
-		(void)hipSetDevice(c->kids[0]->device);
+		const int dev = c->kids[0]->device;            // the parent's buffers live there
+		(void)hipSetDevice(dev);
 		(void)hipDeviceSynchronize();
-		DevBuf* mb[9] = { &c->gath, &c->gath_acc, &c->img, &c->img_acc, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays };
-		for (auto b : mb) if (b->p) (void)hipFree(b->p);
 		if (c->ev_g0) (void)hipEventDestroy(c->ev_g0);
 		if (c->ev_g1) (void)hipEventDestroy(c->ev_g1);
 		for (size_t r = 0; r < c->ev_tile.size(); ++r) { (void)hipSetDevice(c->kids[r]->device); (void)hipEventDestroy(c->ev_tile[r]); }
 		for (sphip_ctx* k : c->kids) sphip_destroy(k);
-		delete c;
+		(void)hipSetDevice(dev);
+		delete c;                                      // every DevBuf frees itself
 		return;
 	}
 	(void)hipSetDevice(c->device);
 	if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-	DevBuf* bufs[] = { &c->tris, &c->mats, &c->scan, &c->filt, &c->bounds, &c->samp, &c->rays, &c->rgba, &c->accum, &c->counter, &c->work,
-	                   &c->bvh_nodes, &c->bvh_rec, &c->bvh_idx, &c->sort_kv, &c->sort_hist, &c->bvh_meta, &c->cyl_rec, &c->cyl_cnt, &c->cyl_hdr, &c->prim, &c->cylm_rec, &c->cylm_hdr, &c->cylm_big,
-	                   &c->acc_rays, &c->acc_sum, &c->adp_s12, &c->adp_cnt, &c->adp_list[0], &c->adp_list[1], &c->adp_rays, &c->adp_keep,
-	                   &c->adp_blk, &c->adp_nact_d, &c->adp_wst, &c->dn_cls, &c->dn_hit, &c->dn_gbuf, &c->dn_a, &c->dn_b, &c->dn_rays, &c->nee_tab, &c->spec, &c->vnorm };
-	for (auto b : bufs) if (b->p) (void)hipFree(b->p);
 	hipEvent_t evs[6] = { c->ev_k0, c->ev_k1, c->ev_u0, c->ev_u1, c->ev_d0, c->ev_d1 };
 	for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
 	if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1617,8 +1650,7 @@ int sphip_set_scene(sphip_t* c, const float* tris, const float* mats, size_t n_t
 }
 
 int sphip_set_scene_device(sphip_t* c, const void* d_tris, const void* d_mats, size_t n_tris, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	if (!d_tris || !d_mats || n_tris == 0 || n_tris > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad scene arguments (n_tris=%zu)", n_tris);
 	c->acc_stale = c->acc_on;
 	c->dn_cls_valid = false;
@@ -1655,42 +1687,16 @@ int sphip_set_specular(sphip_t* c, const float* spec) {
 			            (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
 		}
 	}
-	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old table
-	if (!c->kids.empty()) {
-		c->have_spec = false;                      // a device that refuses leaves no device with a table: they must never differ
-		for (sphip_ctx* k : c->kids)
-			if (const int rc = sphip_set_specular(k, spec)) {
-				for (sphip_ctx* q : c->kids) q->have_spec = false;
-				return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-			}
-		c->have_spec = spec != nullptr;
-		return SPHIP_OK;
-	}
-	c->have_spec = false;
-	if (!spec) return SPHIP_OK;
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure(c, c->spec, c->n_tris * 16))) return rc;
-	HIP_TRY(c, hipMemcpyAsync(c->spec.p, spec, c->n_tris * 16, hipMemcpyHostToDevice, c->own_stream));
-	HIP_TRY(c, hipStreamSynchronize(c->own_stream));   // spec is borrowed: do not outlive the call
-	c->have_spec = true;
-	return SPHIP_OK;
+	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_spec, sphip_set_specular, spec);
+	return set_tri_table(c, c->spec, c->have_spec, spec, 16, hipMemcpyHostToDevice, c->own_stream, true);
 }
 
 int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_specular_device called before a scene was set");
-	c->acc_stale = c->acc_on;
-	c->have_spec = false;
-	if (!d_spec) return SPHIP_OK;
-	if (c->n_tris >= (size_t)sp::kSpecBit) return fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris);
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure(c, c->spec, c->n_tris * 16))) return rc;
-	HIP_TRY(c, hipMemcpyAsync(c->spec.p, d_spec, c->n_tris * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-	c->have_spec = true;
-	return SPHIP_OK;
+	const bool big = d_spec && c->n_tris >= (size_t)sp::kSpecBit;      // refused, and like every call it leaves no table behind
+	const int rc = set_tri_table(c, c->spec, c->have_spec, big ? nullptr : d_spec, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return big ? fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris) : rc;
 }
 
 int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
@@ -1705,47 +1711,19 @@ int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
 					            (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5], (double)q[6], (double)q[7], (double)q[8]);
 				}
 	}
-	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old normals
-	if (!c->kids.empty()) {
-		c->have_vnorm = false;                     // a device that refuses leaves no device with a table: they must never differ
-		for (sphip_ctx* k : c->kids)
-			if (const int rc = sphip_set_vertex_normals(k, vn)) {
-				for (sphip_ctx* q : c->kids) q->have_vnorm = false;
-				return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-			}
-		c->have_vnorm = vn != nullptr;
-		return SPHIP_OK;
-	}
-	c->have_vnorm = false;
-	if (!vn) return SPHIP_OK;
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure(c, c->vnorm, c->n_tris * 36))) return rc;
-	HIP_TRY(c, hipMemcpyAsync(c->vnorm.p, vn, c->n_tris * 36, hipMemcpyHostToDevice, c->own_stream));
-	HIP_TRY(c, hipStreamSynchronize(c->own_stream));   // vn is borrowed: do not outlive the call
-	c->have_vnorm = true;
-	return SPHIP_OK;
+	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_vnorm, sphip_set_vertex_normals, vn);
+	return set_tri_table(c, c->vnorm, c->have_vnorm, vn, 36, hipMemcpyHostToDevice, c->own_stream, true);
 }
 
 int sphip_set_vertex_normals_device(sphip_t* c, const void* d_vn, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals_device called before a scene was set");
-	c->acc_stale = c->acc_on;
-	c->have_vnorm = false;
-	if (!d_vn) return SPHIP_OK;
-	HIP_TRY(c, hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure(c, c->vnorm, c->n_tris * 36))) return rc;
-	HIP_TRY(c, hipMemcpyAsync(c->vnorm.p, d_vn, c->n_tris * 36, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-	c->have_vnorm = true;
-	return SPHIP_OK;
+	return set_tri_table(c, c->vnorm, c->have_vnorm, d_vn, 36, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
 }
 
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
                         size_t n_samples, uint64_t seed, int mode, int flags, void* d_out_rgba, void* d_out_accum, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
 	return launch_render(c, d_rays, n_rays, shard, image_width, n_samples, seed, mode, flags, d_out_rgba, d_out_accum, (hipStream_t)stream);
@@ -1754,8 +1732,7 @@ int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sph
 int sphip_render_device_accum(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
                               uint64_t sample_base, size_t n_samples, uint64_t seed, int flags, void* d_sum,
                               void* d_out_rgba, void* d_out_mean, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	if (!d_sum) return fail(c, SPHIP_E_INVALID, "null sum pointer");
 	if (sample_base > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "sample_base %llu: the total must stay below 2^31", (unsigned long long)sample_base);
 	HIP_TRY(c, hipSetDevice(c->device));
@@ -1797,22 +1774,10 @@ int sphip_accum_counts(sphip_t* c, uint32_t* out_counts, uint64_t* n_active_out)
 		HIP_TRY(c, hipStreamSynchronize(c->own_stream));
 		return SPHIP_OK;
 	}
-	// a query, not the hot path: each device's counts in its shard's order, put in image order here
+	// each device's counts in its shard's order, put in image order
 	const int g = (int)c->kids.size();
 	const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
-	std::vector<uint32_t> loc;
-	for (int r = 0; r < g; ++r) {
-		sphip_ctx* k = c->kids[(size_t)r];
-		const size_t n = plan.n_rays(r);
-		if (n == 0) continue;
-		loc.resize(n);
-		HIP_TRY(c, hipSetDevice(k->device));
-		HIP_TRY(c, hipMemcpyAsync(loc.data(), k->adp_cnt.p, n * 4, hipMemcpyDeviceToHost, k->own_stream));
-		HIP_TRY(c, hipStreamSynchronize(k->own_stream));
-		const sphip_shard sh = plan.shard(r);
-		for (size_t i = 0; i < n; ++i) out_counts[sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px] = loc[i];
-	}
-	return SPHIP_OK;
+	return read_shards(c, plan, { { &sphip_ctx::adp_cnt, 4, out_counts } });
 }
 
 int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out_mean, uint64_t* total_out) {
@@ -1844,11 +1809,7 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 				if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
 				                         out_mean ? c->accum.p : nullptr, st, nullptr, &p, nullptr, c->acc_has_cam ? &ca : nullptr))) return rc2;
 			}
-			HIP_TRY(c, hipEventRecord(c->ev_d0, st));
-			HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
-			if (out_mean) HIP_TRY(c, hipMemcpyAsync(out_mean, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
-			HIP_TRY(c, hipEventRecord(c->ev_d1, st));
-			HIP_TRY(c, hipStreamSynchronize(st));
+			if ((rc2 = download_frame(c, n, out_rgba, out_mean, st))) return rc2;
 			c->adp_nact = c->adp_nact_rb;
 			c->timed_upload = false;
 			c->timed_download = true;
@@ -1867,8 +1828,7 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 }
 
 int sphip_viewport_device(sphip_t* c, const sphip_camera* cam, void* d_rays_out, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	return launch_viewport(c, cam, d_rays_out, (hipStream_t)stream);
 }
@@ -1884,8 +1844,7 @@ int sphip_set_lens(sphip_t* c, const sphip_lens* lens) {
 }
 
 int sphip_camera_rays_device(sphip_t* c, const sphip_camera* cam, uint64_t seed, uint32_t sample, void* d_rays_out, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	if (!cam || !d_rays_out) return fail(c, SPHIP_E_INVALID, "null camera or ray pointer");
 	if (cam->res_x == 0 || cam->res_y == 0 || (uint64_t)cam->res_x * cam->res_y > 0xffffffffull)
 		return fail(c, SPHIP_E_INVALID, "bad viewport size %ux%u", cam->res_x, cam->res_y);
@@ -1911,11 +1870,7 @@ int sphip_render_camera(sphip_t* c, const sphip_camera* cam, size_t n_samples, u
 	const sp::CamArgs ca = cam_args_of(cam, c->lens);
 	if ((rc = launch_render(c, c->rays.p, n, nullptr, cam->res_x, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st,
 	                        nullptr, nullptr, nullptr, &ca))) return rc;
-	HIP_TRY(c, hipEventRecord(c->ev_d0, st));
-	HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
-	if (out_accum) HIP_TRY(c, hipMemcpyAsync(out_accum, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
-	HIP_TRY(c, hipEventRecord(c->ev_d1, st));
-	HIP_TRY(c, hipStreamSynchronize(st));
+	if ((rc = download_frame(c, n, out_rgba, out_accum, st))) return rc;
 	c->timed_upload = false;
 	c->timed_download = true;
 	return SPHIP_OK;
@@ -1923,8 +1878,7 @@ int sphip_render_camera(sphip_t* c, const sphip_camera* cam, size_t n_samples, u
 
 int sphip_closest_hit_device(sphip_t* c, const void* d_rays, size_t n_rays, const void* d_src_idx, int flags,
                              void* d_out_idx, void* d_out_dist, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
 	return launch_render(c, d_rays, n_rays, nullptr, 0, 1, 0, kModeHits, flags, d_out_idx, d_out_dist, (hipStream_t)stream, (const int*)d_src_idx);
@@ -1945,11 +1899,7 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 	HIP_TRY(c, hipMemcpyAsync(c->rays.p, rays, n * 24, hipMemcpyHostToDevice, st));
 	HIP_TRY(c, hipEventRecord(c->ev_u1, st));
 	if ((rc = launch_render(c, c->rays.p, n, nullptr, w, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st))) return rc;
-	HIP_TRY(c, hipEventRecord(c->ev_d0, st));
-	HIP_TRY(c, hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st));
-	if (out_accum) HIP_TRY(c, hipMemcpyAsync(out_accum, c->accum.p, n * 12, hipMemcpyDeviceToHost, st));
-	HIP_TRY(c, hipEventRecord(c->ev_d1, st));
-	HIP_TRY(c, hipStreamSynchronize(st));           // blocking, like every reference backend (main.cpp:70-83)
+	if ((rc = download_frame(c, n, out_rgba, out_accum, st))) return rc;
 	c->timed_upload = c->timed_download = true;
 	return SPHIP_OK;
 }
@@ -2006,12 +1956,8 @@ int sphip_selftest_stage1(sphip_t* c, const float* rays, size_t n_rays, uint32_t
 	if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n_rays * 24, hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) {
 		sp::CylStream cs{ (const float4*)c->cylm_rec.p, (const uint32_t*)c->cylm_hdr.p, (const float4*)c->cylm_big.p };
-		if (c->cylm_wide)
-			hipLaunchKernelGGL(sp::cylm512::k_selftest_stage1, dim3((unsigned)(n_rays / 64)), dim3(64), 0, st, (const float*)d_rays, (uint32_t)n_rays, cs,
-		                   (const unsigned int*)c->bounds.p, (uint32_t*)d_words, (uint32_t*)d_tri, (int*)d_order);
-		else
-			hipLaunchKernelGGL(sp::cylm256::k_selftest_stage1, dim3((unsigned)(n_rays / 64)), dim3(64), 0, st, (const float*)d_rays, (uint32_t)n_rays, cs,
-		                   (const unsigned int*)c->bounds.p, (uint32_t*)d_words, (uint32_t*)d_tri, (int*)d_order);
+		hipLaunchKernelGGL(c->cylm_wide ? sp::cylm512::k_selftest_stage1 : sp::cylm256::k_selftest_stage1, dim3((unsigned)(n_rays / 64)), dim3(64), 0, st,
+		                   (const float*)d_rays, (uint32_t)n_rays, cs, (const unsigned int*)c->bounds.p, (uint32_t*)d_words, (uint32_t*)d_tri, (int*)d_order);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(out_words, d_words, words_b, hipMemcpyDeviceToHost, st);
@@ -2036,8 +1982,7 @@ void sphip_denoise_defaults(sphip_denoise* out) {
 }
 
 int sphip_gbuffer_device(sphip_t* c, const void* d_rays, size_t n_rays, int flags, void* d_out_gbuf, void* stream) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
 	return gbuffer_dev(c, d_rays, n_rays, flags, d_out_gbuf, (hipStream_t)stream);
@@ -2048,7 +1993,7 @@ int sphip_denoise_device(sphip_t* c, const sphip_denoise* P, size_t w, size_t h,
 	if (!c) return SPHIP_E_INVALID;
 	int rc;
 	if ((rc = check_denoise(c, P))) return rc;
-	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "device-pointer entry points need a single-device context (sphip_create)");
+	if ((rc = single_device_entry(c))) return rc;
 	if (!d_mean || !d_gbuf || !d_out_rgba) return fail(c, SPHIP_E_INVALID, "null mean, G-buffer or output pointer");
 	if (w == 0 || h == 0 || w >= (1u << 30) || h >= (1u << 30) || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad image size (w=%zu h=%zu)", w, h);
 	HIP_TRY(c, hipSetDevice(c->device));
@@ -2063,10 +2008,7 @@ int sphip_denoise_device(sphip_t* c, const sphip_denoise* P, size_t w, size_t h,
 	if ((rc = atrous_run(c, c->dn_a, c->dn_b, P, w, h, d_var != nullptr, d_gbuf, (uint32_t*)d_out_rgba, (float*)d_out_rgb, st, &c->stats.n_launches))) return rc;
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
 	c->timed_upload = c->timed_download = false;
-	c->have_render = true;
-	c->last_stream = st;
-	c->stats.n_pixels = n;
-	c->stats.n_tris = c->n_tris;
+	note_render(c, st, n, (int)c->stats.kernel_variant);       // the variant of the last render stays
 	return SPHIP_OK;
 }
 
@@ -2080,21 +2022,11 @@ int sphip_accum_gbuffer(sphip_t* c, void* out_gbuf) {
 		// the whole frame's rays on the first device, as the denoiser builds it there
 		const int g = (int)c->kids.size();
 		const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
-		std::vector<float> rays(n * 6), lrays;
-		for (int r = 0; r < g; ++r) {
-			sphip_ctx* k = c->kids[(size_t)r];
-			const size_t nr = plan.n_rays(r);
-			if (nr == 0) continue;
-			HIP_TRY(c, hipSetDevice(k->device));
-			lrays.resize(nr * 6);
-			HIP_TRY(c, hipMemcpyAsync(lrays.data(), k->acc_rays.p, nr * 24, hipMemcpyDeviceToHost, k->own_stream));
-			HIP_TRY(c, hipStreamSynchronize(k->own_stream));
-			const sphip_shard sh = plan.shard(r);
-			for (size_t i = 0; i < nr; ++i) std::memcpy(&rays[(sh.pixel_base + (i / sh.tile_px) * sh.tile_stride_px + i % sh.tile_px) * 6], &lrays[i * 6], 24);
-		}
+		std::vector<float> rays(n * 6);
+		int rc;
+		if ((rc = read_shards(c, plan, { { &sphip_ctx::acc_rays, 24, rays.data() } }))) return rc;
 		sphip_ctx* root = c->kids[0];
 		HIP_TRY(c, hipSetDevice(root->device));
-		int rc;
 		if ((rc = ensure(c, c->dn_rays, n * 24)) || (rc = ensure(c, c->dn_gbuf, n * 32))) return rc;
 		HIP_TRY(c, hipMemcpyAsync(c->dn_rays.p, rays.data(), n * 24, hipMemcpyHostToDevice, root->own_stream));
 		if (!c->dn_gbuf_ok && (rc = gbuffer_dev(root, c->dn_rays.p, n, c->acc_flags, c->dn_gbuf.p, root->own_stream))) {
