@@ -116,17 +116,18 @@ SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int
 	if (steps_out) { *steps_out = n_steps; *leaves_out = n_leaves; }
 }
 
-// kernels: the same integrator / flat / hit bodies as the exact scans (sp_kernels.h), with the BVH as the scan
-// (a trailing AccumArgs: progressive accumulation in path-tracing mode; AdaptArgs: adaptive sampling; sp_kernels.h)
+// kernels: the same integrator / flat / hit bodies as the exact scans (sp_kernels.h), with the BVH as the scan; what the bodies
+// share is in sp_integrator.h
+// (a trailing AccumArgs: progressive accumulation in path-tracing mode; AdaptArgs: adaptive sampling; sp_integrator.h)
 template <int MODE /* 0 flat, 1 pt, 2 hits */, typename... Acc>
 __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, const int* __restrict__ src_idx,
                                                int* __restrict__ out_idx, float* __restrict__ out_d, const Acc... acc_args) {
 	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
 	const bool valid = k < a.n_rays;
 	const uint32_t kk = valid ? k : a.n_rays - 1;
-	constexpr bool cam = IsCam<Acc...>::value;         // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
+	constexpr bool cam = IsCam<Acc...>::value;         // per-sample camera rays (sp_integrator.h CamArgs): KArgs::rays is not read
 	f3 po = mk3(0.0f, 0.0f, 0.0f), pdir = po;
-	if constexpr (!cam) {
+	if constexpr (!cam) {                              // load_ray, written out: the call moves this kernel's instructions (tools/listing_diff.py)
 		const float* r = a.rays + (size_t)kk * 6;
 		po = mk3(r[0], r[1], r[2]); pdir = mk3(r[3], r[4], r[5]);
 	}
@@ -146,18 +147,17 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	if (MODE == 0) {
 		float bd; int bi;
 		scan_bvh(B, po, pdir, -1, bd, bi);
-		uint32_t px = 0;
-		if (bi >= 0) { const float* m = a.mats + (size_t)bi * 6; px = vec3_rgba(mk3(m[0], m[1], m[2])); }
+		const uint32_t px = flat_px(a, bi);
 		if (valid) a.out_rgba[k] = px;
 		wave_add_scans(a.scans, valid ? 1u : 0u);
 		return;
 	}
-	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_kernels.h AdaptArgs)
-	constexpr bool nee = IsNee<Acc...>::value;         // next-event estimation (sp_kernels.h NeeArgs)
-	constexpr bool mis = IsMis<Acc...>::value;         // MIS on top of it (sp_kernels.h MisArgs): the folded terms D_0..D_4
-	constexpr bool spc = IsSpec<Acc...>::value;        // specular reflection (sp_kernels.h SpecArgs): kSpecBit in hidx marks a mirror bounce
+	constexpr bool adapt = IsAdapt<Acc...>::value;     // adaptive: ray k is local pixel list[k] (sp_integrator.h AdaptArgs)
+	constexpr bool nee = IsNee<Acc...>::value;         // next-event estimation (sp_integrator.h NeeArgs)
+	constexpr bool mis = IsMis<Acc...>::value;         // MIS on top of it (sp_integrator.h MisArgs): the folded terms D_0..D_4
+	constexpr bool spc = IsSpec<Acc...>::value;        // specular reflection (sp_integrator.h SpecArgs): kSpecBit in hidx marks a mirror bounce
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
-	constexpr bool smo = IsNorm<Acc...>::value;        // smooth shading (sp_kernels.h NormArgs): ns of shade_normal shades, n guards
+	constexpr bool smo = IsNorm<Acc...>::value;        // smooth shading (sp_integrator.h NormArgs): ns of shade_normal shades, n guards
 	static_assert(!smo || mis || !nee, "smooth shading: plain or NEE|MIS (DESIGN.md section 5.8)");
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	}
 	accum = scale3(accum, a.inv_n);
 	if (valid) {
-		a.out_rgba[k] = vec3_rgba(mk3(clamp01(accum.x), clamp01(accum.y), clamp01(accum.z)));
+		a.out_rgba[k] = clamped_rgba(accum);
 		if (a.out_accum) { a.out_accum[(size_t)k * 3] = accum.x; a.out_accum[(size_t)k * 3 + 1] = accum.y; a.out_accum[(size_t)k * 3 + 2] = accum.z; }
 	}
 	wave_add_scans(a.scans, my_scans);

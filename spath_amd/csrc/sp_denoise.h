@@ -14,7 +14,7 @@
 namespace sp {
 
 // one G-buffer entry per ray from the closest hit (idx, dist) of sphip_closest_hit_device; cls[t] = material class of triangle t.
-// With a trailing NormArgs (smooth shading, sp_kernels.h: k_gbuffer_smooth) the normal is the path kernels' shading normal of the primary ray.
+// With a trailing NormArgs (smooth shading, sp_integrator.h: k_gbuffer_smooth) the normal is the path kernels' shading normal of the primary ray.
 template <typename... Norm>
 SP_DEV void gbuffer_entry(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
                           const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256) k_gbuffer_smooth(const float* __restrict_
 }
 
 SP_DEV void dn_emit(uint32_t p, float r, float g, float b, uint32_t* __restrict__ rgba, float* __restrict__ rgb) {
-	if (rgba) rgba[p] = vec3_rgba(mk3(clamp01(r), clamp01(g), clamp01(b)));
+	if (rgba) rgba[p] = clamped_rgba(mk3(r, g, b));
 	if (rgb) { rgb[(size_t)p * 3 + 0] = r; rgb[(size_t)p * 3 + 1] = g; rgb[(size_t)p * 3 + 2] = b; }
 }
 

@@ -1,0 +1,309 @@
+// The path integrator's shared device code: the argument structs of the path kernels and the device functions that a path calls
+// at a surface hit (shade_normal, nee_light, mis_emit, spec_lobe / spec_reflect / spec_unwind), with the small pieces the kernels
+// share around the integrator (load_ray, flat_px, clamped_rgba).
+//
+// k_pt (sp_kernels.h), k_accel (sp_bvh.h) and both branches of k_pt_filter (sp_scan_kernels.h) call these in the same sequence at a
+// hit; the sequence itself is still written out in each of the four (DESIGN.md section 5.9 names its steps and says why).  A new
+// material or estimator term gets its arithmetic here, once, and its call in each of the four.
+#pragma once
+
+#include "sp_device_math.h"
+
+#include <type_traits>
+
+namespace sp {
+
+// scan record: 48 B = 3 x float4, produced by k_repack
+//   q0 = v0.x v0.y v0.z e1.x   q1 = e1.y e1.z e2.x e2.y   q2 = e2.z 0 0 0
+struct KArgs {
+	const float*  rays;        // n_rays * 6
+	const float4* scan;        // n_tris * 3
+	const float*  tris;        // n_tris * 12 (normals live at +9)
+	const float*  mats;        // n_tris * 6
+	uint32_t*     out_rgba;    // n_rays
+	float*        out_accum;   // n_rays * 3 or nullptr
+	unsigned long long* scans; // device counter
+	uint32_t n_rays, n_tris, n_samples, flags;
+	uint64_t seed;
+	uint64_t pixel_base, tile_px, tile_stride_px;
+	float inv_n;               // float(1.0/n_samples), cpu_renderer.cpp:77
+	// sample chunks (filter kernels): blockIdx = chunk * px_blocks + pixel block; every sample's radiance is written to
+	// samp[(sample * 3 + c) * samp_stride + ray] and k_resolve adds them up in sample order.  n_chunks <= 1: off
+	uint32_t n_chunks, px_blocks, samp_stride;
+	float* samp;
+	// primary-hit reuse of the two-stage kernels (flags & 0x100): closest hit of every ray of the launch, from a pre-pass
+	// (k_hit_filter, one scan per PIXEL); k_pt_filter starts every sample of the pixel from it.  nullptr: off
+	const int*   prim_idx;     // n_rays
+	const float* prim_d;       // n_rays
+};
+
+// progressive accumulation (sphip_render_device_accum, sphip_accum_step): sample j of a launch is global sample
+// sample_base + j (what keys the counter RNG), and the per-pixel f32 sum starts from sum[3k..3k+2] and is written back there
+// raw, in place.  sample_base == 0: sum is not read (a fresh accumulation needs no cleared buffer).  inv_n is then
+// float(1.0/(sample_base + n_samples)), so a run of steps ends in the image of one render of all their samples, bit for bit:
+// the samples are added to the same f32 sum one at a time, in the same order.
+// The path-tracing kernels take it as an optional trailing argument (a parameter pack of zero or one AccumArgs): without it a
+// kernel is the same code as before the switch existed, which is what sphip_render launches.
+struct AccumArgs {
+	float* sum;                // n_rays * 3, AoS like out_accum
+	uint32_t sample_base;
+};
+
+// adaptive sampling (sphip_accum_begin_adaptive, sp_adaptive.h): a progressive launch over the still-active pixels only.  Ray k
+// of the launch is local pixel list[k]: the host gathers the active rays into a dense buffer in list order, so the ray reads
+// (and the primary-hit pre-pass) are those of a plain launch, while list[k] keys the RNG (shard_pixel) and indexes the running
+// sum and the statistics s12[2 list[k] + {0, 1}] = S1, S2 of the per-sample luminance proxy y (lum_proxy), added in sample
+// order like the f32 sum, in double.  The launch writes no pixels: k_adapt_resolve turns sums and counts into the whole frame.
+// wst: the two-stage kernels park S1, S2 of every work slot there (2 x n_work doubles), as they park the f32 accumulator.
+struct AdaptArgs : AccumArgs {
+	const uint32_t* list;      // n_rays local pixel indices, ascending
+	double* s12;               // n_local * 2
+	double* wst;               // 2 * n_work (two-stage kernels only)
+};
+// next-event estimation (SPHIP_FLAG_NEE): the scene's light table, built on the host once per scene.
+// Emitter e of the table is triangle tri[e]; cdf is the running double sum of the weights A * Esum; ipdf = (float)(W / Esum).
+// It rides as the LAST element of the trailing pack: k_pt<V, NeeArgs>, k_pt_filter<R, S, SCAN, AccumArgs, NeeArgs>, ...  L: the
+// two-stage kernels park the direct light of depth d there, L[(d * 3 + c) * n_work + slot] (12 B per depth and slot).
+struct NeeArgs {
+	const double* cdf;         // n ascending
+	const int*    tri;         // n emitter triangle indices, ascending
+	const float*  ipdf;        // n
+	uint32_t n;                // emitters of positive weight (0: no direct light)
+	double W;                  // cdf[n - 1]
+	float* L;                  // two-stage kernels only
+};
+constexpr int kNeeDepths = 4;                                    // light samples at hits 0..3; the 5th hit would carry nothing
+constexpr float kShadowMargin = 1.0f - 0x1p-10f;                  // tmax = dist * (1 - 2^-10)
+constexpr float kTwoOverPi = (float)(2.0 / kPi);                  // 2 pi x the reference's direction density (nee_light)
+// multiple importance sampling (SPHIP_FLAG_MIS with SPHIP_FLAG_NEE): NeeArgs plus the light table's pdf by
+// triangle, tipdf[i] = ipdf of triangle i's table entry, 0 for a triangle not in the table.  It rides in NeeArgs' place:
+// k_pt<V, MisArgs>, k_pt_filter<R, S, SCAN, AccumArgs, MisArgs>, ...  L: the two-stage kernels park the folded direct term D_d of
+// depths 0..4 there (15 floats per slot instead of 12).
+struct MisArgs : NeeArgs {
+	const float* tipdf;        // n_tris
+};
+constexpr int kMisDepths = 5;                                     // MIS traces the 5th hit again: its emission counts
+constexpr float kTwoPi = (float)(2.0 * kPi);
+constexpr float kPiSq = (float)(kPi * kPi);
+
+// ---- view::camera::get_viewport (view.h:94-132) on the device: one thread per pixel.
+// The eight step constants are computed on the host in the reference's mixed double/float way (view.h:101-108).
+struct ViewArgs {
+	float x_max, x_step, h_x_step, y_max, y_step, h_y_step;
+	float focal, cos_y, sin_y, cos_x, sin_x;
+	float px, py, pz;
+	uint32_t res_x, res_y;
+	// which pixels: ray k of the output is global pixel pixel_base + (k / tile_px) * tile_stride_px + k % tile_px (sphip_shard);
+	// the whole image is {0, res_x*res_y, 0} with n_local = res_x*res_y
+	uint64_t pixel_base, tile_px, tile_stride_px;
+	uint32_t n_local;
+};
+// per-sample camera rays (SPHIP_FLAG_CAMERA_SAMPLES): the viewport constants (the shard fields unused: the
+// kernels key the ray by the global pixel they already know) and the lens.  It rides as the LAST element of the trailing pack:
+// k_pt<V, CamArgs>, k_pt_filter<R, S, SCAN, AccumArgs, NeeArgs, CamArgs>, ...  Every sample's primary ray is then generated from
+// (seed, global pixel, global sample) instead of being read from KArgs::rays.
+struct CamArgs {
+	ViewArgs v;
+	float aperture;            // lens radius on the image plane, 0 = pinhole
+	float focus_dist;          // local z of the plane in focus (aperture > 0)
+};
+
+// specular reflection (SPHIP_FLAG_SPECULAR, include/spath_hip.h): the scene's specular table, one float4 per
+// triangle: ks.r ks.g ks.b p.  It rides between the estimator and the camera: k_pt<V, MisArgs, SpecArgs, CamArgs>, ...  A hit of
+// depth d takes the mirror lobe iff the first uniform of Philox stream kSpecStream + d is below p; the path history marks such a
+// hit with kSpecBit in its triangle index (triangle indices stay below 2^30: sphip_set_specular checks it).
+struct SpecArgs {
+	const float4* spec;        // n_tris
+};
+constexpr uint32_t kSpecStream = 32u;
+constexpr int kSpecBit = 0x40000000;
+
+// smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
+// n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
+// CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
+struct NormArgs {
+	const float* vnorm;        // n_tris * 9
+};
+
+// the pack's optional elements, found by type wherever they sit (MisArgs is a NeeArgs, AdaptArgs an AccumArgs)
+template <typename T, typename... P> struct PackHas { static constexpr bool value = (std::is_same<T, P>::value || ...); };
+template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHas<AdaptArgs, Acc...>::value; };
+template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
+template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
+template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
+template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value; };
+template <typename... Acc> struct IsNorm { static constexpr bool value = PackHas<NormArgs, Acc...>::value; };
+// a running sum rides in the pack (progressive or adaptive)
+template <typename... Acc> struct HasAccum { static constexpr bool value = PackHas<AccumArgs, Acc...>::value || IsAdapt<Acc...>::value; };
+// the first element of the pack that is a T
+template <typename T, typename H, typename... R>
+SP_DEV const T& pack_get(const H& h, const R&... r) {
+	if constexpr (std::is_base_of<T, H>::value) return h;
+	else return pack_get<T>(r...);
+}
+template <typename... P> SP_DEV const AdaptArgs& adapt_args(const P&... p) { return pack_get<AdaptArgs>(p...); }
+template <typename... P> SP_DEV const AccumArgs& accum_args(const P&... p) { return pack_get<AccumArgs>(p...); }
+template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return pack_get<NeeArgs>(p...); }
+template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
+template <typename... P> SP_DEV const float4* spec_table(const P&... p) { return pack_get<SpecArgs>(p...).spec; }
+template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
+template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
+// local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
+template <typename... Acc>
+SP_DEV uint32_t local_px(uint32_t k, const Acc&... acc_args) {
+	if constexpr (IsAdapt<Acc...>::value) return adapt_args(acc_args...).list[k];
+	else return k;
+}
+// the per-sample luminance proxy of the convergence rule: ((double)r + (double)g) + (double)b of the sample's f32 radiance
+SP_DEV double lum_proxy(float r, float g, float b) { return ((double)r + (double)g) + (double)b; }
+
+// ---- smooth shading (include/spath_hip.h): the shading normal ns of the hit of ray (o, dir) on the triangle
+// whose vertices are tv[0..8] (v0 v1 v2) and whose vertex normals are vn[0..8]; n is the triangle's stored normal turned against dir.
+//   bary:    u, v exactly as ray_tri_strict computed them for this triangle (geom.h:200-212), once, for the winning triangle
+//   interp:  w = (1 - u) - v;  m = (n0 w + n1 u) + n2 v;  l2 = dot3(m, m);  smooth iff l2 > 0 and finite
+//            ns = m / sqrtf(l2) per component, turned to n's side; otherwise ns = n and the hit is the flat one
+// Returns whether the hit is smooth.  uv: where the selftest wants u, v.
+// The light sample of a smooth hit (nee_light with ns for n) counts only when its direction is above the stored normal as well
+// (smooth_light_ok): both strategies of MIS then integrate over {w . ns > 0, w . n > 0}.
+SP_DEV bool shade_normal(const float* __restrict__ tv, const float* __restrict__ vn, f3 o, f3 dir, f3 n, f3& ns, float* uv = nullptr) {
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);   // geom.h:200-201
+	const f3 h = cross3(dir, e2);                    // :202
+	const float a = dot3(e1, h);                     // :203
+	const float f = recip_ieee(a);                   // :206
+	const f3 s = sub3(o, v0);                        // :207
+	const float u = f * dot3(s, h);                  // :208
+	const f3 q = cross3(s, e1);                      // :211
+	const float v = f * dot3(dir, q);                // :212
+	if (uv) { uv[0] = u; uv[1] = v; }
+	const float w = (1.0f - u) - v;
+	const f3 m = add3(add3(scale3(mk3(vn[0], vn[1], vn[2]), w), scale3(mk3(vn[3], vn[4], vn[5]), u)), scale3(mk3(vn[6], vn[7], vn[8]), v));
+	const float l2 = dot3(m, m);
+	const bool sm = l2 > 0.0f && l2 < __builtin_inff();
+	ns = n;
+	if (sm) {
+		const float l = __builtin_sqrtf(l2);
+		ns = mk3(m.x / l, m.y / l, m.z / l);
+		if (dot3(ns, n) < 0.0f) ns = scale3(ns, -1.0f);
+	}
+	return sm;
+}
+
+SP_DEV bool smooth_light_ok(bool sm, f3 wd, f3 n) { return !sm || dot3(wd, n) > 0.0f; }
+
+// ---- MIS (include/spath_hip.h): u = p_l / q, the light table's density over the reference's BSDF density,
+// both per solid angle, for a direction w that reaches emitter j at distance sqrt(dist2) under cos_y.  A NaN quotient (0/0 or
+// inf/inf) counts as 0, so 1 / (1 + u) is a weight in [0, 1] for every input.
+SP_DEV float mis_u(float sxz, float dist2, float cos_y, float ipdf) {
+	const float u = ((kPiSq * sxz) * dist2) / (cos_y * ipdf);
+	return u == u ? u : 0.0f;
+}
+// the emission e_d of the triangle bi that the BSDF direction dir found at distance bd (d >= 1), weighted by the balance heuristic:
+// e_d / (1 + u_b), or e_d itself when bi is not in the light table (tipdf[bi] = 0: the light sample never picks it)
+SP_DEV f3 mis_emit(const KArgs& a, const float* tipdf, f3 dir, float bd, int bi) {
+	const float* m = a.mats + (size_t)bi * 6;
+	const f3 e = mk3(m[3], m[4], m[5]);
+	const float ip = tipdf[bi];
+	if (!(ip > 0.0f)) return e;
+	const float* tn = a.tris + (size_t)bi * 12 + 9;
+	const float cos_y = fabsf(dot3(dir, mk3(tn[0], tn[1], tn[2])));
+	const float sxz = __builtin_sqrtf(dir.x * dir.x + dir.z * dir.z);
+	const float opu = 1.0f + mis_u(sxz, bd * bd, cos_y, ip);
+	return mk3(e.x / opu, e.y / opu, e.z / opu);
+}
+
+// ---- next-event estimation: one light sample at the hit x of a path (include/spath_hip.h).
+// n: the hit triangle's normal as the path uses it (turned against the incoming ray); src: the hit triangle.  Returns whether a
+// shadow ray (x, wd) with the bound tmax is to be traced, and then L = the direct light it carries when nothing occludes it.
+// MIS: L carries the balance heuristic's weight u / (1 + u), and sxz = 0 is no early-out (L is finite).
+template <bool MIS = false>
+SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_t sample, int depth, f3 x, f3 n, int src,
+                      f3& wd, float& tmax, f3& L) {
+	if (ne.n == 0) return false;
+	double r3, r4, r5, r6;
+	philox_uniforms(a.seed, pixel, sample, 8u + (uint32_t)depth, &r3, &r4);
+	philox_uniforms(a.seed, pixel, sample, 16u + (uint32_t)depth, &r5, &r6);
+	// the first emitter whose cdf exceeds r5 W, the last one when rounding leaves none
+	const double t = r5 * ne.W;
+	uint32_t lo = 0, hi = ne.n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (ne.cdf[mid] > t) hi = mid; else lo = mid + 1u;
+	}
+	const int li = ne.tri[lo];
+	if (li == src) return false;
+	const float* tv = a.tris + (size_t)li * 12;
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);
+	const float ua = (float)__builtin_sqrt(r3), ub = (float)r4;
+	const f3 y = add3(add3(v0, scale3(e1, ua * (1.0f - ub))), scale3(e2, ua * ub));
+	const f3 w = sub3(y, x);
+	const float dist2 = dot3(w, w);
+	if (!(dist2 > 0.0f)) return false;
+	const float dist = __builtin_sqrtf(dist2);
+	wd = mk3(w.x / dist, w.y / dist, w.z / dist);
+	const float cos_x = dot3(wd, n);
+	const float cos_y = fabsf(dot3(wd, mk3(tv[9], tv[10], tv[11])));      // emitters are two-sided
+	// the reference's direction sampler (rand_unit_vec, geom.h:164-177) draws the elevation from the world y plane uniformly in ANGLE:
+	// density q = 1 / (pi^2 sqrt(x^2 + z^2)) per solid angle, while the path weight assumes 1/p = 2 pi.  The plain estimator's
+	// expectation therefore carries 2 pi q(w) per bounce; the light sample carries the same factor, 2 / (pi sxz), so that both
+	// estimate the same image
+	const float sxz = __builtin_sqrtf(wd.x * wd.x + wd.z * wd.z);
+	if constexpr (MIS) {
+		if (!(cos_x > 0.0f) || !(cos_y > 0.0f)) return false;
+	} else {
+		if (!(cos_x > 0.0f) || !(cos_y > 0.0f) || !(sxz > 0.0f)) return false;
+	}
+	tmax = dist * kShadowMargin;
+	const float* me = a.mats + (size_t)li * 6;
+	const float* ms = a.mats + (size_t)src * 6;
+	float g;
+	// MIS: g (u / (1 + u)) with u = ((pi^2 sxz) dist2) / (cos_y ipdf): the 1 / dist2 and 1 / sxz factors cancel, g <= 2 pi
+	if constexpr (MIS) g = (kTwoPi * cos_x) / (1.0f + mis_u(sxz, dist2, cos_y, ne.ipdf[lo]));
+	else g = (((cos_x * cos_y) / dist2) * ne.ipdf[lo]) * (kTwoOverPi / sxz);
+	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
+	return true;
+}
+
+// ---- specular reflection (include/spath_hip.h).  The lobe of the hit of depth d on a triangle of mirror
+// probability p: specular iff r7 < (double)p, r7 the first uniform of stream kSpecStream + d
+SP_DEV bool spec_lobe(uint64_t seed, uint32_t pixel, uint32_t sample, int depth, float p) {
+	double r7, r8;
+	philox_uniforms(seed, pixel, sample, kSpecStream + (uint32_t)depth, &r7, &r8);
+	return r7 < (double)p;
+}
+// the mirror direction of dir about n: dir - n * (c + c), c = dot3(dir, n); not renormalised
+SP_DEV f3 spec_reflect(f3 dir, f3 n) {
+	const float c = dot3(dir, n);
+	return sub3(dir, scale3(n, c + c));
+}
+// one step of the unwind at a hit on triangle id whose lobe was specular (sl) or diffuse: E + ((ks * rec) * (1 / p)), or today's
+// expression scaled once more, by 1 / (1 - p)
+SP_DEV f3 spec_unwind(const float4 q, bool sl, f3 e, f3 brdf, f3 rec, float ct) {
+	if (sl) return add3(e, scale3(mul3(mk3(q.x, q.y, q.z), rec), 1.0f / q.w));
+	return add3(e, scale3(scale3(scale3(mul3(brdf, rec), ct), kInvP), 1.0f / (1.0f - q.w)));
+}
+
+// ---- what the kernels share around the integrator: each is used where the kernel keeps its instructions with it (DESIGN.md
+// section 5.9 lists the sites that keep their own lines)
+
+// ray kk of the launch (the caller clamps kk below n_rays)
+SP_DEV void load_ray(const KArgs& a, uint32_t kk, f3& o, f3& dir) {
+	const float* r = a.rays + (size_t)kk * 6;
+	o = mk3(r[0], r[1], r[2]); dir = mk3(r[3], r[4], r[5]);
+}
+
+// renderer::render_flat's pixel (cpu_renderer.cpp:89-96): the nearest triangle's reflectance, RGBA{0,0,0,0} for a miss
+SP_DEV uint32_t flat_px(const KArgs& a, int bi) {
+	uint32_t px = 0;
+	if (bi >= 0) {
+		const float* m = a.mats + (size_t)bi * 6;
+		px = vec3_rgba(mk3(m[0], m[1], m[2]));
+	}
+	return px;
+}
+
+// cpu_renderer.cpp:78: the mean clamped to [0, 1] and quantised to RGBA8
+SP_DEV uint32_t clamped_rgba(f3 v) { return vec3_rgba(mk3(clamp01(v.x), clamp01(v.y), clamp01(v.z))); }
+
+} // namespace sp

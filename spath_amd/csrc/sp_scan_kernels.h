@@ -43,8 +43,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_hit_filter(
 		k[r] = blockIdx.x * (scan_block<SCAN>() * R) + r * scan_block<SCAN>() + threadIdx.x;
 		const bool valid = k[r] < a.n_rays;
 		const uint32_t kk = valid ? k[r] : a.n_rays - 1;
-		const float* p = a.rays + (size_t)kk * 6;
-		s.o[r] = mk3(p[0], p[1], p[2]); s.dir[r] = mk3(p[3], p[4], p[5]);
+		load_ray(a, kk, s.o[r], s.dir[r]);
 		s.src[r] = src_idx ? src_idx[kk] : -1; s.act[r] = valid;
 	}
 	float bd[R]; int bi[R];
@@ -68,8 +67,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 		k[r] = blockIdx.x * (scan_block<SCAN>() * R) + r * scan_block<SCAN>() + tid;
 		valid[r] = k[r] < a.n_rays;
 		const uint32_t kk = valid[r] ? k[r] : a.n_rays - 1;
-		const float* p = a.rays + (size_t)kk * 6;
-		s.o[r] = mk3(p[0], p[1], p[2]); s.dir[r] = mk3(p[3], p[4], p[5]);
+		load_ray(a, kk, s.o[r], s.dir[r]);
 		s.src[r] = -1; s.act[r] = valid[r];
 	}
 	float bd[R]; int bi[R];
@@ -77,11 +75,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 	uint32_t nsc = 0;
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
-		uint32_t px = 0;
-		if (bi[r] >= 0) {
-			const float* m = a.mats + (size_t)bi[r] * 6;
-			px = vec3_rgba(mk3(m[0], m[1], m[2]));
-		}
+		const uint32_t px = flat_px(a, bi[r]);
 		if (valid[r]) { a.out_rgba[k[r]] = px; nsc++; }
 	}
 	wave_add_scans(a.scans, nsc);
@@ -96,13 +90,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 // global work buffer between scans instead of being held in VGPRs through the scan loop: 52 B per slot,
 // touched once per bounce, against ~10^5 VALU instructions per bounce.
 //   work layout: hist[depth][k] = {idx, cos bits} (8 B), then acc[c][k] (3 floats), k < n_work
-// With a trailing AccumArgs (progressive accumulation, sp_kernels.h) the running sum enters the slot's accumulator at the start
+// With a trailing AccumArgs (progressive accumulation, sp_integrator.h) the running sum enters the slot's accumulator at the start
 // and leaves it at the end -- with SPLIT only slot 0 carries it; a sample-chunked launch leaves both to k_resolve.
 // With a trailing AdaptArgs (adaptive sampling) the same holds for S1, S2, parked in AdaptArgs::wst[2][n_work] (16 B per slot,
 // touched once per sample, never inside the scan), and ray k is local pixel list[k] for the RNG and the running sums.
-// With a SpecArgs (specular reflection, sp_kernels.h) a hit that took the mirror lobe carries kSpecBit in its history index: the
+// With a SpecArgs (specular reflection, sp_integrator.h) a hit that took the mirror lobe carries kSpecBit in its history index: the
 // slot stays 8 B per depth, and the unwind (and the next hit's MIS weight) reads the lobe back from there.
-// With a NormArgs (smooth shading, sp_kernels.h) the barycentric coordinates are recomputed for the winning triangle after the
+// With a NormArgs (smooth shading, sp_integrator.h) the barycentric coordinates are recomputed for the winning triangle after the
 // scan (shade_normal), never inside its tile loops; a path whose bounce leaves the surface's upper side stops being active.
 template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
@@ -117,13 +111,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	const uint32_t chunk = chunked ? blockIdx.x / a.px_blocks : 0u;
 	const uint32_t kr0 = SPLIT ? pblk * B + tid : pblk * (B * R) + tid;
 	constexpr bool adapt = IsAdapt<Acc...>::value;
-	constexpr bool nee = IsNee<Acc...>::value;               // next-event estimation: L_d parked in NeeArgs::L (sp_kernels.h)
+	constexpr bool nee = IsNee<Acc...>::value;               // next-event estimation: L_d parked in NeeArgs::L (sp_integrator.h)
 	static_assert(!nee || SCAN >= 2, "NEE needs the bounded form of the scan");
-	constexpr bool mis = IsMis<Acc...>::value;               // MIS: D_d parked in NeeArgs::L for d = 0..4 (sp_kernels.h MisArgs)
-	constexpr bool cam = IsCam<Acc...>::value;               // per-sample camera rays (sp_kernels.h CamArgs): KArgs::rays is not read
-	constexpr bool spc = IsSpec<Acc...>::value;              // specular reflection (sp_kernels.h SpecArgs)
+	constexpr bool mis = IsMis<Acc...>::value;               // MIS: D_d parked in NeeArgs::L for d = 0..4 (sp_integrator.h MisArgs)
+	constexpr bool cam = IsCam<Acc...>::value;               // per-sample camera rays (sp_integrator.h CamArgs): KArgs::rays is not read
+	constexpr bool spc = IsSpec<Acc...>::value;              // specular reflection (sp_integrator.h SpecArgs)
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
-	constexpr bool smo = IsNorm<Acc...>::value;              // smooth shading (sp_kernels.h NormArgs)
+	constexpr bool smo = IsNorm<Acc...>::value;              // smooth shading (sp_integrator.h NormArgs)
 	static_assert(!smo || ((mis || !nee) && SCAN >= 3), "smooth shading: plain or NEE|MIS, the default scan (DESIGN.md section 5.8)");
 	uint32_t pixel[R];
 #pragma unroll
@@ -181,10 +175,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			smp[r] = SPLIT ? it * R + r : it;
 			live[r] = (k < a.n_rays) && (smp[r] < a.n_samples);
 			if constexpr (cam) camera_ray(cam_args(acc_args...), a.seed, pixel[r], s0 + smp[r], s.o[r], s.dir[r]);
-			else {
-				const float* pr = a.rays + (size_t)(k < a.n_rays ? k : a.n_rays - 1) * 6;
-				s.o[r] = mk3(pr[0], pr[1], pr[2]); s.dir[r] = mk3(pr[3], pr[4], pr[5]);
-			}
+			else load_ray(a, k < a.n_rays ? k : a.n_rays - 1, s.o[r], s.dir[r]);
 			s.src[r] = -1; s.act[r] = live[r];
 			nh[r] = 0;
 		}
@@ -407,7 +398,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				}
 			}
 			const f3 av = scale3(mk3(acc[kw], acc[(size_t)n_work + kw], acc[(size_t)2 * n_work + kw]), a.inv_n);
-			a.out_rgba[k] = vec3_rgba(mk3(clamp01(av.x), clamp01(av.y), clamp01(av.z)));
+			a.out_rgba[k] = clamped_rgba(av);
 			if (a.out_accum) {
 				a.out_accum[(size_t)k * 3 + 0] = av.x;
 				a.out_accum[(size_t)k * 3 + 1] = av.y;
