@@ -20,12 +20,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hip_checks import E_INVALID, E_STATE, H, W, cam_rays
+from path_model import _bits
 from spath_amd import capi, scene, view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "spath_amd", "host", "build", "spath_cli")
-E_INVALID, E_STATE = r"\[-1\]", r"\[-3\]"
-W, H = 48, 32
 SPLITS = [[4] * 8, [3, 5, 8], [7, 9]]
 SCENES = {"closed_room_200": lambda: scene.closed_room(200), "default": scene.default_scene, "open_clutter_100": lambda: scene.open_clutter(100)}
 
@@ -55,17 +55,6 @@ def model(y, split, t, floor, min_samples):
             active[idx[v / nn <= d * d]] = False
         out.append((counts.copy(), int(active.sum()), total))
     return out
-
-
-def _rays(w=W, h=H, moves=((0.1, -0.2, 0.3), (0.05, 0.1, 0.0))):
-    cam = view.Camera(w, h)
-    cam.set_delta_mov(moves[0])
-    cam.set_delta_rot(moves[1])
-    return cam, np.ascontiguousarray(cam.get_viewport(), dtype=np.float32)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _check_pixels(counts, img, mean, one_shot):
@@ -170,7 +159,7 @@ def _sample_y(hip, rays, w, h, seed, flags, n_total, shard=None):
 @pytest.mark.parametrize("split", SPLITS, ids=["4x8", "3-5-8", "7-9"])
 def test_every_pixel_equals_a_one_shot_render_of_its_count(hip, scene_name, split):
     t, m = SCENES[scene_name]()
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     seed, rule = 0x5EED, (0.25, 0.05, 3)
     plain = _cached(lambda n: hip.render(rays, W, H, n, seed=seed, want_accum=True))
@@ -201,7 +190,7 @@ def test_every_pixel_equals_a_one_shot_render_of_its_count(hip, scene_name, spli
 @pytest.mark.parametrize("split", SPLITS, ids=["4x8", "3-5-8", "7-9"])
 def test_decisions_are_the_rule(hip, split):
     t, m = scene.closed_room(200)
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     seed = 77
     y = _sample_y(hip, rays, W, H, seed, 0, sum(split))
@@ -220,7 +209,7 @@ def test_decisions_are_the_rule(hip, split):
 @pytest.mark.gpu
 def test_no_stop_before_min_samples(hip):
     t, m = scene.closed_room(200)
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     for flags in (0, capi.FLAG_PRIMARY_REUSE, capi.flag_chunks(1)):
         plain, adaptive = [], []
@@ -238,7 +227,7 @@ def test_no_stop_before_min_samples(hip):
 def test_stopped_pixels_skip_work(hip):
     import torch
     t, m = scene.open_clutter(100)
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     d_rays = torch.from_numpy(rays).cuda()
     d_idx = torch.zeros(W * H, dtype=torch.int32, device="cuda")
@@ -279,8 +268,8 @@ def test_stopped_pixels_skip_work(hip):
 def test_isolation_and_state(hip):
     t, m = scene.closed_room(200)
     hip.set_scene(t, m)
-    _, rays = _rays()
-    cam2, rays2 = _rays(37, 21, ((0.0, 0.2, 0.1), (0.0, 0.3, 0.0)))
+    _, rays = cam_rays()
+    cam2, rays2 = cam_rays(37, 21, ((0.0, 0.2, 0.1), (0.0, 0.3, 0.0)))
     rule, split = (0.3, 0.05, 3), [3, 5, 8]
     runs = []
     for interleave in (False, True):
@@ -334,7 +323,7 @@ def test_multi_device_equals_single_context(hip, devices):
     mc.set_scene(t, m)
     rule = (0.3, 0.05, 3)
     for (w, h) in [(61, 37), (16, 5)]:
-        cam, rays = _rays(w, h)
+        cam, rays = cam_rays(w, h)
         hip.accum_begin(rays=rays, w=w, h=h, seed=21, adaptive=rule)
         want = []
         for n in [2, 3, 1, 4]:

@@ -15,9 +15,11 @@ import os
 import numpy as np
 import pytest
 
+import hip_checks as hc
+from hip_checks import E_INVALID, _torch_first  # noqa: F401 (_torch_first: a fixture)
 from oracle import oracle as O
+from path_model import _bits, _philox
 from spath_amd import capi, scene, view
-from test_hip_nee import E_INVALID, _bits, _philox
 
 F = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,13 +111,6 @@ def test_model_focus_geometry():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU part
-@pytest.fixture(autouse=True, scope="module")
-def _torch_first():
-    """torch's device runtime is brought up before the library's first context, as conftest.py's hip fixture does"""
-    import torch
-    torch.cuda.is_available()
-
-
 def _torch():
     import torch
     return torch
@@ -127,12 +122,6 @@ def _dev_rays(c, cam, seed, sample):
     c.camera_rays_device(cam, sample, d.data_ptr(), seed=seed, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     return d.cpu().numpy().reshape(-1, 6)
-
-
-def _ctx(t, m):
-    c = capi.Context(0)
-    c.set_scene(t, m)
-    return c
 
 
 @pytest.mark.gpu
@@ -182,7 +171,7 @@ def test_composition(variant, est):
     t, m = scene.closed_room(200)
     cam = _cam()
     f = variant | ESTIMATORS[est]
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     c.set_lens(0.06, 2.5)
     img, mean = c.render_camera(cam, 4, seed=11, flags=f | CAM, want_accum=True)
     st = c.stats()
@@ -200,7 +189,7 @@ def test_steps_chunks_multi_device(est):
     t, m = scene.open_clutter(100)
     cam = _cam()
     f = ESTIMATORS[est] | CAM
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     c.set_lens(0.05, 3.0)
     one = {n: c.render_camera(cam, n, seed=4, flags=f, want_accum=True) for n in (1, 3, 6, 8)}
     for extra in (capi.flag_chunks(1), capi.flag_chunks(4), 15):
@@ -233,7 +222,7 @@ def test_adaptive():
     cam = _cam()
     counts = {}
     for variant in (16, 15, 2, 1):
-        c = _ctx(t, m)
+        c = hc.ctx(t, m)
         c.set_lens(0.05, 3.0)
         c.accum_begin(cam=cam, seed=9, flags=variant | CAM, adaptive=(0.3, 0.05, 4))
         for n in (4, 4, 8):
@@ -316,7 +305,7 @@ def test_meaning(case):
     cam = view.Camera(32, 24)
     t, m = edge_scene(depth)
     N = 2048
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     c.set_lens(aperture, focus)
     plain = c.render_camera(cam, 16, seed=2, want_accum=True)[1][:, 0]
     mean = c.render_camera(cam, N, seed=2, flags=CAM, want_accum=True)[1][:, 0].astype(np.float64)
@@ -345,7 +334,7 @@ def test_error_contract():
     cam = _cam()
     n = cam.res_x * cam.res_y
     rays = view.Camera(cam.res_x, cam.res_y).get_viewport()
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     with pytest.raises(RuntimeError, match=E_INVALID):                   # paths that take rays
         c.render(rays, cam.res_x, cam.res_y, 2, seed=1, flags=CAM)
     with pytest.raises(RuntimeError, match=E_INVALID):
@@ -412,7 +401,7 @@ def test_cli_and_adapter(tmp_path):
     scene.write_scene(sp, t, m)
     w, h = 40, 24
     cam = view.Camera(w, h)
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     aa = c.render_camera(cam, 8, seed=9, flags=CAM)
     c.set_lens(0.05, 2.5)
     dof = c.render_camera(cam, 8, seed=9, flags=CAM)

@@ -18,11 +18,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hip_checks import E_INVALID, E_STATE, cam_rays
+from path_model import _bits
 from spath_amd import capi, scene, view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "spath_amd", "host", "build", "spath_cli")
-E_INVALID, E_STATE = r"\[-1\]", r"\[-3\]"
 F = np.float32
 INF = F(np.inf)
 SCENES = {"default": scene.default_scene, "closed_room_200": lambda: scene.closed_room(200), "open_clutter_100": lambda: scene.open_clutter(100)}
@@ -141,10 +142,6 @@ def var_of(y, counts):
         q = vv / n
         out[p] = F(q if q > 0.0 else 0.0)
     return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _hand_gb(mat, dist=None, n=(0.0, 0.0, 1.0)):
@@ -271,13 +268,6 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _rays(w, h, moves=((0.1, -0.2, 0.3), (0.05, 0.1, 0.0))):
-    cam = view.Camera(w, h)
-    cam.set_delta_mov(moves[0])
-    cam.set_delta_rot(moves[1])
-    return cam, np.ascontiguousarray(cam.get_viewport(), dtype=np.float32)
-
-
 def _gbuffer(hip, rays, flags=0):
     import torch
     n = rays.shape[0]
@@ -297,7 +287,7 @@ def _gbuffer(hip, rays, flags=0):
 def test_gbuffer_is_the_closest_hit(hip, O, scene_name):
     t, m = SCENES[scene_name]()
     hip.set_scene(t, m)
-    _, rays = _rays(40, 28)
+    _, rays = cam_rays(40, 28)
     want_idx, want_d = O.closest_hits(rays, t)
     cases = [v for v in capi.available_variants() if v != capi.kernel_variants()["accel_lbvh"]]
     cases = cases + [0, capi.FLAG_PRIMARY_REUSE, capi.FLAG_ACCEL, capi.FLAG_ACCEL | capi.FLAG_PRIMARY_REUSE]
@@ -316,7 +306,7 @@ def test_gbuffer_classes_follow_the_scene(hip):
     m = m.copy()
     m[5] = m[0]                                                   # bitwise duplicates share the smallest index
     hip.set_scene(t, m)
-    _, rays = _rays(32, 24)
+    _, rays = cam_rays(32, 24)
     g, idx, _ = _gbuffer(hip, rays)
     assert np.array_equal(g["mat"], np.where(idx >= 0, classes(m)[np.where(idx >= 0, idx, 0)], -1))
     m2 = m.copy()
@@ -349,7 +339,7 @@ def test_denoise_device_matches_the_model(hip, scene_name, kernel, monkeypatch):
     hip.set_scene(t, m)
     rng = np.random.default_rng(5)
     for (w, h) in [(1, 1), (1, 7), (7, 1), (17, 13), (48, 32)]:
-        _, rays = _rays(w, h)
+        _, rays = cam_rays(w, h)
         g, _, _ = _gbuffer(hip, rays)
         _, real = hip.render(rays, w, h, 4, seed=3, want_accum=True)
         rnd = rng.uniform(0, 1.2, (w * h, 3)).astype(F)
@@ -393,7 +383,7 @@ def test_accum_denoise_matches_the_model(hip, kind):
     t, m = scene.closed_room(200)
     hip.set_scene(t, m)
     w, h, seed = 40, 24, 7
-    _, rays = _rays(w, h)
+    _, rays = cam_rays(w, h)
     steps = [1, 3, 4, 8]
     rule = {"plain": None, "adaptive": (0.3, 0.05, 3), "never_stop": NEVER_STOP}[kind]
     y = _sample_y(hip, rays, w, h, seed, 0, sum(steps)) if rule else None
@@ -438,7 +428,7 @@ def test_never_stopping_rule_keeps_the_plain_image(hip):
     t, m = scene.open_clutter(100)
     hip.set_scene(t, m)
     w, h = 33, 21
-    cam, rays = _rays(w, h)
+    cam, rays = cam_rays(w, h)
     plain, stop = [], []
     hip.accum_begin(cam=cam, seed=3)
     for n in (1, 2, 5):
@@ -456,7 +446,7 @@ def test_raw_steps_stay_one_shot_renders_with_denoise_between(hip):
     t, m = scene.default_scene()
     hip.set_scene(t, m)
     w, h = 32, 20
-    _, rays = _rays(w, h)
+    _, rays = cam_rays(w, h)
     for flags in (0, capi.FLAG_PRIMARY_REUSE, capi.FLAG_ACCEL):
         hip.accum_begin(rays=rays, w=w, h=h, seed=11, flags=flags)
         total = 0
@@ -478,7 +468,7 @@ def test_multi_device_equals_single_context(hip, devices, rule):
     mc = capi.Context.multi(devices)
     mc.set_scene(t, m)
     for (w, h) in [(61, 37), (16, 5)]:
-        cam, rays = _rays(w, h)
+        cam, rays = cam_rays(w, h)
         hip.accum_begin(rays=rays, w=w, h=h, seed=21, adaptive=rule)
         mc.accum_begin(cam=cam, seed=21, adaptive=rule)
         for n in (2, 3, 4):
@@ -504,7 +494,7 @@ def test_error_contract(hip):
     t, m = scene.closed_room(200)
     hip.set_scene(t, m)
     w, h = 16, 8
-    _, rays = _rays(w, h)
+    _, rays = cam_rays(w, h)
     hip.accum_begin(rays=rays, w=w, h=h, seed=1)
     with pytest.raises(capi.SpathHipError, match=E_STATE):
         hip.accum_denoise()                                      # before the first step

@@ -2,10 +2,8 @@
 section 5.5): the light samples at hits 0..3 and the emission that BSDF directions find at hits 1..4, combined by the balance
 heuristic.
 
-The estimator is stated operation by operation in the header, so it is replayed here in numpy on top of the NEE replay's pieces
-(tests/test_hip_nee.py): closest hits of path and shadow rays through the oracle's strict scan, draws and directions through the
-oracle's device math, every other step in f32 in the stated order.  STATED TOLERANCE: 0 -- images, means and scan counts bit for
-bit.
+The estimator is stated operation by operation in the header, so it is replayed in numpy (tests/path_model.py, est="mis").
+STATED TOLERANCE: 0 -- images, means and scan counts bit for bit.
 
 CPU part: the flag's value; the light table's pdf by triangle on a hand-made scene.
 GPU part: the replay for every shipped scan variant and scene kind; composition with progressive and adaptive accumulation,
@@ -16,120 +14,13 @@ import os
 import numpy as np
 import pytest
 
-from oracle import oracle as O
+import hip_checks as hc
+import path_model
+from hip_checks import E_INVALID, NEE_MIS, SPP, H, W, many_emitters, small_light_room
+from path_model import F, PI_SQ, _bits, _u, light_table
 from spath_amd import capi, scene, view
-from test_hip_nee import (E_INVALID, INV_P, INV_PI, MARGIN, SCENES, SPP, H, W, _bits, _dot, _philox, _rays, _unit_vec,
-                          light_table, many_emitters, small_light_room)
 
-F = np.float32
-PI_SQ = F(np.pi * np.pi)
-TWO_PI = F(2.0 * np.pi)
-NEE_MIS = capi.FLAG_NEE | capi.FLAG_MIS
-
-
-def _u(sxz, dist2, cos_y, ipdf):
-    """u = p_l / q, a NaN quotient (0/0, inf/inf) counting as 0"""
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        u = ((PI_SQ * sxz) * dist2) / (cos_y * ipdf)
-    return np.where(np.isnan(u), F(0), u).astype(F)
-
-
-def model_samples(rays, tris, mats, seed, s0, n):
-    """radiance [npix, n, 3] of global samples s0 .. s0 + n - 1 under MIS, and the scans (path + shadow) they take"""
-    tris = np.ascontiguousarray(tris, F).reshape(-1, 12)
-    mats = np.ascontiguousarray(mats, F).reshape(-1, 6)
-    rays = np.ascontiguousarray(rays, F).reshape(-1, 6)
-    npix = rays.shape[0]
-    lt, cdf, ipdf, Wt, tip = scene.light_table(tris, mats)
-    P = npix * n
-    pix = np.repeat(np.arange(npix, dtype=np.uint32), n)
-    smp = np.tile(np.arange(s0, s0 + n, dtype=np.uint32), npix)
-    o, d = rays[pix, :3].copy(), rays[pix, 3:].copy()
-    src = np.full(P, -1, np.int32)
-    alive = np.ones(P, bool)
-    hidx = np.full((5, P), -1, np.int64)
-    hct = np.zeros((5, P), F)
-    D = np.zeros((5, P, 3), F)
-    scans = 0
-    for depth in range(5):
-        a = np.flatnonzero(alive)
-        if a.size == 0:
-            break
-        scans += a.size
-        idx, dist = O.closest_hits(np.concatenate([o[a], d[a]], 1), tris, src[a])
-        hit = idx >= 0
-        alive[a[~hit]] = False
-        a, idx, dist = a[hit], idx[hit].astype(np.int64), dist[hit]
-        nrm = tris[idx, 9:12].copy()
-        flip = _dot(nrm, d[a]) > F(0)
-        nrm[flip] = nrm[flip] * F(-1)
-        x = o[a] + d[a] * dist[:, None]
-        # e_d w_b: the BSDF direction's emission, weighted where the triangle is in the light table (not at the camera hit)
-        De = mats[idx, 3:6].copy()
-        if depth > 0:
-            ip = tip[idx]
-            w = np.flatnonzero(ip > F(0))
-            if w.size:
-                db = d[a[w]]
-                cyb = np.abs(_dot(db, tris[idx[w], 9:12]))
-                sxzb = np.sqrt(db[:, 0] * db[:, 0] + db[:, 2] * db[:, 2])
-                opu = F(1) + _u(sxzb, dist[w] * dist[w], cyb, ip[w])
-                De[w] = De[w] / opu[:, None]
-        L = np.zeros((a.size, 3), F)
-        if depth < 4 and lt.size:
-            r3, r4 = _philox(seed, pix[a], smp[a], 8 + depth)
-            r5, _ = _philox(seed, pix[a], smp[a], 16 + depth)
-            e = np.minimum(np.searchsorted(cdf, r5 * Wt, side="right"), lt.size - 1)
-            li = lt[e]
-            v0 = tris[li, 0:3]
-            e1, e2 = tris[li, 3:6] - v0, tris[li, 6:9] - v0
-            ua, ub = np.sqrt(r3).astype(F), r4.astype(F)
-            y = (v0 + e1 * (ua * (F(1) - ub))[:, None]) + e2 * (ua * ub)[:, None]
-            wv = y - x
-            dist2 = _dot(wv, wv)
-            ok = (li != idx) & (dist2 > F(0))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                dd = np.sqrt(dist2)
-                wd = wv / dd[:, None]
-                cx = _dot(wd, nrm)
-                cy = np.abs(_dot(wd, tris[li, 9:12]))
-                sxz = np.sqrt(wd[:, 0] * wd[:, 0] + wd[:, 2] * wd[:, 2])
-                ok &= (cx > F(0)) & (cy > F(0))                       # sxz = 0 is no early-out under MIS
-                tmax = dd * MARGIN
-                g = (TWO_PI * cx) / (F(1) + _u(sxz, dist2, cy, ipdf[e]))
-                Lc = (mats[idx, 0:3] * INV_PI) * (mats[li, 3:6] * g[:, None])
-            k = np.flatnonzero(ok)
-            scans += k.size
-            if k.size:
-                sidx, sd = O.closest_hits(np.concatenate([x[k], wd[k]], 1), tris, idx[k].astype(np.int32))
-                vis = ~((sidx >= 0) & (sd < tmax[k]))
-                L[k[vis]] = Lc[k[vis]]
-        D[depth, a] = De + L if depth < 4 else De
-        r1, r2 = _philox(seed, pix[a], smp[a], depth)
-        nd = _unit_vec(nrm, r1, r2)
-        hct[depth, a] = _dot(nd, nrm)
-        hidx[depth, a] = idx
-        o[a], d[a], src[a] = x, nd, idx.astype(np.int32)
-    rec = np.zeros((P, 3), F)
-    for depth in range(4, -1, -1):
-        h = np.flatnonzero(hidx[depth] >= 0)
-        brdf = mats[hidx[depth, h], 0:3] * INV_PI
-        rec[h] = D[depth, h] + ((brdf * rec[h]) * hct[depth, h][:, None]) * INV_P
-    return rec.reshape(npix, n, 3), scans
-
-
-def model_render(rays, tris, mats, n, seed):
-    """-> (rgba [npix, 4] u8, mean [npix, 3] f32, scans) of a one-shot MIS render of n samples"""
-    rec, scans = model_samples(rays, tris, mats, seed, 0, n)
-    acc = np.zeros((rec.shape[0], 3), F)
-    for s in range(n):
-        acc = acc + rec[:, s]
-    mean = acc * F(1.0 / n)
-    c = np.clip(mean, F(0), F(1)) * F(255) + F(0.5)
-    q = np.where(c < 0, 0, np.where(c > 255, 255, c.astype(np.uint32) & 0xFF)).astype(np.uint8)
-    rgba = np.zeros((rec.shape[0], 4), np.uint8)
-    rgba[:, :3] = q
-    return rgba, mean, scans
+SCENES = hc.NEE_SCENES
 
 
 def sample_bound(mats):
@@ -177,20 +68,14 @@ def test_u_has_no_nan():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU part
-def _ctx(t, m):
-    c = capi.Context(0)
-    c.set_scene(t, m)
-    return c
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant", [1, 2, 15, 16])
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_model_bit_exact(name, variant):
     t, m = SCENES[name]()
-    rays = _rays()
-    want_img, want_mean, want_scans = model_render(rays, t, m, SPP, 3)
-    c = _ctx(t, m)
+    rays = hc.rays()
+    want_img, want_mean, want_scans, _ = path_model.render(rays, t, m, SPP, 3, "mis")
+    c = hc.ctx(t, m)
     img, mean = c.render(rays, W, H, SPP, seed=3, flags=NEE_MIS | variant, want_accum=True)
     st = c.stats()
     c.close()
@@ -203,22 +88,17 @@ def test_model_bit_exact(name, variant):
 @pytest.mark.gpu
 def test_accel_geometric_parity():
     """the BVH gives the same image up to its rare rounding-noise accepts (test_hip_accel.py's rule: almost every pixel equal)"""
-    t, m = scene.closed_room(200)
-    rays = _rays()
-    c = _ctx(t, m)
-    a = c.render(rays, W, H, SPP, seed=3, flags=NEE_MIS | 16, want_accum=True)[1]
-    b = c.render(rays, W, H, SPP, seed=3, flags=NEE_MIS | capi.FLAG_ACCEL, want_accum=True)[1]
+    c = hc.ctx(*scene.closed_room(200))
+    hc.check_accel_parity(c, NEE_MIS)
     c.close()
-    same = np.all(_bits(a) == _bits(b), axis=1)
-    assert same.mean() >= 0.99, same.mean()
 
 
 @pytest.mark.gpu
 def test_isolated():
     """MIS renders repeat; NEE and plain renders are what they were before and after one; flat renders and the G-buffer ignore it"""
     t, m = scene.closed_room(200)
-    rays = _rays()
-    c = _ctx(t, m)
+    rays = hc.rays()
+    c = hc.ctx(t, m)
     plain0 = c.render(rays, W, H, SPP, seed=5, want_accum=True)[1]
     nee0 = c.render(rays, W, H, SPP, seed=5, flags=capi.FLAG_NEE, want_accum=True)[1]
     mis0 = c.render(rays, W, H, SPP, seed=5, flags=NEE_MIS, want_accum=True)[1]
@@ -244,52 +124,15 @@ def test_isolated():
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant", [16, 15, 2])
 def test_progressive_adaptive_denoise(variant):
-    t, m = many_emitters()
-    rays = _rays()
-    f = NEE_MIS | variant
-    c = _ctx(t, m)
-    one = {n: c.render(rays, W, H, n, seed=9, flags=f, want_accum=True) for n in (3, 8, 16)}
-    c.accum_begin(rays=rays, w=W, h=H, seed=9, flags=f)
-    tot = 0
-    for n in (3, 5, 8):
-        img, mean, tot = c.accum_step(n, want_mean=True)
-        assert np.array_equal(img, one[tot][0]) and np.array_equal(_bits(mean), _bits(one[tot][1])), tot
-    c.accum_begin(rays=rays, w=W, h=H, seed=9, flags=f, adaptive=(0.3, 0.05, 4))
-    for n in (4, 4, 8):
-        img, mean, _ = c.accum_step(n, want_mean=True)
-    counts, _ = c.accum_counts()
-    cnt = counts.ravel()
-    for n in np.unique(cnt):
-        want = one.get(int(n)) or c.render(rays, W, H, int(n), seed=9, flags=f, want_accum=True)
-        sel = cnt == n
-        assert np.array_equal(img[sel], want[0][sel]) and np.array_equal(_bits(mean[sel]), _bits(want[1][sel])), n
-    assert len(np.unique(cnt)) > 1                   # some pixels stopped early
-    den0 = c.accum_denoise()
-    den1 = c.accum_denoise()
-    assert den0.shape == (W * H, 4) and np.array_equal(den0, den1)
+    c = hc.ctx(*many_emitters())
+    cnt = hc.check_progressive_adaptive_denoise(c, NEE_MIS | variant)
     c.close()
+    assert len(np.unique(cnt)) > 1                   # some pixels stopped early
 
 
 @pytest.mark.gpu
 def test_reuse_chunks_multi_device():
-    t, m = scene.open_clutter(100)
-    rays = _rays()
-    c = _ctx(t, m)
-    want = c.render(rays, W, H, SPP, seed=4, flags=NEE_MIS, want_accum=True)
-    for extra in (capi.FLAG_PRIMARY_REUSE, capi.flag_chunks(1), capi.flag_chunks(4)):
-        got = c.render(rays, W, H, SPP, seed=4, flags=NEE_MIS | extra, want_accum=True)
-        assert np.array_equal(got[0], want[0]) and np.array_equal(_bits(got[1]), _bits(want[1])), extra
-    c.close()
-    for devs in ([0, 0], [0, 0, 0]):
-        mc = capi.Context.multi(devs)
-        mc.set_scene(t, m)
-        got = mc.render(rays, W, H, SPP, seed=4, flags=NEE_MIS, want_accum=True)
-        mc.close()
-        assert np.array_equal(got[0], want[0]) and np.array_equal(_bits(got[1]), _bits(want[1])), devs
-
-
-def _seeds_means(c, rays, w, h, spp, flags, seeds):
-    return np.stack([c.render(rays, w, h, spp, seed=s, flags=flags, want_accum=True)[1].astype(np.float64) for s in seeds])
+    hc.check_reuse_chunks_multi_device(*scene.open_clutter(100), NEE_MIS, ())
 
 
 UNBIASED_SCENES = {"open_clutter_100": lambda: scene.open_clutter(100), "small_light_room": small_light_room,
@@ -303,23 +146,13 @@ def test_unbiased(name):
     < 5 in every cell of a 4 x 4 grid).  closed_room(200) hangs its panel 0.05 below the ceiling: NEE's firefly case"""
     t, m = UNBIASED_SCENES[name]()
     w = h = 32
-    rays = _rays(w, h)
-    c = _ctx(t, m)
+    rays = hc.rays(w, h)
+    c = hc.ctx(t, m)
     seeds = list(range(100, 116))
-    a = _seeds_means(c, rays, w, h, 256, NEE_MIS, seeds).reshape(16, h, w, 3).sum(-1)
-    b = _seeds_means(c, rays, w, h, 256, 0, seeds).reshape(16, h, w, 3).sum(-1)
+    a = hc.seeds_means(c, rays, w, h, 256, NEE_MIS, seeds)
+    b = hc.seeds_means(c, rays, w, h, 256, 0, seeds)
     c.close()
-    dd = a - b
-
-    def z(x):
-        v = x.reshape(16, -1).mean(1)
-        return v.mean() / (v.std(ddof=1) / 4.0)
-    print(f"{name}: z(image) {z(dd):+.2f}")
-    assert abs(z(dd)) < 4, z(dd)
-    for by in range(4):
-        for bx in range(4):
-            zc = z(dd[:, 8 * by:8 * by + 8, 8 * bx:8 * bx + 8])
-            assert abs(zc) < 5, (by, bx, zc)
+    hc.z_grid(a, b, h, w, f"{name}: MIS vs plain")
 
 
 # fixed once (not searched at test time): at seed 3 and 2 spp, NEE's mean breaks the bound in a few pixels.  The bound is loose here
@@ -332,9 +165,9 @@ def test_bounded_samples():
     """closed_room(200): no MIS pixel mean exceeds the per-sample bound (relative slack 1e-5 for f32 rounding) at 2 and 16 spp;
     NEE's does at 2 spp, so the frame has fireflies to tame"""
     t, m = scene.closed_room(200)
-    rays = _rays()
+    rays = hc.rays()
     bound = sample_bound(m) * (1 + 1e-5)
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     mis = [c.render(rays, W, H, n, seed=BOUND_SEED, flags=NEE_MIS, want_accum=True)[1].astype(np.float64) for n in (BOUND_SPP, 16)]
     nee = c.render(rays, W, H, BOUND_SPP, seed=BOUND_SEED, flags=capi.FLAG_NEE, want_accum=True)[1].astype(np.float64)
     c.close()
@@ -355,8 +188,8 @@ def test_lower_noise_small_light():
     unmeasured bar of 0.5x was missed: the MI355X measured 0.583x (NEE alone: 0.131x); the bar is 0.6x"""
     t, m = small_light_room()
     w = h = 32
-    rays = _rays(w, h)
-    c = _ctx(t, m)
+    rays = hc.rays(w, h)
+    c = hc.ctx(t, m)
     ref = c.render(rays, w, h, 4096, seed=77, want_accum=True)[1].astype(np.float64)
     plain = c.render(rays, w, h, 16, seed=1, want_accum=True)[1]
     mis = c.render(rays, w, h, 16, seed=1, flags=NEE_MIS, want_accum=True)[1]
@@ -371,8 +204,8 @@ def test_lower_noise_closed_room():
     """closed_room(200) at 32 x 32, 16 spp: MIS's full-range RMS error is below the plain estimator's and below NEE's"""
     t, m = scene.closed_room(200)
     w = h = 32
-    rays = _rays(w, h)
-    c = _ctx(t, m)
+    rays = hc.rays(w, h)
+    c = hc.ctx(t, m)
     ref = c.render(rays, w, h, 4096, seed=77, want_accum=True)[1].astype(np.float64)
     plain = c.render(rays, w, h, 16, seed=1, want_accum=True)[1]
     nee = c.render(rays, w, h, 16, seed=1, flags=capi.FLAG_NEE, want_accum=True)[1]
@@ -386,16 +219,16 @@ def test_lower_noise_closed_room():
 @pytest.mark.gpu
 def test_error_contract():
     t, m = scene.closed_room(200)
-    rays = _rays()
+    rays = hc.rays()
     for bad in (-0.5, np.nan, np.inf):
         mb = m.copy()
         mb[40, 4] = bad
-        c = _ctx(t, mb)
+        c = hc.ctx(t, mb)
         with pytest.raises(RuntimeError, match=E_INVALID):
             c.render(rays, W, H, 2, seed=1, flags=NEE_MIS)
         c.render(rays, W, H, 2, seed=1)                   # the plain estimator does not look at it
         c.close()
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     with pytest.raises(RuntimeError, match=E_INVALID):    # MIS is a form of NEE
         c.render(rays, W, H, 2, seed=1, flags=capi.FLAG_MIS)
     with pytest.raises(RuntimeError, match=E_INVALID):
@@ -406,7 +239,7 @@ def test_error_contract():
     c.close()
     m0 = m.copy()
     m0[:, 3:6] = 0
-    c = _ctx(t, m0)                                       # no emitter: black
+    c = hc.ctx(t, m0)                                       # no emitter: black
     img, mean = c.render(rays, W, H, 2, seed=1, flags=NEE_MIS, want_accum=True)
     c.close()
     assert not img.any() and not mean.any()
@@ -423,7 +256,7 @@ def test_cli_and_adapter(tmp_path):
     scene.write_scene(sp, t, m)
     w, h = 40, 24
     rays = np.ascontiguousarray(view.Camera(w, h).get_viewport(), dtype=F)
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     want = c.render(rays, w, h, 8, seed=9, flags=NEE_MIS)
     nee = c.render(rays, w, h, 8, seed=9, flags=capi.FLAG_NEE)
     c.close()

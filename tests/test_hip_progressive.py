@@ -17,21 +17,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from hip_checks import E_INVALID, E_STATE, H, W, cam_rays
 from spath_amd import capi, scene, view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "spath_amd", "host", "build", "spath_cli")
-E_INVALID, E_STATE = r"\[-1\]", r"\[-3\]"
-W, H = 48, 32
 SPLITS = [[1] * 6, [3, 5, 8], [7, 9]]
 SCENES = {"closed_room_200": lambda: scene.closed_room(200), "default": scene.default_scene, "open_clutter_100": lambda: scene.open_clutter(100)}
-
-
-def _rays(w=W, h=H, moves=((0.1, -0.2, 0.3), (0.05, 0.1, 0.0))):
-    cam = view.Camera(w, h)
-    cam.set_delta_mov(moves[0])
-    cam.set_delta_rot(moves[1])
-    return cam, np.ascontiguousarray(cam.get_viewport(), dtype=np.float32)
 
 
 def _check_steps(ctx, one_shot, split, on_step=None):
@@ -87,7 +79,7 @@ def oracle_cache(O):
 @pytest.mark.parametrize("split", SPLITS, ids=["ones", "3-5-8", "7-9"])
 def test_steps_equal_one_shot_for_every_variant_and_chunking(hip, oracle_cache, scene_name, split):
     t, m = SCENES[scene_name]()
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     seed = 0x5EED
     for variant in [0] + capi.available_variants():
@@ -109,7 +101,7 @@ def test_steps_equal_one_shot_for_every_variant_and_chunking(hip, oracle_cache, 
                          ids=["primary_reuse", "accel", "primary_reuse_chunks8"])
 def test_steps_equal_one_shot_with_flags(hip, flags):
     t, m = scene.closed_room(200)
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     for split in SPLITS:
         hip.accum_begin(rays=rays, w=W, h=H, seed=3, flags=flags)
@@ -121,7 +113,7 @@ def test_steps_equal_one_shot_with_flags(hip, flags):
 def test_device_form_on_shards(hip, g):
     import torch
     t, m = scene.closed_room(200)
-    _, rays = _rays()
+    _, rays = cam_rays()
     hip.set_scene(t, m)
     seed, steps = 11, [3, 5, 2]
     tr = capi.plan_tile_rows(H, g)
@@ -164,7 +156,7 @@ def test_device_form_on_shards(hip, g):
 def test_camera_begin_equals_rays_begin(hip):
     t, m = scene.open_clutter(100)
     hip.set_scene(t, m)
-    cam, rays = _rays(W, H, ((0.3, 0.1, -0.5), (0.1, -0.25, 0.0)))
+    cam, rays = cam_rays(W, H, ((0.3, 0.1, -0.5), (0.1, -0.25, 0.0)))
     cam.set_delta_focal(0.5)
     rays = np.ascontiguousarray(cam.get_viewport(), dtype=np.float32)
     results = []
@@ -181,8 +173,8 @@ def test_camera_begin_equals_rays_begin(hip):
 def test_renders_between_steps_do_not_disturb_the_accumulation(hip):
     t, m = scene.closed_room(200)
     hip.set_scene(t, m)
-    _, rays = _rays()
-    cam2, rays2 = _rays(37, 21, ((0.0, 0.2, 0.1), (0.0, 0.3, 0.0)))
+    _, rays = cam_rays()
+    cam2, rays2 = cam_rays(37, 21, ((0.0, 0.2, 0.1), (0.0, 0.3, 0.0)))
     hip.accum_begin(rays=rays, w=W, h=H, seed=9)
 
     def interleave(total, img, mean):
@@ -201,7 +193,7 @@ def test_multi_device_steps_equal_single_context_one_shot(hip, devices):
     mc = capi.Context.multi(devices)
     mc.set_scene(t, m)
     for (w, h) in [(61, 37), (16, 5)]:
-        cam, rays = _rays(w, h)
+        cam, rays = cam_rays(w, h)
         for begin in (lambda: mc.accum_begin(rays=rays, w=w, h=h, seed=21), lambda: mc.accum_begin(cam=cam, seed=21)):
             begin()
             total = 0
@@ -220,7 +212,7 @@ def test_multi_device_steps_equal_single_context_one_shot(hip, devices):
 @pytest.mark.gpu
 def test_error_contract(hip):
     t, m = scene.default_scene()
-    _, rays = _rays()
+    _, rays = cam_rays()
     fresh = capi.Context(0)
     with pytest.raises(capi.SpathHipError, match=E_STATE):
         fresh.accum_begin(rays=rays, w=W, h=H)                                  # before any scene

@@ -1,14 +1,14 @@
 """Smooth shading (include/spath_hip.h: SPHIP_FLAG_SMOOTH with sphip_set_vertex_normals): per-vertex normals
 beside the scene; every hit shades with the normal interpolated at the hit point, the stored normal guards the surface's upper side.
 
-The arithmetic is stated operation by operation in the header, so it is replayed here in numpy on top of the specular replay
-(tests/test_hip_specular.py) and its NEE and MIS pieces: the four rules bary/interp, diffuse, mirror and light in f32 in the stated
-order.  STATED TOLERANCE: 0 -- images, means, scan counts, G-buffer normals and the selftest bit for bit.  The one statistical bar
-(plain against NEE|MIS under the flag) is the project's: |z| < 4 for the image and < 5 in every cell of a 4 x 4 grid over 16 seeds
-x 256 spp at 32 x 32, for two disjoint seed sets, as tests/test_hip_specular.py::test_unbiased_plain_vs_mis.
+The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/path_model.py with normals `vn`):
+the four rules bary/interp, diffuse, mirror and light in f32 in the stated order.  STATED TOLERANCE: 0 -- images, means, scan
+counts, G-buffer normals and the selftest bit for bit.  The one statistical bar (plain against NEE|MIS under the flag) is the
+project's: |z| < 4 for the image and < 5 in every cell of a 4 x 4 grid over 16 seeds x 256 spp at 32 x 32, for two disjoint seed
+sets, as tests/test_hip_specular.py::test_unbiased_plain_vs_mis.
 
 CPU part: the flag and the symbols; scene.vertex_normals, scene.icosphere and the normals file; the model by hand; a table of zeros
-and a table of the stored normals against the specular model; the coverage of the replay cases; the null-context contract.
+and a table of the stored normals against the model without normals; the coverage of the replay cases; the null-context contract.
 GPU part: selftest 7; the replay for variants 1 and 16, both estimators, three scenes, with and without a specular table; variant
 16 in both workgroup shapes; zero table = no flag; the BVH's parity; the G-buffer; the compositions; plain against NEE|MIS; the
 error contract; the front ends."""
@@ -18,255 +18,18 @@ import os
 import numpy as np
 import pytest
 
+import hip_checks as hc
+import path_model
+from hip_checks import (E_INVALID, E_STATE, ESTIMATORS, NEE_MIS, REPLAY_SEED, SPP, H, W, _torch_first, shape,  # noqa: F401
+                        smooth_case as _case)                                               # (_torch_first, shape: fixtures)
 from oracle import oracle as O
+from path_model import F, _bits, _dot, shade_normal
 from spath_amd import capi, scene, view
-from test_hip_nee import E_INVALID, INV_P, INV_PI, MARGIN, SPP, H, W, _bits, _dot, _philox, _rays, _unit_vec
-from test_hip_mis import TWO_PI, NEE_MIS, _u
-from test_hip_specular import E_STATE, ESTIMATORS, _hand_scene, _same, _seeds_means, _z_grid, shape  # noqa: F401 (shape: a fixture)
-from test_hip_specular import model_samples as spec_model_samples
 
-F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMOOTH = capi.FLAG_SMOOTH
 SPEC = capi.FLAG_SPECULAR
-REPLAY_SEED = 3
-
-
-def _cross(a, b):
-    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
-
-
-def shade_normal(o, d, tv, vn, nrm):
-    """rules bary and interp of the header for rays (o, d) on triangles with vertices tv [k, 9], vertex normals vn [k, 9] and stored
-    normals nrm (turned against d) -> (u, v, ns, sm)"""
-    with np.errstate(all="ignore"):
-        v0 = tv[:, 0:3]
-        e1, e2 = tv[:, 3:6] - v0, tv[:, 6:9] - v0
-        h = _cross(d, e2)
-        a = _dot(e1, h)
-        f = F(1) / a
-        s = o - v0
-        u = f * _dot(s, h)
-        q = _cross(s, e1)
-        v = f * _dot(d, q)
-        w = (F(1) - u) - v
-        m = (vn[:, 0:3] * w[:, None] + vn[:, 3:6] * u[:, None]) + vn[:, 6:9] * v[:, None]
-        l2 = _dot(m, m)
-        sm = (l2 > F(0)) & np.isfinite(l2)
-        ns = nrm.copy()
-        k = np.flatnonzero(sm)
-        if k.size:
-            nk = (m[k] / np.sqrt(l2[k])[:, None]).astype(F)
-            fl = _dot(nk, nrm[k]) < F(0)
-            nk[fl] = nk[fl] * F(-1)
-            ns[k] = nk
-    return u, v, ns, sm
-
-
-def model_samples(rays, tris, mats, spec, vn, seed, s0, n, mis, first_ns=None):
-    """tests/test_hip_specular.py's model_samples with the vertex normals vn [N, 9] and the four rules of smooth shading: radiance
-    [npix, n, 3] of global samples s0 .. s0 + n - 1, the scans they take, and the shares the coverage test asserts: hits, hits with sm,
-    paths ended by the diffuse and by the mirror rule, light samples drawn and those cut by the geometric guard.
-    first_ns: a list that receives (pixel, ns) of every sample's first hit (the G-buffer's normal)"""
-    tris = np.ascontiguousarray(tris, F).reshape(-1, 12)
-    mats = np.ascontiguousarray(mats, F).reshape(-1, 6)
-    spec = np.ascontiguousarray(spec, F).reshape(-1, 4)
-    vn = np.ascontiguousarray(vn, F).reshape(-1, 9)
-    rays = np.ascontiguousarray(rays, F).reshape(-1, 6)
-    npix = rays.shape[0]
-    lt, cdf, ipdf, Wt, tip = scene.light_table(tris, mats)
-    P = npix * n
-    pix = np.repeat(np.arange(npix, dtype=np.uint32), n)
-    smp = np.tile(np.arange(s0, s0 + n, dtype=np.uint32), npix)
-    o, d = rays[pix, :3].copy(), rays[pix, 3:].copy()
-    src = np.full(P, -1, np.int32)
-    alive = np.ones(P, bool)
-    hidx = np.full((5, P), -1, np.int64)
-    hct = np.zeros((5, P), F)
-    hspec = np.zeros((5, P), bool)
-    E = np.zeros((5, P, 3), F)
-    prev_spec = np.zeros(P, bool)
-    info = {"hits": 0, "sm": 0, "ended_diffuse": 0, "ended_mirror": 0, "lights": 0, "lights_cut": 0, "inexact": set(), "accepts": []}
-    scans = 0
-    for depth in range(5):
-        a = np.flatnonzero(alive)
-        if a.size == 0:
-            break
-        scans += a.size
-        idx, dist = O.closest_hits(np.concatenate([o[a], d[a]], 1), tris, src[a])
-        hit = idx >= 0
-        alive[a[~hit]] = False
-        a, idx, dist = a[hit], idx[hit].astype(np.int64), dist[hit]
-        ps = prev_spec[a]
-        nrm = tris[idx, 9:12].copy()
-        flip = _dot(nrm, d[a]) > F(0)
-        nrm[flip] = nrm[flip] * F(-1)
-        x = o[a] + d[a] * dist[:, None]
-        # bary, interp: the shading normal
-        _, _, ns, sm = shade_normal(o[a], d[a], tris[idx, 0:9], vn[idx], nrm)
-        info["hits"] += a.size
-        info["sm"] += int(sm.sum())
-        info["accepts"].append((o[a].copy(), d[a].copy(), idx.copy()))           # every hit the float test accepted: path rays ...
-        info["inexact"] |= set(idx[sm & (_bits(ns) != _bits(nrm)).any(1)].tolist())
-        if depth == 0 and first_ns is not None:
-            first_ns.append((pix[a], ns.copy()))
-        p = spec[idx, 3]
-        r7, _ = _philox(seed, pix[a], smp[a], 32 + depth)
-        sl = r7 < p.astype(np.float64)
-        with np.errstate(divide="ignore"):
-            wD = F(1) / (F(1) - p)
-        De = mats[idx, 3:6].copy()
-        if mis:
-            ip = tip[idx]
-            w = np.flatnonzero((ip > F(0)) & ~ps) if depth > 0 else np.zeros(0, np.int64)
-            if w.size:
-                db = d[a[w]]
-                cyb = np.abs(_dot(db, tris[idx[w], 9:12]))
-                sxzb = np.sqrt(db[:, 0] * db[:, 0] + db[:, 2] * db[:, 2])
-                opu = F(1) + _u(sxzb, dist[w] * dist[w], cyb, ip[w])
-                De[w] = De[w] / opu[:, None]
-            L = np.zeros((a.size, 3), F)
-            if depth < 4 and lt.size:
-                r3, r4 = _philox(seed, pix[a], smp[a], 8 + depth)
-                r5, _ = _philox(seed, pix[a], smp[a], 16 + depth)
-                e = np.minimum(np.searchsorted(cdf, r5 * Wt, side="right"), lt.size - 1)
-                li = lt[e]
-                v0 = tris[li, 0:3]
-                e1, e2 = tris[li, 3:6] - v0, tris[li, 6:9] - v0
-                ua, ub = np.sqrt(r3).astype(F), r4.astype(F)
-                y = (v0 + e1 * (ua * (F(1) - ub))[:, None]) + e2 * (ua * ub)[:, None]
-                wv = y - x
-                dist2 = _dot(wv, wv)
-                ok = (li != idx) & (dist2 > F(0)) & ~sl
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    dd = np.sqrt(dist2)
-                    wd = wv / dd[:, None]
-                    cx = _dot(wd, ns)                               # light: cos_x by the shading normal
-                    cy = np.abs(_dot(wd, tris[li, 9:12]))           # the emitter keeps its stored normal
-                    sxz = np.sqrt(wd[:, 0] * wd[:, 0] + wd[:, 2] * wd[:, 2])
-                    ok &= (cx > F(0)) & (cy > F(0))
-                    cut = ok & sm & ~(_dot(wd, nrm) > F(0))         # ... and nothing from below the stored normal
-                    ok &= ~cut
-                    tmax = dd * MARGIN
-                    g = (TWO_PI * cx) / (F(1) + _u(sxz, dist2, cy, ipdf[e]))
-                    Lc = (mats[idx, 0:3] * INV_PI) * (mats[li, 3:6] * g[:, None])
-                info["lights"] += int(ok.sum() + cut.sum())
-                info["lights_cut"] += int(cut.sum())
-                k = np.flatnonzero(ok)
-                scans += k.size
-                if k.size:
-                    sidx, sd = O.closest_hits(np.concatenate([x[k], wd[k]], 1), tris, idx[k].astype(np.int32))
-                    vis = ~((sidx >= 0) & (sd < tmax[k]))
-                    info["accepts"].append((x[k][sidx >= 0], wd[k][sidx >= 0], sidx[sidx >= 0].astype(np.int64)))   # ... and shadow rays
-                    kv = k[vis]
-                    L[kv] = Lc[kv] * wD[kv][:, None]
-            E[depth, a] = De + L if depth < 4 else De
-        else:
-            E[depth, a] = De
-        # mirror: c = dot3(dir, ns); nd = dir - ns * (c + c); ends when sm and (!(c < 0) or dot3(nd, n) < 0)
-        c = _dot(d[a], ns)
-        t = c + c
-        nd = (d[a] - ns * t[:, None]).astype(F)
-        ended = sl & sm & (~(c < F(0)) | (_dot(nd, nrm) < F(0)))
-        info["ended_mirror"] += int(ended.sum())
-        ct = np.zeros(a.size, F)
-        df = np.flatnonzero(~sl)
-        if df.size:
-            # diffuse: nd = rand_unit_vec(ns, r1, r2); ct = dot3(nd, ns); ends when sm and dot3(nd, n) < 0
-            r1, r2 = _philox(seed, pix[a[df]], smp[a[df]], depth)
-            ndd = _unit_vec(ns[df], r1, r2)
-            nd[df] = ndd
-            ct[df] = _dot(ndd, ns[df])
-            end_d = sm[df] & (_dot(ndd, nrm[df]) < F(0))
-            ended[df] = end_d
-            info["ended_diffuse"] += int(end_d.sum())
-        hct[depth, a] = ct
-        hidx[depth, a] = idx
-        hspec[depth, a] = sl
-        prev_spec[a] = sl
-        o[a], d[a], src[a] = x, nd, idx.astype(np.int32)
-        alive[a[ended]] = False                                     # the hit keeps E_d; rec_{d+1} = 0; nothing more is scanned
-    rec = np.zeros((P, 3), F)
-    for depth in range(4, -1, -1):
-        h = np.flatnonzero(hidx[depth] >= 0)
-        i = hidx[depth, h]
-        p = spec[i, 3]
-        brdf = mats[i, 0:3] * INV_PI
-        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-            wS = (F(1) / p)[:, None]
-            wD = (F(1) / (F(1) - p))[:, None]
-            dif = E[depth, h] + (((brdf * rec[h]) * hct[depth, h][:, None]) * INV_P) * wD
-            spe = E[depth, h] + (spec[i, 0:3] * rec[h]) * wS
-        rec[h] = np.where(hspec[depth, h][:, None], spe, dif).astype(F)
-    info["samples"] = P
-    return rec.reshape(npix, n, 3), scans, info
-
-
-def model_render(rays, tris, mats, spec, vn, n, seed, mis, first_ns=None):
-    """-> (rgba [npix, 4] u8, mean [npix, 3] f32, scans, info) of a one-shot flagged render of n samples"""
-    rec, scans, info = model_samples(rays, tris, mats, spec, vn, seed, 0, n, mis, first_ns)
-    acc = np.zeros((rec.shape[0], 3), F)
-    for s in range(n):
-        acc = acc + rec[:, s]
-    mean = acc * F(1.0 / n)
-    c = np.clip(mean, F(0), F(1)) * F(255) + F(0.5)
-    q = np.where(c < 0, 0, np.where(c > 255, 255, c.astype(np.uint32) & 0xFF)).astype(np.uint8)
-    rgba = np.zeros((rec.shape[0], 4), np.uint8)
-    rgba[:, :3] = q
-    return rgba, mean, scans, info
-
-
-# ---------------------------------------------------------------------------------------------------------------- scenes
-SPHERE_C, SPHERE_R = (0.0, -0.35, -0.9), 0.5
-
-
-def _sphere_scene(mirror):
-    """default_scene plus icosphere(1) (80 triangles) in front of the pyramid, under the light: a pure mirror or diffuse"""
-    t0, m0 = scene.default_scene()
-    ts, ms = scene.icosphere(1, SPHERE_C, SPHERE_R, (0.1, 0.1, 0.1, 0, 0, 0) if mirror else (0.8, 0.7, 0.6, 0, 0, 0))
-    t, m = np.concatenate([t0, ts]), np.concatenate([m0, ms])
-    s = np.zeros((t.shape[0], 4), F)
-    if mirror:
-        s[7:] = (0.9, 0.85, 0.8, 1.0)
-    vn = scene.vertex_normals(t, which=np.arange(7, t.shape[0]))
-    return t, m, s, vn
-
-
-def mirror_sphere():
-    return _sphere_scene(True)
-
-
-def diffuse_sphere():
-    return _sphere_scene(False)
-
-
-def bad_room():
-    """closed_room(200) with vertex_normals over everything at crease_deg = 180: the box's corners average three walls, which gives
-    deliberately bad normals and so many terminations"""
-    t, m = scene.closed_room(200)
-    return t, m, np.zeros((t.shape[0], 4), F), scene.vertex_normals(t, 180.0)
-
-
-def _mixed(t, m, s):
-    """a mixed specular table over the non-emitters on top of s: p in (0.2, 0.8) and ks by a fixed pattern over the index"""
-    j = np.arange(t.shape[0], dtype=F)
-    x = s.copy()
-    k = (m[:, 3:6].sum(1) == 0) & (s[:, 3] == 0)
-    x[k, 0] = (F(0.3) + F(0.1) * (j % 5))[k]
-    x[k, 1] = (F(0.2) + F(0.15) * (j % 4))[k]
-    x[k, 2] = (F(0.5) + F(0.05) * (j % 7))[k]
-    x[k, 3] = (F(0.2) + F(0.1) * (j % 7))[k]
-    return x
-
-
-SCENES = {"mirror_sphere": mirror_sphere, "diffuse_sphere": diffuse_sphere, "bad_room": bad_room}
-
-
-def _case(name, mixed):
-    t, m, s, vn = SCENES[name]()
-    return t, m, (_mixed(t, m, s) if mixed else s), vn
-
-
+SCENES = hc.SMOOTH_SCENES
 _MODEL = {}
 
 
@@ -276,7 +39,7 @@ def _model(name, mixed, est):
     if key not in _MODEL:
         t, m, s, vn = _case(name, mixed)
         fn = []
-        _MODEL[key] = model_render(_rays(), t, m, s, vn, SPP, REPLAY_SEED, bool(ESTIMATORS[est]), fn) + (fn[0],)
+        _MODEL[key] = path_model.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, fn, ("accepts",)) + (fn[0],)
     return _MODEL[key]
 
 
@@ -379,14 +142,13 @@ def test_model_by_hand(est):
     the reflection into (0.8, 0.6, 0), which reaches the emitter in the plane x = 2 that the flat normal's reflection (straight up)
     misses: exactly ks * E against 0 without the table.  Vertex normals (2, 1, 0) send it to (0.8, -0.6, 0), below the surface: the
     path ends after the first hit, which keeps its own emission"""
-    t, m, s, rays = _hand_scene()
+    t, m, s, rays = hc.hand_scene()
     rays = rays[2:3]
-    mis = bool(ESTIMATORS[est])
     vn = np.zeros((3, 9), F)
-    flat, scans, _ = model_samples(rays, t, m, s, vn, 7, 0, 3, mis)
+    flat, scans, _ = path_model.samples(rays, t, m, 7, 0, 3, est, s, vn)
     assert not flat.any() and scans == 3 * 2                      # mirror, miss
     vn[0] = [1, 2, 0] * 3
-    rec, scans, info = model_samples(rays, t, m, s, vn, 7, 0, 3, mis)
+    rec, scans, info = path_model.samples(rays, t, m, 7, 0, 3, est, s, vn)
     want = s[0, 0:3] * m[1, 3:6]
     for k in range(3):
         assert np.array_equal(_bits(rec[0, k]), _bits(want)), rec[0, k]
@@ -395,14 +157,14 @@ def test_model_by_hand(est):
     vn[0] = [2, 1, 0] * 3
     m = m.copy()
     m[0, 3:6] = (0.25, 0.5, 1.0)
-    rec, scans, info = model_samples(rays, t, m, s, vn, 7, 0, 3, mis)
+    rec, scans, info = path_model.samples(rays, t, m, 7, 0, 3, est, s, vn)
     for k in range(3):
         assert np.array_equal(_bits(rec[0, k]), _bits(m[0, 3:6])), rec[0, k]
     assert scans == 3 * 1 and info["ended_mirror"] == 3 and info["hits"] == 3
     # the same tilt on a diffuse triangle: some directions about ns fall below the surface and end the path there
     s = s.copy()
     s[0] = 0
-    rec, scans, info = model_samples(np.repeat(rays, 16, 0), t, m, s, vn, 7, 0, 4, mis)
+    rec, scans, info = path_model.samples(np.repeat(rays, 16, 0), t, m, 7, 0, 4, est, s, vn)
     assert 0 < info["ended_diffuse"] < 64
     assert scans >= 64 + (64 - info["ended_diffuse"])
 
@@ -411,21 +173,19 @@ def test_model_by_hand(est):
 @pytest.mark.parametrize("name", ["closed_room_200", "open_clutter_100"])
 def test_zero_and_stored_normals_are_the_specular_model(name, est):
     """a table of zeros, and a table of the stored normal at all three vertices on the triangles where m / sqrtf(dot3(m, m))
-    reproduces n bitwise at every hit, each reproduce tests/test_hip_specular.py's model bit for bit, scans included"""
-    from test_hip_specular import mixed_room
-    mis = bool(ESTIMATORS[est])
+    reproduces n bitwise at every hit, each reproduce the model without vertex normals bit for bit, scans included"""
     if name == "closed_room_200":
-        t, m, s = mixed_room()
+        t, m, s = hc.mixed_room()
     else:
         t, m = scene.open_clutter(100)
         s = np.zeros((100, 4), F)
-    rays = _rays(16, 12)
-    want, want_scans, _ = spec_model_samples(rays, t, m, s, 5, 1, 3, mis)
-    rec, scans, info = model_samples(rays, t, m, s, np.zeros((t.shape[0], 9), F), 5, 1, 3, mis)
+    rays = hc.rays(16, 12)
+    want, want_scans, _ = path_model.samples(rays, t, m, 5, 1, 3, est, s)
+    rec, scans, info = path_model.samples(rays, t, m, 5, 1, 3, est, s, np.zeros((t.shape[0], 9), F))
     assert np.array_equal(_bits(rec), _bits(want)) and scans == want_scans and info["sm"] == 0
     vn = np.tile(t[:, 9:12], (1, 3))
     for _ in range(8):                                            # drop the triangles where a hit does not reproduce n, until none is left
-        rec, scans, info = model_samples(rays, t, m, s, vn, 5, 1, 3, mis)
+        rec, scans, info = path_model.samples(rays, t, m, 5, 1, 3, est, s, vn, collect=("inexact",))
         if not info["inexact"]:
             break
         vn[sorted(info["inexact"])] = 0
@@ -452,23 +212,6 @@ def test_replay_cases_are_covered(name, mixed, est):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU part
-@pytest.fixture(autouse=True, scope="module")
-def _torch_first():
-    """torch's device runtime is brought up before the library's first context, as conftest.py's hip fixture does"""
-    import torch
-    torch.cuda.is_available()
-
-
-def _ctx(t, m, s=None, vn=None):
-    c = capi.Context(0)
-    c.set_scene(t, m)
-    if s is not None:
-        c.set_specular(s)
-    if vn is not None:
-        c.set_vertex_normals(vn)
-    return c
-
-
 @pytest.mark.gpu
 def test_selftest_shade_normal():
     """the device function the kernels call against numpy for 4096 random triangles and rays, degenerate tables included: zero rows,
@@ -512,10 +255,10 @@ def test_selftest_shade_normal():
 @pytest.mark.parametrize("name", sorted(SCENES))
 def test_model_bit_exact(name, mixed, variant, est):
     t, m, s, vn = _case(name, mixed)
-    rays = _rays()
+    rays = hc.rays()
     want_img, want_mean, want_scans, info, _ = _model(name, mixed, est)
     _covered(info, name, mixed, bool(ESTIMATORS[est]))
-    c = _ctx(t, m, s, vn)
+    c = hc.ctx(t, m, s, vn)
     img, mean = c.render(rays, W, H, SPP, seed=REPLAY_SEED, flags=SMOOTH | SPEC | ESTIMATORS[est] | variant, want_accum=True)
     st = c.stats()
     c.close()
@@ -531,40 +274,10 @@ def test_model_bit_exact(name, mixed, variant, est):
 def test_both_block_shapes(shape, name, est):
     """variant 16 in its 256- and its 512-thread shape: the replay, a progressive and an adaptive split, primary-hit reuse, camera
     samples, and zero table = no flag; the tile size of the stream says which shape ran"""
-    from test_hip_shapes import _tiles
     t, m, s, vn = _case(name, True)
-    rays = _rays()
-    f = ESTIMATORS[est] | 16 | SPEC
-    want_img, want_mean, want_scans, _, _ = _model(name, True, est)
-    c = _ctx(t, m, s, vn)
-    got = c.render(rays, W, H, SPP, seed=REPLAY_SEED, flags=f | SMOOTH, want_accum=True)
-    st = c.stats()
-    assert _tiles(c, rays)[1] == shape and st["kernel_variant"] == 16
-    assert np.array_equal(_bits(got[1]), _bits(want_mean)) and np.array_equal(got[0], want_img)
-    assert st["scans_executed"] == want_scans
-    assert _same(c.render(rays, W, H, SPP, seed=REPLAY_SEED, flags=f | SMOOTH | capi.FLAG_PRIMARY_REUSE, want_accum=True), got)
-    c.accum_begin(rays=rays, w=W, h=H, seed=REPLAY_SEED, flags=f | SMOOTH)
-    c.accum_step(1)
-    img, mean, _ = c.accum_step(SPP - 1, want_mean=True)
-    assert _same((img, mean), got)
-    c.accum_begin(rays=rays, w=W, h=H, seed=REPLAY_SEED, flags=f | SMOOTH, adaptive=(0.0, 0.0, 0xFFFFFFFF))   # never stops a pixel
-    c.accum_step(1)
-    img, mean, _ = c.accum_step(SPP - 1, want_mean=True)
-    assert _same((img, mean), got)
-    cam = view.Camera(40, 26)
-    cam.set_delta_mov([0.1, 0.2, 0.3])
-    ca = c.render_camera(cam, SPP, seed=6, flags=f | SMOOTH | capi.FLAG_CAMERA_SAMPLES, want_accum=True)
-    c.accum_begin(cam=cam, seed=6, flags=f | SMOOTH | capi.FLAG_CAMERA_SAMPLES)
-    c.accum_step(2)
-    img, mean, _ = c.accum_step(SPP - 2, want_mean=True)
-    assert _same((img, mean), ca)
-    c.set_vertex_normals(np.zeros_like(vn))
-    for extra in (0, capi.FLAG_CAMERA_SAMPLES):
-        want = c.render_camera(cam, SPP, seed=6, flags=f | extra, want_accum=True)
-        ws = c.stats()["scans_executed"]
-        flagged = c.render_camera(cam, SPP, seed=6, flags=f | extra | SMOOTH, want_accum=True)
-        assert _same(flagged, want) and c.stats()["scans_executed"] == ws, extra
-    assert _tiles(c, rays)[1] == shape
+    c = hc.ctx(t, m, s, vn)
+    hc.check_both_block_shapes(c, shape, ESTIMATORS[est] | 16 | SPEC, SMOOTH, _model(name, True, est)[:3],
+                               lambda c: c.set_vertex_normals(np.zeros_like(vn)))
     c.close()
 
 
@@ -576,23 +289,12 @@ def test_zero_table_is_no_flag(variant, spec, est):
     """a table of zeros: the flagged render is the unflagged one bit for bit, scans included, from rays and, with and without camera
     samples, from a camera; with and without a specular table"""
     t, m, s, vn = _case("bad_room", spec)
-    rays = _rays()
+    rays = hc.rays()
     f = ESTIMATORS[est] | variant | (SPEC if spec else 0)
-    cam = view.Camera(40, 26)
-    cam.set_delta_mov([0.1, 0.2, 0.3])
-    c = _ctx(t, m, s if spec else None, np.zeros_like(vn))
-    c.set_lens(0.05, 2.5)
-    want = c.render(rays, W, H, SPP, seed=6, flags=f, want_accum=True)
-    ws = c.stats()["scans_executed"]
-    got = c.render(rays, W, H, SPP, seed=6, flags=f | SMOOTH, want_accum=True)
-    assert _same(got, want) and c.stats()["scans_executed"] == ws
-    for extra in (0, capi.FLAG_CAMERA_SAMPLES):
-        want = c.render_camera(cam, SPP, seed=6, flags=f | extra, want_accum=True)
-        ws = c.stats()["scans_executed"]
-        got = c.render_camera(cam, SPP, seed=6, flags=f | extra | SMOOTH, want_accum=True)
-        assert _same(got, want) and c.stats()["scans_executed"] == ws, extra
+    c = hc.ctx(t, m, s if spec else None, np.zeros_like(vn))
+    hc.check_zero_table_is_no_flag(c, f, SMOOTH)
     c.set_vertex_normals(vn)                                       # and the table matters
-    assert not _same(c.render(rays, W, H, SPP, seed=6, flags=f | SMOOTH, want_accum=True), c.render(rays, W, H, SPP, seed=6, flags=f, want_accum=True))
+    assert not hc.same(c.render(rays, W, H, SPP, seed=6, flags=f | SMOOTH, want_accum=True), c.render(rays, W, H, SPP, seed=6, flags=f, want_accum=True))
     c.close()
 
 
@@ -634,17 +336,12 @@ def test_accel_parity_scene_keeps_noise_accepts_rare(est):
 def test_accel_geometric_parity(est):
     """the BVH gives the same image up to its rare rounding-noise accepts: agreement in at least 99 % of the pixels (section 5.7's bar)"""
     t, m, s, vn = _case("diffuse_sphere", True)
-    rays = _rays()
-    c = _ctx(t, m, s, vn)
+    c = hc.ctx(t, m, s, vn)
     f = SMOOTH | SPEC | ESTIMATORS[est]
-    a = c.render(rays, W, H, SPP, seed=3, flags=f | 16, want_accum=True)[1]
-    b = c.render(rays, W, H, SPP, seed=3, flags=f | capi.FLAG_ACCEL, want_accum=True)[1]
+    b = hc.check_accel_parity(c, f)
     assert c.stats()["kernel_variant"] == 8
-    unflagged = c.render(rays, W, H, SPP, seed=3, flags=(f & ~SMOOTH) | capi.FLAG_ACCEL, want_accum=True)[1]
+    unflagged = c.render(hc.rays(), W, H, SPP, seed=3, flags=(f & ~SMOOTH) | capi.FLAG_ACCEL, want_accum=True)[1]
     c.close()
-    same = np.all(_bits(a) == _bits(b), axis=1)
-    print("BVH agrees with variant 16 in", same.mean(), "of the pixels")
-    assert same.mean() >= 0.99, same.mean()
     assert not np.array_equal(_bits(b), _bits(unflagged))
 
 
@@ -654,10 +351,10 @@ def test_gbuffer_and_denoise(est):
     """the G-buffer's normals are the model's ns of the primary ray; dist, albedo and mat are the unflagged G-buffer's; the flagged
     G-buffer differs from the unflagged one on the sphere and equals it elsewhere; denoising repeats bit for bit"""
     t, m, s, vn = _case("diffuse_sphere", False)
-    rays = _rays()
+    rays = hc.rays()
     f = ESTIMATORS[est] | 16
     pixn = _model("diffuse_sphere", False, est)[4]
-    c = _ctx(t, m, s, vn)
+    c = hc.ctx(t, m, s, vn)
     c.accum_begin(rays=rays, w=W, h=H, seed=REPLAY_SEED, flags=f | SMOOTH)
     c.accum_step(SPP)
     g1 = c.accum_gbuffer()
@@ -684,7 +381,7 @@ def test_gbuffer_device_direct():
     the flag the unflagged one although a table is set; the flag without a table is SPHIP_E_STATE and leaves the context usable"""
     import torch
     t, m, s, vn = _case("diffuse_sphere", False)
-    rays = _rays()
+    rays = hc.rays()
     pix, ns = _model("diffuse_sphere", False, "plain")[4]
     first = np.unique(pix, return_index=True)[1]
     d_rays = torch.from_numpy(rays).to("cuda")
@@ -696,7 +393,7 @@ def test_gbuffer_device_direct():
         torch.cuda.synchronize()
         return d_g.cpu().numpy().view(capi.gbuffer_dtype())
 
-    c = _ctx(t, m)
+    c = hc.ctx(t, m)
     g0 = direct(c, 0)
     with pytest.raises(RuntimeError, match=E_STATE):
         direct(c, SMOOTH)
@@ -720,26 +417,8 @@ def test_gbuffer_device_direct():
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
 @pytest.mark.parametrize("variant", [16, 1, capi.FLAG_ACCEL])
 def test_progressive_adaptive(variant, est):
-    t, m, s, vn = _case("bad_room", True)
-    rays = _rays()
-    f = SMOOTH | SPEC | ESTIMATORS[est] | variant
-    c = _ctx(t, m, s, vn)
-    one = {n: c.render(rays, W, H, n, seed=9, flags=f, want_accum=True) for n in (3, 8, 16)}
-    c.accum_begin(rays=rays, w=W, h=H, seed=9, flags=f)
-    for n in (3, 5, 8):
-        img, mean, tot = c.accum_step(n, want_mean=True)
-        assert np.array_equal(img, one[tot][0]) and np.array_equal(_bits(mean), _bits(one[tot][1])), tot
-    c.accum_begin(rays=rays, w=W, h=H, seed=9, flags=f, adaptive=(0.3, 0.05, 4))
-    for n in (4, 4, 8):
-        img, mean, _ = c.accum_step(n, want_mean=True)
-    counts, _ = c.accum_counts()
-    cnt = counts.ravel()
-    for n in np.unique(cnt):
-        want = one.get(int(n)) or c.render(rays, W, H, int(n), seed=9, flags=f, want_accum=True)
-        sel = cnt == n
-        assert np.array_equal(img[sel], want[0][sel]) and np.array_equal(_bits(mean[sel]), _bits(want[1][sel])), n
-    den0, den1 = c.accum_denoise(), c.accum_denoise()
-    assert np.array_equal(den0, den1)
+    c = hc.ctx(*_case("bad_room", True))
+    hc.check_progressive_adaptive_denoise(c, SMOOTH | SPEC | ESTIMATORS[est] | variant)
     c.close()
 
 
@@ -747,30 +426,11 @@ def test_progressive_adaptive(variant, est):
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
 def test_reuse_chunks_multi_device(est):
     t, m, s, vn = _case("mirror_sphere", True)
-    rays = _rays()
-    f = SMOOTH | SPEC | ESTIMATORS[est]
-    c = _ctx(t, m, s, vn)
-    want = c.render(rays, W, H, SPP, seed=4, flags=f, want_accum=True)
-    unflagged = c.render(rays, W, H, SPP, seed=4, flags=f & ~SMOOTH, want_accum=True)
-    assert not _same(want, unflagged)
-    for extra in (capi.FLAG_PRIMARY_REUSE, capi.flag_chunks(1), capi.flag_chunks(4), 16 | capi.FLAG_PRIMARY_REUSE, 1 | capi.FLAG_PRIMARY_REUSE):
-        got = c.render(rays, W, H, SPP, seed=4, flags=f | extra, want_accum=True)
-        assert _same(got, want), extra
-    c.close()
-    for devs in ([0, 0], [0, 0, 0]):
-        mc = capi.Context.multi(devs)
-        mc.set_scene(t, m)
-        mc.set_specular(s)
-        mc.set_vertex_normals(vn)
-        got = mc.render(rays, W, H, SPP, seed=4, flags=f, want_accum=True)
-        mc.accum_begin(rays=rays, w=W, h=H, seed=4, flags=f)
-        mc.accum_step(1)
-        img, mean, _ = mc.accum_step(SPP - 1, want_mean=True)
-        g = mc.accum_gbuffer()
-        mc.close()
-        assert _same(got, want), devs
-        assert _same((img, mean), want), devs
-        assert g.shape[0] == W * H
+
+    def gbuffer_is_there(mc):
+        assert mc.accum_gbuffer().shape[0] == W * H
+    hc.check_reuse_chunks_multi_device(t, m, SMOOTH | SPEC | ESTIMATORS[est], (16 | capi.FLAG_PRIMARY_REUSE, 1 | capi.FLAG_PRIMARY_REUSE),
+                                       spec=s, vn=vn, unflag=SMOOTH, each_multi=gbuffer_is_there)
 
 
 @pytest.mark.gpu
@@ -779,33 +439,11 @@ def test_reuse_chunks_multi_device(est):
 def test_camera_samples_and_device_table(variant, est):
     """camera samples with the flag are the chain of one-sample accumulations over sphip_camera_rays_device's rays; the normals come
     from a device pointer here"""
-    import torch
     t, m, s, vn = _case("mirror_sphere", True)
-    cam = view.Camera(40, 26)
-    cam.set_delta_mov([0.1, 0.2, 0.3])
-    cam.set_delta_rot([0.05, -0.1, 0.0])
-    f = SMOOTH | SPEC | ESTIMATORS[est] | variant
-    c = _ctx(t, m, s)
-    st = torch.cuda.current_stream().cuda_stream
-    d_vn = torch.from_numpy(vn).to("cuda")
-    c.set_vertex_normals_device(d_vn.data_ptr(), st)
-    torch.cuda.synchronize()
-    del d_vn                                              # the table was copied
-    c.set_lens(0.06, 2.5)
-    img, mean = c.render_camera(cam, 4, seed=11, flags=f | capi.FLAG_CAMERA_SAMPLES, want_accum=True)
-    npix = cam.res_x * cam.res_y
-    d_rays = torch.empty(npix * 6, dtype=torch.float32, device="cuda")
-    d_sum = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
-    d_out = torch.zeros(npix * 4, dtype=torch.uint8, device="cuda")
-    d_mean = torch.zeros(npix * 3, dtype=torch.float32, device="cuda")
-    for k in range(4):
-        c.camera_rays_device(cam, k, d_rays.data_ptr(), seed=11, stream=st)
-        c.render_device_accum(d_rays.data_ptr(), npix, k, 1, d_sum.data_ptr(), d_out.data_ptr(), seed=11, flags=f,
-                              image_width=cam.res_x, d_out_mean=d_mean.data_ptr(), stream=st)
-    torch.cuda.synchronize()
+    c = hc.ctx(t, m, s)
+    hc.set_device_table(c.set_vertex_normals_device, vn)
+    hc.check_camera_samples(c, SMOOTH | SPEC | ESTIMATORS[est] | variant)
     c.close()
-    assert np.array_equal(img, d_out.cpu().numpy().reshape(-1, 4))
-    assert np.array_equal(_bits(mean), _bits(d_mean.cpu().numpy().reshape(-1, 3)))
 
 
 @pytest.mark.gpu
@@ -816,13 +454,13 @@ def test_unbiased_plain_vs_mis(name, seed0):
     and sample count, for two disjoint sets of 16 seeds"""
     t, m, s, vn = _case(name, False)
     w = h = 32
-    rays = _rays(w, h)
+    rays = hc.rays(w, h)
     seeds = list(range(seed0, seed0 + 16))
-    c = _ctx(t, m, s, vn)
-    a = _seeds_means(c, rays, w, h, 256, SMOOTH | SPEC | NEE_MIS, seeds)
-    b = _seeds_means(c, rays, w, h, 256, SMOOTH | SPEC, seeds)
+    c = hc.ctx(t, m, s, vn)
+    a = hc.seeds_means(c, rays, w, h, 256, SMOOTH | SPEC | NEE_MIS, seeds)
+    b = hc.seeds_means(c, rays, w, h, 256, SMOOTH | SPEC, seeds)
     c.close()
-    _z_grid(a, b, h, w, f"{name}: MIS vs plain under SMOOTH, seeds {seed0}..{seed0 + 15}")
+    hc.z_grid(a, b, h, w, f"{name}: MIS vs plain under SMOOTH, seeds {seed0}..{seed0 + 15}", alike_is_zero=True)
 
 
 @pytest.mark.gpu
@@ -831,20 +469,20 @@ def test_unbiased_plain_vs_mis_where_the_guard_fires():
     silhouette, test_replay_cases_are_covered): a guard that cut too much or too little would bias NEE|MIS against plain there"""
     t, m, s, vn = _case("diffuse_sphere", False)
     w = h = 32
-    rays = _rays(w, h)
+    rays = hc.rays(w, h)
     seeds = list(range(500, 516))
-    c = _ctx(t, m, s, vn)
-    a = _seeds_means(c, rays, w, h, 256, SMOOTH | SPEC | NEE_MIS, seeds)
-    b = _seeds_means(c, rays, w, h, 256, SMOOTH | SPEC, seeds)
+    c = hc.ctx(t, m, s, vn)
+    a = hc.seeds_means(c, rays, w, h, 256, SMOOTH | SPEC | NEE_MIS, seeds)
+    b = hc.seeds_means(c, rays, w, h, 256, SMOOTH | SPEC, seeds)
     c.close()
-    _z_grid(a, b, h, w, "diffuse_sphere: MIS vs plain under SMOOTH, seeds 500..515")
+    hc.z_grid(a, b, h, w, "diffuse_sphere: MIS vs plain under SMOOTH, seeds 500..515", alike_is_zero=True)
 
 
 @pytest.mark.gpu
 def test_error_contract():
     t, m, s, vn = _case("bad_room", False)
-    rays = _rays()
-    c = _ctx(t, m)
+    rays = hc.rays()
+    c = hc.ctx(t, m)
     L = capi.load()
 
     def refused(code, fn):
@@ -879,14 +517,14 @@ def test_error_contract():
         with pytest.raises(RuntimeError, match=E_INVALID) as e:
             c.set_vertex_normals(vb)
         assert "triangle 40 " in str(e.value), str(e.value)
-        assert _same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)         # the table stays as it was
+        assert hc.same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)         # the table stays as it was
     # without the flag the table is ignored
     c.set_vertex_normals(None)
     refused(E_STATE, lambda: c.render(rays, W, H, 2, seed=1, flags=SMOOTH))                     # NULL cleared it
     unflagged = c.render(rays, W, H, 2, seed=1, want_accum=True)
     c.set_vertex_normals(vn)
-    assert _same(c.render(rays, W, H, 2, seed=1, want_accum=True), unflagged)
-    assert not _same(good, unflagged)
+    assert hc.same(c.render(rays, W, H, 2, seed=1, want_accum=True), unflagged)
+    assert not hc.same(good, unflagged)
     # set_scene clears the table
     c.set_scene(t, m)
     refused(E_STATE, lambda: c.render(rays, W, H, 2, seed=1, flags=SMOOTH))
@@ -904,7 +542,7 @@ def test_error_contract():
     with pytest.raises(RuntimeError, match=E_STATE) as by_setter:
         c.accum_step(2)
     assert str(by_setter.value) == str(by_scene.value)
-    assert _same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
+    assert hc.same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
     c.close()
     # table before scene
     c = capi.Context(0)
@@ -915,7 +553,7 @@ def test_error_contract():
     assert L.sphip_last_error(c._h)
     c.set_scene(t, m)
     c.set_vertex_normals(vn)
-    assert _same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
+    assert hc.same(c.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
     c.close()
     # the device-pointer form on a multi-device context; a multi-device accumulation ended by the setter
     mc = capi.Context.multi([0, 0])
@@ -926,7 +564,7 @@ def test_error_contract():
     with pytest.raises(RuntimeError, match=E_STATE):
         mc.render(rays, W, H, 2, seed=1, flags=SMOOTH)
     mc.set_vertex_normals(vn)
-    assert _same(mc.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
+    assert hc.same(mc.render(rays, W, H, 2, seed=1, flags=SMOOTH, want_accum=True), good)
     mc.accum_begin(rays=rays, w=W, h=H, seed=1, flags=SMOOTH)
     mc.accum_step(1)
     mc.set_vertex_normals(vn)
@@ -934,7 +572,7 @@ def test_error_contract():
         mc.accum_step(1)
     mc.accum_begin(rays=rays, w=W, h=H, seed=1, flags=SMOOTH)
     img, mean, _ = mc.accum_step(2, want_mean=True)
-    assert _same((img, mean), good)
+    assert hc.same((img, mean), good)
     mc.close()
 
 
@@ -953,7 +591,7 @@ def test_cli_and_adapter(tmp_path):
     w, h = 40, 24
     cam = view.Camera(w, h)
     rays = np.ascontiguousarray(cam.get_viewport(), dtype=F)
-    c = _ctx(t, m, s, vn)
+    c = hc.ctx(t, m, s, vn)
     smooth = c.render(rays, w, h, 8, seed=9, flags=SMOOTH)
     smooth_spec = c.render(rays, w, h, 8, seed=9, flags=SMOOTH | SPEC)
     smooth_mis = c.render(rays, w, h, 8, seed=9, flags=SMOOTH | NEE_MIS)
