@@ -74,8 +74,11 @@ enum {
 	SPHIP_FLAG_SPECULAR = 0x2000,    /* OPT-IN mirror and mixed diffuse/mirror materials from the context's specular table
 	                                   (sphip_set_specular) for SPHIP_MODE_PT; see "specular reflection" below.  Without the flag the
 	                                   table is ignored. */
-	SPHIP_FLAG_SMOOTH = 0x4000       /* OPT-IN smooth shading by the context's per-vertex normals (sphip_set_vertex_normals) for
+	SPHIP_FLAG_SMOOTH = 0x4000,      /* OPT-IN smooth shading by the context's per-vertex normals (sphip_set_vertex_normals) for
 	                                   SPHIP_MODE_PT; see "smooth shading" below.  Without the flag the normals are ignored. */
+	SPHIP_FLAG_DIELECTRIC = 0x8000   /* OPT-IN transparency: dielectric (glass) triangles with Fresnel reflection and refraction from the
+	                                   context's dielectric table (sphip_set_dielectric) for SPHIP_MODE_PT; see "transparency" below.
+	                                   Without the flag the table is ignored. */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -202,7 +205,8 @@ int sphip_plan_shard(size_t width, size_t height, int n_devices, size_t tile_row
  *        5  vec3_rgba      (scene.h:32-39)                         in f32[3n]                         out u32[n]
  *        6  the f16 matrix-pipe side product of sp_cylm_scan.h      in f32[12n] 5 triangle values, 5 ray values, P_a (a half), 0
  *                                                                  out f32[2n] the instruction's result, the same 16 products summed in double
- *        7  shade_normal   ("smooth shading" below)                in f32[24n] pos dir v0 v1 v2 n0 n1 n2   out f32[6n] u, v, ns.xyz, sm */
+ *        7  shade_normal   ("smooth shading" below)                in f32[24n] pos dir v0 v1 v2 n0 n1 n2   out f32[6n] u, v, ns.xyz, sm
+ *        8  dielectric     ("transparency" below)                  in f32[8n] dir ns ior entering          out f32[6n] Fr, tir, nt.xyz, c */
 int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void* out);
 
 /* TEST-ONLY: stage 1 of the default scan ALONE -- the conservative reject that decides which (ray, triangle) pairs ever reach
@@ -509,6 +513,57 @@ int sphip_set_vertex_normals(sphip_t* ctx, const float* vn);
  * `stream` alone, and copied, so the caller may free d_vn once the stream has passed the call.  It does NOT validate the values:
  * non-finite normals give undefined images (never out-of-bounds accesses: the table is indexed by triangle alone). */
 int sphip_set_vertex_normals_device(sphip_t* ctx, const void* d_vn, void* stream);
+
+/* ---- transparency (SPHIP_FLAG_DIELECTRIC): a per-triangle dielectric table beside the scene, 4 f32 per
+ * triangle: kt.r, kt.g, kt.b, ior.  ior = 0 leaves the triangle what it is.  ior >= 1 makes it a smooth interface between vacuum, on
+ * the side its stored normal points to, and a dielectric of index ior behind it: its diffuse reflectance and its row of the specular
+ * table are ignored, its emittance still counts in E_d as always, and kt tints what is transmitted through it.  Every interface is
+ * decided locally from the stored normal: there is no medium stack, and a ray that leaks through a mesh edge is simply in vacuum at
+ * the next interface it meets from the normal's side.  The 6-float material and sphip_set_scene are unchanged.
+ *
+ * Valid for SPHIP_MODE_PT with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with variants 1, 8 (SPHIP_FLAG_ACCEL)
+ * and 16 (both workgroup shapes), with or without SPHIP_FLAG_SPECULAR and SPHIP_FLAG_SMOOTH, with SPHIP_FLAG_CAMERA_SAMPLES,
+ * progressive and adaptive accumulation, denoising (the G-buffer is unchanged), sample chunks, primary-hit reuse, shards and
+ * multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT; with SPHIP_FLAG_NEE without SPHIP_FLAG_MIS; with any other variant
+ * (2 and 15 are A/B scans, as for smooth shading).  SPHIP_E_STATE: the flag without a table.  Hit queries ignore the flag.  Without
+ * the flag every render is bit for bit what it is without a table; with the flag and a table of zeros too.
+ *
+ * The arithmetic, at hit d of the path of (seed, global pixel, global sample) on triangle i with ior > 0 by the ray (o, dir); n is the
+ * stored normal turned against dir as always, ns the shading normal (n, or shade_normal's under smooth shading),
+ * entering = !(dot3(n_stored, dir) > 0); f32, every operation rounded on its own, nothing fused,
+ * dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, IEEE / and sqrtf:
+ *   eta = entering ? 1.0f / ior : ior
+ *   c   = dot3(dir, ns);  ci = -c
+ *   k   = 1.0f - (eta * eta) * (1.0f - ci * ci);        tir = !(k > 0)
+ *   ct  = sqrtf(k);  a = eta * ci;  b = eta * ct
+ *   rs  = (a - ct) / (a + ct);  rp = (ci - b) / (ci + b);  Fr = 0.5f * (rs * rs + rp * rp)
+ *   lobe:     (r7, _) = philox_uniforms(seed, pixel, sample, 32 + d)   (the specular lobe's stream: that lobe is not drawn on such a triangle)
+ *             transmit iff !tir and (double)Fr <= r7   (a NaN Fr reflects);  otherwise reflect
+ *   reflect:  nd = dir - ns * (c + c)   (the mirror's direction)      rec_d = E_d + rec_{d+1}
+ *   transmit: nd = dir * eta + ns * (a - ct)   (per component)         rec_d = E_d + kt * rec_{d+1}   (per channel)
+ * The origin x = o + dir * dist and source-triangle skipping are as always; nd is not renormalised.  Fresnel's probability and weight
+ * cancel, so neither lobe carries a division.  There is no eta^2 radiance scale: camera paths start and end in vacuum.
+ * Under smooth shading, when the hit is smooth (sm): the path ENDS after the hit when !(c < 0); a reflection ends it when
+ * dot3(nd, n) < 0 (the mirror's rule); a transmission ends it when !(dot3(nd, n) < 0).
+ * With SPHIP_FLAG_NEE | SPHIP_FLAG_MIS a hit on such a triangle is a specular hit in every respect: it draws no light sample and traces
+ * no shadow ray, and the hit after it counts its emission in full (Ew_{d+1} = e_{d+1}).  Shadow rays treat glass as an occluder, so
+ * light through glass is found by the BSDF strategy alone, with full weight: both estimators keep one expectation.  scans_executed
+ * counts what ran.
+ *
+ * sphip_selftest_device what 8: in f32[8 n] (dir.xyz ns.xyz ior entering as 0/1), out f32[6 n] (Fr, tir as 0/1, nt.xyz, c), nt the
+ * transmitted direction: the device function the kernels call (Fr and nt mean nothing when tir). */
+
+/* The context's dielectric table: n_tris * 4 f32 on the host for the scene last set (NULL clears the table); blocking, the array is
+ * borrowed for the call; accepted by multi-device contexts (every device keeps the whole table, like the scene).  Every set_scene
+ * clears the table.  During an accumulation it ends the accumulation as a set_scene does (the next step: SPHIP_E_STATE).
+ * SPHIP_E_STATE without a scene; SPHIP_E_INVALID when a value is not finite, a kt < 0, ior neither 0 nor >= 1 (the message names the
+ * first such triangle; the table stays as it was) or the scene has 2^29 triangles or more (bit 29 of a triangle index marks a
+ * transmitted bounce in the kernels' path history, beside bit 30 for every specular bounce). */
+int sphip_set_dielectric(sphip_t* ctx, const float* glass);
+/* The same from a device pointer, by the rules of sphip_set_specular_device: single-device contexts (SPHIP_E_STATE otherwise), ordered
+ * by `stream` alone, and copied.  It does NOT validate the values: a table that breaks the rules above gives undefined images (never
+ * out-of-bounds accesses: the table is indexed by triangle alone). */
+int sphip_set_dielectric_device(sphip_t* ctx, const void* d_glass, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

@@ -21,6 +21,7 @@ FLAG_MIS = 0x800            # with FLAG_NEE: multiple importance sampling of its
 FLAG_CAMERA_SAMPLES = 0x1000  # per-sample camera rays on the camera paths: pixel antialiasing, thin lens
 FLAG_SPECULAR = 0x2000      # mirror and mixed diffuse/mirror materials from the context's specular table
 FLAG_SMOOTH = 0x4000        # smooth shading by the context's per-vertex normals
+FLAG_DIELECTRIC = 0x8000    # transparency: glass triangles from the context's dielectric table
 
 
 def flag_chunks(n: int) -> int:
@@ -42,6 +43,7 @@ SYMBOLS = (
     "sphip_set_lens", "sphip_camera_rays_device",
     "sphip_set_specular", "sphip_set_specular_device",
     "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
+    "sphip_set_dielectric", "sphip_set_dielectric_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -204,6 +206,10 @@ def load():
     L.sphip_set_vertex_normals.argtypes = [vp, vp]
     L.sphip_set_vertex_normals_device.restype = C.c_int
     L.sphip_set_vertex_normals_device.argtypes = [vp, vp, vp]
+    L.sphip_set_dielectric.restype = C.c_int
+    L.sphip_set_dielectric.argtypes = [vp, vp]
+    L.sphip_set_dielectric_device.restype = C.c_int
+    L.sphip_set_dielectric_device.argtypes = [vp, vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -348,6 +354,18 @@ class Context:
             raise ValueError("one row of vertex normals per triangle of the scene")
         self._check(self._L.sphip_set_vertex_normals(self._h, vn.ctypes.data), "sphip_set_vertex_normals")
 
+    def set_dielectric(self, glass):
+        """sphip_set_dielectric: the dielectric table of FLAG_DIELECTRIC renders, (n_tris, 4) f32 rows kt.r, kt.g, kt.b, ior for the
+        scene last set (scene.dielectric_table builds one); None clears it.  Every set_scene clears it too."""
+        import numpy as np
+        if glass is None:
+            self._check(self._L.sphip_set_dielectric(self._h, None), "sphip_set_dielectric")
+            return
+        glass = np.ascontiguousarray(glass, dtype=np.float32).reshape(-1, 4)
+        if glass.shape[0] != getattr(self, "_n_tris", glass.shape[0]):
+            raise ValueError("one dielectric row per triangle of the scene")
+        self._check(self._L.sphip_set_dielectric(self._h, glass.ctypes.data), "sphip_set_dielectric")
+
     def render(self, rays, w, h, n_samples, seed=1, mode=MODE_PT, flags=0, want_accum=False):
         import numpy as np
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
@@ -371,6 +389,10 @@ class Context:
     def set_vertex_normals_device(self, d_vn: int, stream: int = 0):
         """sphip_set_vertex_normals_device: the normals from a device pointer (n_tris * 9 f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_vertex_normals_device(self._h, d_vn, stream), "sphip_set_vertex_normals_device")
+
+    def set_dielectric_device(self, d_glass: int, stream: int = 0):
+        """sphip_set_dielectric_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_dielectric_device(self._h, d_glass, stream), "sphip_set_dielectric_device")
 
     def render_device(self, d_rays: int, n_rays: int, n_samples: int, d_out_rgba: int, *, seed=1, mode=MODE_PT,
                       flags=0, shard=None, image_width=0, d_out_accum: int = 0, stream: int = 0):
@@ -507,7 +529,7 @@ class Context:
         return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
-                    7: ("float32", 6)}
+                    7: ("float32", 6), 8: ("float32", 6)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""

@@ -159,6 +159,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	constexpr bool smo = IsNorm<Acc...>::value;        // smooth shading (sp_integrator.h NormArgs): ns of shade_normal shades, n guards
 	static_assert(!smo || mis || !nee, "smooth shading: plain or NEE|MIS (DESIGN.md section 5.8)");
+	constexpr bool gls = IsGlass<Acc...>::value;       // transparency (sp_integrator.h GlassArgs, in SpecArgs' place): kTransBit beside kSpecBit
+	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	uint32_t my_scans = 0;
@@ -201,7 +203,12 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
 					bool sl = false;                              // specular: this hit takes the mirror lobe
 					float pm = 0.0f;
-					if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
+					float gi = 0.0f;                              // transparency: the triangle's ior; > 0: an interface, a specular hit
+					if constexpr (gls) {
+						gi = glass_table(acc_args...)[bi].w;
+						if (gi > 0.0f) sl = true;
+						else { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
+					} else if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
 					if constexpr (mis) {
 						f3 wd, Lc; float tm;
 						const f3 x = add3(o, scale3(dir, bd));
@@ -229,7 +236,9 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						}
 					}
 					f3 nd;
-					if (spc && sl) {
+					bool tr = false;                              // transparency: the bounce is a transmission
+					if (gls && gi > 0.0f) { tr = glass_bounce(a, pixel, s0 + s, depth, bi, gi, dir, ns, sm, nd, ended); hcos[depth] = 0.0f; }
+					else if (spc && sl) {
 						nd = spec_reflect(dir, ns); hcos[depth] = 0.0f;
 						if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
 					} else {
@@ -240,6 +249,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						if constexpr (smo) ended = sm && dot3(nd, n) < 0.0f;
 					}
 					hidx[depth] = spc && sl ? bi | kSpecBit : bi;
+					if constexpr (gls) if (tr) hidx[depth] |= kTransBit;
 					o = add3(o, scale3(dir, bd));
 					dir = nd;
 					src = bi;
@@ -254,13 +264,14 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 #pragma unroll
 		for (int depth = 4; depth >= 0; --depth) {
 			if (depth < nh) {
-				const int id = spc ? hidx[depth] & ~kSpecBit : hidx[depth];
+				const int id = spc ? hidx[depth] & hmask : hidx[depth];
 				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = hD[depth];
 				else if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
-				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hidx[depth] & kSpecBit) != 0, e, brdf, rec, hcos[depth]);
+				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hidx[depth], e, brdf, rec, hcos[depth]);
+				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hidx[depth] & kSpecBit) != 0, e, brdf, rec, hcos[depth]);
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
 			}
 		}

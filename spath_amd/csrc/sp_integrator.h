@@ -118,6 +118,17 @@ struct SpecArgs {
 constexpr uint32_t kSpecStream = 32u;
 constexpr int kSpecBit = 0x40000000;
 
+// transparency (SPHIP_FLAG_DIELECTRIC, include/spath_hip.h): the scene's dielectric table, one float4 per
+// triangle: kt.r kt.g kt.b ior; ior = 0 leaves the triangle what it is.  It rides IN SpecArgs' PLACE (as MisArgs rides in NeeArgs'):
+// k_pt<V, MisArgs, GlassArgs, NormArgs, CamArgs>, ...; spec is the scene's specular table, or a table of zeros when
+// SPHIP_FLAG_SPECULAR is not set (p = 0, wD = 1.0f: the diffuse arithmetic's bits).  A hit on a dielectric triangle is a specular
+// hit (kSpecBit) whose lobe is drawn from the same stream kSpecStream + d against the Fresnel reflectance; a transmitted bounce
+// carries kTransBit as well (triangle indices stay below 2^29: sphip_set_dielectric checks it).
+struct GlassArgs : SpecArgs {
+	const float4* glass;       // n_tris
+};
+constexpr int kTransBit = 0x20000000;
+
 // smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
 // n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
 // CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
@@ -131,7 +142,10 @@ template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHa
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
-template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value; };
+template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value; };
+template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value || IsGlass<Acc...>::value; };
+// what clears the marks of the path history from a triangle index
+template <typename... Acc> struct HistMask { static constexpr int value = IsGlass<Acc...>::value ? ~(kSpecBit | kTransBit) : ~kSpecBit; };
 template <typename... Acc> struct IsNorm { static constexpr bool value = PackHas<NormArgs, Acc...>::value; };
 // a running sum rides in the pack (progressive or adaptive)
 template <typename... Acc> struct HasAccum { static constexpr bool value = PackHas<AccumArgs, Acc...>::value || IsAdapt<Acc...>::value; };
@@ -146,6 +160,7 @@ template <typename... P> SP_DEV const AccumArgs& accum_args(const P&... p) { ret
 template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return pack_get<NeeArgs>(p...); }
 template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
 template <typename... P> SP_DEV const float4* spec_table(const P&... p) { return pack_get<SpecArgs>(p...).spec; }
+template <typename... P> SP_DEV const float4* glass_table(const P&... p) { return pack_get<GlassArgs>(p...).glass; }
 template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
@@ -282,6 +297,52 @@ SP_DEV f3 spec_reflect(f3 dir, f3 n) {
 SP_DEV f3 spec_unwind(const float4 q, bool sl, f3 e, f3 brdf, f3 rec, float ct) {
 	if (sl) return add3(e, scale3(mul3(mk3(q.x, q.y, q.z), rec), 1.0f / q.w));
 	return add3(e, scale3(scale3(scale3(mul3(brdf, rec), ct), kInvP), 1.0f / (1.0f - q.w)));
+}
+
+// ---- transparency (include/spath_hip.h "transparency"): Snell and Fresnel at a smooth interface of index ior
+// for the ray dir and the shading normal ns (turned against dir); entering: the ray comes from the vacuum side.  f32, every operation
+// rounded on its own.  Fr: the unpolarised reflectance; tir: total internal reflection (Fr and nt then mean nothing); nt: the
+// refracted direction, not renormalised; c = dot3(dir, ns)
+SP_DEV void dielectric(f3 dir, f3 ns, float ior, bool entering, float& Fr, bool& tir, f3& nt, float& c) {
+	const float eta = entering ? 1.0f / ior : ior;
+	c = dot3(dir, ns);
+	const float ci = -c;
+	const float k = 1.0f - (eta * eta) * (1.0f - ci * ci);
+	tir = !(k > 0.0f);
+	const float ct = __builtin_sqrtf(k);
+	const float a = eta * ci, b = eta * ct;
+	const float rs = (a - ct) / (a + ct), rp = (ci - b) / (ci + b);
+	Fr = 0.5f * (rs * rs + rp * rp);
+	nt = add3(scale3(dir, eta), scale3(ns, a - ct));
+}
+// the bounce of the hit of depth d on dielectric triangle bi (ior > 0): the lobe is drawn from the specular lobe's stream (that
+// lobe is not drawn on such a triangle), transmit iff !tir and (double)Fr <= r7 (a NaN Fr reflects).  sm: the hit is smooth
+// (shade_normal); the path then ends when dir is not against ns, when a reflection goes below the stored normal (the mirror's rule)
+// or when a transmission stays above it.  Returns whether the bounce is a transmission
+SP_DEV bool glass_bounce(const KArgs& a, uint32_t pixel, uint32_t sample, int depth, int bi, float ior, f3 dir, f3 ns, bool sm, f3& nd, bool& ended) {
+	const float* tn = a.tris + (size_t)bi * 12 + 9;
+	f3 n = mk3(tn[0], tn[1], tn[2]);
+	const bool entering = !(dot3(n, dir) > 0.0f);
+	if (!entering) n = scale3(n, -1.0f);
+	float Fr, c;
+	bool tir;
+	f3 nt;
+	dielectric(dir, ns, ior, entering, Fr, tir, nt, c);
+	double r7, r8;
+	philox_uniforms(a.seed, pixel, sample, kSpecStream + (uint32_t)depth, &r7, &r8);
+	const bool tr = !tir && (double)Fr <= r7;
+	nd = tr ? nt : spec_reflect(dir, ns);
+	const bool below = dot3(nd, n) < 0.0f;
+	ended = sm && (!(c < 0.0f) || (tr ? !below : below));
+	return tr;
+}
+// one step of the unwind with a dielectric table: E + rec after a reflection at an interface, E + kt * rec after a transmission,
+// spec_unwind's step at every other triangle.  id: the history's index with its marks
+SP_DEV f3 glass_unwind(const float4* __restrict__ glass, const float4* __restrict__ spec, int id, f3 e, f3 brdf, f3 rec, float ct) {
+	const int i = id & ~(kSpecBit | kTransBit);
+	const float4 g = glass[i];
+	if (g.w > 0.0f) return (id & kTransBit) ? add3(e, mul3(mk3(g.x, g.y, g.z), rec)) : add3(e, rec);
+	return spec_unwind(spec[i], (id & kSpecBit) != 0, e, brdf, rec, ct);
 }
 
 // ---- what the kernels share around the integrator: each is used where the kernel keeps its instructions with it (DESIGN.md

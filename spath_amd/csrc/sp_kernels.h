@@ -197,6 +197,19 @@ __global__ void __launch_bounds__(256) k_selftest_shade(const float* __restrict_
 	w[0] = uv[0]; w[1] = uv[1]; w[2] = ns.x; w[3] = ns.y; w[4] = ns.z; w[5] = sm ? 1.0f : 0.0f;
 }
 
+// what 8: dielectric.  dir ns ior entering(0/1) -> Fr tir(0/1) nt.xyz c
+__global__ void __launch_bounds__(256) k_selftest_glass(const float* __restrict__ in, uint32_t n, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const float* q = in + 8 * (size_t)i;
+	float Fr, c;
+	bool tir;
+	f3 nt;
+	dielectric(mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), q[6], q[7] != 0.0f, Fr, tir, nt, c);
+	float* w = out + 6 * (size_t)i;
+	w[0] = Fr; w[1] = tir ? 1.0f : 0.0f; w[2] = nt.x; w[3] = nt.y; w[4] = nt.z; w[5] = c;
+}
+
 SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	const uint64_t t = (uint64_t)k / a.tile_px;
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
@@ -335,6 +348,9 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	constexpr bool smo = IsNorm<Acc...>::value;                  // smooth shading (NormArgs): ns of shade_normal shades, n guards
 	static_assert(!smo || ((mis || !nee) && VARIANT == 1), "smooth shading: plain or NEE|MIS, variant 1 (DESIGN.md section 5.8)");
+	constexpr bool gls = IsGlass<Acc...>::value;                 // transparency (GlassArgs, in SpecArgs' place): kTransBit beside kSpecBit
+	static_assert(!gls || VARIANT == 1, "transparency: variant 1 (DESIGN.md section 5.10)");
+	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
 	const bool reuse = !cam && (a.flags & 0x100u) != 0;          // the host rejects reuse with camera samples
@@ -390,7 +406,12 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
 				bool sl = false;                                  // specular: this hit takes the mirror lobe
 				float pm = 0.0f;
-				if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
+				float gi = 0.0f;                                  // transparency: the triangle's ior; > 0: an interface, a specular hit
+				if constexpr (gls) {
+					gi = glass_table(acc_args...)[bi].w;
+					if (gi > 0.0f) sl = true;
+					else { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
+				} else if constexpr (spc) { pm = spec_table(acc_args...)[bi].w; sl = spec_lobe(a.seed, pixel, s0 + s, depth, pm); }
 				if constexpr (mis) {
 					if (depth == 0 || (spc && pspec)) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
 					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
@@ -400,7 +421,9 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
 				f3 nd;
 				float ct = 0.0f;
-				if (spc && sl) {
+				bool tr = false;                                  // transparency: the bounce is a transmission
+				if (gls && gi > 0.0f) tr = glass_bounce(a, pixel, s0 + s, depth, bi, gi, dir, ns, sm, nd, ended);
+				else if (spc && sl) {
 					nd = spec_reflect(dir, ns);
 					if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
 				} else {
@@ -414,6 +437,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				dir = nd;
 				src = bi;
 				if constexpr (spc) { pspec = sl; if (sl) bi |= kSpecBit; }
+				if constexpr (gls) if (tr) bi |= kTransBit;
 				if (depth == 0) { idx0 = bi; c0 = ct; }
 				else if (depth == 1) { idx1 = bi; c1 = ct; }
 				else if (depth == 2) { idx2 = bi; c2 = ct; }
@@ -445,7 +469,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			const int id = depth == 0 ? idx0 : depth == 1 ? idx1 : depth == 2 ? idx2 : depth == 3 ? idx3 : idx4;
 			const float ct = depth == 0 ? c0 : depth == 1 ? c1 : depth == 2 ? c2 : depth == 3 ? c3 : c4;
 			if (id >= 0) {
-				const float* m = a.mats + (size_t)(spc ? id & ~kSpecBit : id) * 6;
+				const float* m = a.mats + (size_t)(spc ? id & hmask : id) * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                     // :63
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = depth == 0 ? D0 : depth == 1 ? D1 : depth == 2 ? D2 : depth == 3 ? D3 : D4;   // D_d
@@ -453,7 +477,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 					if (depth > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, depth == 0 ? L0 : depth == 1 ? L1 : depth == 2 ? L2 : L3);
 				}
-				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id & ~kSpecBit], (id & kSpecBit) != 0, e, brdf, rec, ct);
+				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), id, e, brdf, rec, ct);
+				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id & ~kSpecBit], (id & kSpecBit) != 0, e, brdf, rec, ct);
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), ct), kInvP));            // :67
 			}
 		}

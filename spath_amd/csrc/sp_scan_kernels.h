@@ -119,6 +119,9 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	static_assert(!spc || mis || !nee, "specular reflection: plain or NEE|MIS (DESIGN.md section 5.7)");
 	constexpr bool smo = IsNorm<Acc...>::value;              // smooth shading (sp_integrator.h NormArgs)
 	static_assert(!smo || ((mis || !nee) && SCAN >= 3), "smooth shading: plain or NEE|MIS, the default scan (DESIGN.md section 5.8)");
+	constexpr bool gls = IsGlass<Acc...>::value;             // transparency (sp_integrator.h GlassArgs, in SpecArgs' place)
+	static_assert(!gls || SCAN >= 3, "transparency: the default scan (DESIGN.md section 5.10)");
+	constexpr int hmask = HistMask<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
@@ -232,6 +235,9 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 								if (depth > 0) full = (hist[(size_t)(depth - 1) * n_work + k0 + r * B].x & kSpecBit) != 0;
 								const float pm = spec_table(acc_args...)[bi[r]].w;
 								slr[r] = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, pm);
+								// an interface is a specular hit whatever its row of the specular table: no light sample; its own lobe is drawn
+								// after the shadow scan
+								if constexpr (gls) if (glass_table(acc_args...)[bi[r]].w > 0.0f) slr[r] = true;
 								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc);
 								if constexpr (smo) sh.act[r] = sh.act[r] && smooth_light_ok(smr[r], wd, n);
 								if (sh.act[r]) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
@@ -295,10 +301,16 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 							ct = dot3(nd, nadj[r]);
 							if constexpr (smo) ended = smr[r] && dot3(nd, ng) < 0.0f;
 						}
+						bool tr = false;                             // transparency: the bounce is a transmission
+						if constexpr (gls) {                         // an interface took the mirror's branch above (ct = 0): its bounce replaces the mirror's
+							const float gi = glass_table(acc_args...)[sh.src[r]].w;
+							if (gi > 0.0f) tr = glass_bounce(a, pixel[r], s0 + smp[r], depth, sh.src[r], gi, s.dir[r], nadj[r], smr[r], nd, ended);
+						}
 						s.o[r] = sh.o[r];
 						s.dir[r] = nd;
 						s.src[r] = sh.src[r];
-						hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && slr[r] ? sh.src[r] | kSpecBit : sh.src[r], (int)__float_as_uint(ct));
+						if constexpr (gls) hist[(size_t)depth * n_work + k0 + r * B] = make_int2(sh.src[r] | (slr[r] ? kSpecBit : 0) | (tr ? kTransBit : 0), (int)__float_as_uint(ct));
+						else hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && slr[r] ? sh.src[r] | kSpecBit : sh.src[r], (int)__float_as_uint(ct));
 						nh[r] = depth + 1;
 					}
 					s.act[r] = hitr[r] && !ended;
@@ -317,10 +329,16 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					bool sm = false;
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
 					bool sl = false;
-					if constexpr (spc) sl = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, spec_table(acc_args...)[bi[r]].w);
+					float gi = 0.0f;                             // transparency: the triangle's ior; > 0: an interface, a specular hit
+					if constexpr (gls) {
+						gi = glass_table(acc_args...)[bi[r]].w;
+						sl = gi > 0.0f || spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, spec_table(acc_args...)[bi[r]].w);
+					} else if constexpr (spc) sl = spec_lobe(a.seed, pixel[r], s0 + smp[r], depth, spec_table(acc_args...)[bi[r]].w);
 					f3 nd;
 					float ct = 0.0f;
-					if (spc && sl) {
+					bool tr = false;                             // transparency: the bounce is a transmission
+					if (gls && gi > 0.0f) tr = glass_bounce(a, pixel[r], s0 + smp[r], depth, bi[r], gi, s.dir[r], ns, sm, nd, ended);
+					else if (spc && sl) {
 						nd = spec_reflect(s.dir[r], ns);
 						if constexpr (smo) ended = sm && (!(dot3(s.dir[r], ns) < 0.0f) || dot3(nd, n) < 0.0f);
 					} else {
@@ -333,7 +351,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					s.o[r] = add3(s.o[r], scale3(s.dir[r], bd[r]));
 					s.dir[r] = nd;
 					s.src[r] = bi[r];
-					hist[(size_t)depth * n_work + k0 + r * B] = make_int2(spc && sl ? bi[r] | kSpecBit : bi[r], (int)__float_as_uint(ct));
+					hist[(size_t)depth * n_work + k0 + r * B] = make_int2((spc && sl ? bi[r] | kSpecBit : bi[r]) | (gls && tr ? kTransBit : 0), (int)__float_as_uint(ct));
 					nh[r] = depth + 1;
 				}
 				s.act[r] = hit && !ended;
@@ -345,7 +363,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			f3 rec = mk3(0.0f, 0.0f, 0.0f);
 			for (int d = nh[r] - 1; d >= 0; --d) {
 				const int2 hc = hist[(size_t)d * n_work + kw];
-				const int id = spc ? hc.x & ~kSpecBit : hc.x;
+				const int id = spc ? hc.x & hmask : hc.x;
 				const float* m = a.mats + (size_t)id * 6;
 				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
@@ -357,7 +375,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					if (d > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]));
 				}
-				if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hc.x & kSpecBit) != 0, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
+				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hc.x, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
+				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hc.x & kSpecBit) != 0, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), __uint_as_float((uint32_t)hc.y)), kInvP));
 			}
 			// cpu_renderer.cpp:75 accum += sample, in sample order: with SPLIT the slots are consecutive samples of one

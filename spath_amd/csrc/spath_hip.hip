@@ -114,6 +114,10 @@ struct sphip_ctx {
 	// ---- smooth shading (SPHIP_FLAG_SMOOTH): the scene's vertex normals, 9 floats per triangle, kept and dropped like the specular table
 	DevBuf vnorm;
 	bool have_vnorm = false;
+	// ---- transparency (SPHIP_FLAG_DIELECTRIC): the scene's dielectric table, 4 floats per triangle, kept and dropped like the specular
+	// table, and the table of zeros that stands in for the specular table when SPHIP_FLAG_SPECULAR is not set (sized with the scene)
+	DevBuf glass, spec_zero;
+	bool have_glass = false;
 };
 
 namespace {
@@ -219,6 +223,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->nee_valid = false;
 	c->have_spec = false;                          // the specular table belongs to the old scene
 	c->have_vnorm = false;                         // and so do the vertex normals
+	c->have_glass = false;                         // and the dielectric table
 	return SPHIP_OK;
 }
 
@@ -422,7 +427,7 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
+               const sp::GlassArgs* gls, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
 			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
@@ -434,6 +439,7 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
 				last();
 			};
+			if constexpr (tables) { if (gls) { tail(*gls); return; } }      // the dielectric table carries the specular one
 			if constexpr (tables) { if (spc) { tail(*spc); return; } }
 			tail();
 		};
@@ -489,6 +495,7 @@ int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_
 struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; };
 const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_shipped, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
 const TableRule kSmoothRule{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" };
+const TableRule kGlassRule{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" };
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
 	if (mode == SPHIP_MODE_FLAT) return fail(c, SPHIP_E_INVALID, "%s is valid for SPHIP_MODE_PT only", r.flag);
@@ -572,11 +579,16 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ne.W = c->nee_W;
 	}
 	if ((rc = check_camera_rule(c, flags, variant, mode, cams != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, variant, mode)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode))) return rc;
+	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode)) || (rc = check_table_rule(c, kGlassRule, flags, variant, mode))) return rc;
 	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) cams = nullptr;
 	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR), smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
 	const sp::SpecArgs spa{ (const float4*)c->spec.p };
 	const sp::NormArgs nra{ (const float*)c->vnorm.p };
+	// transparency: the dielectric table in the specular table's place, with that table or, without SPHIP_FLAG_SPECULAR, the zeros
+	const bool glassf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_DIELECTRIC);
+	sp::GlassArgs gla{};
+	gla.spec = (const float4*)(specf ? c->spec.p : c->spec_zero.p);
+	gla.glass = (const float4*)c->glass.p;
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -688,7 +700,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
 	}
 	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
-	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf ? &spa : nullptr, smoothf ? &nra : nullptr, cams, f); };
+	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf && !glassf ? &spa : nullptr, glassf ? &gla : nullptr, smoothf ? &nra : nullptr, cams, f); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
@@ -719,7 +731,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 				// smooth shading for the default scan's two shapes
 				if constexpr ((S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value ||
 				                               sp::IsSpec<std::decay_t<decltype(p)>...>::value)) &&
-				              (S::SCAN >= 3 || !sp::IsNorm<std::decay_t<decltype(p)>...>::value))
+				              (S::SCAN >= 3 || !(sp::IsNorm<std::decay_t<decltype(p)>...>::value || sp::IsGlass<std::decay_t<decltype(p)>...>::value)))
 					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
 					                   a, src2, bnd, hist, acc, n_work, p...);
 			});
@@ -727,7 +739,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	} else {
 		with_exact([&](auto v) {
 			pt_pack([&](const auto&... p) {
-				if constexpr (decltype(v)::value == 1 || !sp::IsNorm<std::decay_t<decltype(p)>...>::value)   // smooth shading: variant 1 only (checked above)
+				if constexpr (decltype(v)::value == 1 || !(sp::IsNorm<std::decay_t<decltype(p)>...>::value || sp::IsGlass<std::decay_t<decltype(p)>...>::value))   // smooth shading, transparency: variant 1 only (checked above)
 					hipLaunchKernelGGL((sp::k_pt<decltype(v)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, p...);
 			});
 		});
@@ -913,6 +925,7 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	c->have_scene = true;
 	c->have_spec = false;
 	c->have_vnorm = false;
+	c->have_glass = false;
 	return SPHIP_OK;
 }
 
@@ -1243,7 +1256,7 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	const int v = pick_variant(flags, c->n_tris);
 	int rc;
 	if ((rc = check_camera_rule(c, flags, v, SPHIP_MODE_PT, cam != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, v, SPHIP_MODE_PT)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT))) return rc;
+	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT)) || (rc = check_table_rule(c, kGlassRule, flags, v, SPHIP_MODE_PT))) return rc;
 	if (!c->kids.empty()) {
 		if ((rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr))) return rc;
 	} else {
@@ -1721,6 +1734,51 @@ int sphip_set_vertex_normals_device(sphip_t* c, const void* d_vn, void* stream) 
 	return set_tri_table(c, c->vnorm, c->have_vnorm, d_vn, 36, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
 }
 
+// the first row of a dielectric table that breaks the rules (finite, kt >= 0, ior 0 or >= 1), or n_tris
+static size_t glass_first_bad(const float* g, size_t n_tris) {
+	for (size_t i = 0; i < n_tris; ++i) {
+		const float* q = g + i * 4;
+		for (int k = 0; k < 4; ++k) if (!std::isfinite(q[k]) || !(q[k] >= 0.0f)) return i;
+		if (q[3] != 0.0f && !(q[3] >= 1.0f)) return i;
+	}
+	return n_tris;
+}
+
+// the zeros that stand in for the specular table of a dielectric render without SPHIP_FLAG_SPECULAR: one row per triangle
+static int ensure_spec_zero(sphip_ctx* c, hipStream_t st) {
+	HIP_TRY(c, hipSetDevice(c->device));
+	if (const int rc = ensure(c, c->spec_zero, c->n_tris * 16)) return rc;
+	HIP_TRY(c, hipMemsetAsync(c->spec_zero.p, 0, c->n_tris * 16, st));
+	return SPHIP_OK;
+}
+
+int sphip_set_dielectric(sphip_t* c, const float* glass) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric called before a scene was set");
+	if (glass) {
+		// kTransBit marks a transmitted bounce in the path history: triangle indices must stay below it
+		if (c->n_tris >= (size_t)sp::kTransBit) return fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris);
+		const size_t bad = glass_first_bad(glass, c->n_tris);
+		if (bad < c->n_tris) {
+			const float* q = glass + bad * 4;
+			return fail(c, SPHIP_E_INVALID, "dielectric table: triangle %zu has {kt %g %g %g, ior %g} (every value finite, kt >= 0, ior 0 or >= 1)", bad,
+			            (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
+		}
+	}
+	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_glass, sphip_set_dielectric, glass);
+	if (glass) if (const int rc = ensure_spec_zero(c, c->own_stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
+	return set_tri_table(c, c->glass, c->have_glass, glass, 16, hipMemcpyHostToDevice, c->own_stream, true);
+}
+
+int sphip_set_dielectric_device(sphip_t* c, const void* d_glass, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric_device called before a scene was set");
+	const bool big = d_glass && c->n_tris >= (size_t)sp::kTransBit;    // refused, and like every call it leaves no table behind
+	if (d_glass && !big) if (const int rc = ensure_spec_zero(c, (hipStream_t)stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
+	const int rc = set_tri_table(c, c->glass, c->have_glass, big ? nullptr : d_glass, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return big ? fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris) : rc;
+}
+
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
                         size_t n_samples, uint64_t seed, int mode, int flags, void* d_out_rgba, void* d_out_accum, void* stream) {
 	if (const int rc = single_device_entry(c)) return rc;
@@ -1906,8 +1964,8 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[8] = { 4, 4, 20, 40, 60, 12, 48, 96 }, out_b[8] = { 8, 4, 16, 12, 4, 4, 8, 24 };
-	if (what < 0 || what > 7 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[9] = { 4, 4, 20, 40, 60, 12, 48, 96, 32 }, out_b[9] = { 8, 4, 16, 12, 4, 4, 8, 24, 24 };
+	if (what < 0 || what > 8 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
 	HIP_TRY(c, hipSetDevice(k->device));
 	void *d_in = nullptr, *d_out = nullptr;
@@ -1915,7 +1973,8 @@ int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* 
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 7) hipLaunchKernelGGL(sp::k_selftest_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
+		if (what == 8) hipLaunchKernelGGL(sp::k_selftest_glass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
+		else if (what == 7) hipLaunchKernelGGL(sp::k_selftest_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 6) hipLaunchKernelGGL(sp::cylm256::k_selftest_cylm, dim3((unsigned)n), dim3(64), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else hipLaunchKernelGGL(sp::k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, what, (const void*)d_in, (uint32_t)n, d_out);
 		e = hipGetLastError();

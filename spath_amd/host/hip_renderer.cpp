@@ -57,6 +57,8 @@ struct hip_r : public basic_renderer {
 	std::vector<float> spec;
 	// smooth shading (set_vertex_normals): likewise, 9 floats per triangle and SPHIP_FLAG_SMOOTH
 	std::vector<float> vnorm;
+	// transparency (set_dielectric): likewise, 4 floats per triangle and SPHIP_FLAG_DIELECTRIC
+	std::vector<float> glass;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
@@ -101,10 +103,15 @@ struct hip_r : public basic_renderer {
 			if (vnorm.size() != n_tris * 9) throw std::runtime_error("hip_renderer: the vertex normals and the scene differ in size");
 			h = fnv(vnorm.data(), vnorm.size() * sizeof(float), h);
 		}
+		if (!glass.empty()) {
+			if (glass.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the dielectric table and the scene differ in size");
+			h = fnv(glass.data(), glass.size() * sizeof(float), h);
+		}
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
 			if (!spec.empty()) check(sphip_set_specular(ctx, spec.data()), "set_specular");
 			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
+			if (!glass.empty()) check(sphip_set_dielectric(ctx, glass.data()), "set_dielectric");
 			scene_hash = h; scene_n = n_tris;
 		}
 	}
@@ -176,7 +183,7 @@ struct hip_r : public basic_renderer {
 
 	int table_flags(const int mode) const {              // the flags of the tables that are set
 		if (mode != SPHIP_MODE_PT) return 0;
-		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0);
+		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0);
 	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
@@ -271,6 +278,14 @@ namespace hip_renderer {
 		if (!p) return;
 		if (spec && n_tris) p->spec.assign(spec, spec + n_tris * 4);
 		else p->spec.clear();
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+	}
+
+	void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (glass && n_tris) p->glass.assign(glass, glass + n_tris * 4);
+		else p->glass.clear();
 		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
 	}
 

@@ -45,6 +45,11 @@ namespace hip_renderer {
 	// (render_flat is unchanged).  NULL or n_tris = 0 removes them.  Normals the library refuses make the next frame throw
 	// std::runtime_error, as do ones whose size differs from the scene's.  Changing them begins a new progressive accumulation.
 	extern void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris);
+	// transparency (sphip_set_dielectric, SPHIP_FLAG_DIELECTRIC; include/spath_hip.h "transparency"): a table of n_tris rows
+	// kt.r kt.g kt.b ior (copied) beside the materials of the scenes rendered next; while one is set, path-traced frames refract by it
+	// (render_flat is unchanged).  NULL or n_tris = 0 removes it.  A table the library refuses makes the next frame throw
+	// std::runtime_error, as does one whose size differs from the scene's.  Changing it begins a new progressive accumulation.
+	extern void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -23,6 +23,8 @@
 //   ('SPSP', n, n x {ks.r ks.g ks.b p} f32: spath_amd/scene.py write_specular); path tracing only, not with --nee without --mis
 // --normals FILE.bin: smooth shading (SPHIP_FLAG_SMOOTH) by the vertex normals in FILE.bin, a file of its own beside the scene file
 //   ('SPVN', n, n x {n0.xyz n1.xyz n2.xyz} f32: spath_amd/scene.py write_vertex_normals); path tracing only, not with --nee without --mis
+// --glass FILE.bin: transparency (SPHIP_FLAG_DIELECTRIC) by the dielectric table in FILE.bin, a file of its own beside the scene file
+//   ('SPDI', n, n x {kt.r kt.g kt.b ior} f32: spath_amd/scene.py write_dielectric); path tracing only, not with --nee without --mis
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
 #include "hip_renderer.h"
 #include "spath_hip.h"
@@ -151,12 +153,13 @@ bool load_table(const char* path, uint32_t magic, size_t row, std::vector<float>
 }
 bool load_specular(const char* path, std::vector<float>& spec) { return load_table(path, 0x50535053u, 4, spec); }
 bool load_normals(const char* path, std::vector<float>& vn) { return load_table(path, 0x4E565053u, 9, vn); }
+bool load_dielectric(const char* path, std::vector<float>& glass) { return load_table(path, 0x49445053u, 4, glass); }
 
 } // namespace
 
 int main(int argc, char** argv) {
 	try {
-		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg;
+		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg;
 		bool device_viewport = false;
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
@@ -179,6 +182,7 @@ int main(int argc, char** argv) {
 			if (k == "--scene") { need(1); scene_arg = argv[++i]; }
 			else if (k == "--spec") { need(1); spec_arg = argv[++i]; }
 			else if (k == "--normals") { need(1); normals_arg = argv[++i]; }
+			else if (k == "--glass") { need(1); glass_arg = argv[++i]; }
 			else if (k == "--w") { need(1); w = std::atoi(argv[++i]); }
 			else if (k == "--h") { need(1); h = std::atoi(argv[++i]); }
 			else if (k == "--spp") { need(1); spp = (size_t)std::atoll(argv[++i]); }
@@ -262,6 +266,12 @@ int main(int argc, char** argv) {
 			if (!load_normals(normals_arg.c_str(), vn)) throw std::runtime_error("cannot read vertex-normal file " + normals_arg);
 			if (vn.size() != tris.size() * 9) throw std::runtime_error("the vertex-normal file " + normals_arg + " and the scene differ in size");
 			hip_renderer::set_vertex_normals(r.get(), vn.data(), tris.size());
+		}
+		if (!glass_arg.empty()) {
+			std::vector<float> glass;
+			if (!load_dielectric(glass_arg.c_str(), glass)) throw std::runtime_error("cannot read dielectric file " + glass_arg);
+			if (glass.size() != tris.size() * 4) throw std::runtime_error("the dielectric file " + glass_arg + " and the scene differ in size");
+			hip_renderer::set_dielectric(r.get(), glass.data(), tris.size());
 		}
 		hip_renderer::set_lens(r.get(), lens_a, lens_f);
 		if (aa) device_viewport = true;                                  // camera samples live on the camera path

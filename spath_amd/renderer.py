@@ -102,6 +102,14 @@ class HipRenderer(BasicRenderer):
         self.last_stats = None
         self._spec = None
         self._vnorm = None
+        self._glass = None
+
+    def set_dielectric(self, glass):
+        """The dielectric table of capi.FLAG_DIELECTRIC renders ([n_tris, 4] float32, scene.dielectric_table; None: no table), like
+        hip_renderer::set_dielectric: it goes to the library with the next scene upload and begins a new accumulation, and while one
+        is set every path-traced frame carries capi.FLAG_DIELECTRIC (render_flat never does)."""
+        self._glass = None if glass is None else np.ascontiguousarray(glass, dtype=np.float32).reshape(-1, 4).copy()
+        self._scene_key = None
 
     def set_vertex_normals(self, vn):
         """The per-vertex normals of capi.FLAG_SMOOTH renders ([n_tris, 9] float32, scene.vertex_normals; None: none), like
@@ -118,10 +126,12 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR and FLAG_SMOOTH on while their tables are set, and never on the flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH and FLAG_DIELECTRIC on while their tables are set, and never on the
+        flat pass"""
         if mode == capi.MODE_FLAT:
-            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH)
+            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC)
         flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
+        flags = flags | capi.FLAG_DIELECTRIC if self._glass is not None else flags
         return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
 
     def get_description(self) -> str:
@@ -132,13 +142,15 @@ class HipRenderer(BasicRenderer):
         mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 6)[:n_tris]
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
         key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
-               None if self._vnorm is None else hash(self._vnorm.tobytes()))
+               None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
             if self._spec is not None:
                 self.ctx.set_specular(self._spec[:n_tris])
             if self._vnorm is not None:
                 self.ctx.set_vertex_normals(self._vnorm[:n_tris])
+            if self._glass is not None:
+                self.ctx.set_dielectric(self._glass[:n_tris])
             self._scene_key = key
 
     def _begin_rule(self):

@@ -19,6 +19,7 @@ F = np.float32
 SCENE_MAGIC = 0x43535053  # 'SPSC'
 SPEC_MAGIC = 0x50535053   # 'SPSP'
 VNORM_MAGIC = 0x4E565053  # 'SPVN'
+GLASS_MAGIC = 0x49445053  # 'SPDI'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -225,6 +226,33 @@ def write_specular(path, spec: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(struct.pack("<II", SPEC_MAGIC, spec.shape[0]))
         f.write(spec.tobytes())
+
+
+def dielectric_table(tris: np.ndarray, ior=1.5, kt=1.0, which=None) -> np.ndarray:
+    """A dielectric table for capi.Context.set_dielectric (include/spath_hip.h, "transparency"): float32 [N, 4] rows kt.r kt.g kt.b ior.
+    ior: the index of the dielectric behind the triangle's stored normal, a scalar or [N] (finite, >= 1); kt: the tint of what is
+    transmitted, a scalar, an rgb triple or an [N, 3] array (finite, >= 0); which: the triangles that get the row (an index array or
+    a boolean mask; None = all), every other row is zero (the triangle stays as it is)."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    n = t.shape[0]
+    sel = np.ones(n, bool) if which is None else np.zeros(n, bool)
+    if which is not None:
+        sel[np.asarray(which)] = True
+    g = np.zeros((n, 4), F)
+    g[:, 0:3] = np.broadcast_to(np.asarray(kt, F), (n, 3)) if np.ndim(kt) else F(kt)
+    g[:, 3] = np.broadcast_to(np.asarray(ior, F), (n,))
+    if not (np.isfinite(g).all() and (g[:, 0:3] >= 0).all() and (g[:, 3] >= 1).all()):
+        raise ValueError("dielectric table: every value finite, kt >= 0, ior >= 1")
+    g[~sel] = 0.0
+    return g
+
+
+def write_dielectric(path, glass: np.ndarray) -> None:
+    """Dielectric file read by the headless CLI (--glass), beside the scene file: 'SPDI', n, n * 4 float32."""
+    glass = np.ascontiguousarray(glass, dtype=F).reshape(-1, 4)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", GLASS_MAGIC, glass.shape[0]))
+        f.write(glass.tobytes())
 
 
 def vertex_normals(tris: np.ndarray, crease_deg: float = 180.0, which=None) -> np.ndarray:
