@@ -228,6 +228,31 @@ int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void
  * Blocking; host pointers; single-device contexts. */
 int sphip_selftest_stage1(sphip_t* ctx, const float* rays, size_t n_rays, uint32_t* out_words, uint32_t* out_tri, int32_t* out_order, uint32_t* tiles_out);
 
+/* TEST-ONLY: the code underneath the opt-in acceleration structure on its own (tests/test_hip_sort.py, tests/test_hip_bvh_build.py,
+ * tests/bvh_checks.py).  Blocking; host pointers; single-device contexts.  Additive: the ABI version does not change.
+ *
+ * sphip_selftest_sort: the context's own stable radix sort (4-bit digits; the one both the default scan's prepass and the BVH build call)
+ * on n caller (key, value) pairs by the low key_bits bits of the key (1..32, rounded up to a whole digit; higher bits are ignored).
+ * out_keys / out_vals [n]: the pairs in ascending key order, equal keys in input order.  Needs no scene and disturbs none.
+ *
+ * sphip_selftest_bvh_dump: builds the linear BVH of the context's scene if it is not built and copies it out.  *n_leaves_out: leaves of the
+ * complete tree (a power of two); call with the other outputs NULL first to size them (each may be NULL on its own):
+ *   out_meta  u32[16]                      the builder's words: [0..2] scene lo.xyz, [3..5] hi.xyz as ordered uints, [6] / [7] triangles wider than
+ *                                          1/4 / 1/2 of the scene, [8] n_big, [9..15] zero
+ *   out_nodes f32[2 * n_leaves][8]         heap order (root 1, children 2 i and 2 i + 1, leaf l at n_leaves + l): lo.xyz, hi.xyz, 0, 0; node 0 is
+ *                                          never written
+ *   out_rec   f32[4 * n_leaves + 256][12]  v0.xyz, e1.xyz, e2.xyz, 0, 0, 0 per slot: four slots per leaf in tree order, then the big list
+ *   out_idx   i32[4 * n_leaves + 256]      the slot's triangle, -1 for padding
+ *
+ * sphip_selftest_bvh_walk: the traversal the render kernels call (scan_bvh) on n_rays caller rays f32[n][6] against the context's scene.
+ * src_idx (may be NULL: none) i32[n] the triangle each ray leaves; tmax (may be NULL: unbounded) f32[n] only hits with d < tmax count;
+ * any_hit != 0: stop at the first such hit (the shadow form).  out_idx / out_d [n]: the hit, or -1 and the ray's tmax; out_steps [n]:
+ * steps of the walk, which ends unfinished when they reach 4 * n_leaves + 64; out_leaves [n]: leaves visited. */
+int sphip_selftest_sort(sphip_t* ctx, const uint32_t* keys, const uint32_t* vals, size_t n, uint32_t key_bits, uint32_t* out_keys, uint32_t* out_vals);
+int sphip_selftest_bvh_dump(sphip_t* ctx, uint32_t* n_leaves_out, uint32_t* out_meta, float* out_nodes, float* out_rec, int32_t* out_idx);
+int sphip_selftest_bvh_walk(sphip_t* ctx, const float* rays, size_t n_rays, const int32_t* src_idx, const float* tmax, int any_hit,
+                            int32_t* out_idx, float* out_d, uint32_t* out_steps, uint32_t* out_leaves);
+
 /* ---- progressive rendering: accumulate samples across calls while the view stands still.
  * The counter RNG is keyed by (seed, global pixel, sample index, depth), and samples are added to an f32 sum one at a time in
  * sample order, so after steps of n_1, n_2, ... samples the image (and the mean) is bit-identical to one render of

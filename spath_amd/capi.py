@@ -37,6 +37,7 @@ SYMBOLS = (
     "sphip_render_device", "sphip_closest_hit_device", "sphip_get_stats", "sphip_viewport_device", "sphip_render_camera",
     "sphip_create_multi", "sphip_device_count", "sphip_plan_tile_rows", "sphip_plan_shard", "sphip_selftest_device",
     "sphip_kernel_available", "sphip_selftest_stage1", "sphip_build_info",
+    "sphip_selftest_sort", "sphip_selftest_bvh_dump", "sphip_selftest_bvh_walk",
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
@@ -174,6 +175,13 @@ def load():
     if hasattr(L, "sphip_selftest_stage1"):
         L.sphip_selftest_stage1.restype = C.c_int
         L.sphip_selftest_stage1.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "sphip_selftest_sort"):
+        L.sphip_selftest_sort.restype = C.c_int
+        L.sphip_selftest_sort.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp]
+        L.sphip_selftest_bvh_dump.restype = C.c_int
+        L.sphip_selftest_bvh_dump.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp, vp, vp]
+        L.sphip_selftest_bvh_walk.restype = C.c_int
+        L.sphip_selftest_bvh_walk.argtypes = [vp, vp, sz, vp, vp, C.c_int, vp, vp, vp, vp]
     L.sphip_render_device_accum.restype = C.c_int
     L.sphip_render_device_accum.argtypes = [vp, vp, sz, C.POINTER(Shard), sz, C.c_uint64, sz, C.c_uint64, C.c_int, vp, vp, vp, vp]
     L.sphip_accum_begin.restype = C.c_int
@@ -539,6 +547,48 @@ class Context:
         out = np.zeros(n * k, dtype=dt)
         self._check(self._L.sphip_selftest_device(self._h, what, inp.ctypes.data, n, out.ctypes.data), "sphip_selftest_device")
         return out
+
+    def selftest_sort(self, keys, vals, key_bits=32):
+        """sphip_selftest_sort (test-only): the context's stable radix sort on caller (key, value) pairs -> (keys, vals) sorted."""
+        import numpy as np
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        assert keys.shape == vals.shape and keys.ndim == 1
+        ok, ov = np.zeros_like(keys), np.zeros_like(vals)
+        self._check(self._L.sphip_selftest_sort(self._h, keys.ctypes.data, vals.ctypes.data, keys.size, key_bits, ok.ctypes.data, ov.ctypes.data),
+                    "sphip_selftest_sort")
+        return ok, ov
+
+    def selftest_bvh_dump(self):
+        """sphip_selftest_bvh_dump (test-only): the linear BVH of the context's scene as built -> dict(n_leaves, meta u32[16],
+        nodes f32[2 n_leaves, 8] (row 0 is never written), rec f32[4 n_leaves + 256, 12], idx i32[4 n_leaves + 256])."""
+        import numpy as np
+        nl = C.c_uint32(0)
+        self._check(self._L.sphip_selftest_bvh_dump(self._h, C.byref(nl), None, None, None, None), "sphip_selftest_bvh_dump")
+        n = nl.value
+        meta = np.zeros(16, dtype=np.uint32)
+        nodes = np.zeros((2 * n, 8), dtype=np.float32)
+        rec = np.zeros((4 * n + 256, 12), dtype=np.float32)
+        idx = np.zeros(4 * n + 256, dtype=np.int32)
+        self._check(self._L.sphip_selftest_bvh_dump(self._h, C.byref(nl), meta.ctypes.data, nodes.ctypes.data, rec.ctypes.data, idx.ctypes.data),
+                    "sphip_selftest_bvh_dump")
+        assert nl.value == n
+        return {"n_leaves": n, "meta": meta, "nodes": nodes, "rec": rec, "idx": idx}
+
+    def selftest_bvh_walk(self, rays, src=None, tmax=None, any_hit=False):
+        """sphip_selftest_bvh_walk (test-only): the BVH traversal itself on caller rays -> (idx i32[n], d f32[n], steps u32[n], leaves u32[n])."""
+        import numpy as np
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        src = None if src is None else np.ascontiguousarray(src, dtype=np.int32)
+        tmax = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32)
+        assert (src is None or src.shape == (n,)) and (tmax is None or tmax.shape == (n,))
+        idx, d = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
+        steps, leaves = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._check(self._L.sphip_selftest_bvh_walk(self._h, rays.ctypes.data, n, None if src is None else src.ctypes.data,
+                                                    None if tmax is None else tmax.ctypes.data, int(bool(any_hit)), idx.ctypes.data, d.ctypes.data,
+                                                    steps.ctypes.data, leaves.ctypes.data), "sphip_selftest_bvh_walk")
+        return idx, d, steps, leaves
 
     def selftest_stage1(self, rays, per_triangle=True):
         """sphip_selftest_stage1 (test-only): stage 1 of the default scan alone for the given rays (padded to a multiple of 64)

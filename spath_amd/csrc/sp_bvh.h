@@ -13,7 +13,8 @@
 // Parity: the box test is conservative (boxes inflated, comparisons inclusive), so every GEOMETRIC hit the reference
 // finds is found with the same index and the same distance bits.  What a bounding-volume cull cannot reproduce are
 // the reference's noise accepts (a ray almost coplanar with a far-away triangle: a and s.h are both rounding noise and
-// u, v land in [0,1] by chance -- DESIGN.md section 8).  tests/test_hip_accel.py measures how rare those are.
+// u, v land in [0,1] by chance -- DESIGN.md section 8).  tests/test_hip_accel.py measures how rare those are;
+// tests/test_hip_bvh_walk.py holds every ray to the oracle and every difference to that explanation (float64 barycentrics outside).
 #pragma once
 
 #include "sp_kernels.h"
@@ -45,6 +46,9 @@ SP_DEV bool box_hit(const float4 a, const float4 b, f3 o, f3 inv, float tbest, f
 }
 
 // tmax < kMaxDist, any_hit: the shadow form -- only hits with d < tmax count, and the walk stops at the first one
+// (SELFTEST only gives the test kernel at the end of this file an instantiation of its own: the one the render kernels share then keeps
+// exactly its call sites, none of which asks for the counts, and their code does not move -- tools/listing_diff.py)
+template <bool SELFTEST = false>
 SP_DEV void scan_bvh(const BvhArgs& B, f3 o, f3 dir, int src, float& best_d, int& best_i, uint32_t* steps_out = nullptr, uint32_t* leaves_out = nullptr,
                      float tmax = kMaxDist, bool any_hit = false) {
 	uint32_t n_steps = 0, n_leaves = 0;
@@ -297,6 +301,20 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		if (a.out_accum) { a.out_accum[(size_t)k * 3] = accum.x; a.out_accum[(size_t)k * 3 + 1] = accum.y; a.out_accum[(size_t)k * 3 + 2] = accum.z; }
 	}
 	wave_add_scans(a.scans, my_scans);
+}
+
+// test-only (sphip_selftest_bvh_walk): scan_bvh itself on caller rays, in either form, with the walk's own counts -- steps taken
+// (reaching 4 * n_leaves + 64 means the belt-and-braces bound ended the walk) and leaves visited
+__global__ void __launch_bounds__(256) k_selftest_bvh_walk(const float* __restrict__ rays, uint32_t n_rays, const BvhArgs B, const int* __restrict__ src_idx,
+                                                           const float* __restrict__ tmax, int any_hit, int* __restrict__ out_idx, float* __restrict__ out_d,
+                                                           uint32_t* __restrict__ out_steps, uint32_t* __restrict__ out_leaves) {
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	if (k >= n_rays) return;
+	const float* r = rays + (size_t)k * 6;
+	float bd; int bi;
+	uint32_t st = 0, lv = 0;                           // a shadow ray stopped by the big list never starts the walk
+	scan_bvh<true>(B, mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]), src_idx ? src_idx[k] : -1, bd, bi, &st, &lv, tmax ? tmax[k] : kMaxDist, any_hit != 0);
+	out_idx[k] = bi; out_d[k] = bd; out_steps[k] = st; out_leaves[k] = lv;
 }
 
 } // namespace sp

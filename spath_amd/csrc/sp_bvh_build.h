@@ -10,7 +10,7 @@
 namespace sp {
 
 // meta words (device): [0..2] scene lo.xyz, [3..5] hi.xyz as ordered uints; [6] triangles wider than 1/4 of the scene,
-// [7] wider than 1/2; [8] n_big actually used; [9] n_tree; [10] threshold bits (float)
+// [7] wider than 1/2; [8] n_big actually used; [9..15] stay zero (n_tree = n - n_big and the threshold are recomputed where needed)
 constexpr uint32_t kBvhMaxBig = 256;
 
 SP_DEV uint32_t f2ord(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }

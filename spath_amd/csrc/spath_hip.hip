@@ -2031,6 +2031,90 @@ int sphip_selftest_stage1(sphip_t* c, const float* rays, size_t n_rays, uint32_t
 	return SPHIP_OK;
 }
 
+// The sort uses c->sort_kv and c->sort_hist as the builders do.  Both are scratch of a build: build_cylm and ensure_bvh read the sorted
+// half while they lay out cylm_rec / bvh_rec / bvh_idx / bvh_nodes and keep no pointer into either buffer afterwards (CylStream and BvhArgs
+// name only the laid-out buffers), so a sort between two renders leaves every built stream valid.
+int sphip_selftest_sort(sphip_t* c, const uint32_t* keys, const uint32_t* vals, size_t n, uint32_t key_bits, uint32_t* out_keys, uint32_t* out_vals) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "sphip_selftest_sort needs a single-device context (sphip_create)");
+	if (!keys || !vals || !out_keys || !out_vals || n == 0 || n > 0x0fffffffull || key_bits == 0 || key_bits > 32)
+		return fail(c, SPHIP_E_INVALID, "bad sort selftest arguments (n=%zu key_bits=%u)", n, key_bits);
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	int rc = ensure(c, c->sort_kv, n * 16);
+	if (rc) return rc;
+	uint32_t* kv = (uint32_t*)c->sort_kv.p;
+	HIP_TRY(c, hipMemcpyAsync(kv, keys, n * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipMemcpyAsync(kv + 2 * n, vals, n * 4, hipMemcpyHostToDevice, st));
+	int half = 0;
+	if ((rc = radix_sort(c, (uint32_t)n, key_bits, st, &half))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(out_keys, kv + (size_t)half * n, n * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(out_vals, kv + (size_t)(2 + half) * n, n * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	return SPHIP_OK;
+}
+
+int sphip_selftest_bvh_dump(sphip_t* c, uint32_t* n_leaves_out, uint32_t* out_meta, float* out_nodes, float* out_rec, int32_t* out_idx) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "sphip_selftest_bvh_dump needs a single-device context (sphip_create)");
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_selftest_bvh_dump called before a scene was set");
+	if (!n_leaves_out) return fail(c, SPHIP_E_INVALID, "n_leaves_out is NULL");
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	int rc = ensure_bvh(c, st);
+	if (rc) return rc;
+	const size_t nl = c->bvh_leaves, slots = nl * 4 + sp::kBvhMaxBig;
+	*n_leaves_out = c->bvh_leaves;
+	if (out_meta) HIP_TRY(c, hipMemcpyAsync(out_meta, c->bvh_meta.p, 16 * 4, hipMemcpyDeviceToHost, st));
+	if (out_nodes) HIP_TRY(c, hipMemcpyAsync(out_nodes, c->bvh_nodes.p, 2 * nl * 32, hipMemcpyDeviceToHost, st));
+	if (out_rec) HIP_TRY(c, hipMemcpyAsync(out_rec, c->bvh_rec.p, slots * 48, hipMemcpyDeviceToHost, st));
+	if (out_idx) HIP_TRY(c, hipMemcpyAsync(out_idx, c->bvh_idx.p, slots * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	return SPHIP_OK;
+}
+
+int sphip_selftest_bvh_walk(sphip_t* c, const float* rays, size_t n_rays, const int32_t* src_idx, const float* tmax, int any_hit,
+                            int32_t* out_idx, float* out_d, uint32_t* out_steps, uint32_t* out_leaves) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "sphip_selftest_bvh_walk needs a single-device context (sphip_create)");
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_selftest_bvh_walk called before a scene was set");
+	if (!rays || !out_idx || !out_d || !out_steps || !out_leaves || n_rays == 0 || n_rays > 0x7fffffffull)
+		return fail(c, SPHIP_E_INVALID, "bad BVH walk selftest arguments (n_rays=%zu)", n_rays);
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	int rc = ensure_bvh(c, st);
+	if (rc) return rc;
+	// one allocation: rays | src | tmax | idx | d | steps | leaves
+	const size_t n = n_rays;
+	char* d_all = nullptr;
+	HIP_TRY(c, hipMalloc((void**)&d_all, n * (24 + 6 * 4)));
+	float* d_rays = (float*)d_all;
+	int* d_src = (int*)(d_all + n * 24);
+	float* d_tmax = (float*)(d_all + n * 28);
+	int* d_idx = (int*)(d_all + n * 32);
+	float* d_d = (float*)(d_all + n * 36);
+	uint32_t *d_steps = (uint32_t*)(d_all + n * 40), *d_leaves = (uint32_t*)(d_all + n * 44);
+	hipError_t e = hipMemcpyAsync(d_rays, rays, n * 24, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess && src_idx) e = hipMemcpyAsync(d_src, src_idx, n * 4, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess && tmax) e = hipMemcpyAsync(d_tmax, tmax, n * 4, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) {
+		sp::BvhArgs B{};
+		B.nodes = (const float4*)c->bvh_nodes.p; B.leaf_rec = (const float4*)c->bvh_rec.p; B.leaf_idx = (const int*)c->bvh_idx.p;
+		B.n_leaves = c->bvh_leaves; B.first_leaf = c->bvh_leaves; B.meta = (const uint32_t*)c->bvh_meta.p;
+		hipLaunchKernelGGL(sp::k_selftest_bvh_walk, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (uint32_t)n, B,
+		                   src_idx ? (const int*)d_src : nullptr, tmax ? (const float*)d_tmax : nullptr, any_hit, d_idx, d_d, d_steps, d_leaves);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out_idx, d_idx, n * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_d, d_d, n * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_steps, d_steps, n * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_leaves, d_leaves, n * 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	(void)hipFree(d_all);
+	if (e != hipSuccess) return fail(c, SPHIP_E_DEVICE, "BVH walk selftest failed: %s", hipGetErrorString(e));
+	return SPHIP_OK;
+}
+
 void sphip_denoise_defaults(sphip_denoise* out) {
 	if (!out) return;
 	std::memset(out, 0, sizeof *out);

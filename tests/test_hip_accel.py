@@ -1,12 +1,16 @@
 """the opt-in acceleration structure (SPHIP_FLAG_ACCEL, linear BVH).  Not the brute-force path and not
 what bench.py measures.  Contract checked here: every GEOMETRIC hit is the brute-force scan's hit, index and distance
 bits alike; the only permitted differences are the reference's rounding-noise accepts (rays almost coplanar with a
-far-away triangle), which must be rare and are recognised by the brute-force scan reporting a hit whose point lies
-outside the triangle by far more than rounding."""
+far-away triangle).  They must be rare (the shares below), and each ray that differs is examined on its own
+(bvh_checks.check_walk): the BVH's answer is an accept of the strict float test, and every accept the reference
+preferred to it has its exact (float64) barycentric point outside the triangle.  The walk, the build and the sort
+underneath have tests of their own: test_hip_bvh_walk.py, test_hip_bvh_build.py, test_hip_sort.py."""
 import numpy as np
 import pytest
 import torch
 
+import bvh_checks as bc
+import bvh_model
 from spath_amd import capi, scene, view
 
 pytestmark = pytest.mark.gpu
@@ -43,6 +47,14 @@ def test_accel_hits_equal_brute_force(hip, O, maker, n):
         same = (ai == bi) & (ad.view(np.uint32) == bd.view(np.uint32))
         assert same.mean() >= 0.9999, (same.mean(), n)
         assert (bi >= 0).mean() > 0.3
+        # the rays that differ, one by one against the oracle (at n = 10 000 those among the first 4096 rays: the oracle tests every pair)
+        rows = np.flatnonzero(~same)
+        rows = rows[rows < 4096] if n > 1500 else rows
+        if rows.size:
+            sub, ssub = rays[rows], None if s is None else s[rows]
+            walked = hip.selftest_bvh_walk(sub, ssub)                # the walk the hit kernel ran, with its step counts
+            assert np.array_equal(walked[0], ai[rows]) and np.array_equal(walked[1].view(np.uint32), ad[rows].view(np.uint32))
+            bc.check_walk(O, t, sub, walked, bvh_model.n_leaves_for(t.shape[0]), src=ssub, tag=f"{maker.__name__}({n}) differing rays")
     if n <= 300:                                               # and against the CPU oracle
         oi, od = O.closest_hits(rays[:5000], t)
         ai, ad = _hits(hip, rays[:5000], capi.FLAG_ACCEL)

@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 import torch
 
+import bvh_checks as bc
+import bvh_model
 from spath_amd import capi, scene, view
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +26,16 @@ def _hits(hip, O, t, rays, tag):
     return want_idx
 
 
+def _accel_leg(hip, O, t, rays, tag):
+    """variant 8 (the opt-in BVH), which _hits leaves out by design: its walk is held to the oracle ray by ray, every difference
+    explained as a rounding-noise accept (bvh_checks.check_walk), with no source triangle and with a random one"""
+    nl = bvh_model.n_leaves_for(t.shape[0])
+    rng = np.random.default_rng(rays.shape[0])
+    for src in (None, rng.integers(-1, t.shape[0], rays.shape[0]).astype(np.int32)):
+        with np.errstate(all="ignore"):
+            bc.check_walk(O, t, rays, hip.selftest_bvh_walk(rays, src), nl, src=src, tag=f"accel {tag} src={'none' if src is None else 'random'}")
+
+
 def _rays(rng, n, scale, center):
     o = rng.uniform(-1.4, 1.4, (n, 3)) * [1, 0.5, 1]
     d = rng.normal(size=(n, 3))
@@ -41,6 +53,7 @@ def test_scaled_and_shifted_scenes(hip, O, scale, shift):
     hip.set_scene(t, m)
     rays = _rays(np.random.default_rng(4), 3000, scale, shift)
     idx = _hits(hip, O, t, rays, (scale, shift))
+    _accel_leg(hip, O, t, rays, (scale, shift))
     if scale <= 1e4:                     # beyond ~1e11 the distances exceed MAX_VALUE_DIST = 1e12 and the reference itself reports misses
         assert (idx >= 0).mean() > 0.9
 
@@ -56,6 +69,7 @@ def test_products_near_float_overflow(hip, O, scale, dir_len):
     rays = _rays(np.random.default_rng(12), 3000, scale, 0.0)
     rays[:, 3:] = (rays[:, 3:].astype(np.float64) * dir_len * np.random.default_rng(13).uniform(0.1, 1.0, (3000, 1))).astype(np.float32)
     _hits(hip, O, t, rays, (scale, dir_len))
+    _accel_leg(hip, O, t, rays, (scale, dir_len))
 
 
 def test_nonfinite_and_degenerate_inputs(hip, O):

@@ -20,6 +20,7 @@ import pytest
 
 import hip_checks as hc
 import path_model
+from bvh_model import noise_accept_share
 from hip_checks import (E_INVALID, E_STATE, ESTIMATORS, NEE_MIS, REPLAY_SEED, SPP, H, W, _torch_first, shape,  # noqa: F401
                         smooth_case as _case)                                               # (_torch_first, shape: fixtures)
 from oracle import oracle as O
@@ -296,26 +297,6 @@ def test_zero_table_is_no_flag(variant, spec, est):
     c.set_vertex_normals(vn)                                       # and the table matters
     assert not hc.same(c.render(rays, W, H, SPP, seed=6, flags=f | SMOOTH, want_accum=True), c.render(rays, W, H, SPP, seed=6, flags=f, want_accum=True))
     c.close()
-
-
-def noise_accept_share(accepts, tris):
-    """the share of the float test's accepted hits whose exact barycentric point lies outside the triangle (the reference's noise
-    accepts, DESIGN.md section 8, tools/accel_noise_rate.py): u and v of the header's bary rule recomputed in double from the f32
-    ray and vertices, outside when u < 0, v < 0 or u + v > 1 (or the ray is parallel to the plane in double)"""
-    o = np.concatenate([a[0] for a in accepts]).astype(np.float64)
-    d = np.concatenate([a[1] for a in accepts]).astype(np.float64)
-    i = np.concatenate([a[2] for a in accepts])
-    v = np.asarray(tris, F).reshape(-1, 12)[i, :9].astype(np.float64)
-    v0, e1, e2 = v[:, 0:3], v[:, 3:6] - v[:, 0:3], v[:, 6:9] - v[:, 0:3]
-    h = np.cross(d, e2)
-    a = (e1 * h).sum(1)
-    with np.errstate(all="ignore"):
-        f = 1.0 / a
-        s = o - v0
-        u = f * (s * h).sum(1)
-        vv = f * (d * np.cross(s, e1)).sum(1)
-        outside = ~((u >= 0.0) & (vv >= 0.0) & (u + vv <= 1.0))
-    return float(outside.mean()), int(outside.size)
 
 
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
