@@ -76,9 +76,13 @@ enum {
 	                                   table is ignored. */
 	SPHIP_FLAG_SMOOTH = 0x4000,      /* OPT-IN smooth shading by the context's per-vertex normals (sphip_set_vertex_normals) for
 	                                   SPHIP_MODE_PT; see "smooth shading" below.  Without the flag the normals are ignored. */
-	SPHIP_FLAG_DIELECTRIC = 0x8000   /* OPT-IN transparency: dielectric (glass) triangles with Fresnel reflection and refraction from the
+	SPHIP_FLAG_DIELECTRIC = 0x8000,  /* OPT-IN transparency: dielectric (glass) triangles with Fresnel reflection and refraction from the
 	                                   context's dielectric table (sphip_set_dielectric) for SPHIP_MODE_PT; see "transparency" below.
 	                                   Without the flag the table is ignored. */
+	SPHIP_FLAG_ENVIRONMENT = 0x1000000 /* OPT-IN environment lighting by the context's octahedral radiance map (sphip_set_environment) for
+	                                   SPHIP_MODE_PT: a ray that leaves the scene carries the map's radiance, and NEE|MIS samples the map;
+	                                   see "environment lighting" below.  Without the flag the map is ignored.  (Bits 16..23 are the
+	                                   sample chunks.) */
 };
 
 /* Pixel-shard descriptor: which global pixel the k-th ray of a shard is.
@@ -206,7 +210,10 @@ int sphip_plan_shard(size_t width, size_t height, int n_devices, size_t tile_row
  *        6  the f16 matrix-pipe side product of sp_cylm_scan.h      in f32[12n] 5 triangle values, 5 ray values, P_a (a half), 0
  *                                                                  out f32[2n] the instruction's result, the same 16 products summed in double
  *        7  shade_normal   ("smooth shading" below)                in f32[24n] pos dir v0 v1 v2 n0 n1 n2   out f32[6n] u, v, ns.xyz, sm
- *        8  dielectric     ("transparency" below)                  in f32[8n] dir ns ior entering          out f32[6n] Fr, tir, nt.xyz, c */
+ *        8  dielectric     ("transparency" below)                  in f32[8n] dir ns ior entering          out f32[6n] Fr, tir, nt.xyz, c
+ *        9  env_lookup     ("environment lighting" below)          in f32[3n] d                            out f32[4n] i, j, r3, valid
+ *       10  env_sample     ("environment lighting" below)          in f64[4n] r8 r9 r3 r4                  out f32[6n] i, j, wd.xyz, r3
+ *           9 and 10 run against the context's environment map (SPHIP_E_STATE without one) */
 int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void* out);
 
 /* TEST-ONLY: stage 1 of the default scan ALONE -- the conservative reject that decides which (ray, triangle) pairs ever reach
@@ -589,6 +596,86 @@ int sphip_set_dielectric(sphip_t* ctx, const float* glass);
  * by `stream` alone, and copied.  It does NOT validate the values: a table that breaks the rules above gives undefined images (never
  * out-of-bounds accesses: the table is indexed by triangle alone). */
 int sphip_set_dielectric_device(sphip_t* ctx, const void* d_glass, void* stream);
+
+/* ---- environment lighting: an octahedral radiance map beside the scene, n x n RGB texels (f32, row-major,
+ * texel (i, j) at texels[(j * n + i) * 3], i along a, j along b) over the square (a, b) in [-1, 1]^2 with +y at the centre and -y at the
+ * four corners, and the tables that importance-sample it.  SPHIP_FLAG_ENVIRONMENT lights SPHIP_MODE_PT renders with it: with the plain
+ * estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS; variants 1, 8 (SPHIP_FLAG_ACCEL) and 16 in both workgroup shapes; with
+ * SPHIP_FLAG_SPECULAR, _SMOOTH, _DIELECTRIC and _CAMERA_SAMPLES on or off; progressive and adaptive accumulation and denoising (the
+ * G-buffer is unchanged and miss pixels pass through the filter: the background stays sharp), sample chunks, primary-hit reuse, shards
+ * and multi-device contexts.  SPHIP_E_INVALID with SPHIP_MODE_FLAT, with SPHIP_FLAG_NEE without SPHIP_FLAG_MIS and with any other variant;
+ * SPHIP_E_STATE for the flag without a map; hit queries ignore the flag.  Without the flag every render is bit for bit what it is without
+ * a map, images and scans_executed, and with the flag and an all-zero map too.
+ *
+ * The arithmetic.  f32 unless marked double, every operation rounded on its own, nothing fused, dot3 as above, sgn(t) = t < 0 ? -1 : 1.
+ *
+ * env_lookup(d) -> (i, j, r3), for any non-zero d (the mapping does not depend on the scale of d: mirror and refracted directions are not
+ * renormalised):
+ *   s = (|d.x| + |d.y|) + |d.z|;  no texel when !(s > 0) or s is not finite
+ *   p = d / s per component
+ *   (a, b) = (p.x, p.z) when p.y >= 0, otherwise ((1 - |p.z|) sgn(p.x), (1 - |p.x|) sgn(p.z))
+ *   i = clamp((int)((a * 0.5f + 0.5f) * (float)n), 0, n - 1);  j likewise from b
+ *   l2 = dot3(p, p);  r3 = sqrtf(l2) * l2                       (da db = r3 d omega, on the folded half too: the fold is an isometry)
+ *
+ * The importance tables, in double, built by the library's own kernels behind both setters and equal to numpy's sequential cumsum:
+ *   (a_c, b_c) = (-1 + (2 i + 1) / n, -1 + (2 j + 1) / n);  y_c = (1 - |a_c|) - |b_c|
+ *   (x_c, z_c) = (a_c, b_c) when y_c >= 0, otherwise ((1 - |b_c|) sgn(a_c), (1 - |a_c|) sgn(b_c));  l2c = (x_c x_c + y_c y_c) + z_c z_c
+ *   wt[j n + i]  = (((double)R + G) + B) / (sqrt(l2c) * l2c)
+ *   rc[j][i]     = rc[j][i - 1] + wt[j n + i]   (one thread per row, in that order);  marg[j] = marg[j - 1] + rc[j][n - 1]   (one thread)
+ *   T = marg[n - 1];  Phi = T * (4.0 / ((double)n * n))
+ * and, with the scene (rebuilt on first use after the map or the scene changes), for the light table's environment entry:
+ *   R2    = 0.25 * ((dx dx + dy dy) + dz dz), dx dy dz the extents of the bounding box of the scene's vertices, in double
+ *   w_env = (0.5 * R2) * Phi   (the power through the scene's bounding disc, in the units A * Esum of the light table)
+ *   W     = W_triangles + w_env;  when !(w_env > 0) (a black map: T = 0; a scene whose box is a point: R2 = 0) there is no entry: w_env = 0, W = W_triangles, tpdf = 0
+ *   tpdf[t] = (float)(((w_env / W) * (wt[t] / T)) * ((double)n * n / 4.0))   (selection probability x density per unit (a, b) area)
+ *
+ * env_sample(r8, r9, r3, r4) -> (i, j, wd, r3), four uniforms in [0, 1) as doubles:
+ *   j = the first row with marg[j] > r8 * T, the last if none;  i = the first column with rc[j][i] > r9 * rc[j][n - 1], the last if none
+ *   a = ((float)i + (float)r3) * (2.0f / (float)n) - 1.0f;  b likewise from j, r4
+ *   y = (1 - |a|) - |b|;  (x, z) = (a, b) when y >= 0, otherwise ((1 - |b|) sgn(a), (1 - |a|) sgn(b))
+ *   g = (x, y, z);  l2 = dot3(g, g);  l = sqrtf(l2);  wd = g / l;  r3 = l * l2
+ * The sample keeps the texel it was drawn from; env_lookup(wd) names the same texel except for a measured share of draws on texel
+ * edges.
+ *
+ * The flagged light table.  With the flag the context keeps a second light table beside the unflagged one: the triangle entries as in
+ * "next-event estimation", plus, when w_env > 0, one last entry for the map, of weight w_env; the running sum ends in W = W_triangles + w_env
+ * and every ipdf is (float)(W / Esum) under that W.  A map without an entry (all zero) leaves W, ipdf and every bit as without the flag.
+ *
+ * Balance ratio against the BSDF density q = 1 / (pi^2 sxz), as in mis_u:  u_env(sxz, r3, t) = ((kPiSq * sxz) * r3) * tpdf[t], 0 where
+ * that is NaN.
+ *
+ * Light sample at hit d, d = 0..3 (NEE|MIS).  r5 selects the table entry as for triangles.  When it is the map's entry:
+ *   (r8, r9) = philox_uniforms(seed, pixel, sample, 40 + d);  (i, j, wd, r3) = env_sample(r8, r9, r3, r4), (r3, r4) of stream 8 + d
+ *   t = j n + i: the sample keeps its texel for Le and tpdf, there is no second lookup
+ *   cos_x = dot3(wd, ns); no sample when !(cos_x > 0); under smooth shading smooth_light_ok applies
+ *   the shadow ray (x, wd) skips src with tmax = 1e12f and is occluded iff anything is hit; one scan in scans_executed
+ *   L_d = (reflectance_src * (1/pi)) * (Le_t * ((kTwoPi * cos_x) / (1 + u_env(sxz(wd), r3, t)))), then the wD scale as for triangle lights
+ * It never exceeds 2 reflectance Le.  A specular or glass hit draws no light sample.
+ *
+ * Miss of the ray of depth d, d = 0..4:  (i, j, r3) = env_lookup(dir), t = j n + i, Le = texels[t] (0 without a texel).
+ *   plain estimator:  E_miss = Le
+ *   NEE|MIS:          E_miss = Le when d = 0, when hit d - 1 was specular or transmitted, or when !(tpdf[t] > 0);
+ *                     otherwise Le / (1 + u_env(sqrtf(dir.x dir.x + dir.z dir.z), r3, t)) per channel
+ * The unwind starts from rec = E_miss at a miss, where it starts from 0 without the flag; a path that ends for any other reason (the
+ * fifth hit, the smooth and glass ending rules) starts from 0.  The primary miss makes the map the background, and
+ * SPHIP_FLAG_CAMERA_SAMPLES antialiases it like anything else. */
+
+/* The context's environment map: n * n * 3 f32 on the host (NULL clears the map); blocking, the array is borrowed for the call; accepted
+ * by multi-device contexts (every device keeps the map and its tables).  Unlike the per-triangle tables the map is NOT cleared by
+ * sphip_set_scene and needs no scene (the scene-dependent part, w_env, W and tpdf, is rebuilt with the flagged light table on the first
+ * flagged render after either changes).  During an accumulation it ends the accumulation as sphip_set_specular does.  SPHIP_E_INVALID for
+ * n == 0, for n > 2048, or for a value that is negative or not finite (the message names the first such texel; the map stays as it was). */
+int sphip_set_environment(sphip_t* ctx, const float* texels, uint32_t n);
+/* The same from a device pointer, by the rules of sphip_set_specular_device: single-device contexts (SPHIP_E_STATE otherwise), ordered
+ * by `stream` alone (the tables are built on it), and copied.  It does NOT validate the values: a map that breaks the rules above gives
+ * undefined tables (never out-of-bounds accesses: n is checked, and every table index is bounded by n). */
+int sphip_set_environment_device(sphip_t* ctx, const void* d_texels, uint32_t n, void* stream);
+/* TEST-ONLY: copies out the tables above for the context's map and scene (SPHIP_E_STATE without either).  *n_out: the map's n; call with
+ * the other outputs NULL first to size them (each may be NULL on its own): out_wt f64[n n], out_rc f64[n n], out_marg f64[n],
+ * out_tpdf f32[n n], out_T_wenv_W f64[3] = T, w_env, W.  Blocking; host pointers; on a multi-device context the first device's.
+ * This call and sphip_selftest_device what 9 and 10 read the tables on the context's own stream: after sphip_set_environment_device the
+ * caller synchronises the stream it gave before calling them (nothing else orders the two streams). */
+int sphip_selftest_env_dump(sphip_t* ctx, uint32_t* n_out, double* out_wt, double* out_rc, double* out_marg, float* out_tpdf, double* out_T_wenv_W);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

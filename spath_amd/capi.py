@@ -22,6 +22,7 @@ FLAG_CAMERA_SAMPLES = 0x1000  # per-sample camera rays on the camera paths: pixe
 FLAG_SPECULAR = 0x2000      # mirror and mixed diffuse/mirror materials from the context's specular table
 FLAG_SMOOTH = 0x4000        # smooth shading by the context's per-vertex normals
 FLAG_DIELECTRIC = 0x8000    # transparency: glass triangles from the context's dielectric table
+FLAG_ENVIRONMENT = 0x1000000  # environment lighting by the context's octahedral map
 
 
 def flag_chunks(n: int) -> int:
@@ -45,6 +46,7 @@ SYMBOLS = (
     "sphip_set_specular", "sphip_set_specular_device",
     "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
     "sphip_set_dielectric", "sphip_set_dielectric_device",
+    "sphip_set_environment", "sphip_set_environment_device", "sphip_selftest_env_dump",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -218,6 +220,12 @@ def load():
     L.sphip_set_dielectric.argtypes = [vp, vp]
     L.sphip_set_dielectric_device.restype = C.c_int
     L.sphip_set_dielectric_device.argtypes = [vp, vp, vp]
+    L.sphip_set_environment.restype = C.c_int
+    L.sphip_set_environment.argtypes = [vp, vp, C.c_uint32]
+    L.sphip_set_environment_device.restype = C.c_int
+    L.sphip_set_environment_device.argtypes = [vp, vp, C.c_uint32, vp]
+    L.sphip_selftest_env_dump.restype = C.c_int
+    L.sphip_selftest_env_dump.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp, vp, vp, vp]
     L.sphip_create_multi.restype = C.c_int
     L.sphip_create_multi.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
     L.sphip_device_count.restype = C.c_int
@@ -374,6 +382,18 @@ class Context:
             raise ValueError("one dielectric row per triangle of the scene")
         self._check(self._L.sphip_set_dielectric(self._h, glass.ctypes.data), "sphip_set_dielectric")
 
+    def set_environment(self, texels):
+        """sphip_set_environment: the octahedral environment map, (n, n, 3) f32 with texel (i, j) at [j, i] (scene.sky_environment and
+        scene.environment_from_latlong build one); None clears it.  set_scene keeps it."""
+        import numpy as np
+        if texels is None:
+            self._check(self._L.sphip_set_environment(self._h, None, 0), "sphip_set_environment")
+            return
+        texels = np.ascontiguousarray(texels, dtype=np.float32)
+        if texels.ndim != 3 or texels.shape[0] != texels.shape[1] or texels.shape[2] != 3:
+            raise ValueError("an environment map is (n, n, 3)")
+        self._check(self._L.sphip_set_environment(self._h, texels.ctypes.data, texels.shape[0]), "sphip_set_environment")
+
     def render(self, rays, w, h, n_samples, seed=1, mode=MODE_PT, flags=0, want_accum=False):
         import numpy as np
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
@@ -401,6 +421,10 @@ class Context:
     def set_dielectric_device(self, d_glass: int, stream: int = 0):
         """sphip_set_dielectric_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_dielectric_device(self._h, d_glass, stream), "sphip_set_dielectric_device")
+
+    def set_environment_device(self, d_texels: int, n: int, stream: int = 0):
+        """sphip_set_environment_device: the map from a device pointer (n * n * 3 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_environment_device(self._h, d_texels or None, n, stream or None), "sphip_set_environment_device")
 
     def render_device(self, d_rays: int, n_rays: int, n_samples: int, d_out_rgba: int, *, seed=1, mode=MODE_PT,
                       flags=0, shard=None, image_width=0, d_out_accum: int = 0, stream: int = 0):
@@ -537,7 +561,7 @@ class Context:
         return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
-                    7: ("float32", 6), 8: ("float32", 6)}
+                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""
@@ -574,6 +598,20 @@ class Context:
                     "sphip_selftest_bvh_dump")
         assert nl.value == n
         return {"n_leaves": n, "meta": meta, "nodes": nodes, "rec": rec, "idx": idx}
+
+    def selftest_env_dump(self):
+        """sphip_selftest_env_dump (test-only): the importance tables of the context's map and scene -> dict(n, wt f64[n, n], rc f64[n, n],
+        marg f64[n], tpdf f32[n, n], T, w_env, W), the 2-d arrays indexed [j, i]."""
+        import numpy as np
+        nn = C.c_uint32(0)
+        self._check(self._L.sphip_selftest_env_dump(self._h, C.byref(nn), None, None, None, None, None), "sphip_selftest_env_dump")
+        n = nn.value
+        wt, rc, marg = np.zeros((n, n)), np.zeros((n, n)), np.zeros(n)
+        tpdf, s = np.zeros((n, n), dtype=np.float32), np.zeros(3)
+        self._check(self._L.sphip_selftest_env_dump(self._h, C.byref(nn), wt.ctypes.data, rc.ctypes.data, marg.ctypes.data, tpdf.ctypes.data,
+                                                    s.ctypes.data), "sphip_selftest_env_dump")
+        assert nn.value == n
+        return {"n": n, "wt": wt, "rc": rc, "marg": marg, "tpdf": tpdf, "T": float(s[0]), "w_env": float(s[1]), "W": float(s[2])}
 
     def selftest_bvh_walk(self, rays, src=None, tmax=None, any_hit=False):
         """sphip_selftest_bvh_walk (test-only): the BVH traversal itself on caller rays -> (idx i32[n], d f32[n], steps u32[n], leaves u32[n])."""

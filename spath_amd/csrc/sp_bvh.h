@@ -164,6 +164,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	constexpr bool smo = IsNorm<Acc...>::value;        // smooth shading (sp_integrator.h NormArgs): ns of shade_normal shades, n guards
 	static_assert(!smo || mis || !nee, "smooth shading: plain or NEE|MIS (DESIGN.md section 5.8)");
 	constexpr bool gls = IsGlass<Acc...>::value;       // transparency (sp_integrator.h GlassArgs, in SpecArgs' place): kTransBit beside kSpecBit
+	constexpr bool env = IsEnv<Acc...>::value;         // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place): a miss carries the map's radiance
+	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -192,6 +194,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		f3 hD[kMisDepths];
 		int nh = 0;
 		bool alive = valid;
+		f3 Em = mk3(0.0f, 0.0f, 0.0f);                  // environment: what the ray that left the scene carries
 #pragma unroll
 		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {
 			if (alive) {
@@ -220,7 +223,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						const bool full = depth == 0 || (spc && (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);   // after a mirror bounce e_d counts in full
 						const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
 						f3 Ld = mk3(0.0f, 0.0f, 0.0f);
-						if (depth < kNeeDepths && !sl && nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, ns, bi, wd, tm, Lc) && (!smo || smooth_light_ok(sm, wd, n))) {
+						if (depth < kNeeDepths && !sl && nee_light<true, env>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, ns, bi, wd, tm, Lc, env_map(acc_args...)) && (!smo || smooth_light_ok(sm, wd, n))) {
 							float sd; int si;
 							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
 							my_scans++;
@@ -260,11 +263,13 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					nh = depth + 1;
 					if constexpr (smo) if (ended) alive = false;
 				} else {
+					if constexpr (env) Em = env_miss<mis>(env_args(acc_args...).env, dir, depth == 0 || (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);
 					alive = false;
 				}
 			}
 		}
 		f3 rec = mk3(0.0f, 0.0f, 0.0f);
+		if constexpr (env) rec = Em;
 #pragma unroll
 		for (int depth = 4; depth >= 0; --depth) {
 			if (depth < nh) {

@@ -1,5 +1,5 @@
 // The path integrator's shared device code: the argument structs of the path kernels and the device functions that a path calls
-// at a surface hit (shade_normal, nee_light, mis_emit, spec_lobe / spec_reflect / spec_unwind), with the small pieces the kernels
+// at a surface hit (shade_normal, nee_light, mis_emit, spec_lobe / spec_reflect / spec_unwind) and at a miss (env_miss), with the small pieces the kernels
 // share around the integrator (load_ray, flat_px, clamped_rgba).
 //
 // k_pt (sp_kernels.h), k_accel (sp_bvh.h) and both branches of k_pt_filter (sp_scan_kernels.h) call these in the same sequence at a
@@ -129,6 +129,29 @@ struct GlassArgs : SpecArgs {
 };
 constexpr int kTransBit = 0x20000000;
 
+// the context's map as the device functions see it.  rc[j * n + i]: the running double sum of wt along row j; marg[j]: the running
+// double sum of rc[j][n - 1]; T = marg[n - 1]; tpdf: the scene-dependent density per texel (0 everywhere until a light table is built)
+struct EnvMap {
+	const float*  texels;      // n * n * 3, texel (i, j) at (j * n + i) * 3
+	const double* rc;          // n * n
+	const double* marg;        // n
+	const float*  tpdf;        // n * n
+	double T;
+	uint32_t n;
+};
+constexpr uint32_t kEnvMaxN = 2048;
+
+// environment lighting (SPHIP_FLAG_ENVIRONMENT, include/spath_hip.h): the map and its tables beside the tables of
+// GlassArgs, IN GlassArgs' PLACE (as GlassArgs rides in SpecArgs'): k_pt<V, MisArgs, EnvArgs, NormArgs, CamArgs>, ...  spec and glass are the
+// scene's tables, or tables of zeros when SPHIP_FLAG_SPECULAR or SPHIP_FLAG_DIELECTRIC is not set (p = 0, ior = 0: the diffuse
+// arithmetic's bits).  With MisArgs the light table of the NeeArgs fields is the flagged one: its last entry, tri = -1, is the map.
+// M: the two-stage kernels park the miss term of a path there, M[c * n_work + slot]
+struct EnvArgs : GlassArgs {
+	EnvMap env;
+	float* M;                  // two-stage kernels only
+};
+constexpr uint32_t kEnvStream = 40u;
+
 // smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
 // n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
 // CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
@@ -142,7 +165,8 @@ template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHa
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
-template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value; };
+template <typename... Acc> struct IsEnv { static constexpr bool value = PackHas<EnvArgs, Acc...>::value; };
+template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value || IsEnv<Acc...>::value; };
 template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value || IsGlass<Acc...>::value; };
 // what clears the marks of the path history from a triangle index
 template <typename... Acc> struct HistMask { static constexpr int value = IsGlass<Acc...>::value ? ~(kSpecBit | kTransBit) : ~kSpecBit; };
@@ -161,6 +185,12 @@ template <typename... P> SP_DEV const NeeArgs& nee_args(const P&... p) { return 
 template <typename... P> SP_DEV const CamArgs& cam_args(const P&... p) { return pack_get<CamArgs>(p...); }
 template <typename... P> SP_DEV const float4* spec_table(const P&... p) { return pack_get<SpecArgs>(p...).spec; }
 template <typename... P> SP_DEV const float4* glass_table(const P&... p) { return pack_get<GlassArgs>(p...).glass; }
+template <typename... P> SP_DEV const EnvArgs& env_args(const P&... p) { return pack_get<EnvArgs>(p...); }
+// the map of the pack for nee_light, nullptr without one
+template <typename... P> SP_DEV const EnvMap* env_map(const P&... p) {
+	if constexpr (IsEnv<P...>::value) return &pack_get<EnvArgs>(p...).env;
+	else return nullptr;
+}
 template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
@@ -227,13 +257,116 @@ SP_DEV f3 mis_emit(const KArgs& a, const float* tipdf, f3 dir, float bd, int bi)
 	return mk3(e.x / opu, e.y / opu, e.z / opu);
 }
 
+// ---- environment lighting (include/spath_hip.h "environment lighting").  Both mappings need only + - * /,
+// fabsf, sqrtf and selects, so the numpy model (tests/env_model.py) restates them bit for bit.
+SP_DEV float env_sgn(float t) { return t < 0.0f ? -1.0f : 1.0f; }
+SP_DEV uint32_t env_cell(float a, uint32_t n) {
+	const int i = (int)((a * 0.5f + 0.5f) * (float)n);
+	return i < 0 ? 0u : i > (int)n - 1 ? n - 1u : (uint32_t)i;
+}
+
+// the texel that direction d sees (any scale of d), and r3 = |p|^3 for p = d / (|d.x| + |d.y| + |d.z|): da db = r3 d omega, so a density
+// per unit (a, b) area times r3 is one per solid angle.
+// Returns whether there is a texel: not for a zero, an infinite or a NaN direction
+SP_DEV bool env_lookup(f3 d, uint32_t n, uint32_t& i, uint32_t& j, float& r3) {
+	const float s = (fabsf(d.x) + fabsf(d.y)) + fabsf(d.z);
+	i = 0; j = 0; r3 = 0.0f;
+	if (!(s > 0.0f) || !(s < __builtin_inff())) return false;
+	const f3 p = mk3(d.x / s, d.y / s, d.z / s);
+	float a = p.x, b = p.z;
+	if (!(p.y >= 0.0f)) {                                          // the lower half, folded outwards over the square's diagonals
+		a = (1.0f - fabsf(p.z)) * env_sgn(p.x);
+		b = (1.0f - fabsf(p.x)) * env_sgn(p.z);
+	}
+	i = env_cell(a, n);
+	j = env_cell(b, n);
+	const float l2 = dot3(p, p);
+	r3 = __builtin_sqrtf(l2) * l2;
+	return true;
+}
+
+// the first k in [0, m) with t[k] > x, m - 1 when there is none (t ascending)
+SP_DEV uint32_t env_first_above(const double* __restrict__ t, uint32_t m, double x) {
+	uint32_t lo = 0, hi = m - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (t[mid] > x) hi = mid; else lo = mid + 1u;
+	}
+	return lo;
+}
+
+// one draw from the map's tables: (r8, r9) pick the texel (row by marg, column by the row's rc), (r3u, r4u) the place in it.
+// wd: the unit direction of that place; r3 = |g|^3 of the octahedron point g it came from
+SP_DEV void env_sample(const EnvMap& e, double r8, double r9, double r3u, double r4u, uint32_t& i, uint32_t& j, f3& wd, float& r3) {
+	j = env_first_above(e.marg, e.n, r8 * e.T);
+	const double* row = e.rc + (size_t)j * e.n;
+	i = env_first_above(row, e.n, r9 * row[e.n - 1u]);
+	const float step = 2.0f / (float)e.n;
+	const float a = ((float)i + (float)r3u) * step - 1.0f;
+	const float b = ((float)j + (float)r4u) * step - 1.0f;
+	const float y = (1.0f - fabsf(a)) - fabsf(b);
+	float x = a, z = b;
+	if (!(y >= 0.0f)) {
+		x = (1.0f - fabsf(b)) * env_sgn(a);
+		z = (1.0f - fabsf(a)) * env_sgn(b);
+	}
+	const f3 g = mk3(x, y, z);
+	const float l2 = dot3(g, g);
+	const float l = __builtin_sqrtf(l2);
+	wd = mk3(g.x / l, g.y / l, g.z / l);
+	r3 = l * l2;
+}
+
+
+// the balance ratio of a direction of texel density tp (per unit (a, b) area) against the BSDF density q = 1 / (pi^2 sxz):
+// ((pi^2 sxz) r3) tp, 0 where that is NaN
+SP_DEV float env_u(float sxz, float r3, float tp) {
+	const float u = ((kPiSq * sxz) * r3) * tp;
+	return u == u ? u : 0.0f;
+}
+// what the ray of direction dir that left the scene carries: the texel's radiance, under MIS (and unless full: the camera's ray, or
+// the ray after a specular or transmitted bounce) weighted by 1 / (1 + u_env) where the light sample can draw the texel
+template <bool MIS>
+SP_DEV f3 env_miss(const EnvMap& e, f3 dir, bool full) {
+	uint32_t i, j;
+	float r3;
+	if (!env_lookup(dir, e.n, i, j, r3)) return mk3(0.0f, 0.0f, 0.0f);
+	const size_t t = (size_t)j * e.n + i;
+	const f3 Le = mk3(e.texels[t * 3], e.texels[t * 3 + 1], e.texels[t * 3 + 2]);
+	if constexpr (!MIS) return Le;
+	const float tp = e.tpdf[t];
+	if (full || !(tp > 0.0f)) return Le;
+	const float opu = 1.0f + env_u(__builtin_sqrtf(dir.x * dir.x + dir.z * dir.z), r3, tp);
+	return mk3(Le.x / opu, Le.y / opu, Le.z / opu);
+}
+// the light sample that picked the map's entry of the light table, at a hit on triangle src of shading normal n: (r3u, r4u) are the
+// uniforms of stream 8 + d that place a triangle sample.  The shadow ray (x, wd) is unbounded: anything it hits occludes
+SP_DEV bool env_light(const KArgs& a, const EnvMap& e, uint32_t pixel, uint32_t sample, int depth, f3 n, int src, double r3u, double r4u,
+                      f3& wd, float& tmax, f3& L) {
+	double r8, r9;
+	philox_uniforms(a.seed, pixel, sample, kEnvStream + (uint32_t)depth, &r8, &r9);
+	uint32_t i, j;
+	float r3;
+	env_sample(e, r8, r9, r3u, r4u, i, j, wd, r3);
+	const float cos_x = dot3(wd, n);
+	if (!(cos_x > 0.0f)) return false;
+	const size_t t = (size_t)j * e.n + i;
+	const float sxz = __builtin_sqrtf(wd.x * wd.x + wd.z * wd.z);
+	const float g = (kTwoPi * cos_x) / (1.0f + env_u(sxz, r3, e.tpdf[t]));
+	tmax = kMaxDist;
+	const float* ms = a.mats + (size_t)src * 6;
+	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(e.texels[t * 3], e.texels[t * 3 + 1], e.texels[t * 3 + 2]), g));
+	return true;
+}
+
 // ---- next-event estimation: one light sample at the hit x of a path (include/spath_hip.h).
 // n: the hit triangle's normal as the path uses it (turned against the incoming ray); src: the hit triangle.  Returns whether a
 // shadow ray (x, wd) with the bound tmax is to be traced, and then L = the direct light it carries when nothing occludes it.
 // MIS: L carries the balance heuristic's weight u / (1 + u), and sxz = 0 is no early-out (L is finite).
-template <bool MIS = false>
+// ENV: the table is the flagged one, whose entry of triangle -1 is the environment map *em (env_light)
+template <bool MIS = false, bool ENV = false>
 SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_t sample, int depth, f3 x, f3 n, int src,
-                      f3& wd, float& tmax, f3& L) {
+                      f3& wd, float& tmax, f3& L, const EnvMap* em = nullptr) {
 	if (ne.n == 0) return false;
 	double r3, r4, r5, r6;
 	philox_uniforms(a.seed, pixel, sample, 8u + (uint32_t)depth, &r3, &r4);
@@ -247,6 +380,7 @@ SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_
 	}
 	const int li = ne.tri[lo];
 	if (li == src) return false;
+	if constexpr (ENV) if (li < 0) return env_light(a, *em, pixel, sample, depth, n, src, r3, r4, wd, tmax, L);
 	const float* tv = a.tris + (size_t)li * 12;
 	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
 	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);

@@ -350,6 +350,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	static_assert(!smo || ((mis || !nee) && VARIANT == 1), "smooth shading: plain or NEE|MIS, variant 1 (DESIGN.md section 5.8)");
 	constexpr bool gls = IsGlass<Acc...>::value;                 // transparency (GlassArgs, in SpecArgs' place): kTransBit beside kSpecBit
 	static_assert(!gls || VARIANT == 1, "transparency: variant 1 (DESIGN.md section 5.10)");
+	constexpr bool env = IsEnv<Acc...>::value;                   // environment lighting (EnvArgs, in GlassArgs' place): a miss carries the map's radiance
+	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -385,6 +387,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		bool pspec = false;                                          // specular: the previous hit took the mirror lobe
 		f3 L0 = mk3(0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0, L3 = L0;   // NEE: direct light sampled at hits 0..3
 		f3 D0 = L0, D1 = L0, D2 = L0, D3 = L0, D4 = L0;             // MIS: D_d = e_d w_b + L_d
+		f3 Em = L0;                                                  // environment: what the ray that left the scene carries
 #pragma unroll 1
 		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {   // :33 depth >= 5 -> black (NEE: the 5th hit carries nothing)
 			if (!__syncthreads_or(alive ? 1 : 0)) break;   // block-uniform: the LDS scan has barriers
@@ -392,6 +395,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			if (depth == 0 && reuse) { bd = pd; bi = pi; }
 			else { closest_hit<VARIANT>(a, o, dir, src, bd, bi); my_scans += alive ? 1u : 0u; }
 			const bool hit = alive && (bi >= 0);                  // :51 miss -> black
+			if constexpr (env) if (alive && bi < 0) Em = env_miss<mis>(env_args(acc_args...).env, dir, depth == 0 || pspec);
 			bool sh = false;                                      // NEE: this lane traces a shadow ray
 			f3 wd = dir, Lc = mk3(0.0f, 0.0f, 0.0f);
 			float tm = kMaxDist;
@@ -415,7 +419,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				if constexpr (mis) {
 					if (depth == 0 || (spc && pspec)) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
 					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
-					if (depth < kNeeDepths && !sl) sh = nee_light<true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc);
+					if (depth < kNeeDepths && !sl) sh = nee_light<true, env>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc, env_map(acc_args...));
 					if constexpr (smo) sh = sh && smooth_light_ok(sm, wd, n);
 					if constexpr (spc) if (sh) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
@@ -464,6 +468,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		}
 		// unwind: rec(depth) = E + (((BRDF * rec(depth+1)) * cos) * (1/p)), rec beyond the last hit = 0
 		f3 rec = mk3(0.0f, 0.0f, 0.0f);
+		if constexpr (env) rec = Em;
 #pragma unroll
 		for (int depth = 4; depth >= 0; --depth) {
 			const int id = depth == 0 ? idx0 : depth == 1 ? idx1 : depth == 2 ? idx2 : depth == 3 ? idx3 : idx4;

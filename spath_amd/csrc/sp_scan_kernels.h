@@ -121,6 +121,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	static_assert(!smo || ((mis || !nee) && SCAN >= 3), "smooth shading: plain or NEE|MIS, the default scan (DESIGN.md section 5.8)");
 	constexpr bool gls = IsGlass<Acc...>::value;             // transparency (sp_integrator.h GlassArgs, in SpecArgs' place)
 	static_assert(!gls || SCAN >= 3, "transparency: the default scan (DESIGN.md section 5.10)");
+	constexpr bool env = IsEnv<Acc...>::value;               // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place)
+	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
@@ -172,6 +174,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		int nh[R];                       // surface hits of this path so far
 		uint32_t smp[R];
 		bool live[R];                    // this slot carries a sample in this iteration
+		bool ms[R];                      // environment: this path left the scene, its miss term is parked in EnvArgs::M
 #pragma unroll
 		for (int r = 0; r < R; ++r) {
 			const uint32_t k = kr0 + r * kstep;
@@ -181,6 +184,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 			else load_ray(a, k < a.n_rays ? k : a.n_rays - 1, s.o[r], s.dir[r]);
 			s.src[r] = -1; s.act[r] = live[r];
 			nh[r] = 0;
+			ms[r] = false;
 		}
 #pragma unroll 1
 		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {   // NEE: the 5th hit would carry nothing
@@ -209,6 +213,13 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 #pragma unroll
 				for (int r = 0; r < R; ++r) {
 					hitr[r] = s.act[r] && (bi[r] >= 0);
+					if constexpr (env) if (s.act[r] && bi[r] < 0) {         // the ray left the scene (depth > 0: the slot holds the hit of depth - 1)
+						const bool full = depth == 0 || (hist[(size_t)(depth > 0 ? depth - 1 : 0) * n_work + k0 + r * B].x & kSpecBit) != 0;
+						const f3 Em = env_miss<mis>(env_args(acc_args...).env, s.dir[r], full);
+						float* Mp = env_args(acc_args...).M + k0 + r * B;
+						Mp[0] = Em.x; Mp[n_work] = Em.y; Mp[(size_t)2 * n_work] = Em.z;
+						ms[r] = true;
+					}
 					sh.o[r] = s.o[r]; sh.dir[r] = s.dir[r]; sh.src[r] = s.src[r]; sh.act[r] = false; tmx[r] = kMaxDist;
 					nadj[r] = s.dir[r];
 					slr[r] = false;
@@ -238,7 +249,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 								// an interface is a specular hit whatever its row of the specular table: no light sample; its own lobe is drawn
 								// after the shadow scan
 								if constexpr (gls) if (glass_table(acc_args...)[bi[r]].w > 0.0f) slr[r] = true;
-								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc);
+								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true, env>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc, env_map(acc_args...));
 								if constexpr (smo) sh.act[r] = sh.act[r] && smooth_light_ok(smr[r], wd, n);
 								if (sh.act[r]) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 							}
@@ -320,6 +331,12 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 #pragma unroll
 			for (int r = 0; r < R; ++r) {
 				const bool hit = s.act[r] && (bi[r] >= 0);
+				if constexpr (env) if (s.act[r] && bi[r] < 0) {      // the ray left the scene
+					const f3 Em = env_miss<false>(env_args(acc_args...).env, s.dir[r], true);
+					float* Mp = env_args(acc_args...).M + k0 + r * B;
+					Mp[0] = Em.x; Mp[n_work] = Em.y; Mp[(size_t)2 * n_work] = Em.z;
+					ms[r] = true;
+				}
 				bool ended = false;                              // smooth shading: the bounce left the surface's upper side
 				if (hit) {
 					const float* tn = a.tris + (size_t)bi[r] * 12 + 9;
@@ -361,6 +378,10 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 		for (int r = 0; r < R; ++r) {
 			const uint32_t kw = k0 + r * B;
 			f3 rec = mk3(0.0f, 0.0f, 0.0f);
+			if constexpr (env) if (ms[r]) {
+				const float* Mp = env_args(acc_args...).M + kw;
+				rec = mk3(Mp[0], Mp[n_work], Mp[(size_t)2 * n_work]);
+			}
 			for (int d = nh[r] - 1; d >= 0; --d) {
 				const int2 hc = hist[(size_t)d * n_work + kw];
 				const int id = spc ? hc.x & hmask : hc.x;

@@ -13,6 +13,7 @@
 #include "sp_bvh_build.h"
 #include "sp_adaptive.h"
 #include "sp_denoise.h"
+#include "sp_environment.h"
 
 #include <hip/hip_runtime.h>
 
@@ -118,6 +119,21 @@ struct sphip_ctx {
 	// table, and the table of zeros that stands in for the specular table when SPHIP_FLAG_SPECULAR is not set (sized with the scene)
 	DevBuf glass, spec_zero;
 	bool have_glass = false;
+	// ---- environment lighting (sp_environment.h): the octahedral map env_n x env_n x 3 f32 and its importance tables wt, rc, marg (double),
+	// built on the device by both setters; every device of a multi-device context keeps them.  NOT dropped by set_scene: the map does not
+	// depend on the triangles.  What does (env_T read back, w_env, W and tpdf: ensure_env_lights) is rebuilt on first use after either changes
+	DevBuf env_tex, env_wt, env_rc, env_marg, env_tpdf;
+	bool have_env = false, env_lights_valid = false;
+	uint32_t env_n = 0;
+	double env_T = 0.0, env_wenv = 0.0, env_W = 0.0;
+	// SPHIP_FLAG_ENVIRONMENT: the flagged light table (the triangle entries under the total W that includes w_env, then the map's entry;
+	// laid out like nee_tab), built by ensure_env_lights from the host copy of the unflagged one; without an entry it is nee_tab itself.
+	// env_M: where the two-stage kernels park the miss term.  zero_rows: the triangles that spec_zero holds zeros for
+	DevBuf env_tab, env_M;
+	uint32_t env_nee_n = 0;
+	std::vector<double> nee_cdf_h, nee_esum_h;
+	std::vector<int> nee_tri_h;
+	size_t zero_rows = 0;
 };
 
 namespace {
@@ -194,7 +210,7 @@ bool variant_built(int v) {
 
 // the two-stage path-tracing kernels' work buffer, per work slot (sp_scan_kernels.h): the path history (5 x int2), the accumulator
 // (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adaptive sampling parks S1, S2 (2 doubles) in a buffer of its own (adp_wst)
-constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16;
+constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12;
 constexpr size_t work_slot_bytes(bool nee, bool mis) { return kSlotHist + kSlotAcc + (mis ? kSlotMisD : nee ? kSlotNeeL : 0); }
 
 int pick_variant(int flags, size_t n_tris) {
@@ -221,6 +237,8 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->have_scene = true;
 	c->bvh_valid = c->filt_valid = c->cyl_valid = c->cylm_valid = false;
 	c->nee_valid = false;
+	c->env_lights_valid = false;                   // w_env and tpdf follow the scene; the map itself stays
+	c->zero_rows = 0;
 	c->have_spec = false;                          // the specular table belongs to the old scene
 	c->have_vnorm = false;                         // and so do the vertex normals
 	c->have_glass = false;                         // and the dielectric table
@@ -408,7 +426,108 @@ int ensure_lights(sphip_ctx* c, hipStream_t st) {
 	}
 	c->nee_n = (uint32_t)ne;
 	c->nee_W = W;
+	c->nee_cdf_h = cdf; c->nee_tri_h = tri; c->nee_esum_h = esum;     // what the flagged table is made from (ensure_env_lights)
 	c->nee_valid = true;
+	return SPHIP_OK;
+}
+
+// ---- environment lighting (include/spath_hip.h "environment lighting").  The map's own tables, on the stream
+// that carries the texels: wt per texel, rc one thread per row, marg one thread (the order of the double additions is the contract)
+int build_env_tables(sphip_ctx* c, uint32_t n, hipStream_t st) {
+	const size_t nn = (size_t)n * n;
+	int rc;
+	if ((rc = ensure(c, c->env_wt, nn * 8)) || (rc = ensure(c, c->env_rc, nn * 8)) || (rc = ensure(c, c->env_marg, (size_t)n * 8)) || (rc = ensure(c, c->env_tpdf, nn * 4))) return rc;
+	hipLaunchKernelGGL(sp::k_env_wt, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (const float*)c->env_tex.p, n, (double*)c->env_wt.p);
+	hipLaunchKernelGGL(sp::k_env_rows, dim3((n + 255u) / 256u), dim3(256), 0, st, (const double*)c->env_wt.p, n, (double*)c->env_rc.p);
+	hipLaunchKernelGGL(sp::k_env_marg, dim3(1), dim3(64), 0, st, (const double*)c->env_rc.p, n, (double*)c->env_marg.p);
+	HIP_TRY(c, hipGetLastError());
+	HIP_TRY(c, hipMemsetAsync(c->env_tpdf.p, 0, nn * 4, st));       // no light table yet: the map is not sampled
+	return SPHIP_OK;
+}
+
+// the map of a single-device context from src (n * n * 3 f32), or no map with src == nullptr; sync: src is borrowed host memory
+int set_env_map(sphip_ctx* c, const void* src, uint32_t n, hipMemcpyKind kind, hipStream_t st, bool sync) {
+	c->acc_stale = c->acc_on;                      // the running sum was rendered under the old map
+	c->have_env = false;
+	c->env_lights_valid = false;
+	if (!src) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	const size_t bytes = (size_t)n * n * 12;
+	int rc;
+	if ((rc = ensure(c, c->env_tex, bytes))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->env_tex.p, src, bytes, kind, st));
+	if ((rc = build_env_tables(c, n, st))) return rc;
+	if (sync) HIP_TRY(c, hipStreamSynchronize(st));
+	c->env_n = n;
+	c->have_env = true;
+	return SPHIP_OK;
+}
+
+// the scene-dependent part, on first use after the map or the scene changed: T = marg[n - 1] read back, Phi = T * (4 / (n n)),
+// w_env = 0.5 * R2 * Phi with R2 a quarter of the squared diagonal of the scene's bounding box (the power through the scene's bounding
+// disc, in the light table's units A * Esum), W = the triangle table's total + w_env, and tpdf.  !(T > 0): no entry, W is the triangles'
+int ensure_env_lights(sphip_ctx* c, hipStream_t st) {
+	if (c->env_lights_valid) return SPHIP_OK;
+	int rc;
+	if ((rc = ensure_lights(c, st))) return rc;
+	const size_t nt = c->n_tris;
+	const uint32_t n = c->env_n;
+	std::vector<float> t(nt * 12);
+	double T = 0.0;
+	HIP_TRY(c, hipMemcpyAsync(t.data(), c->tris.p, nt * 48, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipMemcpyAsync(&T, (const double*)c->env_marg.p + (n - 1u), 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	float lo[3] = { t[0], t[1], t[2] }, hi[3] = { t[0], t[1], t[2] };
+	for (size_t i = 0; i < nt; ++i)
+		for (int v = 0; v < 3; ++v)
+			for (int k = 0; k < 3; ++k) {
+				const float x = t[i * 12 + 3 * v + k];
+				if (x < lo[k]) lo[k] = x;
+				if (x > hi[k]) hi[k] = x;
+			}
+	const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
+	const double R2 = 0.25 * ((dx * dx + dy * dy) + dz * dz);
+	const double Phi = T * (4.0 / ((double)n * (double)n));
+	const double w_env = T > 0.0 ? (0.5 * R2) * Phi : 0.0;
+	const bool entry = w_env > 0.0;                // a black map, or a scene whose bounding box is a point: no entry
+	c->env_T = T;
+	c->env_wenv = entry ? w_env : 0.0;
+	c->env_W = entry ? c->nee_W + c->env_wenv : c->nee_W;
+	const double sel = entry ? c->env_wenv / c->env_W : 0.0;
+	const size_t nn = (size_t)n * n;
+	hipLaunchKernelGGL(sp::k_env_tpdf, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (const double*)c->env_wt.p, n, sel, T, (float*)c->env_tpdf.p);
+	HIP_TRY(c, hipGetLastError());
+	// the flagged light table: every triangle entry again with ipdf = (float)(W / Esum) under the new W, then the map's entry
+	// {cdf W, triangle -1, ipdf 0}.  A black map adds nothing: the render then reads the unflagged table, bit for bit
+	c->env_nee_n = c->nee_n;
+	if (entry) {
+		const size_t ne = c->nee_cdf_h.size(), m = ne + 1;
+		std::vector<double> cdf(c->nee_cdf_h);
+		std::vector<int> tri(c->nee_tri_h);
+		std::vector<float> ipdf(m, 0.0f), tipdf(nt, 0.0f);
+		cdf.push_back(c->env_W);
+		tri.push_back(-1);
+		for (size_t k = 0; k < ne; ++k) { ipdf[k] = (float)(c->env_W / c->nee_esum_h[k]); tipdf[(size_t)tri[k]] = ipdf[k]; }
+		if ((rc = ensure(c, c->env_tab, m * 16 + nt * 4 + 16))) return rc;
+		std::vector<char> blob(m * 16 + nt * 4);
+		memcpy(blob.data(), cdf.data(), m * 8);
+		memcpy(blob.data() + m * 8, tri.data(), m * 4);
+		memcpy(blob.data() + m * 12, ipdf.data(), m * 4);
+		memcpy(blob.data() + m * 16, tipdf.data(), nt * 4);
+		HIP_TRY(c, hipMemcpyAsync(c->env_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+		HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
+		c->env_nee_n = (uint32_t)m;
+	}
+	c->env_lights_valid = true;
+	return SPHIP_OK;
+}
+
+// the zeros that stand in for a per-triangle table whose flag is off in an environment render: one float4 row per triangle of the scene
+int ensure_zero_rows(sphip_ctx* c, hipStream_t st) {
+	if (c->zero_rows == c->n_tris) return SPHIP_OK;
+	if (const int rc = ensure(c, c->spec_zero, c->n_tris * 16)) return rc;
+	HIP_TRY(c, hipMemsetAsync(c->spec_zero.p, 0, c->n_tris * 16, st));
+	c->zero_rows = c->n_tris;
 	return SPHIP_OK;
 }
 
@@ -427,7 +546,7 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::GlassArgs* gls, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
+               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
 			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
@@ -439,6 +558,7 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
 				last();
 			};
+			if constexpr (tables) { if (env) { tail(*env); return; } }      // the environment map carries the dielectric and the specular table
 			if constexpr (tables) { if (gls) { tail(*gls); return; } }      // the dielectric table carries the specular one
 			if constexpr (tables) { if (spc) { tail(*spc); return; } }
 			tail();
@@ -496,6 +616,8 @@ struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphi
 const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_shipped, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
 const TableRule kSmoothRule{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" };
 const TableRule kGlassRule{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" };
+// environment lighting follows the same rules with the context's map for a table
+const TableRule kEnvRule{ SPHIP_FLAG_ENVIRONMENT, "SPHIP_FLAG_ENVIRONMENT", variant_smooth, &sphip_ctx::have_env, "an environment map (sphip_set_environment)" };
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
 	if (mode == SPHIP_MODE_FLAT) return fail(c, SPHIP_E_INVALID, "%s is valid for SPHIP_MODE_PT only", r.flag);
@@ -579,7 +701,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ne.W = c->nee_W;
 	}
 	if ((rc = check_camera_rule(c, flags, variant, mode, cams != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, variant, mode)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode)) || (rc = check_table_rule(c, kGlassRule, flags, variant, mode))) return rc;
+	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode)) || (rc = check_table_rule(c, kGlassRule, flags, variant, mode)) ||
+	    (rc = check_table_rule(c, kEnvRule, flags, variant, mode))) return rc;
 	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) cams = nullptr;
 	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR), smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
 	const sp::SpecArgs spa{ (const float4*)c->spec.p };
@@ -589,6 +712,24 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	sp::GlassArgs gla{};
 	gla.spec = (const float4*)(specf ? c->spec.p : c->spec_zero.p);
 	gla.glass = (const float4*)c->glass.p;
+	// environment lighting: the map in the dielectric table's place, with the zeros for either table whose flag is off; under NEE|MIS the
+	// estimator reads the flagged light table (the unflagged one when the map is black and adds no entry)
+	const bool envf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_ENVIRONMENT);
+	sp::EnvArgs ena{};
+	if (envf) {
+		if ((!specf || !glassf) && (rc = ensure_zero_rows(c, st))) return rc;
+		if (nee && (rc = ensure_env_lights(c, st))) return rc;
+		ena.spec = (const float4*)(specf ? c->spec.p : c->spec_zero.p);      // read after ensure_zero_rows: it may have allocated the zeros
+		ena.glass = (const float4*)(glassf ? c->glass.p : c->spec_zero.p);
+		ena.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
+		if (nee && c->env_nee_n != c->nee_n) {
+			ne.cdf = (const double*)c->env_tab.p;
+			ne.tri = (const int*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 8);
+			ne.ipdf = (const float*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 12);
+			ne.n = c->env_nee_n;
+			ne.W = c->env_W;
+		}
+	}
 	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
 	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
@@ -620,7 +761,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			if (samp_bytes > kChunkMaxBytes) chunks = 1;
 			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
 			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * (work_slot_bytes(nee, mis) + (adapt ? kSlotAdaptWst : 0));
+				const uint64_t work_bytes = lanes * chunks * (work_slot_bytes(nee, mis) + (adapt ? kSlotAdaptWst : 0) + (envf ? kSlotEnvM : 0));
 				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
@@ -655,6 +796,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ne.L = (float*)((char*)c->work.p + (size_t)n_work * (kSlotHist + kSlotAcc));     // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
 		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * kSlotAdaptWst))) return rc;   // S1, S2 per work slot
 		ad.wst = (double*)c->adp_wst.p;
+		if (envf && (rc = ensure(c, c->env_M, (size_t)n_work * kSlotEnvM))) return rc;          // the miss term per work slot
+		ena.M = (float*)c->env_M.p;
 	}
 	sp::ScanSrc src2{};
 	if (is_ts && (ts.scan == 1 || ts.scan == 2) && (rc = ensure_cyl(c, st))) return rc;
@@ -698,9 +841,10 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	if (mis) {
 		static_cast<sp::NeeArgs&>(me) = ne;
 		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
+		if (envf && c->env_nee_n != c->nee_n) me.tipdf = (const float*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 16);
 	}
 	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
-	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf && !glassf ? &spa : nullptr, glassf ? &gla : nullptr, smoothf ? &nra : nullptr, cams, f); };
+	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf && !glassf && !envf ? &spa : nullptr, glassf && !envf ? &gla : nullptr, envf ? &ena : nullptr, smoothf ? &nra : nullptr, cams, f); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
@@ -1256,7 +1400,8 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	const int v = pick_variant(flags, c->n_tris);
 	int rc;
 	if ((rc = check_camera_rule(c, flags, v, SPHIP_MODE_PT, cam != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, v, SPHIP_MODE_PT)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT)) || (rc = check_table_rule(c, kGlassRule, flags, v, SPHIP_MODE_PT))) return rc;
+	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT)) || (rc = check_table_rule(c, kGlassRule, flags, v, SPHIP_MODE_PT)) ||
+	    (rc = check_table_rule(c, kEnvRule, flags, v, SPHIP_MODE_PT))) return rc;
 	if (!c->kids.empty()) {
 		if ((rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr))) return rc;
 	} else {
@@ -1779,6 +1924,36 @@ int sphip_set_dielectric_device(sphip_t* c, const void* d_glass, void* stream) {
 	return big ? fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris) : rc;
 }
 
+int sphip_set_environment(sphip_t* c, const float* texels, uint32_t n) {
+	if (!c) return SPHIP_E_INVALID;
+	if (texels) {
+		if (n == 0 || n > sp::kEnvMaxN) return fail(c, SPHIP_E_INVALID, "environment map: n = %u (1 <= n <= %u)", n, sp::kEnvMaxN);
+		const size_t cnt = (size_t)n * n * 3;
+		for (size_t k = 0; k < cnt; ++k)
+			if (!std::isfinite(texels[k]) || !(texels[k] >= 0.0f))
+				return fail(c, SPHIP_E_INVALID, "environment map: texel (%zu, %zu) has component %zu = %g (every value finite and >= 0)", (k / 3) % n, (k / 3) / n,
+				            k % 3, (double)texels[k]);
+	}
+	if (c->kids.empty()) return set_env_map(c, texels, n, hipMemcpyHostToDevice, c->own_stream, true);
+	c->acc_stale = c->acc_on;
+	c->have_env = false;
+	for (sphip_ctx* k : c->kids)                                   // the texels were validated above, once
+		if (const int rc = set_env_map(k, texels, n, hipMemcpyHostToDevice, k->own_stream, true)) {   // a device that refuses leaves no device with a map: they must never differ
+			for (sphip_ctx* q : c->kids) q->have_env = false;
+			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+		}
+	c->have_env = texels != nullptr;
+	c->env_n = texels ? n : 0;
+	return SPHIP_OK;
+}
+
+int sphip_set_environment_device(sphip_t* c, const void* d_texels, uint32_t n, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	const bool bad = d_texels && (n == 0 || n > sp::kEnvMaxN);        // refused, and like every call it leaves no map behind
+	const int rc = set_env_map(c, bad ? nullptr : d_texels, n, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return bad ? fail(c, SPHIP_E_INVALID, "environment map: n = %u (1 <= n <= %u)", n, sp::kEnvMaxN) : rc;
+}
+
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
                         size_t n_samples, uint64_t seed, int mode, int flags, void* d_out_rgba, void* d_out_accum, void* stream) {
 	if (const int rc = single_device_entry(c)) return rc;
@@ -1964,16 +2139,25 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[9] = { 4, 4, 20, 40, 60, 12, 48, 96, 32 }, out_b[9] = { 8, 4, 16, 12, 4, 4, 8, 24, 24 };
-	if (what < 0 || what > 8 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[11] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32 }, out_b[11] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24 };
+	if (what < 0 || what > 10 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
+	if (what >= 9 && !k->have_env) return fail(c, SPHIP_E_STATE, "selftest %d needs an environment map (sphip_set_environment)", what);
 	HIP_TRY(c, hipSetDevice(k->device));
+	sp::EnvMap em{};
+	if (what == 10) {                                                // T alone: the tables of the map itself, no scene needed
+		em = sp::EnvMap{ (const float*)k->env_tex.p, (const double*)k->env_rc.p, (const double*)k->env_marg.p, (const float*)k->env_tpdf.p, 0.0, k->env_n };
+		HIP_TRY(c, hipMemcpyAsync(&em.T, (const double*)k->env_marg.p + (k->env_n - 1u), 8, hipMemcpyDeviceToHost, k->own_stream));
+		HIP_TRY(c, hipStreamSynchronize(k->own_stream));
+	}
 	void *d_in = nullptr, *d_out = nullptr;
 	HIP_TRY(c, hipMalloc(&d_in, n * in_b[what]));
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 8) hipLaunchKernelGGL(sp::k_selftest_glass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
+		if (what == 10) hipLaunchKernelGGL(sp::k_selftest_env_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, em, (float*)d_out);
+		else if (what == 9) hipLaunchKernelGGL(sp::k_selftest_env_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, k->env_n, (float*)d_out);
+		else if (what == 8) hipLaunchKernelGGL(sp::k_selftest_glass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 7) hipLaunchKernelGGL(sp::k_selftest_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 6) hipLaunchKernelGGL(sp::cylm256::k_selftest_cylm, dim3((unsigned)n), dim3(64), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else hipLaunchKernelGGL(sp::k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, what, (const void*)d_in, (uint32_t)n, d_out);
@@ -2070,6 +2254,26 @@ int sphip_selftest_bvh_dump(sphip_t* c, uint32_t* n_leaves_out, uint32_t* out_me
 	if (out_rec) HIP_TRY(c, hipMemcpyAsync(out_rec, c->bvh_rec.p, slots * 48, hipMemcpyDeviceToHost, st));
 	if (out_idx) HIP_TRY(c, hipMemcpyAsync(out_idx, c->bvh_idx.p, slots * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(c, hipStreamSynchronize(st));
+	return SPHIP_OK;
+}
+
+int sphip_selftest_env_dump(sphip_t* c, uint32_t* n_out, double* out_wt, double* out_rc, double* out_marg, float* out_tpdf, double* out_T_wenv_W) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!n_out) return fail(c, SPHIP_E_INVALID, "n_out is NULL");
+	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
+	if (!k->have_scene) return fail(c, SPHIP_E_STATE, "sphip_selftest_env_dump called before a scene was set");
+	if (!k->have_env) return fail(c, SPHIP_E_STATE, "sphip_selftest_env_dump needs an environment map (sphip_set_environment)");
+	HIP_TRY(c, hipSetDevice(k->device));
+	hipStream_t st = k->own_stream;
+	if (const int rc = ensure_env_lights(k, st)) return k == c ? rc : fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+	const size_t n = k->env_n, nn = n * n;
+	*n_out = k->env_n;
+	if (out_wt) HIP_TRY(c, hipMemcpyAsync(out_wt, k->env_wt.p, nn * 8, hipMemcpyDeviceToHost, st));
+	if (out_rc) HIP_TRY(c, hipMemcpyAsync(out_rc, k->env_rc.p, nn * 8, hipMemcpyDeviceToHost, st));
+	if (out_marg) HIP_TRY(c, hipMemcpyAsync(out_marg, k->env_marg.p, n * 8, hipMemcpyDeviceToHost, st));
+	if (out_tpdf) HIP_TRY(c, hipMemcpyAsync(out_tpdf, k->env_tpdf.p, nn * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	if (out_T_wenv_W) { out_T_wenv_W[0] = k->env_T; out_T_wenv_W[1] = k->env_wenv; out_T_wenv_W[2] = k->env_W; }
 	return SPHIP_OK;
 }
 

@@ -59,13 +59,17 @@ struct hip_r : public basic_renderer {
 	std::vector<float> vnorm;
 	// transparency (set_dielectric): likewise, 4 floats per triangle and SPHIP_FLAG_DIELECTRIC
 	std::vector<float> glass;
+	// environment lighting (set_environment): the map, env_n x env_n x 3 floats, and SPHIP_FLAG_ENVIRONMENT; the library keeps it across
+	// scenes, but it travels with the scene upload like the tables so that one key covers everything a frame depends on
+	std::vector<float> env;
+	uint32_t env_n;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
-	                                                                   cam_samples(false) {
+	                                                                   cam_samples(false), env_n(0) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
 		std::memset(&lens, 0, sizeof lens);
 		std::memset(&acc_lens, 0, sizeof acc_lens);
@@ -107,8 +111,10 @@ struct hip_r : public basic_renderer {
 			if (glass.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the dielectric table and the scene differ in size");
 			h = fnv(glass.data(), glass.size() * sizeof(float), h);
 		}
+		if (!env.empty()) h = fnv(env.data(), env.size() * sizeof(float), h);
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
+			check(sphip_set_environment(ctx, env.empty() ? 0 : env.data(), env_n), "set_environment");
 			if (!spec.empty()) check(sphip_set_specular(ctx, spec.data()), "set_specular");
 			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
 			if (!glass.empty()) check(sphip_set_dielectric(ctx, glass.data()), "set_dielectric");
@@ -183,7 +189,8 @@ struct hip_r : public basic_renderer {
 
 	int table_flags(const int mode) const {              // the flags of the tables that are set
 		if (mode != SPHIP_MODE_PT) return 0;
-		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0);
+		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0) |
+		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0);
 	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
@@ -287,6 +294,14 @@ namespace hip_renderer {
 		if (glass && n_tris) p->glass.assign(glass, glass + n_tris * 4);
 		else p->glass.clear();
 		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+	}
+
+	void set_environment(scene::renderer* r, const float* texels, uint32_t n) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (texels && n) { p->env.assign(texels, texels + (size_t)n * n * 3); p->env_n = n; }
+		else { p->env.clear(); p->env_n = 0; }
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the map (or none) with it
 	}
 
 	void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris) {

@@ -50,6 +50,11 @@ namespace hip_renderer {
 	// (render_flat is unchanged).  NULL or n_tris = 0 removes it.  A table the library refuses makes the next frame throw
 	// std::runtime_error, as does one whose size differs from the scene's.  Changing it begins a new progressive accumulation.
 	extern void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris);
+	// environment lighting (sphip_set_environment, SPHIP_FLAG_ENVIRONMENT; include/spath_hip.h "environment lighting"): an octahedral
+	// radiance map of n x n x 3 floats (copied); while one is set, path-traced frames are lit by it and show it behind the scene
+	// (render_flat is unchanged).  NULL or n = 0 removes it.  A map the library refuses makes the next frame throw std::runtime_error.
+	// Changing it begins a new progressive accumulation.
+	extern void set_environment(scene::renderer* r, const float* texels, uint32_t n);
 	// Progressive rendering for a viewer whose view stands still (off by default: render() then behaves like the reference's).
 	// When on, render() adds its n_samples to the samples of the previous calls while the viewport rays (compared bit for bit),
 	// the scene, the seed and the flags are unchanged, and the bitmap is the image of all of them -- bit-identical to one

@@ -103,6 +103,15 @@ class HipRenderer(BasicRenderer):
         self._spec = None
         self._vnorm = None
         self._glass = None
+        self._env = None
+
+    def set_environment(self, env):
+        """The environment map of capi.FLAG_ENVIRONMENT renders ([n, n, 3] float32, scene.sky_environment or
+        scene.environment_from_latlong; None: no map), like hip_renderer::set_environment: it goes to the library with the next scene
+        upload and begins a new accumulation, and while one is set every path-traced frame carries capi.FLAG_ENVIRONMENT (render_flat
+        never does)."""
+        self._env = None if env is None else np.ascontiguousarray(env, dtype=np.float32).copy()
+        self._scene_key = None
 
     def set_dielectric(self, glass):
         """The dielectric table of capi.FLAG_DIELECTRIC renders ([n_tris, 4] float32, scene.dielectric_table; None: no table), like
@@ -126,11 +135,12 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH and FLAG_DIELECTRIC on while their tables are set, and never on the
-        flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC and FLAG_ENVIRONMENT on while their tables or the map
+        are set, and never on the flat pass"""
         if mode == capi.MODE_FLAT:
-            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC)
+            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT)
         flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
+        flags = flags | capi.FLAG_ENVIRONMENT if self._env is not None else flags
         flags = flags | capi.FLAG_DIELECTRIC if self._glass is not None else flags
         return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
 
@@ -142,7 +152,8 @@ class HipRenderer(BasicRenderer):
         mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 6)[:n_tris]
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
         key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
-               None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()))
+               None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()),
+               None if self._env is None else hash(self._env.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
             if self._spec is not None:
@@ -151,6 +162,7 @@ class HipRenderer(BasicRenderer):
                 self.ctx.set_vertex_normals(self._vnorm[:n_tris])
             if self._glass is not None:
                 self.ctx.set_dielectric(self._glass[:n_tris])
+            self.ctx.set_environment(self._env)
             self._scene_key = key
 
     def _begin_rule(self):

@@ -20,6 +20,7 @@ SCENE_MAGIC = 0x43535053  # 'SPSC'
 SPEC_MAGIC = 0x50535053   # 'SPSP'
 VNORM_MAGIC = 0x4E565053  # 'SPVN'
 GLASS_MAGIC = 0x49445053  # 'SPDI'
+ENV_MAGIC = 0x4E455053    # 'SPEN'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -253,6 +254,67 @@ def write_dielectric(path, glass: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(struct.pack("<II", GLASS_MAGIC, glass.shape[0]))
         f.write(glass.tobytes())
+
+
+def octahedral_directions(n: int) -> np.ndarray:
+    """The unit directions of the texel centres of an n x n octahedral environment map (include/spath_hip.h, "environment lighting"):
+    float64 [n, n, 3] indexed [j, i], texel (i, j) centred at (a, b) = (-1 + (2 i + 1) / n, -1 + (2 j + 1) / n), +y at the centre of the
+    square and -y at its corners."""
+    c = -1.0 + (2.0 * np.arange(n) + 1.0) / n
+    a, b = np.meshgrid(c, c, indexing="xy")
+    y = (1.0 - np.abs(a)) - np.abs(b)
+    x = np.where(y >= 0, a, (1.0 - np.abs(b)) * np.where(a < 0, -1.0, 1.0))
+    z = np.where(y >= 0, b, (1.0 - np.abs(a)) * np.where(b < 0, -1.0, 1.0))
+    g = np.stack([x, y, z], axis=-1)
+    return g / np.sqrt((g * g).sum(-1, keepdims=True))
+
+
+def sky_environment(n: int, sun_dir=(0.3, 0.8, 0.5), sun_radiance=(50.0, 45.0, 35.0), sun_halfangle: float = 0.1,
+                    sky_radiance=(0.4, 0.6, 1.0), ground_radiance=(0.15, 0.12, 0.1)) -> np.ndarray:
+    """A procedural environment map for capi.Context.set_environment: float32 [n, n, 3] indexed [j, i].  Above the horizon the sky's
+    radiance fades linearly with the direction's height from the full value at the zenith to half of it at the horizon; below it the
+    ground's radiance is constant; every texel whose centre lies within sun_halfangle (radians) of sun_dir has the sun's radiance added."""
+    d = octahedral_directions(n)
+    up = d[..., 1:2]
+    env = np.where(up >= 0, np.asarray(sky_radiance, np.float64) * (0.5 + 0.5 * up), np.asarray(ground_radiance, np.float64))
+    sd = np.asarray(sun_dir, np.float64)
+    sd = sd / np.sqrt((sd * sd).sum())
+    sun = (d * sd).sum(-1) >= np.cos(sun_halfangle)
+    env = env + sun[..., None] * np.asarray(sun_radiance, np.float64)
+    env = env.astype(F)
+    if not (np.isfinite(env).all() and (env >= 0).all()):
+        raise ValueError("environment map: every value finite and >= 0")
+    return env
+
+
+def environment_from_latlong(img: np.ndarray, n: int) -> np.ndarray:
+    """Resample a latitude-longitude radiance image [h, w, 3] (y up: row 0 is the zenith, the last row the nadir; column 0 is the
+    direction -z, the azimuth atan2(x, -z) grows with the column) to an n x n octahedral map, float32 [n, n, 3] indexed [j, i].
+    Every texel takes the bilinear sample of the image at its centre's direction (wrapping in azimuth, clamping at the poles).  A host-side
+    convenience in float64, not part of the bit-exact contract; a map much smaller than the image undersamples it (shrink the image first)."""
+    img = np.asarray(img, np.float64)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("a lat-long image is (h, w, 3)")
+    h, w = img.shape[:2]
+    d = octahedral_directions(n)
+    u = (np.arctan2(d[..., 0], -d[..., 2]) / (2.0 * np.pi)) % 1.0 * w - 0.5
+    v = np.arccos(np.clip(d[..., 1], -1.0, 1.0)) / np.pi * h - 0.5
+    u0, v0 = np.floor(u), np.floor(v)
+    fu, fv = (u - u0)[..., None], (v - v0)[..., None]
+    x0, x1 = u0.astype(np.int64) % w, (u0.astype(np.int64) + 1) % w
+    y0, y1 = np.clip(v0.astype(np.int64), 0, h - 1), np.clip(v0.astype(np.int64) + 1, 0, h - 1)
+    env = (img[y0, x0] * (1 - fu) + img[y0, x1] * fu) * (1 - fv) + (img[y1, x0] * (1 - fu) + img[y1, x1] * fu) * fv
+    return np.maximum(env, 0.0).astype(F)
+
+
+def write_environment(path, env: np.ndarray) -> None:
+    """Environment file, a file of its own beside the scene file: 'SPEN', n, n * n * 3 float32 (texel (i, j) at [(j * n + i) * 3])."""
+    env = np.ascontiguousarray(env, dtype=F)
+    if env.ndim != 3 or env.shape[0] != env.shape[1] or env.shape[2] != 3:
+        raise ValueError("an environment map is (n, n, 3)")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", ENV_MAGIC, env.shape[0]))
+        f.write(env.tobytes())
 
 
 def vertex_normals(tris: np.ndarray, crease_deg: float = 180.0, which=None) -> np.ndarray:
