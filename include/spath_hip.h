@@ -142,9 +142,9 @@ const char* sphip_kernel_name(int variant);         /* NULL when the variant doe
 const char* sphip_build_info(void);                 /* "src=<16 hex digits>": hash of the sources and compiler flags this library was built
                                                        from (__graft_entry__.source_hash), "src=unknown" for a hand-made build; profiler-derived
                                                        figures under profiles/ carry the same stamp */
-int  sphip_kernel_available(int variant);           /* 1 when this build of the library carries the variant (the shipped build: the
-                                                       default scan, the exact-only scans, one f32 filter scan for A/B runs and the
-                                                       opt-in BVH; -DSP_ALL_VARIANTS builds: every generation), else 0 */
+int  sphip_kernel_available(int variant);           /* 1 when the library carries the variant (1 and 2, the exact-only scans; 8, the
+                                                       opt-in BVH; 15, one f32 filter scan for A/B runs; 16, the default scan), else 0:
+                                                       the numbers of the retired scans keep their names and are refused */
 
 /* ---- host-pointer path: exactly what renderer::render / render_flat receive
  * (src/renderer.h:31-32): borrowed host arrays, valid only during the call; blocking. */
@@ -369,8 +369,8 @@ int  sphip_accum_gbuffer(sphip_t* ctx, void* out_gbuf);
 int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba, float* out_rgb /* or NULL */);
 
 /* ---- next-event estimation (SPHIP_FLAG_NEE): at each of the first four surface hits of a path, one light
- * sample and one shadow ray.  Valid for SPHIP_MODE_PT on every render and accumulation entry point and with the shipped variants 1,
- * 2, 8 (SPHIP_FLAG_ACCEL), 15 and 16 (SPHIP_E_INVALID with a variant of -DSP_ALL_VARIANTS builds); flat and hit queries ignore it.
+ * sample and one shadow ray.  Valid for SPHIP_MODE_PT on every render and accumulation entry point and with the variants 1,
+ * 2, 8 (SPHIP_FLAG_ACCEL), 15 and 16, every one the library carries (a retired number is SPHIP_E_INVALID with or without the flag); flat and hit queries ignore it.
  * Every operation below is f32 unless marked double; dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
  *
  * Paths: the same closest hits and BSDF directions as without the flag (philox_uniforms(seed, pixel, sample, depth)), but at most

@@ -260,8 +260,8 @@ def build_source_hash() -> str:
 
 
 def available_variants():
-    """ids (> 0) of the kernel variants THIS build of the library carries (the shipped build leaves the earlier filter
-    generations out; a -DSP_ALL_VARIANTS build has them all)."""
+    """ids (> 0) of the kernel variants the library carries: 1, 2, 8, 15, 16 (the numbers of the earlier filter generations
+    keep their names and are refused)."""
     L = load()
     ids = sorted(v for v in kernel_variants().values() if v > 0)
     if not hasattr(L, "sphip_kernel_available"):

@@ -1,11 +1,12 @@
-// Two-stage closest-hit scan, second generation ("rpl_cyl"): a 7-instruction conservative reject per (ray, triangle),
+// Two-stage closest-hit scan with f32 arithmetic ("rpl_cylw4s"): a 7-instruction conservative reject per (ray, triangle),
 // survivors remembered as ONE BIT per (4-triangle group, ray) in a per-lane register word, the reference's exact
-// Moeller-Trumbore (ray_tri_strict) for the bits that are set.  Bit-identical results.
+// Moeller-Trumbore (ray_tri_strict) for the bits that are set.  Bit-identical results.  The record builder, CylRay and
+// cyl_setup below also serve the default scan (sp_cylm_scan.h).
 //
-// Stage 1.  sp_filter_scan.h rejects a pair when the ray misses the slab spanned by the triangle's longest edge and
-// the parallel line through the opposite vertex:  |gm| - |t| > Dq  with  gm = w.P - dir.Mc  (6 multiply-adds),
+// Stage 1.  The slab test of DESIGN.md section 4.1 rejects a pair when the ray misses the slab spanned by the triangle's
+// longest edge and the parallel line through the opposite vertex:  |gm| - |t| > Dq  with  gm = w.P - dir.Mc  (6 multiply-adds),
 // t = dir.h (3), P = pos x dir, w = unit(longest edge), Mc = w x (mid-point of the two lines' anchors), h = w x
-// (their half-difference); DESIGN.md section 4 proves that this never rejects a pair geom::ray_intersect accepts
+// (their half-difference); that section proves that this never rejects a pair geom::ray_intersect accepts
 // (geom.h:197-222).  Here |t| is replaced by an upper bound that costs one multiply-add instead of three,
 //     |t| = |dir.h| <= |dir|_2 |h|_2 =: D * H          (H per triangle, D per ray, both rounded up),
 //     reject  <=>  |gm| - H*D > Dq,
@@ -18,15 +19,12 @@
 // lexicographically -- the same closest hit and the same tie rule as "ascending index, first strictly smaller d wins"
 // (cpu_renderer.cpp:39-49).
 //
-// Survivor bookkeeping.  About twice as many pairs survive the cylinder test as the slab test (0.5 % against 0.24 % at
-// BASELINE configs[2]), and in the first generation it was the bookkeeping, not the arithmetic, that cost: a wave-level
-// branch per 8 pairs, taken 70 % of the time, with eight compare-and-push blocks behind it, and an LDS queue per lane.
-// Here each lane folds the four x = |gm| - H*D of a group into their minimum, subtracts the margin and shifts the SIGN
-// BIT of the difference into a 32-bit word (v_min3_f32, v_min_f32, v_sub_f32, v_alignbit_b32: one instruction per pair,
-// no branch, no VCC).  At the end of a tile the set bits are resolved (stage 2): the group's four records are re-read, the four x
-// recomputed, ray_tri_strict run on each survivor -- by the lane that owns the ray (scan_cyl: 1-2 rays per lane), or by whichever
-// lane of the wave is free (scan_cylw further down: 4 rays per lane, the default).  There is no queue, hence no overflow: a scene
-// of huge triangles degrades smoothly to the exact-only scan.
+// Survivor bookkeeping.  Each lane folds the four x = |gm| - H*D of a group into their minimum, subtracts the margin and
+// shifts the SIGN BIT of the difference into a 32-bit word (v_min3_f32, v_min_f32, v_sub_f32, v_alignbit_b32: one
+// instruction per pair, no branch, no VCC).  At the end of a tile the set bits are resolved (stage 2, scan_cylw further
+// down): the group's four records are re-read, the four x recomputed and ray_tri_strict run on each survivor, by whichever
+// lane of the wave is free.  There is no queue, hence no overflow: a scene of huge triangles degrades smoothly to the
+// exact-only scan.
 //
 // record: 6 floats + the index (class a, with (a,b,c) a cyclic rotation of (x,y,z)):
 //   q0 = w_b/w_a  w_c/w_a  Mc.x/w_a  Mc.y/w_a        (Mc.z/w_a, H/|w_a|)        bits(original index)
@@ -37,18 +35,26 @@
 #pragma once
 
 #include "sp_kernels.h"
-#include "sp_filter_scan.h"
+
+#ifndef SP_PT_WAVES
+#define SP_PT_WAVES 4      // occupancy target (waves per SIMD) of the path-trace kernel: 4 workgroups of 36 KB LDS per CU
+#endif
 
 namespace sp {
+
+template <int R>
+struct RaySlots {
+	f3 o[R], dir[R];
+	int src[R];
+	bool act[R];
+};
 
 #ifndef SP_CYL_TILE
 #define SP_CYL_TILE 384
 #endif
-// Triangles per LDS tile.  Stage 2 runs once per tile; with the per-lane form it lasts as long as the lane with the most set bits
-// needs, and the maximum over 64 lanes of a count grows more slowly than its mean, so larger tiles mean fewer stage-2 rounds per
-// triangle (measured, 4 rays per lane: 12.85 rounds per 256 triangles with 256-triangle tiles, 12.09 with 384); the wave-shared
-// form fills its 64-entry rounds better with more entries per slot.  384 x 32 B, double-buffered, plus the bit words of scan_cyl
-// (12 KB at 4 rays per lane) or the lists and best-hit cells of scan_cylw (14 KB) is what four workgroups per CU can afford.
+// Triangles per LDS tile.  Stage 2 runs once per tile and slot, and the wave-shared stage 2 fills its 64-entry rounds better with
+// more entries per slot.  384 x 32 B, double-buffered, plus the lists and best-hit cells of scan_cylw (14 KB) is what four
+// workgroups per CU can afford.
 constexpr uint32_t kCylTile = SP_CYL_TILE;
 static_assert(kCylTile % 128 == 0, "whole waves per LDS-DMA pass, whole words of group bits");
 constexpr uint32_t kCylTileQ = 2u * kCylTile;     // float4 per tile
@@ -100,7 +106,7 @@ SP_DEV int cyl_record(const float* __restrict__ t, uint32_t idx, float4& q0, flo
 	const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2];
 	const double l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
 	const double lc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-	// narrowest slab = along the longest edge (sp_filter_scan.h, k_repack_filter)
+	// narrowest slab = along the longest edge
 	const double* w3; const double* p0; const double* p1; double len2;
 	if (l2 >= l1 && l2 >= lc) { w3 = e2; p0 = A; p1 = B; len2 = l2; }
 	else if (l1 >= lc)        { w3 = e1; p0 = A; p1 = C; len2 = l1; }
@@ -236,10 +242,10 @@ template <int R>
 struct CylRay {            // per-slot filter state
 	float Pa[R], Pb[R], Pc[R];     // ray moment pos x dir, rotated to the current class
 	float ndx[R], ndy[R], ndz[R];  // -dir
-	float D[R], Dq[R];             // |dir|_2 rounded up; margin (sp_filter_scan.h) a hair above, or +-inf
+	float D[R], Dq[R];             // |dir|_2 rounded up; margin a hair above, or +-inf
 };
 
-// per-slot filter state of the R rays of a lane (shared by scan_cyl and scan_cylw)
+// per-slot filter state of the R rays of a lane (shared by scan_cylw and scan_cylm)
 template <int R>
 SP_DEV void cyl_setup(float rv, const RaySlots<R>& s, CylRay<R>& f) {
 #pragma unroll
@@ -264,156 +270,10 @@ SP_DEV void cyl_setup(float rv, const RaySlots<R>& s, CylRay<R>& f) {
 	}
 }
 
-// Closest hit for the R rays of every lane.  Block-uniform call (barriers inside).
-template <int R>
-SP_DEV void scan_cyl(const KArgs& a, const CylStream cs, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R]) {
-	__shared__ float4 sm[2 * kCylTileQ];
-	static_assert(R == 1 || R == 2 || R == 4, "bits per group must divide 32");
-	constexpr uint32_t kGPW = 32u / R;                 // groups of 4 triangles per 32-bit word
-	constexpr int kNW = (int)((kCylTile / 4u) / kGPW);   // words per tile
-	// the tile's bit words, [word][thread]: written once per word by the hot loop, read back by stage 2 when a lane moves on to
-	// its next non-empty word (in registers they would have to be picked and cleared through select cascades)
-	__shared__ uint32_t wq[kNW * 256];
-	const uint32_t tid = threadIdx.x;
-	const uint32_t wbase = tid & ~63u;
-
-	CylRay<R> f;
-	cyl_setup<R>(rv, s, f);
-#pragma unroll
-	for (int r = 0; r < R; ++r) { bd[r] = kMaxDist; bi[r] = -1; }
-
-	// the stream is one run of tiles: class 0's, then class 1's, then class 2's (each class starts on a tile boundary)
-	const uint32_t total_tiles = cs.hdr[6];
-	uint32_t cls = 0;
-	__syncthreads();                                  // readers of the previous scan are done with sm
-	cyl_tile_dma(cs.rec, sm, tid, wbase);
-	__syncthreads();                                  // (the barrier's fence waits for the DMA: vmcnt(0))
-	for (uint32_t gt = 0; gt < total_tiles; ++gt) {
-		// entering the next class: rotate the moment so that the class's dominant axis sits in Pa (wave-uniform)
-		while (cls < 2u && gt >= cs.hdr[4 + cls]) {
-#pragma unroll
-			for (int r = 0; r < R; ++r) { const float t0 = f.Pa[r]; f.Pa[r] = f.Pb[r]; f.Pb[r] = f.Pc[r]; f.Pc[r] = t0; }
-			++cls;
-		}
-		const float4* cur = sm + (gt & 1u) * kCylTileQ;
-		const uint32_t left = cs.hdr[cls] - (gt - cs.hdr[3 + cls]) * kCylTile;
-		const uint32_t ngroups = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((left < kCylTile ? left : kCylTile) + 3u) / 4u));   // a scalar loop bound
-		// ---- stage 1: one bit per (group, slot); the first group ends up in the most significant bits
-		uint32_t nz = 0;                                  // bit wi: this lane's word wi has a bit set
-		uint32_t g = 0;
-#pragma unroll
-		for (int wi = 0; wi < kNW; ++wi) {
-			uint32_t wv = 0;
-			const uint32_t gend = ngroups < (uint32_t)(wi + 1) * kGPW ? ngroups : (uint32_t)(wi + 1) * kGPW;
-			const uint32_t g0 = g;
-			for (; g < gend; ++g) {
-				const CylGroup G = cyl_group(cur, g);
-#pragma unroll
-				for (int r = 0; r < R; ++r) {
-					float x[4];
-#pragma unroll
-					for (int u = 0; u < 4; ++u) x[u] = cyl_x(G.q0[u], cyl_mz(G, u), cyl_h(G, u), f.Pa[r], f.Pb[r], f.Pc[r], f.ndx[r], f.ndy[r], f.ndz[r], f.D[r]);
-					const float m = __builtin_fminf(__builtin_fminf(x[0], x[1]), __builtin_fminf(x[2], x[3]));
-					wv = __builtin_amdgcn_alignbit(wv, __float_as_uint(m - f.Dq[r]), 31);      // (wv << 1) | sign(m - Dq)
-				}
-			}
-			const uint32_t done = (g - g0) * R;                       // bits appended; left-align (wave-uniform shift)
-			const uint32_t wd = done == 0u ? 0u : (wv << (32u - done));
-			wq[wi * 256 + tid] = wd;
-			nz |= (wd != 0u ? 1u : 0u) << wi;
-		}
-		// the next tile streams in while the survivors are resolved
-		if (gt + 1u < total_tiles) cyl_tile_dma(cs.rec + (size_t)(gt + 1u) * kCylTileQ, sm + ((gt + 1u) & 1u) * kCylTileQ, tid, wbase);
-#ifdef SP_FILTER_STATS
-		uint32_t st_bits = 0, st_rounds = 0, st_exact = 0;      // experiment build only -> a.scans[1..4]
-#pragma unroll
-		for (int wi = 0; wi < kNW; ++wi) st_bits += (uint32_t)__builtin_popcount(wq[wi * 256 + tid]);
-#endif
-		// ---- stage 2: every lane walks its set bits; one exact test per lane and round
-		uint32_t sub = 0;                                 // candidates of the current group already done (bit u)
-		uint32_t wid = nz ? (uint32_t)__builtin_ctz(nz) : 0u;      // current word of this lane and what is left of it
-		uint32_t curw = nz ? wq[wid * 256 + tid] : 0u;
-		for (;;) {
-			if (!__any(nz != 0u)) break;
-#ifdef SP_FILTER_STATS
-			++st_rounds;
-#endif
-			if (nz != 0u) {
-				// the lane's following non-empty word, requested now and used at the end of the round if the current one runs out
-				// (branch-free on purpose: a conditional reload makes the compiler nest the loop, and lanes then wait for
-				// each other at word boundaries)
-				const uint32_t nz2 = nz & (nz - 1u);
-				const uint32_t wid2 = nz2 ? (uint32_t)__builtin_ctz(nz2) : 0u;
-				const uint32_t nextw = wq[wid2 * 256 + tid];
-				const uint32_t e = (uint32_t)__builtin_clz(curw);             // first set bit: entry within the word
-				const uint32_t grp = wid * kGPW + e / R;
-				const int slot = (int)(e % R);
-				float Pa = f.Pa[0], Pb = f.Pb[0], Pc = f.Pc[0], ndx = f.ndx[0], ndy = f.ndy[0], ndz = f.ndz[0], D = f.D[0], Dq = f.Dq[0];
-				float ox = s.o[0].x, oy = s.o[0].y, oz = s.o[0].z;
-				float dx = s.dir[0].x, dy = s.dir[0].y, dz = s.dir[0].z;
-				int src = s.src[0];
-				float best = bd[0]; int besti = bi[0];
-#pragma unroll
-				for (int r = 1; r < R; ++r) {
-					const bool pick = (slot == r);
-					Pa = pick ? f.Pa[r] : Pa; Pb = pick ? f.Pb[r] : Pb; Pc = pick ? f.Pc[r] : Pc;
-					ndx = pick ? f.ndx[r] : ndx; ndy = pick ? f.ndy[r] : ndy; ndz = pick ? f.ndz[r] : ndz;
-					D = pick ? f.D[r] : D; Dq = pick ? f.Dq[r] : Dq;
-					ox = pick ? s.o[r].x : ox; oy = pick ? s.o[r].y : oy; oz = pick ? s.o[r].z : oz;
-					dx = pick ? s.dir[r].x : dx; dy = pick ? s.dir[r].y : dy; dz = pick ? s.dir[r].z : dz;
-					src = pick ? s.src[r] : src;
-					best = pick ? bd[r] : best; besti = pick ? bi[r] : besti;
-				}
-				// the group's four records (per-lane LDS address) and their x again; the first survivor not yet done
-				uint32_t cand = 0; int idx = 0;
-				const CylGroup G = cyl_group(cur, grp);
-				const float4 gi = cur[cyl_slot(grp, 6u)];
-#pragma unroll
-				for (int u = 3; u >= 0; --u) {
-					const float x = cyl_x(G.q0[u], cyl_mz(G, u), cyl_h(G, u), Pa, Pb, Pc, ndx, ndy, ndz, D);
-					const bool sv = !(x - Dq >= 0.0f) && !((sub >> u) & 1u);      // the sign-bit decision again; NaN -> survivor
-					cand = sv ? (cand | (1u << u)) : cand;
-					idx = sv ? (int)__float_as_uint(u == 0 ? gi.x : u == 1 ? gi.y : u == 2 ? gi.z : gi.w) : idx;   // ends as the lowest surviving u's index
-				}
-				const uint32_t lowest = cand & (0u - cand);
-				const bool last = (cand == lowest);                             // no further survivor in this group
-				sub = last ? 0u : (sub | lowest);
-				curw = last ? (curw & ~(0x80000000u >> e)) : curw;
-				if (cand != 0u) {
-#ifdef SP_FILTER_STATS
-					++st_exact;
-#endif
-					const float4 x0 = a.scan[3 * (size_t)idx + 0], x1 = a.scan[3 * (size_t)idx + 1], x2 = a.scan[3 * (size_t)idx + 2];
-					const float d = ray_tri_strict(mk3(ox, oy, oz), mk3(dx, dy, dz), mk3(x0.x, x0.y, x0.z), mk3(x0.w, x1.x, x1.y), mk3(x1.z, x1.w, x2.x));
-					// ascending-index scan with "first strictly smaller d wins" (cpu_renderer.cpp:44) == lexicographic (d, index) minimum
-					const bool take = (d > 0.0f) && (idx != src) && ((d < best) || (d == best && idx < besti));
-					best = take ? d : best;
-					besti = take ? idx : besti;
-#pragma unroll
-					for (int r = 0; r < R; ++r) { const bool pick = (slot == r); bd[r] = pick ? best : bd[r]; bi[r] = pick ? besti : bi[r]; }
-				}
-				const bool adv = (curw == 0u);                                    // this word is done: on to the lane's next non-empty one
-				nz = adv ? nz2 : nz;
-				wid = adv ? wid2 : wid;
-				curw = adv ? nextw : curw;
-			}
-		}
-#ifdef SP_FILTER_STATS
-		{
-			uint32_t v = st_bits, x = st_exact;
-			for (int off = 32; off > 0; off >>= 1) { v += __shfl_xor(v, off, 64); x += __shfl_xor(x, off, 64); }
-			if ((tid & 63u) == 0) { atomicAdd(a.scans + 1, (unsigned long long)v); atomicAdd(a.scans + 2, (unsigned long long)st_rounds); atomicAdd(a.scans + 3, 1ull); atomicAdd(a.scans + 4, (unsigned long long)x); }
-		}
-#endif
-		__syncthreads();                        // next tile landed (vmcnt(0) in the fence) and this one is free again
-	}
-}
-
-
 // ---------------------------------------------------------------------------------------------------------------------
-// scan_cylw: the same stage 1, stage 2 shared by the whole WAVE.
+// scan_cylw: stage 2 shared by the whole WAVE.
 //
-// In scan_cyl a lane resolves only its own set bits, so a tile's stage 2 lasts as long as the busiest lane needs: 18 rounds per
+// Were a lane to resolve only its own set bits, a tile's stage 2 would last as long as the busiest lane needs: 18 rounds per
 // 384-triangle tile with 42 % of the lanes working (profiles/filter_stats.json).  Here the set bits of one slot (ray r of every
 // lane) are written out as a list of (lane, group) entries in LDS, and ALL 64 lanes take entries from that list, 64 per round:
 //   * the bit words are kept per slot (a group's R sign bits go to R different words: same one instruction per pair), so a

@@ -23,7 +23,7 @@
 // rounded once, has the sign of the exact value.  Stage 1 is where the vector ALU is the limit: the instruction is worth 4 - 5 %.
 //
 // Scaling.  Halves hold 6e-5 .. 65504, so both sides are scaled by EXACT powers of two: S = 2^k in [2Rv, 4Rv) for lengths
-// (Rv = the scene bound of sp_filter_scan.h), s_d = 2^-e for the ray direction (largest |dir| component in [1, 2) afterwards):
+// (Rv = the scene bound of DESIGN.md section 4.1), s_d = 2^-e for the ray direction (largest |dir| component in [1, 2) afterwards):
 //     triangle side:  16 b, 16 c, 16 Mc'/S          (|.| <= 16 and <= 14)         H^ = 256 H / S
 //     ray side:       16 s_d P/S, 16 s_d (-dir)     (|.| <= 2^15 and <= 32)       D^ = s_d D,  Dq^ = 256 s_d Dq / S      (all times t)
 // so that every term of gm^ is 256 s_d / S times the term of gm: the test |gm^| - H^ D^ > Dq^ is the test |gm| - H D > Dq.  A ray

@@ -1,18 +1,16 @@
 // Kernels over the two-stage scans: the closest-hit scan alone, renderer::render_flat, renderer::render.
-// SCAN = 0: sp_filter_scan.h (slab filter, per-lane LDS queues)     SCAN = 1: sp_cyl_scan.h (cylinder filter, bit words, stage 2 per lane)
-// SCAN = 2: sp_cyl_scan.h scan_cylw (the same stage 1, stage 2 shared by the wave)
+// SCAN = 2: sp_cyl_scan.h scan_cylw (cylinder filter in f32, bit words, stage 2 shared by the wave)
 // SCAN = 3: sp_cylm_scan.h scan_cylm (stage 1 on the f16 matrix pipe, one ray per lane, stage 2 shared by the wave), 256-thread workgroups
 // SCAN = 4: the same scan in 512-thread workgroups with 512-triangle tiles (larger scenes)
 #pragma once
 
-#include "sp_filter_scan.h"
 #include "sp_cyl_scan.h"
 #include "sp_cylm_both.h"
 
 namespace sp {
 
 struct ScanSrc {
-	const float4* filt;      // slab records (k_repack_filter)
+	const void* reserved;    // the retired slab records' slot, left null: the members behind it keep their kernel-argument offsets, so every kernel keeps its listing
 	CylStream cyl;           // cylinder records (k_cyl_scatter)
 	CylStream cylm;          // cylinder records + matrix fragments (k_cylm_scatter), in the tile size of the scan that reads them
 };
@@ -20,15 +18,13 @@ struct ScanSrc {
 // threads per workgroup of the kernels below: the matrix-pipe scan shares its (larger) tiles between 8 waves
 template <int SCAN> constexpr uint32_t scan_block() { return SCAN == 4 ? cylm512::kMThreads : 256u; }
 
-// tmax / shadow: the bounded and the any-hit (shadow ray) forms of scans 2-4 (sp_cylm_scan.h, scan_cylm); scans 0 and 1 have none
+// tmax / shadow: the bounded and the any-hit (shadow ray) forms of the scans (sp_cylm_scan.h, scan_cylm)
 template <int R, int SCAN, bool BOUNDED = false>
 SP_DEV void two_stage_scan(const KArgs& a, const ScanSrc& src, float rv, const RaySlots<R>& s, float (&bd)[R], int (&bi)[R],
                            const float* tmax = nullptr, bool shadow = false) {
 	if constexpr (SCAN == 4) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm512::scan_cylm<BOUNDED>(a, src.cylm, rv, s, bd, bi, tmax, shadow); }
 	else if constexpr (SCAN == 3) { static_assert(R == 1, "scan_cylm: one ray per lane"); cylm256::scan_cylm<BOUNDED>(a, src.cylm, rv, s, bd, bi, tmax, shadow); }
-	else if constexpr (SCAN == 2) scan_cylw<R, BOUNDED>(a, src.cyl, rv, s, bd, bi, tmax, shadow);
-	else if constexpr (SCAN == 1) scan_cyl<R>(a, src.cyl, rv, s, bd, bi);
-	else scan_filter<R>(a, src.filt, rv, s, bd, bi);
+	else { static_assert(SCAN == 2, "SCAN: 2, 3 or 4"); scan_cylw<R, BOUNDED>(a, src.cyl, rv, s, bd, bi, tmax, shadow); }
 }
 
 // ---- the closest-hit scan alone with a two-stage scan; R rays per lane

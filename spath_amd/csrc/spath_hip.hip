@@ -6,7 +6,6 @@
 // No exception crosses this boundary; every failure becomes a status + sphip_last_error().
 #include "spath_hip.h"
 #include "sp_kernels.h"
-#include "sp_filter_scan.h"
 #include "sp_cyl_scan.h"
 #include "sp_scan_kernels.h"
 #include "sp_bvh.h"
@@ -48,9 +47,9 @@ struct sphip_ctx {
 	int device = 0;
 	hipStream_t own_stream = nullptr;       // host-pointer path
 	hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_u0 = nullptr, ev_u1 = nullptr, ev_d0 = nullptr, ev_d1 = nullptr;
-	DevBuf tris, mats, scan, filt, bounds, samp, rays, rgba, accum, counter, work, bvh_nodes, bvh_rec, bvh_idx, sort_kv, sort_hist, bvh_meta, cyl_rec, cyl_cnt, cyl_hdr, prim, cylm_rec, cylm_hdr, cylm_big;
+	DevBuf tris, mats, scan, bounds, samp, rays, rgba, accum, counter, work, bvh_nodes, bvh_rec, bvh_idx, sort_kv, sort_hist, bvh_meta, cyl_rec, cyl_cnt, cyl_hdr, prim, cylm_rec, cylm_hdr, cylm_big;
 	// record streams beyond the exact one are derived from `tris` the first time a kernel variant that reads them runs on the scene
-	bool bvh_valid = false, filt_valid = false, cyl_valid = false, cylm_valid = false;
+	bool bvh_valid = false, cyl_valid = false, cylm_valid = false;
 	bool cylm_wide = false;                 // the stream in cylm_rec is laid out for the 512-thread shape of the default scan (sp_cylm_both.h)
 	uint32_t bvh_leaves = 0;
 	size_t n_tris = 0;
@@ -175,38 +174,35 @@ constexpr int kVariantAccel = 8;          // the opt-in acceleration structure (
 constexpr int kVariantLast = 16;
 constexpr uint64_t kChunkTargetBlocks = 262144;         // 256 x the 1024 resident workgroups (measured: profiles/r01_sample_chunks.log)
 constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sample scratch buffer
-const char* const kVariantNames[kVariantLast + 1] = { "auto", "rpl_sload", "rpl_lds", "rpl_filter2", "rpl_filter4", "rpl_filter1", "rpl_filter2s", "rpl_filter4s",
-                                                      "accel_lbvh", "rpl_cyl1", "rpl_cyl2", "rpl_cyl4", "rpl_cyl2s", "rpl_cyl4s", "rpl_cylw4", "rpl_cylw4s", "rpl_cylm" };
-
-// the two-stage scan variants: paths per lane (R), whether the R paths are consecutive samples of ONE pixel (split) or R
-// pixels, and the scan generation (0 = slab filter + LDS queues, sp_filter_scan.h; 1 = cylinder filter + bit words, sp_cyl_scan.h;
-// 2 = the same with stage 2 shared by the wave; 3 = stage 1 on the f16 matrix pipe, sp_cylm_scan.h: the default)
+// One row per variant number.  R = paths per lane of a two-stage scan (0: not one), split = the R paths are consecutive samples of
+// ONE pixel rather than R pixels, scan = the scan (2 = f32 cylinder filter, stage 2 shared by the wave, sp_cyl_scan.h; 3 = stage 1 on
+// the f16 matrix pipe, sp_cylm_scan.h: the default, with its 512-thread shape 4 set by launch_render).  The library carries the
+// exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15) and the default (16).  The slab-filter scans
+// (3-7) and the earlier cylinder scans (9-14) are retired: their numbers keep their names (sphip_kernel_name) and are refused.
 struct TwoStage { int R; bool split; int scan; };
-bool two_stage(int variant, TwoStage* out) {
-	static const TwoStage tab[kVariantLast + 1] = { {0, false, 0}, {0, false, 0}, {0, false, 0}, {2, false, 0}, {4, false, 0}, {1, false, 0}, {2, true, 0}, {4, true, 0},
-	                                                {0, false, 0}, {1, false, 1}, {2, false, 1}, {4, false, 1}, {2, true, 1}, {4, true, 1}, {4, false, 2}, {4, true, 2}, {1, false, 3} };
-	if (variant < 0 || variant > kVariantLast || tab[variant].R == 0) return false;
-	if (out) *out = tab[variant];
-	return true;
-}
-
-// The shipped library carries the exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15: <4, split, 2>)
-// and the default (16: <1, -, 3>, with its 512-thread shape <1, -, 4>).  The slab-filter generation and the per-lane cylinder variants
-// are compiled only with -DSP_ALL_VARIANTS (soak and experiment builds: tools/), and only without NEE, MIS and camera samples.
-constexpr bool shape_shipped(int R, bool split, int scan) { return scan >= 3 || (scan == 2 && R == 4 && split); }
-bool variant_shipped(int v) {
-	TwoStage ts;
-	return v == 1 || v == 2 || v == kVariantAccel || (two_stage(v, &ts) && shape_shipped(ts.R, ts.split, ts.scan));
-}
+struct Variant { const char* name; TwoStage ts; bool carried; };
+const Variant kVariants[kVariantLast + 1] = {
+	{ "auto",         {0, false, 0}, false },
+	{ "rpl_sload",    {0, false, 0}, true  },
+	{ "rpl_lds",      {0, false, 0}, true  },
+	{ "rpl_filter2",  {2, false, 0}, false },
+	{ "rpl_filter4",  {4, false, 0}, false },
+	{ "rpl_filter1",  {1, false, 0}, false },
+	{ "rpl_filter2s", {2, true,  0}, false },
+	{ "rpl_filter4s", {4, true,  0}, false },
+	{ "accel_lbvh",   {0, false, 0}, true  },
+	{ "rpl_cyl1",     {1, false, 1}, false },
+	{ "rpl_cyl2",     {2, false, 1}, false },
+	{ "rpl_cyl4",     {4, false, 1}, false },
+	{ "rpl_cyl2s",    {2, true,  1}, false },
+	{ "rpl_cyl4s",    {4, true,  1}, false },
+	{ "rpl_cylw4",    {4, false, 2}, false },
+	{ "rpl_cylw4s",   {4, true,  2}, true  },
+	{ "rpl_cylm",     {1, false, 3}, true  },
+};
+bool variant_carried(int v) { return v >= 1 && v <= kVariantLast && kVariants[v].carried; }
 // smooth shading is built for the exact scan, the BVH and the default scan (both shapes)
 bool variant_smooth(int v) { return v == 1 || v == kVariantAccel || v == 16; }
-bool variant_built(int v) {
-#ifdef SP_ALL_VARIANTS
-	return v >= 1 && v <= kVariantLast;
-#else
-	return variant_shipped(v);
-#endif
-}
 
 // the two-stage path-tracing kernels' work buffer, per work slot (sp_scan_kernels.h): the path history (5 x int2), the accumulator
 // (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adaptive sampling parks S1, S2 (2 doubles) in a buffer of its own (adp_wst)
@@ -235,7 +231,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	                   (const float*)c->tris.p, (float4*)c->scan.p, (unsigned int*)c->bounds.p, n, n_pad);
 	HIP_TRY(c, hipGetLastError());
 	c->have_scene = true;
-	c->bvh_valid = c->filt_valid = c->cyl_valid = c->cylm_valid = false;
+	c->bvh_valid = c->cyl_valid = c->cylm_valid = false;
 	c->nee_valid = false;
 	c->env_lights_valid = false;                   // w_env and tpdf follow the scene; the map itself stays
 	c->zero_rows = 0;
@@ -324,20 +320,6 @@ int ensure_cyl(sphip_ctx* c, hipStream_t st) {
 	c->cyl_valid = true;
 	return SPHIP_OK;
 }
-
-#ifdef SP_ALL_VARIANTS
-// ---- slab records of the first-generation scan (sp_filter_scan.h)
-int ensure_filt(sphip_ctx* c, hipStream_t st) {
-	if (c->filt_valid) return SPHIP_OK;
-	const uint32_t n = (uint32_t)c->n_tris, n_pad = (n / sp::kTile + 1) * sp::kTile;
-	int rc = ensure(c, c->filt, (size_t)n_pad * 48);
-	if (rc) return rc;
-	hipLaunchKernelGGL(sp::k_repack_filter, dim3((n_pad + 255) / 256), dim3(256), 0, st, (const float*)c->tris.p, (float4*)c->filt.p, n, n_pad);
-	HIP_TRY(c, hipGetLastError());
-	c->filt_valid = true;
-	return SPHIP_OK;
-}
-#endif
 
 // ---- linear BVH for SPHIP_FLAG_ACCEL (sp_bvh.h), built on the device (sp_bvh_build.h) the first time a scene is rendered with the flag
 int ensure_bvh(sphip_ctx* c, hipStream_t st) {
@@ -573,30 +555,18 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 // The one-scan kernels (k_hit_filter, k_flat_filter) take <R, SCAN> of the same shape.
 template <int R_, bool SPLIT_, int SCAN_> struct Shape {
 	static constexpr int R = R_, SCAN = SCAN_;
-	static constexpr bool SPLIT = SPLIT_, shipped = shape_shipped(R_, SPLIT_, SCAN_);
+	static constexpr bool SPLIT = SPLIT_;
 };
-template <int SCAN, typename F>
-void with_lane_shape(const TwoStage& ts, F&& f) {
-	if (ts.split) { if (ts.R == 4) f(Shape<4, true, SCAN>{}); else f(Shape<2, true, SCAN>{}); }
-	else if (ts.R == 4) f(Shape<4, false, SCAN>{});
-	else if (ts.R == 2) f(Shape<2, false, SCAN>{});
-	else f(Shape<1, false, SCAN>{});
-}
 template <typename F>
 void with_scan_shape(const TwoStage& ts, F&& f) {
 	if (ts.scan == 3) f(Shape<1, false, 3>{});
 	else if (ts.scan == 4) f(Shape<1, false, 4>{});
-	else if (ts.scan == 2 && ts.split) f(Shape<4, true, 2>{});
-#ifdef SP_ALL_VARIANTS
-	else if (ts.scan == 2) f(Shape<4, false, 2>{});
-	else if (ts.scan == 1) with_lane_shape<1>(ts, f);
-	else with_lane_shape<0>(ts, f);
-#endif
+	else f(Shape<4, true, 2>{});
 }
 
 // ---- the flag rules that launch_render and accum_begin share (a begin checks as a path-tracing render would: the step would
 // refuse as well, so it says so at once)
-// per-sample camera rays: path tracing behind a camera, with the shipped variants, without primary-hit reuse (the
+// per-sample camera rays: path tracing behind a camera, with the carried variants, without primary-hit reuse (the
 // primary ray is no longer shared by the samples); flat and hit queries ignore the flag
 int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_cam) {
 	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) return SPHIP_OK;
@@ -604,8 +574,8 @@ int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES needs a camera (sphip_render_camera, sphip_accum_begin[_adaptive] with cam), not rays");
 	if (flags & SPHIP_FLAG_PRIMARY_REUSE)
 		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES and SPHIP_FLAG_PRIMARY_REUSE exclude each other (every sample has its own primary ray)");
-	if (!variant_shipped(variant))
-		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+	if (!variant_carried(variant))
+		return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_CAMERA_SAMPLES is not available with kernel variant %d (%s)", variant, kVariants[variant].name);
 	return SPHIP_OK;
 }
 
@@ -613,7 +583,7 @@ int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_
 // A/B scans).  Path tracing with the plain estimator or with NEE|MIS, with the feature's variants, once its table is set; the flat pass
 // has no use for them and says so; hit queries ignore the flags
 struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; };
-const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_shipped, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
+const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_carried, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
 const TableRule kSmoothRule{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" };
 const TableRule kGlassRule{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" };
 // environment lighting follows the same rules with the context's map for a table
@@ -623,7 +593,7 @@ int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, i
 	if (mode == SPHIP_MODE_FLAT) return fail(c, SPHIP_E_INVALID, "%s is valid for SPHIP_MODE_PT only", r.flag);
 	if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
 		return fail(c, SPHIP_E_INVALID, "%s works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone", r.flag);
-	if (!r.variant_ok(variant)) return fail(c, SPHIP_E_INVALID, "%s is not available with kernel variant %d (%s)", r.flag, variant, kVariantNames[variant]);
+	if (!r.variant_ok(variant)) return fail(c, SPHIP_E_INVALID, "%s is not available with kernel variant %d (%s)", r.flag, variant, kVariants[variant].name);
 	if (!(c->*r.have)) return fail(c, SPHIP_E_STATE, "%s needs %s", r.flag, r.needs);
 	return SPHIP_OK;
 }
@@ -682,17 +652,17 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	const int variant = pick_variant(flags, c->n_tris);
 	if (variant == 16 && c->n_tris >= (1ull << sp::kMIdxBits))
 		return fail(c, SPHIP_E_INVALID, "rpl_cylm handles scenes of fewer than 2^%u triangles (this one has %zu); use rpl_cylw4s", sp::kMIdxBits, c->n_tris);
-	if (!variant_built(variant))
-		return fail(c, SPHIP_E_INVALID, "kernel variant %d (%s) is not compiled into this build of libspath_hip (rebuild with -DSP_ALL_VARIANTS)", variant, kVariantNames[variant]);
-	// next-event estimation: path tracing with the shipped variants only (the bounded scans); flat and hit queries ignore the flag.
+	if (!variant_carried(variant))
+		return fail(c, SPHIP_E_INVALID, "kernel variant %d (%s) is retired: libspath_hip no longer carries it", variant, kVariants[variant].name);
+	// next-event estimation: path tracing with the carried variants only (the bounded scans); flat and hit queries ignore the flag.
 	// MIS is a form of it: without SPHIP_FLAG_NEE the flag is an error
 	const bool nee = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_NEE);
 	const bool mis = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_MIS);
 	if (mis && !nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	sp::NeeArgs ne{};
 	if (nee) {
-		if (!variant_shipped(variant))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_NEE is not available with kernel variant %d (%s)", variant, kVariantNames[variant]);
+		if (!variant_carried(variant))
+			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_NEE is not available with kernel variant %d (%s)", variant, kVariants[variant].name);
 		if ((rc = ensure_lights(c, st))) return rc;
 		ne.cdf = (const double*)c->nee_tab.p;
 		ne.tri = (const int*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 8);
@@ -735,8 +705,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
 	// together), so small frames and multi-GPU shards are split along the samples as well
 	uint32_t chunks = 1;
-	TwoStage ts{1, false, 0};
-	const bool is_ts = two_stage(variant, &ts);
+	TwoStage ts = kVariants[variant].ts;
+	const bool is_ts = ts.R != 0;
 	const uint32_t slots = is_ts && ts.split ? (uint32_t)ts.R : 1u;                       // samples of one pixel per lane
 	// the record stream the variant reads, derived from the scene on first use
 	if (is_ts && ts.scan == 3 && (rc = ensure_cylm(c, st))) return rc;
@@ -800,11 +770,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		ena.M = (float*)c->env_M.p;
 	}
 	sp::ScanSrc src2{};
-	if (is_ts && (ts.scan == 1 || ts.scan == 2) && (rc = ensure_cyl(c, st))) return rc;
-#ifdef SP_ALL_VARIANTS
-	if (is_ts && ts.scan == 0 && (rc = ensure_filt(c, st))) return rc;
-#endif
-	src2.filt = (const float4*)c->filt.p;
+	if (is_ts && ts.scan == 2 && (rc = ensure_cyl(c, st))) return rc;
 	src2.cyl.rec = (const float4*)c->cyl_rec.p;
 	src2.cyl.hdr = (const uint32_t*)c->cyl_hdr.p;
 	src2.cylm.rec = (const float4*)c->cylm_rec.p;
@@ -871,11 +837,8 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 		with_scan_shape(ts, [&](auto shape) {
 			using S = decltype(shape);
 			pt_pack([&](const auto&... p) {
-				// NEE (the bounded scans), MIS, camera samples and specular reflection are built for the shipped shapes only (checked above),
-				// smooth shading for the default scan's two shapes
-				if constexpr ((S::shipped || !(sp::IsNee<std::decay_t<decltype(p)>...>::value || sp::IsCam<std::decay_t<decltype(p)>...>::value ||
-				                               sp::IsSpec<std::decay_t<decltype(p)>...>::value)) &&
-				              (S::SCAN >= 3 || !(sp::IsNorm<std::decay_t<decltype(p)>...>::value || sp::IsGlass<std::decay_t<decltype(p)>...>::value)))
+				// smooth shading and transparency are built for the default scan's two shapes only (checked above)
+				if constexpr (S::SCAN >= 3 || !(sp::IsNorm<std::decay_t<decltype(p)>...>::value || sp::IsGlass<std::decay_t<decltype(p)>...>::value))
 					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
 					                   a, src2, bnd, hist, acc, n_work, p...);
 			});
@@ -1635,7 +1598,7 @@ int sphip_abi_version(void) { return SPHIP_ABI_VERSION; }
 
 const char* sphip_kernel_name(int variant) {
 	if (variant < 0 || variant > kVariantLast) return nullptr;
-	return kVariantNames[variant];
+	return kVariants[variant].name;
 }
 
 #ifndef SP_SOURCE_HASH
@@ -1643,7 +1606,7 @@ const char* sphip_kernel_name(int variant) {
 #endif
 const char* sphip_build_info(void) { return "src=" SP_SOURCE_HASH; }
 
-int sphip_kernel_available(int variant) { return variant_built(variant) ? 1 : 0; }
+int sphip_kernel_available(int variant) { return variant_carried(variant) ? 1 : 0; }
 
 int sphip_plan_tile_rows(size_t height, int n_devices) {
 	if (height == 0 || n_devices < 1) return SPHIP_E_INVALID;
@@ -2455,13 +2418,10 @@ int sphip_get_stats(sphip_t* c, sphip_stats* out) {
 	{
 		unsigned long long x[6] = {0, 0, 0, 0, 0, 0};
 		(void)hipMemcpy(x, c->counter.p, sizeof x, hipMemcpyDeviceToHost);
-		if (c->stats.kernel_variant >= 9)
+		if (c->stats.kernel_variant >= 15)
 			fprintf(stderr, "[cyl stats] group bits set=%llu stage-2 rounds(per wave)=%llu wave-tiles=%llu exact tests=%llu -> bits/lane/tile=%.3f rounds/tile=%.2f exact per bit=%.3f lane utilisation in stage 2=%.3f wave-wide exact turns=%llu (%.2f per round, %.3f of their lanes used)\n",
 			        x[1], x[2], x[3], x[4], (double)x[1] / (64.0 * (double)x[3]), (double)x[2] / (double)x[3], (double)x[4] / (double)x[1], (double)x[4] / (64.0 * (double)x[2]),
 			        x[5], (double)x[5] / (double)x[2], (double)x[4] / (64.0 * (double)x[5]));
-		else
-		fprintf(stderr, "[filter stats] survivors=%llu rounds(sum of per-wave max)=%llu wave_flushes=%llu overflows=%llu -> survivors/lane/flush=%.3f rounds/flush=%.2f\n",
-		        x[1], x[2], x[3], x[4], (double)x[1] / (64.0 * (double)x[3]), (double)x[2] / (double)x[3]);
 	}
 #endif
 	c->stats.n_devices = 1; c->stats.gather_kind = SPHIP_GATHER_NONE; c->stats.gather_ms = 0.0; c->stats.kernel_ms_min = c->stats.kernel_ms;

@@ -28,10 +28,12 @@ def test_library_exports_every_declared_symbol():
     assert L.sphip_kernel_name(0) == b"auto" and L.sphip_kernel_name(99) is None
     names = capi.kernel_variants()
     assert set(names) >= {"auto", "rpl_sload", "rpl_lds", "rpl_filter2", "rpl_cyl2s", "rpl_cyl4s", "rpl_cylw4s", "rpl_cylm"}
-    # what the shipped build carries: the exact-only scans, the opt-in BVH, one f32 filter scan for A/B runs, the default
+    # what the library carries: the exact-only scans, the opt-in BVH, one f32 filter scan for A/B runs, the default -- and nothing else
     have = set(capi.available_variants())
-    assert have >= {names["rpl_sload"], names["rpl_lds"], names["accel_lbvh"], names["rpl_cylw4s"], names["rpl_cylm"]}
+    assert have == {names["rpl_sload"], names["rpl_lds"], names["accel_lbvh"], names["rpl_cylw4s"], names["rpl_cylm"]} == {1, 2, 8, 15, 16}
     assert L.sphip_kernel_available(0) == 0 and L.sphip_kernel_available(99) == 0
+    for retired in (3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14):          # the numbers keep their names and are refused
+        assert L.sphip_kernel_available(retired) == 0, retired
 
 
 def test_no_device_is_a_loud_error_not_a_fallback():

@@ -46,7 +46,7 @@ def strict(pos, d, v0, v1, v2):
 
 
 def filter_g(pos, d, w, p0, p1):
-    """k_repack_filter + slab_survives arithmetic: mid-line records rounded to float32, gm and t by FMA chains."""
+    """The slab test of DESIGN.md section 4.1 in float32: mid-line records rounded to float32, gm and t by FMA chains."""
     wn = (w / np.linalg.norm(w, axis=1, keepdims=True)).astype(F)
     wd = wn.astype(np.float64)
     p0d, p1d = p0.astype(np.float64), p1.astype(np.float64)
@@ -99,7 +99,7 @@ def test_error_model_and_conservativeness():
     }
     e1d, e2d = e1.astype(np.float64), e2.astype(np.float64)
     l1, l2, lc = (e1d ** 2).sum(1), (e2d ** 2).sum(1), (c ** 2).sum(1)
-    chosen = np.where((l2 >= l1) & (l2 >= lc), "u", np.where(l1 >= lc, "v", "w"))      # k_repack_filter's rule: the longest edge
+    chosen = np.where((l2 >= l1) & (l2 >= lc), "u", np.where(l1 >= lc, "v", "w"))      # cyl_record's rule: the longest edge
     seen = 0
     for name, (w, p0, p1, x0, x1, bound_u) in slabs.items():
         gm, t = filter_g(pos, d, w.astype(F), p0, p1)
@@ -116,7 +116,7 @@ def test_error_model_and_conservativeness():
         assert r0.max() < bound_u and r1.max() < bound_u, (name, r0.max(), r1.max())
         assert max(r0.max(), r1.max()) < 12.0, (name, r0.max(), r1.max())     # in practice an order of magnitude below the bound
         with np.errstate(all="ignore"):
-            reject = (np.abs(gm) - np.abs(t)).astype(np.float64) > Dq          # float32 subtraction, as slab_survives does it
+            reject = (np.abs(gm) - np.abs(t)).astype(np.float64) > Dq          # float32 subtraction, as DESIGN.md section 4.1 has it
         assert not (reject & acc & ok).any(), (name, int((reject & acc & ok).sum()))
         assert reject[ok].mean() > 0.1                                        # and it does reject
         print(f"slab {name}: {int(ok.sum())} pairs, max discrepancy {max(r0.max(), r1.max()):.2f} u (bound {bound_u:.0f} u), "
@@ -125,7 +125,7 @@ def test_error_model_and_conservativeness():
 
 
 def test_longest_edge_choice_matches_kernel_rule():
-    """k_repack_filter: ties go to e2, then e1 (l2 >= l1 && l2 >= lc; else l1 >= lc)."""
+    """cyl_record: ties go to e2, then e1 (l2 >= l1 && l2 >= lc; else l1 >= lc)."""
     rng = np.random.default_rng(3)
     v0, v1, v2 = (rng.normal(size=(1000, 3)).astype(F) for _ in range(3))
     e1, e2 = (v1 - v0).astype(np.float64), (v2 - v0).astype(np.float64)

@@ -55,8 +55,7 @@ def test_4k_row_tile_slice_exact_scan_and_oracle(hip, O, n_tris, spp, band_px):
     assert np.array_equal(a_img, b_img) and np.array_equal(a_acc, b_acc)
     assert a_st["scans_executed"] == b_st["scans_executed"]
     assert abs(a_st["scans_executed"] - n * spp * 5) <= 2e-4 * n * spp * 5      # closed room: nominal == executed up to edge leaks
-    # the other filter scans of the loaded build as well (shipped build: rpl_cylw4s, the f32 cylinder scan; -DSP_ALL_VARIANTS builds:
-    # the slab-filter scan and a per-lane cylinder scan too)
+    # the other filter scans of the loaded library as well (rpl_cylw4s, the f32 cylinder scan; the retired numbers are skipped)
     have = set(capi.available_variants())
     for var in [v for v in (6, 15, 13 if spp >= 4 else 12) if v in have]:
         c_img, c_acc, c_st = _render_shard(hip, d_rays, n, shard, w, spp, seed, var)

@@ -159,7 +159,7 @@ def test_error_contract():
     c = hc.ctx(t, m0)
     img = c.render(rays, W, H, 2, seed=1, flags=capi.FLAG_NEE)
     assert not img.any()
-    # a variant of -DSP_ALL_VARIANTS builds only, or absent from this build
+    # a retired variant number
     with pytest.raises(RuntimeError, match=E_INVALID):
         c.render(rays, W, H, 2, seed=1, flags=capi.FLAG_NEE | 9)
     c.close()

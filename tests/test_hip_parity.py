@@ -19,10 +19,8 @@ from spath_amd.dist import RowTilePlan, ShardedRenderer
 pytestmark = pytest.mark.gpu
 
 ACCUM_LINF_TOLERANCE = 0.0          # float accumulators: exact
-# Every brute-force variant the loaded build carries (8 is the opt-in acceleration structure, tests/test_hip_accel.py).  The shipped
-# build: rpl_sload (1), rpl_lds (2), rpl_cylw4s (15: f32 cylinder filter, wave-shared stage 2), rpl_cylm (16: the default, stage 1 on
-# the f16 matrix pipe).  A -DSP_ALL_VARIANTS build (tools/pytest_with_lib.py) adds the slab-filter scans 3-7 and the per-lane
-# cylinder scans 9-14.
+# Every brute-force variant the library carries (8 is the opt-in acceleration structure, tests/test_hip_accel.py): rpl_sload (1),
+# rpl_lds (2), rpl_cylw4s (15: f32 cylinder filter, wave-shared stage 2), rpl_cylm (16: the default, stage 1 on the f16 matrix pipe).
 VARIANTS = [v for v in capi.available_variants() if v != 8]
 TWO_STAGE = [v for v in VARIANTS if v >= 3]
 assert 16 in VARIANTS and 2 in VARIANTS

@@ -9,7 +9,7 @@ import bvh_model
 from spath_amd import capi, scene, view
 
 pytestmark = pytest.mark.gpu
-VARIANTS = [v for v in capi.available_variants() if v != 8]     # shipped build: 1, 2, 15, 16 (-DSP_ALL_VARIANTS: every generation)
+VARIANTS = [v for v in capi.available_variants() if v != 8]     # 1, 2, 15, 16
 
 
 def _hits(hip, O, t, rays, tag):

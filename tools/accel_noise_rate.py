@@ -30,12 +30,12 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 16):
     rays = np.concatenate([o, d], axis=1).astype(np.float32)
     d_r = torch.from_numpy(rays).cuda()
     out = {}
-    for name, fl in (("brute", 2), ("accel", capi.FLAG_ACCEL), ("cyl", 11), ("slab", 3)):
+    for name, fl in (("brute", 2), ("accel", capi.FLAG_ACCEL), ("cylm", 16), ("cylw", 15)):
         oi = torch.zeros(B, dtype=torch.int32, device="cuda"); od = torch.zeros(B, dtype=torch.float32, device="cuda")
         ctx.closest_hit_device(d_r.data_ptr(), B, oi.data_ptr(), od.data_ptr(), flags=fl); torch.cuda.synchronize()
         out[name] = (oi.cpu().numpy(), od.cpu().numpy())
     bi, bd = out["brute"]; ai, ad = out["accel"]
-    for name in ("cyl", "slab"):          # the two-stage scans of the product path must reproduce the exact scan in this regime too: bit for bit
+    for name in ("cylm", "cylw"):          # the two-stage scans of the product path must reproduce the exact scan in this regime too: bit for bit
         fi, fd = out[name]
         nbad = int(((fi != bi) | (fd.view(np.uint32) != bd.view(np.uint32))).sum())
         if nbad: print(f"  !!! two-stage scan {name} differs from the exact scan on {nbad} rays (family {it % 3})", flush=True)
@@ -55,5 +55,5 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 16):
         noise += int(outside)
         if dis <= 12:
             print(f"  ray {j}: brute ({bi[j]}, {bd[j]:.6g}) accel ({ai[j]}, {ad[j]:.6g}); brute-force point at barycentric ({uu:.4f}, {vv:.4f}), {off_plane:.3g} off the plane -> {'noise accept' if outside else 'GEOMETRIC HIT MISSED'}", flush=True)
-print(f"two-stage scans (cylinder filter rpl_cyl4, slab filter rpl_filter2) vs exact scan: {filt_bad} differing rays of {tot} x 2", flush=True)
+print(f"two-stage scans (rpl_cylm, rpl_cylw4s) vs exact scan: {filt_bad} differing rays of {tot} x 2", flush=True)
 print(f"{nt} triangles, {tot} rays: {dis} disagreements ({dis / tot:.3g} of the rays), {noise} of them noise accepts of the reference's float test, {dis - noise} geometric hits missed", flush=True)

@@ -1,4 +1,4 @@
-// Micro-benchmark: stage 1 of the two-stage closest-hit scan (sp_filter_scan.h: 9 multiply-adds + |gm|-|t| > Dq per
+// Micro-benchmark: stage 1 of the two-stage closest-hit scan (the slab test of DESIGN.md section 4.1: 9 multiply-adds + |gm|-|t| > Dq per
 // (ray, triangle)) on the FP32 matrix pipe instead of the VALU.
 //
 // v_mfma_f32_4x4x1_16B_f32 computes, for 16 blocks of 4 lanes, D[i][j] = A[i]*B[j] + C[i][j] (K = 1: one fused

@@ -11,7 +11,7 @@ from spath_amd import capi, scene, view
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2026)
 ctx = capi.Context(0)
-TWO = [v for v in capi.available_variants() if v >= 3 and v != 8]        # shipped build: 15, 16; -DSP_ALL_VARIANTS: every generation
+TWO = [v for v in capi.available_variants() if v >= 3 and v != 8]        # 15, 16
 names = {v: k for k, v in capi.kernel_variants().items()}
 
 

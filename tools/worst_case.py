@@ -11,7 +11,7 @@ d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 d_t, d_m, d_r = d(t), d(m), d(view.Camera(w, h).get_viewport())
 ctx.set_scene_device(d_t.data_ptr(), d_m.data_ptr(), nt, 0)
 names = {v: k for k, v in capi.kernel_variants().items()}
-for var in (16, 15, 12, 2):
+for var in (16, 15, 2):
     out = torch.zeros(w * h, 4, dtype=torch.uint8, device="cuda")
     for rep in range(2):
         ctx.render_device(d_r.data_ptr(), w * h, spp, out.data_ptr(), seed=1, flags=var); torch.cuda.synchronize()
