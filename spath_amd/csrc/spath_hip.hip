@@ -13,6 +13,7 @@
 #include "sp_adaptive.h"
 #include "sp_denoise.h"
 #include "sp_environment.h"
+#include "sp_host_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,7 @@
 #include <vector>
 
 namespace {
+using namespace sp_host;       // the launch plan and the light tables: what needs no device (sp_host_plan.h)
 
 thread_local std::string g_create_error;
 
@@ -92,9 +94,8 @@ struct sphip_ctx {
 	// buffers live on the first device, with the whole frame's rays gathered there for the G-buffer.
 	DevBuf dn_cls, dn_hit, dn_gbuf, dn_a, dn_b, dn_rays;
 	bool dn_cls_valid = false;                    // dropped by every set_scene
-	// ---- next-event estimation (SPHIP_FLAG_NEE): the scene's light table {double cdf[n]; int tri[n]; float ipdf[n]}, followed by
-	// MIS's pdf by triangle {float tipdf[n_tris]} (ipdf of the triangle's entry, 0 for a triangle not in the table), built on the host
-	// from a read-back on the first NEE render after a scene change; nee_bad: the scene has an invalid emittance (nee_msg says which)
+	// ---- next-event estimation (SPHIP_FLAG_NEE): the scene's light table (sp_host_plan.h: LightTable, laid out by pack_light_table), built on
+	// the host from a read-back on the first NEE render after a scene change; nee_bad: the scene has an invalid emittance (nee_msg says which)
 	DevBuf nee_tab;
 	bool nee_valid = false, nee_bad = false;      // nee_valid dropped by every set_scene
 	uint32_t nee_n = 0;
@@ -130,8 +131,7 @@ struct sphip_ctx {
 	// env_M: where the two-stage kernels park the miss term.  zero_rows: the triangles that spec_zero holds zeros for
 	DevBuf env_tab, env_M;
 	uint32_t env_nee_n = 0;
-	std::vector<double> nee_cdf_h, nee_esum_h;
-	std::vector<int> nee_tri_h;
+	sp_host::LightTable nee_host;                  // the host copy of nee_tab: what the flagged table is made from
 	size_t zero_rows = 0;
 };
 
@@ -172,14 +172,9 @@ int ensure(sphip_ctx* c, DevBuf& b, size_t bytes) {
 // kernel variants selectable through the low byte of `flags` (sphip_kernel_name); all brute force except 8
 constexpr int kVariantAccel = 8;          // the opt-in acceleration structure (SPHIP_FLAG_ACCEL)
 constexpr int kVariantLast = 16;
-constexpr uint64_t kChunkTargetBlocks = 262144;         // 256 x the 1024 resident workgroups (measured: profiles/r01_sample_chunks.log)
-constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sample scratch buffer
-// One row per variant number.  R = paths per lane of a two-stage scan (0: not one), split = the R paths are consecutive samples of
-// ONE pixel rather than R pixels, scan = the scan (2 = f32 cylinder filter, stage 2 shared by the wave, sp_cyl_scan.h; 3 = stage 1 on
-// the f16 matrix pipe, sp_cylm_scan.h: the default, with its 512-thread shape 4 set by launch_render).  The library carries the
-// exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15) and the default (16).  The slab-filter scans
-// (3-7) and the earlier cylinder scans (9-14) are retired: their numbers keep their names (sphip_kernel_name) and are refused.
-struct TwoStage { int R; bool split; int scan; };
+// One row per variant number, with its TwoStage shape (sp_host_plan.h; scan 3, the default, gets its 512-thread shape 4 from plan_render).
+// The library carries the exact-only scans (1, 2), the opt-in BVH (8), one f32 cylinder scan for A/B runs (15) and the default (16).  The
+// slab-filter scans (3-7) and the earlier cylinder scans (9-14) are retired: their numbers keep their names (sphip_kernel_name) and are refused.
 struct Variant { const char* name; TwoStage ts; bool carried; };
 const Variant kVariants[kVariantLast + 1] = {
 	{ "auto",         {0, false, 0}, false },
@@ -204,11 +199,6 @@ bool variant_carried(int v) { return v >= 1 && v <= kVariantLast && kVariants[v]
 // smooth shading is built for the exact scan, the BVH and the default scan (both shapes)
 bool variant_smooth(int v) { return v == 1 || v == kVariantAccel || v == 16; }
 
-// the two-stage path-tracing kernels' work buffer, per work slot (sp_scan_kernels.h): the path history (5 x int2), the accumulator
-// (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adaptive sampling parks S1, S2 (2 doubles) in a buffer of its own (adp_wst)
-constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12;
-constexpr size_t work_slot_bytes(bool nee, bool mis) { return kSlotHist + kSlotAcc + (mis ? kSlotMisD : nee ? kSlotNeeL : 0); }
-
 int pick_variant(int flags, size_t n_tris) {
 	if (flags & SPHIP_FLAG_ACCEL) return kVariantAccel;
 	const int v = flags & SPHIP_KERNEL_MASK;
@@ -216,7 +206,7 @@ int pick_variant(int flags, size_t n_tris) {
 	if (n_tris < 64) return 1;        // tiny scenes: nothing to filter, the scalar path has no barriers
 	if (n_tris >= (1ull << sp::kMIdxBits)) return 15;      // the default scan packs (ray, triangle index) into 32 bits: 6 + 26
 	// The third-generation scan (sp_cylm_scan.h: stage 1 on the f16 matrix pipe, one ray per lane) for every mode; sample chunks
-	// (launch_render) supply the workgroups a small frame lacks.
+	// (plan_launch) supply the workgroups a small frame lacks.
 	return 16;
 }
 
@@ -353,9 +343,17 @@ int ensure_bvh(sphip_ctx* c, hipStream_t st) {
 	return SPHIP_OK;
 }
 
-// ---- the light table of next-event estimation (include/spath_hip.h), built on the host once per scene:
-// emitters are the triangles with Esum = ((double)Er + Eg) + Eb > 0, weighted by w = A * Esum (A in double from the f32 vertices); the
-// table lists those with w > 0 in ascending index with their running double sum cdf and ipdf = (float)(W / Esum), W = the total
+// a light table (sp_host_plan.h) into device buffer b, which keeps 16 spare bytes so that a table without entries has a buffer too
+int upload_light_table(sphip_ctx* c, DevBuf& b, const LightTable& t, hipStream_t st) {
+	const std::vector<char> blob = pack_light_table(t);
+	if (const int rc = ensure(c, b, blob.size() + 16)) return rc;
+	if (blob.empty()) return SPHIP_OK;
+	HIP_TRY(c, hipMemcpyAsync(b.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
+	return SPHIP_OK;
+}
+
+// ---- the light table of next-event estimation (build_light_table), from a read-back on the first NEE render after a scene change
 int ensure_lights(sphip_ctx* c, hipStream_t st) {
 	if (c->nee_valid) return c->nee_bad ? fail(c, SPHIP_E_INVALID, "%s", c->nee_msg.c_str()) : SPHIP_OK;
 	const size_t n = c->n_tris;
@@ -363,52 +361,20 @@ int ensure_lights(sphip_ctx* c, hipStream_t st) {
 	HIP_TRY(c, hipMemcpyAsync(t.data(), c->tris.p, n * 48, hipMemcpyDeviceToHost, st));
 	HIP_TRY(c, hipMemcpyAsync(m.data(), c->mats.p, n * 24, hipMemcpyDeviceToHost, st));
 	HIP_TRY(c, hipStreamSynchronize(st));
-	std::vector<double> cdf;
-	std::vector<int> tri;
-	std::vector<float> ipdf;
-	std::vector<double> esum;
-	double W = 0.0;
-	c->nee_bad = false;
-	for (size_t i = 0; i < n; ++i) {
-		const float* e = &m[i * 6 + 3];
-		for (int k = 0; k < 3; ++k)
-			if (!(e[k] >= 0.0f) || !std::isfinite(e[k])) {
-				char buf[160];
-				snprintf(buf, sizeof buf, "SPHIP_FLAG_NEE: triangle %zu has emittance component %d = %g (must be finite and >= 0)", i, k, (double)e[k]);
-				c->nee_msg = buf;
-				c->nee_bad = true;
-				c->nee_valid = true;
-				return fail(c, SPHIP_E_INVALID, "%s", buf);
-			}
-		const double es = ((double)e[0] + (double)e[1]) + (double)e[2];
-		if (!(es > 0.0)) continue;
-		const float* v = &t[i * 12];
-		const double e1[3] = { (double)v[3] - (double)v[0], (double)v[4] - (double)v[1], (double)v[5] - (double)v[2] };
-		const double e2[3] = { (double)v[6] - (double)v[0], (double)v[7] - (double)v[1], (double)v[8] - (double)v[2] };
-		const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-		const double w = (0.5 * std::sqrt((cx * cx + cy * cy) + cz * cz)) * es;
-		if (!(w > 0.0) || !std::isfinite(w)) continue;
-		W = W + w;
-		cdf.push_back(W); tri.push_back((int)i); esum.push_back(es);
+	LightTable lt = build_light_table(t.data(), m.data(), n);
+	c->nee_bad = lt.bad_tri != SIZE_MAX;
+	if (c->nee_bad) {
+		char buf[160];
+		snprintf(buf, sizeof buf, "SPHIP_FLAG_NEE: triangle %zu has emittance component %d = %g (must be finite and >= 0)", lt.bad_tri, lt.bad_comp,
+		         (double)m[lt.bad_tri * 6 + 3 + lt.bad_comp]);
+		c->nee_msg = buf;
+		c->nee_valid = true;
+		return fail(c, SPHIP_E_INVALID, "%s", buf);
 	}
-	const size_t ne = cdf.size();
-	for (size_t k = 0; k < ne; ++k) ipdf.push_back((float)(W / esum[k]));
-	std::vector<float> tipdf(n, 0.0f);                    // MIS: the table's ipdf by triangle, 0 = not in the table
-	for (size_t k = 0; k < ne; ++k) tipdf[(size_t)tri[k]] = ipdf[k];
-	int rc;
-	if ((rc = ensure(c, c->nee_tab, ne * 16 + n * 4 + 16))) return rc;
-	std::vector<char> blob(ne * 16 + n * 4);
-	memcpy(blob.data(), cdf.data(), ne * 8);
-	memcpy(blob.data() + ne * 8, tri.data(), ne * 4);
-	memcpy(blob.data() + ne * 12, ipdf.data(), ne * 4);
-	memcpy(blob.data() + ne * 16, tipdf.data(), n * 4);
-	if (!blob.empty()) {
-		HIP_TRY(c, hipMemcpyAsync(c->nee_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-		HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
-	}
-	c->nee_n = (uint32_t)ne;
-	c->nee_W = W;
-	c->nee_cdf_h = cdf; c->nee_tri_h = tri; c->nee_esum_h = esum;     // what the flagged table is made from (ensure_env_lights)
+	if (const int rc = upload_light_table(c, c->nee_tab, lt, st)) return rc;
+	c->nee_n = (uint32_t)lt.cdf.size();
+	c->nee_W = lt.W;
+	c->nee_host = std::move(lt);
 	c->nee_valid = true;
 	return SPHIP_OK;
 }
@@ -479,34 +445,22 @@ int ensure_env_lights(sphip_ctx* c, hipStream_t st) {
 	const size_t nn = (size_t)n * n;
 	hipLaunchKernelGGL(sp::k_env_tpdf, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (const double*)c->env_wt.p, n, sel, T, (float*)c->env_tpdf.p);
 	HIP_TRY(c, hipGetLastError());
-	// the flagged light table: every triangle entry again with ipdf = (float)(W / Esum) under the new W, then the map's entry
-	// {cdf W, triangle -1, ipdf 0}.  A black map adds nothing: the render then reads the unflagged table, bit for bit
+	// the flagged light table (flagged_light_table).  A black map adds nothing: the render then reads the unflagged table, bit for bit
 	c->env_nee_n = c->nee_n;
 	if (entry) {
-		const size_t ne = c->nee_cdf_h.size(), m = ne + 1;
-		std::vector<double> cdf(c->nee_cdf_h);
-		std::vector<int> tri(c->nee_tri_h);
-		std::vector<float> ipdf(m, 0.0f), tipdf(nt, 0.0f);
-		cdf.push_back(c->env_W);
-		tri.push_back(-1);
-		for (size_t k = 0; k < ne; ++k) { ipdf[k] = (float)(c->env_W / c->nee_esum_h[k]); tipdf[(size_t)tri[k]] = ipdf[k]; }
-		if ((rc = ensure(c, c->env_tab, m * 16 + nt * 4 + 16))) return rc;
-		std::vector<char> blob(m * 16 + nt * 4);
-		memcpy(blob.data(), cdf.data(), m * 8);
-		memcpy(blob.data() + m * 8, tri.data(), m * 4);
-		memcpy(blob.data() + m * 12, ipdf.data(), m * 4);
-		memcpy(blob.data() + m * 16, tipdf.data(), nt * 4);
-		HIP_TRY(c, hipMemcpyAsync(c->env_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-		HIP_TRY(c, hipStreamSynchronize(st));             // blob is a local
-		c->env_nee_n = (uint32_t)m;
+		const LightTable ft = flagged_light_table(c->nee_host, c->env_W, nt);
+		if ((rc = upload_light_table(c, c->env_tab, ft, st))) return rc;
+		c->env_nee_n = (uint32_t)ft.cdf.size();
 	}
 	c->env_lights_valid = true;
 	return SPHIP_OK;
 }
 
-// the zeros that stand in for a per-triangle table whose flag is off in an environment render: one float4 row per triangle of the scene
+// the zeros that stand in for a per-triangle table whose flag is off (the specular table of a dielectric render, either table of an
+// environment render): one float4 row per triangle of the scene.  The dielectric setters call this before they make the device current
 int ensure_zero_rows(sphip_ctx* c, hipStream_t st) {
 	if (c->zero_rows == c->n_tris) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
 	if (const int rc = ensure(c, c->spec_zero, c->n_tris * 16)) return rc;
 	HIP_TRY(c, hipMemsetAsync(c->spec_zero.p, 0, c->n_tris * 16, st));
 	c->zero_rows = c->n_tris;
@@ -583,11 +537,13 @@ int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_
 // A/B scans).  Path tracing with the plain estimator or with NEE|MIS, with the feature's variants, once its table is set; the flat pass
 // has no use for them and says so; hit queries ignore the flags
 struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; };
-const TableRule kSpecRule{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_carried, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" };
-const TableRule kSmoothRule{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" };
-const TableRule kGlassRule{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" };
-// environment lighting follows the same rules with the context's map for a table
-const TableRule kEnvRule{ SPHIP_FLAG_ENVIRONMENT, "SPHIP_FLAG_ENVIRONMENT", variant_smooth, &sphip_ctx::have_env, "an environment map (sphip_set_environment)" };
+const TableRule kTableRules[] = {
+	{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_carried, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" },
+	{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" },
+	{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" },
+	// environment lighting follows the same rules with the context's map for a table
+	{ SPHIP_FLAG_ENVIRONMENT, "SPHIP_FLAG_ENVIRONMENT", variant_smooth, &sphip_ctx::have_env, "an environment map (sphip_set_environment)" },
+};
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
 	if (mode == SPHIP_MODE_FLAT) return fail(c, SPHIP_E_INVALID, "%s is valid for SPHIP_MODE_PT only", r.flag);
@@ -596,6 +552,12 @@ int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, i
 	if (!r.variant_ok(variant)) return fail(c, SPHIP_E_INVALID, "%s is not available with kernel variant %d (%s)", r.flag, variant, kVariants[variant].name);
 	if (!(c->*r.have)) return fail(c, SPHIP_E_STATE, "%s needs %s", r.flag, r.needs);
 	return SPHIP_OK;
+}
+// the whole chain, in the order in which a call that breaks several rules hears of them: the camera, then the tables as listed
+int check_feature_rules(sphip_ctx* c, int flags, int variant, int mode, bool have_cam) {
+	int rc = check_camera_rule(c, flags, variant, mode, have_cam);
+	for (const TableRule& r : kTableRules) if (!rc) rc = check_table_rule(c, r, flags, variant, mode);
+	return rc;
 }
 
 // what sphip_get_stats reports of the last launch on c
@@ -607,228 +569,191 @@ void note_render(sphip_ctx* c, hipStream_t st, size_t n_pixels, int variant) {
 	c->stats.kernel_variant = (uint32_t)variant;
 }
 
-// prog != nullptr: progressive accumulation (path tracing only): the launch renders global samples
-// [prog->sample_base, prog->sample_base + n_samples) into the running sum prog->sum, and d_accum receives the mean of all of them
-int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t /*image_width*/,
-                  size_t n_samples, uint64_t seed, int mode, int flags, void* d_rgba, void* d_accum, hipStream_t st,
-                  const int* d_src = nullptr, const sp::AccumArgs* prog = nullptr, const sp::AdaptArgs* adapt = nullptr,
-                  const sp::CamArgs* cams = nullptr) {
-	if (adapt) prog = adapt;                        // an adaptive launch is a progressive one over the active list (sp_kernels.h)
+// ---- One render launch.  RenderCall is what the entry points hand launch_render: the rays, the outputs and the stream, then what only
+// some of them set.  prog: progressive accumulation (path tracing only): the launch renders global samples [prog->sample_base,
+// prog->sample_base + n_samples) into the running sum prog->sum, and accum receives the mean of all of them; adapt: the same over the
+// active list of adaptive sampling; cam: the camera of SPHIP_FLAG_CAMERA_SAMPLES; src: the source triangles of a hit query
+struct RenderCall {
+	const void* rays; size_t n_rays, n_samples; uint64_t seed; int mode, flags; void* rgba; void* accum; hipStream_t st;
+	const sphip_shard* shard = nullptr; const int* src = nullptr;
+	const sp::AccumArgs* prog = nullptr; const sp::AdaptArgs* adapt = nullptr; const sp::CamArgs* cam = nullptr;
+};
+// what the steps hand on: check_render's verdict (the variant, its shape, the feature bits), plan_render's plan, bind_render's arguments
+struct Launch {
+	int variant = 0; TwoStage ts{}; Features f{};
+	uint32_t bthreads = 256;                 // threads per workgroup of the variant's kernels
+	LaunchPlan p;
+	sp::KArgs a{}; sp::ScanSrc src{}; sp::BvhArgs B{}; sp::AdaptArgs ad{}; sp::NormArgs nra{};
+	int2* hist = nullptr; float* acc = nullptr;   // the work buffer's path history and accumulator
+	sp::MisArgs est{};                       // the light table; handed on as NeeArgs or as MisArgs
+	sp::EnvArgs tab{};                       // the per-triangle tables and the map; handed on as SpecArgs, GlassArgs or EnvArgs
+};
+
+// ---- step 1, check: refuse what cannot be rendered and name what will be.  The order is behaviour (a call that is wrong twice hears of
+// the first): no scene; null rays or output; n_rays; mode; a hit query's distance output; n_samples; progressive accumulation's mode and
+// sum, then its sample total; shard.tile_px; the default scan's 2^26 triangles; a retired variant; MIS without NEE; under NEE the scene's
+// emittances (ensure_lights builds the light table here to keep that place: before the feature rules); the camera rule and the table rules
+// (check_feature_rules); and only then anything on the stream: an environment render's zero rows and flagged light table
+int check_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
+	const int mode = r.mode, flags = r.flags;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "render called before a scene was set");
-	if (!d_rays || !d_rgba) return fail(c, SPHIP_E_INVALID, "null ray or output pointer");
-	if (n_rays == 0 || n_rays > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n_rays);
+	if (!r.rays || !r.rgba) return fail(c, SPHIP_E_INVALID, "null ray or output pointer");
+	if (r.n_rays == 0 || r.n_rays > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", r.n_rays);
 	if (mode != SPHIP_MODE_FLAT && mode != SPHIP_MODE_PT && mode != kModeHits) return fail(c, SPHIP_E_INVALID, "unknown mode %d", mode);
-	if (mode == kModeHits && !d_accum) return fail(c, SPHIP_E_INVALID, "null distance output");
-	if (mode == SPHIP_MODE_PT && (n_samples == 0 || n_samples > 0x7fffffffull))
+	if (mode == kModeHits && !r.accum) return fail(c, SPHIP_E_INVALID, "null distance output");
+	const bool pt = mode == SPHIP_MODE_PT;
+	if (pt && (r.n_samples == 0 || r.n_samples > 0x7fffffffull))
 		return fail(c, SPHIP_E_INVALID, "n_samples must be in [1, 2^31) (the reference divides by it, cpu_renderer.cpp:77)");
-	if (prog && (mode != SPHIP_MODE_PT || !prog->sum)) return fail(c, SPHIP_E_INVALID, "progressive accumulation needs path tracing and a sum buffer");
-	if (prog && (uint64_t)prog->sample_base + n_samples > 0x7fffffffull)
-		return fail(c, SPHIP_E_INVALID, "sample_base + n_samples = %llu: the total must stay below 2^31", (unsigned long long)prog->sample_base + n_samples);
-	const uint64_t n_total = (prog ? (uint64_t)prog->sample_base : 0) + n_samples;
-	int rc = ensure(c, c->counter, 16 * sizeof(unsigned long long));
-	if (rc) return rc;
-
-	sp::KArgs a{};
-	a.rays = (const float*)d_rays;
-	a.scan = (const float4*)c->scan.p;
-	a.tris = (const float*)c->tris.p;
-	a.mats = (const float*)c->mats.p;
-	a.out_rgba = (uint32_t*)d_rgba;
-	a.out_accum = (float*)d_accum;
-	a.scans = (unsigned long long*)c->counter.p;
-	a.n_rays = (uint32_t)n_rays;
-	a.n_tris = (uint32_t)c->n_tris;
-	a.n_samples = (uint32_t)n_samples;
-	a.flags = (uint32_t)flags;
-	a.seed = seed;
-	if (shard) {
-		if (shard->tile_px == 0) return fail(c, SPHIP_E_INVALID, "shard.tile_px must be > 0");
-		a.pixel_base = shard->pixel_base; a.tile_px = shard->tile_px; a.tile_stride_px = shard->tile_stride_px;
-	} else {
-		a.pixel_base = 0; a.tile_px = n_rays; a.tile_stride_px = 0;
-	}
-	a.inv_n = (float)(1.0 / (double)(n_total ? n_total : 1));          // cpu_renderer.cpp:77 (all samples so far when accumulating)
-
-	const int variant = pick_variant(flags, c->n_tris);
+	if (r.prog && (!pt || !r.prog->sum)) return fail(c, SPHIP_E_INVALID, "progressive accumulation needs path tracing and a sum buffer");
+	if (r.prog && (uint64_t)r.prog->sample_base + r.n_samples > 0x7fffffffull)
+		return fail(c, SPHIP_E_INVALID, "sample_base + n_samples = %llu: the total must stay below 2^31", (unsigned long long)r.prog->sample_base + r.n_samples);
+	int rc;
+	if ((rc = ensure(c, c->counter, 16 * sizeof(unsigned long long)))) return rc;
+	if (r.shard && r.shard->tile_px == 0) return fail(c, SPHIP_E_INVALID, "shard.tile_px must be > 0");
+	const int variant = L.variant = pick_variant(flags, c->n_tris);
 	if (variant == 16 && c->n_tris >= (1ull << sp::kMIdxBits))
 		return fail(c, SPHIP_E_INVALID, "rpl_cylm handles scenes of fewer than 2^%u triangles (this one has %zu); use rpl_cylw4s", sp::kMIdxBits, c->n_tris);
 	if (!variant_carried(variant))
 		return fail(c, SPHIP_E_INVALID, "kernel variant %d (%s) is retired: libspath_hip no longer carries it", variant, kVariants[variant].name);
-	// next-event estimation: path tracing with the carried variants only (the bounded scans); flat and hit queries ignore the flag.
-	// MIS is a form of it: without SPHIP_FLAG_NEE the flag is an error
-	const bool nee = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_NEE);
-	const bool mis = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_MIS);
-	if (mis && !nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
-	sp::NeeArgs ne{};
-	if (nee) {
-		if (!variant_carried(variant))
-			return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_NEE is not available with kernel variant %d (%s)", variant, kVariants[variant].name);
-		if ((rc = ensure_lights(c, st))) return rc;
-		ne.cdf = (const double*)c->nee_tab.p;
-		ne.tri = (const int*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 8);
-		ne.ipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 12);
-		ne.n = c->nee_n;
-		ne.W = c->nee_W;
+	L.ts = kVariants[variant].ts;
+	// the features are those of path tracing: flat and hit queries ignore the flags.  MIS is a form of NEE
+	auto on = [&](int bit) { return pt && (flags & bit); };
+	const Features f = L.f = { on(SPHIP_FLAG_NEE), on(SPHIP_FLAG_MIS), on(SPHIP_FLAG_SPECULAR), on(SPHIP_FLAG_DIELECTRIC), on(SPHIP_FLAG_ENVIRONMENT),
+	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr };
+	if (f.mis && !f.nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
+	if (f.nee && (rc = ensure_lights(c, r.st))) return rc;
+	if ((rc = check_feature_rules(c, flags, variant, mode, r.cam != nullptr))) return rc;
+	// environment lighting stands zeros in for either table whose flag is off; under NEE|MIS the estimator reads the flagged light table
+	if (f.env && (!f.spec || !f.glass) && (rc = ensure_zero_rows(c, r.st))) return rc;
+	if (f.env && f.nee && (rc = ensure_env_lights(c, r.st))) return rc;
+	return SPHIP_OK;
+}
+
+// ---- step 2, plan: zero the scan counter, derive the default scan's record stream on first use (it decides between the scan's two
+// shapes, and so the threads per workgroup), then plan_launch (sp_host_plan.h): sample chunks, grids, work slots
+int plan_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
+	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), r.st));
+	if (L.ts.scan == 3) {
+		if (const int rc = ensure_cylm(c, r.st)) return rc;
+		if (c->cylm_wide) { L.ts.scan = 4; L.bthreads = sp::cylm512::kMThreads; }      // the 512-thread shape of the same scan (sp_cylm_both.h)
 	}
-	if ((rc = check_camera_rule(c, flags, variant, mode, cams != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, variant, mode)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, variant, mode)) || (rc = check_table_rule(c, kGlassRule, flags, variant, mode)) ||
-	    (rc = check_table_rule(c, kEnvRule, flags, variant, mode))) return rc;
-	if (mode != SPHIP_MODE_PT || !(flags & SPHIP_FLAG_CAMERA_SAMPLES)) cams = nullptr;
-	const bool specf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SPECULAR), smoothf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_SMOOTH);
-	const sp::SpecArgs spa{ (const float4*)c->spec.p };
-	const sp::NormArgs nra{ (const float*)c->vnorm.p };
-	// transparency: the dielectric table in the specular table's place, with that table or, without SPHIP_FLAG_SPECULAR, the zeros
-	const bool glassf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_DIELECTRIC);
-	sp::GlassArgs gla{};
-	gla.spec = (const float4*)(specf ? c->spec.p : c->spec_zero.p);
-	gla.glass = (const float4*)c->glass.p;
-	// environment lighting: the map in the dielectric table's place, with the zeros for either table whose flag is off; under NEE|MIS the
-	// estimator reads the flagged light table (the unflagged one when the map is black and adds no entry)
-	const bool envf = mode == SPHIP_MODE_PT && (flags & SPHIP_FLAG_ENVIRONMENT);
-	sp::EnvArgs ena{};
-	if (envf) {
-		if ((!specf || !glassf) && (rc = ensure_zero_rows(c, st))) return rc;
-		if (nee && (rc = ensure_env_lights(c, st))) return rc;
-		ena.spec = (const float4*)(specf ? c->spec.p : c->spec_zero.p);      // read after ensure_zero_rows: it may have allocated the zeros
-		ena.glass = (const float4*)(glassf ? c->glass.p : c->spec_zero.p);
-		ena.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
-		if (nee && c->env_nee_n != c->nee_n) {
-			ne.cdf = (const double*)c->env_tab.p;
-			ne.tri = (const int*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 8);
-			ne.ipdf = (const float*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 12);
-			ne.n = c->env_nee_n;
-			ne.W = c->env_W;
-		}
+	const uint32_t forced = ((uint32_t)r.flags & SPHIP_FLAG_CHUNKS_MASK) >> SPHIP_FLAG_CHUNKS_SHIFT;
+	L.p = plan_launch(r.n_rays, r.n_samples, forced, r.mode == SPHIP_MODE_PT, L.ts, L.bthreads, L.f, c->samp.cap, c->work.cap, []() -> int64_t {
+		size_t free_b = 0, total_b = 0;
+		return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (int64_t)free_b : -1;
+	});
+	if (L.p.too_large) return fail(c, SPHIP_E_INVALID, "n_rays %zu too large for one launch of this kernel variant; shard the frame", r.n_rays);
+	return SPHIP_OK;
+}
+
+// ---- step 3, bind: the buffers the plan asks for and the kernels' argument structs
+int bind_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
+	const Features& f = L.f;
+	const LaunchPlan& p = L.p;
+	int rc;
+	sp::KArgs& a = L.a;
+	a.rays = (const float*)r.rays; a.out_rgba = (uint32_t*)r.rgba; a.out_accum = (float*)r.accum;
+	a.scan = (const float4*)c->scan.p; a.tris = (const float*)c->tris.p; a.mats = (const float*)c->mats.p;
+	a.scans = (unsigned long long*)c->counter.p;
+	a.n_rays = (uint32_t)r.n_rays; a.n_tris = (uint32_t)c->n_tris; a.n_samples = (uint32_t)r.n_samples;
+	a.flags = (uint32_t)r.flags; a.seed = r.seed;
+	a.pixel_base = 0; a.tile_px = r.n_rays; a.tile_stride_px = 0;
+	if (r.shard) { a.pixel_base = r.shard->pixel_base; a.tile_px = r.shard->tile_px; a.tile_stride_px = r.shard->tile_stride_px; }
+	const uint64_t n_total = (r.prog ? (uint64_t)r.prog->sample_base : 0) + r.n_samples;
+	a.inv_n = (float)(1.0 / (double)(n_total ? n_total : 1));          // cpu_renderer.cpp:77 (all samples so far when accumulating)
+	if (p.chunks > 1) {
+		a.n_chunks = p.chunks; a.px_blocks = p.px_blocks; a.samp_stride = p.samp_stride;
+		if ((rc = ensure(c, c->samp, (size_t)p.samp_bytes))) return rc;
+		a.samp = (float*)c->samp.p;
 	}
-	HIP_TRY(c, hipMemsetAsync(c->counter.p, 0, 16 * sizeof(unsigned long long), st));
-	// sample chunks: the filter kernels keep 1024 workgroups resident (256 CUs x 4); a launch of only a few times that
-	// many ends with a long tail (its time is that of the slowest workgroup, ~12 % above the mean when everything starts
-	// together), so small frames and multi-GPU shards are split along the samples as well
-	uint32_t chunks = 1;
-	TwoStage ts = kVariants[variant].ts;
+	if (r.adapt) L.ad = *r.adapt;
+	if (r.mode == SPHIP_MODE_PT && L.ts.R != 0) {              // the two-stage kernels' work-side buffers: n_work slots of p.slot bytes each
+		if ((rc = ensure(c, c->work, (size_t)p.n_work * p.slot.work))) return rc;
+		if (p.slot.adp_wst && (rc = ensure(c, c->adp_wst, (size_t)p.n_work * p.slot.adp_wst))) return rc;
+		if (p.slot.env_M && (rc = ensure(c, c->env_M, (size_t)p.n_work * p.slot.env_M))) return rc;
+		L.hist = (int2*)c->work.p;
+		L.acc = (float*)((char*)c->work.p + (size_t)p.n_work * kSlotHist);
+		L.est.L = (float*)((char*)c->work.p + (size_t)p.n_work * (kSlotHist + kSlotAcc));     // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
+		L.ad.wst = (double*)c->adp_wst.p;
+		L.tab.M = (float*)c->env_M.p;
+	}
+	if (L.ts.scan == 2 && (rc = ensure_cyl(c, r.st))) return rc;
+	L.src.cyl.rec = (const float4*)c->cyl_rec.p; L.src.cyl.hdr = (const uint32_t*)c->cyl_hdr.p;
+	L.src.cylm.rec = (const float4*)c->cylm_rec.p; L.src.cylm.hdr = (const uint32_t*)c->cylm_hdr.p; L.src.cylm.big = (const float4*)c->cylm_big.p;
+	if (L.variant == kVariantAccel) {
+		if ((rc = ensure_bvh(c, r.st))) return rc;
+		L.B.nodes = (const float4*)c->bvh_nodes.p; L.B.leaf_rec = (const float4*)c->bvh_rec.p; L.B.leaf_idx = (const int*)c->bvh_idx.p;
+		L.B.n_leaves = c->bvh_leaves; L.B.first_leaf = c->bvh_leaves; L.B.meta = (const uint32_t*)c->bvh_meta.p;
+	}
+	if (f.nee) {
+		// an environment map with an entry in the light table: the estimator reads the flagged table (a black map adds none)
+		const bool flagged = f.env && c->env_nee_n != c->nee_n;
+		const uint32_t n = flagged ? c->env_nee_n : c->nee_n;
+		const LightView v = light_view(flagged ? c->env_tab.p : c->nee_tab.p, n);
+		L.est.cdf = v.cdf; L.est.tri = v.tri; L.est.ipdf = v.ipdf; L.est.tipdf = v.tipdf; L.est.n = n; L.est.W = flagged ? c->env_W : c->nee_W;
+	}
+	// the tables whose flags are set, the zeros for the others (read after ensure_zero_rows: it may have allocated them)
+	L.tab.spec = (const float4*)(f.spec ? c->spec.p : c->spec_zero.p);
+	L.tab.glass = (const float4*)(f.glass ? c->glass.p : c->spec_zero.p);
+	if (f.env) L.tab.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
+	L.nra.vnorm = (const float*)c->vnorm.p;
+	return SPHIP_OK;
+}
+
+// ---- step 4, dispatch: ev_k0, the primary-hit pre-pass, the kernel the variant, the mode and the feature bits select, the resolve, ev_k1
+int dispatch_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
+	const Features& f = L.f;
+	const TwoStage& ts = L.ts;
 	const bool is_ts = ts.R != 0;
-	const uint32_t slots = is_ts && ts.split ? (uint32_t)ts.R : 1u;                       // samples of one pixel per lane
-	// the record stream the variant reads, derived from the scene on first use
-	if (is_ts && ts.scan == 3 && (rc = ensure_cylm(c, st))) return rc;
-	if (is_ts && ts.scan == 3 && c->cylm_wide) ts.scan = 4;                               // the 512-thread shape of the same scan (sp_cylm_both.h)
-	const uint32_t bthreads = is_ts && ts.scan == 4 ? sp::cylm512::kMThreads : 256u;      // threads per workgroup of the variant's kernels
-	const uint32_t rays_per_block = is_ts && !ts.split ? bthreads * (uint32_t)ts.R : bthreads;
-	const uint64_t chunk_target = kChunkTargetBlocks * 256u / bthreads;                   // the same number of resident-wave rounds
-	if (mode == SPHIP_MODE_PT && is_ts) {
-		const uint64_t px_blocks = (n_rays + rays_per_block - 1) / rays_per_block;
-		const uint64_t n_iter = (n_samples + slots - 1) / slots;
-		const uint32_t forced = ((uint32_t)flags & SPHIP_FLAG_CHUNKS_MASK) >> SPHIP_FLAG_CHUNKS_SHIFT;
-		if (forced) chunks = forced;
-		else while (px_blocks * chunks < chunk_target && chunks < 128) chunks *= 2;
-		if (chunks > n_iter) chunks = (uint32_t)n_iter;
-		const uint64_t samp_bytes = (uint64_t)n_samples * 12 * ((n_rays + 255) / 256 * 256);
-		if (chunks > 1 && !forced) {
-			// the split is an optimisation: it must never make a render fail that would fit unsplit (52 B per pixel).
-			// Keep the scratch under the cap and under 90 % of what the device has free beyond the cached buffers.
-			// (the device is asked for its free memory only when a buffer has to grow: not on every frame of a running viewer)
-			size_t free_b = 0, total_b = 0;
-			bool asked = false;
-			if (samp_bytes > kChunkMaxBytes) chunks = 1;
-			const uint64_t lanes = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots;
-			while (chunks > 1) {
-				const uint64_t work_bytes = lanes * chunks * (work_slot_bytes(nee, mis) + (adapt ? kSlotAdaptWst : 0) + (envf ? kSlotEnvM : 0));
-				const uint64_t need = (samp_bytes > c->samp.cap ? samp_bytes : 0) + (work_bytes > c->work.cap ? work_bytes : 0);
-				if (need == 0) break;
-				if (!asked) { asked = true; if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { chunks = 1; break; } }
-				if (need <= (uint64_t)((double)free_b * 0.9)) break;
-				chunks /= 2;
-			}
-		}
-		if (chunks > 1) {
-			a.n_chunks = chunks; a.px_blocks = (uint32_t)px_blocks; a.samp_stride = (uint32_t)((n_rays + 255) / 256 * 256);
-			if ((rc = ensure(c, c->samp, (size_t)samp_bytes))) return rc;
-			a.samp = (float*)c->samp.p;
-		}
-	}
-	const dim3 block(256), block_ts(bthreads);
-	const dim3 grid((unsigned)((n_rays + 255) / 256 * chunks));                           // exact-only kernels, accel
-	// one-scan modes (flat pass, hits) have no samples to share a lane: a split variant runs there with R pixels per lane
-	const uint32_t rpb1 = is_ts ? bthreads * (uint32_t)ts.R : 256u;
-	const dim3 grid_px((unsigned)((n_rays + rpb1 - 1) / rpb1));
-	const dim3 grid_pt((unsigned)((n_rays + rays_per_block - 1) / rays_per_block * chunks));
-	// path-history / accumulator work buffer of the two-stage kernels: 5 x int2 + 3 x float per (padded) path and chunk
-	const uint64_t n_work64 = (uint64_t)((n_rays + 1023) / 1024 * 1024) * slots * chunks;
-	if (mode == SPHIP_MODE_PT && is_ts && n_work64 > 0xffffffffull)
-		return fail(c, SPHIP_E_INVALID, "n_rays %zu too large for one launch of this kernel variant; shard the frame", n_rays);
-	const uint32_t n_work = (uint32_t)n_work64;
-	int2* hist = nullptr; float* acc = nullptr;
-	sp::AdaptArgs ad{};
-	if (adapt) ad = *adapt;
-	if (mode == SPHIP_MODE_PT && is_ts) {
-		if ((rc = ensure(c, c->work, (size_t)n_work * work_slot_bytes(nee, mis)))) return rc;
-		hist = (int2*)c->work.p;
-		acc = (float*)((char*)c->work.p + (size_t)n_work * kSlotHist);
-		ne.L = (float*)((char*)c->work.p + (size_t)n_work * (kSlotHist + kSlotAcc));     // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
-		if (adapt && (rc = ensure(c, c->adp_wst, (size_t)n_work * kSlotAdaptWst))) return rc;   // S1, S2 per work slot
-		ad.wst = (double*)c->adp_wst.p;
-		if (envf && (rc = ensure(c, c->env_M, (size_t)n_work * kSlotEnvM))) return rc;          // the miss term per work slot
-		ena.M = (float*)c->env_M.p;
-	}
-	sp::ScanSrc src2{};
-	if (is_ts && ts.scan == 2 && (rc = ensure_cyl(c, st))) return rc;
-	src2.cyl.rec = (const float4*)c->cyl_rec.p;
-	src2.cyl.hdr = (const uint32_t*)c->cyl_hdr.p;
-	src2.cylm.rec = (const float4*)c->cylm_rec.p;
-	src2.cylm.hdr = (const uint32_t*)c->cylm_hdr.p;
-	src2.cylm.big = (const float4*)c->cylm_big.p;
+	const int variant = L.variant, mode = r.mode;
+	hipStream_t st = r.st;
+	sp::KArgs& a = L.a;
+	const dim3 block(256), block_ts(L.bthreads), grid(L.p.grid), grid_px(L.p.grid_px), grid_pt(L.p.grid_pt);
 	const unsigned int* bnd = (const unsigned int*)c->bounds.p;
-	sp::BvhArgs B{};
-	if (variant == kVariantAccel) {
-		if ((rc = ensure_bvh(c, st))) return rc;
-		B.nodes = (const float4*)c->bvh_nodes.p; B.leaf_rec = (const float4*)c->bvh_rec.p; B.leaf_idx = (const int*)c->bvh_idx.p;
-		B.n_leaves = c->bvh_leaves; B.first_leaf = c->bvh_leaves; B.meta = (const uint32_t*)c->bvh_meta.p;
-	}
 	HIP_TRY(c, hipEventRecord(c->ev_k0, st));
 	// the closest-hit scan alone with a two-stage variant, R pixels per lane: hit queries and the primary-hit pre-pass
 	auto hit_filter = [&](const sp::KArgs& ka, const int* src_idx, int* oi, float* od) {
 		with_scan_shape(ts, [&](auto shape) {
 			using S = decltype(shape);
-			hipLaunchKernelGGL((sp::k_hit_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, ka, src2, bnd, src_idx, oi, od);
+			hipLaunchKernelGGL((sp::k_hit_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, ka, L.src, bnd, src_idx, oi, od);
 		});
 	};
 	// primary-hit reuse with a two-stage kernel: one closest-hit scan per PIXEL first (R pixels per lane, the same scan family),
 	// whatever the number of samples and sample chunks; the path-tracing launch then starts every sample from that hit
 	bool prim_pass = false;
-	if (mode == SPHIP_MODE_PT && is_ts && (flags & SPHIP_FLAG_PRIMARY_REUSE)) {
-		if ((rc = ensure(c, c->prim, n_rays * 8))) return rc;
-		int* oi = (int*)c->prim.p; float* od = (float*)((char*)c->prim.p + n_rays * 4);
+	if (mode == SPHIP_MODE_PT && is_ts && (r.flags & SPHIP_FLAG_PRIMARY_REUSE)) {
+		if (const int rc = ensure(c, c->prim, r.n_rays * 8)) return rc;
+		int* oi = (int*)c->prim.p; float* od = (float*)((char*)c->prim.p + r.n_rays * 4);
 		sp::KArgs h = a;
 		h.n_chunks = 0; h.samp = nullptr;
 		hit_filter(h, nullptr, oi, od);
 		a.prim_idx = oi; a.prim_d = od;
 		prim_pass = true;
 	}
-	sp::MisArgs me{};
-	if (mis) {
-		static_cast<sp::NeeArgs&>(me) = ne;
-		me.tipdf = (const float*)((const char*)c->nee_tab.p + (size_t)c->nee_n * 16);
-		if (envf && c->env_nee_n != c->nee_n) me.tipdf = (const float*)((const char*)c->env_tab.p + (size_t)c->env_nee_n * 16);
-	}
-	const sp::AdaptArgs* adp = adapt ? &ad : nullptr;
-	auto pt_pack = [&](auto&& f) { with_pack(prog, adp, nee ? &ne : nullptr, mis ? &me : nullptr, specf && !glassf && !envf ? &spa : nullptr, glassf && !envf ? &gla : nullptr, envf ? &ena : nullptr, smoothf ? &nra : nullptr, cams, f); };
+	// the pack's carriers: the estimator rides as NeeArgs or MisArgs, the tables as the base of EnvArgs that the flags reach
+	const sp::NeeArgs* ne = f.nee ? &L.est : nullptr;
+	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env ? &L.tab : nullptr;
+	const sp::GlassArgs* gls = f.glass && !f.env ? &L.tab : nullptr;
+	const sp::AdaptArgs* adp = f.adapt ? &L.ad : nullptr;
+	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, f.env ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
-		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, B, src_idx, oi, od, p...);
+		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, L.B, src_idx, oi, od, p...);
 	};
-	auto with_exact = [&](auto&& f) {
-		if (variant == 2) f(std::integral_constant<int, 2>{});
-		else f(std::integral_constant<int, 1>{});
+	auto with_exact = [&](auto&& fn) {
+		if (variant == 2) fn(std::integral_constant<int, 2>{});
+		else fn(std::integral_constant<int, 1>{});
 	};
 	if (mode == kModeHits) {
-		int* oi = (int*)d_rgba; float* od = (float*)d_accum;
-		if (variant == kVariantAccel) accel(std::integral_constant<int, 2>{}, d_src, oi, od);
-		else if (is_ts) hit_filter(a, d_src, oi, od);
-		else with_exact([&](auto v) { hipLaunchKernelGGL((sp::k_hit<decltype(v)::value>), grid, block, 0, st, a, d_src, oi, od); });
+		int* oi = (int*)r.rgba; float* od = (float*)r.accum;
+		if (variant == kVariantAccel) accel(std::integral_constant<int, 2>{}, r.src, oi, od);
+		else if (is_ts) hit_filter(a, r.src, oi, od);
+		else with_exact([&](auto v) { hipLaunchKernelGGL((sp::k_hit<decltype(v)::value>), grid, block, 0, st, a, r.src, oi, od); });
 	} else if (mode == SPHIP_MODE_FLAT) {
 		if (variant == kVariantAccel) accel(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr);
 		else if (is_ts) with_scan_shape(ts, [&](auto shape) {
 			using S = decltype(shape);
-			hipLaunchKernelGGL((sp::k_flat_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, a, src2, bnd);
+			hipLaunchKernelGGL((sp::k_flat_filter<S::R, S::SCAN>), grid_px, block_ts, 0, st, a, L.src, bnd);
 		});
 		else with_exact([&](auto v) { hipLaunchKernelGGL((sp::k_flat<decltype(v)::value>), grid, block, 0, st, a); });
 	} else if (variant == kVariantAccel) {
@@ -840,7 +765,7 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 				// smooth shading and transparency are built for the default scan's two shapes only (checked above)
 				if constexpr (S::SCAN >= 3 || !(sp::IsNorm<std::decay_t<decltype(p)>...>::value || sp::IsGlass<std::decay_t<decltype(p)>...>::value))
 					hipLaunchKernelGGL((sp::k_pt_filter<S::R, S::SPLIT, S::SCAN, std::decay_t<decltype(p)>...>), grid_pt, block_ts, 0, st,
-					                   a, src2, bnd, hist, acc, n_work, p...);
+					                   a, L.src, bnd, L.hist, L.acc, L.p.n_work, p...);
 			});
 		});
 	} else {
@@ -851,17 +776,24 @@ int launch_render(sphip_ctx* c, const void* d_rays, size_t n_rays, const sphip_s
 			});
 		});
 	}
-	if (chunks > 1)
-		with_accum(prog, adp, [&](const auto&... q) {
-			hipLaunchKernelGGL((sp::k_resolve<std::decay_t<decltype(q)>...>), dim3((unsigned)((n_rays + 255) / 256)), block, 0, st, a, q...);
+	if (L.p.chunks > 1)
+		with_accum(r.prog, adp, [&](const auto&... q) {
+			hipLaunchKernelGGL((sp::k_resolve<std::decay_t<decltype(q)>...>), dim3((unsigned)((r.n_rays + 255) / 256)), block, 0, st, a, q...);
 		});
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipEventRecord(c->ev_k1, st));
-	note_render(c, st, n_rays, variant);
-	c->stats.n_launches = (chunks > 1 ? 2u : 1u) + (prim_pass ? 1u : 0u);
+	note_render(c, st, r.n_rays, variant);
+	c->stats.n_launches = L.p.n_launches + (prim_pass ? 1u : 0u);
 	return SPHIP_OK;
 }
 
+int launch_render(sphip_ctx* c, RenderCall r) {
+	if (r.adapt) r.prog = r.adapt;                  // an adaptive launch is a progressive one over the active list (sp_kernels.h)
+	Launch L;
+	int rc;
+	if ((rc = check_render(c, r, L)) || (rc = plan_render(c, r, L)) || (rc = bind_render(c, r, L))) return rc;
+	return dispatch_render(c, r, L);
+}
 
 // the viewport constants of view::camera::get_viewport (view.h:101-108: `real` (float) variables initialised from double expressions);
 // the shard fields are the whole image
@@ -1210,8 +1142,9 @@ int multi_render(sphip_ctx* c, const float* rays, const sphip_camera* cam, size_
 	return multi_frame(c, w, h, out_rgba, out_accum, [&](sphip_ctx* k, int r, size_t n, const sphip_shard& sh) -> int {
 		int rc2;
 		if ((rc2 = ensure(k, k->rays, n * 24)) || (rc2 = deal_rays(k, plan, r, rays, cam, k->rays.p, k->own_stream))) return rc2;
-		return launch_render(k, k->rays.p, n, &sh, w, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, k->own_stream,
-		                     nullptr, nullptr, nullptr, cam ? &ca : nullptr);
+		RenderCall call{ k->rays.p, n, n_samples, seed, mode, flags, k->rgba.p, out_accum ? k->accum.p : nullptr, k->own_stream };
+		call.shard = &sh; call.cam = cam ? &ca : nullptr;
+		return launch_render(k, call);
 	});
 }
 
@@ -1248,8 +1181,9 @@ int adapt_step_dev(sphip_ctx* k, const sphip_ctx* par, size_t n, const sphip_sha
 		// every pixel active: the list is the identity, the gathered rays would be the accumulation's own
 		const void* rays = na == n ? k->acc_rays.p : k->adp_rays.p;
 		const sp::CamArgs ca = cam_args_of(&par->acc_cam, par->acc_lens);
-		if ((rc = launch_render(k, rays, na, &sh, par->acc_w, n_samples, par->acc_seed, SPHIP_MODE_PT, par->acc_flags, k->rgba.p, nullptr, st,
-		                        nullptr, nullptr, &q, par->acc_has_cam ? &ca : nullptr))) return rc;
+		RenderCall call{ rays, na, n_samples, par->acc_seed, SPHIP_MODE_PT, par->acc_flags, k->rgba.p, nullptr, st };
+		call.shard = &sh; call.adapt = &q; call.cam = par->acc_has_cam ? &ca : nullptr;
+		if ((rc = launch_render(k, call))) return rc;
 		const sp::AdaptRule rule{ par->adp_t, par->adp_floor, par->adp_min, (uint32_t)n_samples };
 		const dim3 nb((unsigned)((na + 255) / 256));
 		hipLaunchKernelGGL(sp::k_adapt_decide, nb, dim3(256), 0, st, q.list, na, (uint32_t*)k->adp_cnt.p, (const double*)q.s12, rule,
@@ -1317,8 +1251,9 @@ int multi_accum_step(sphip_ctx* c, size_t n_samples, uint8_t* out_rgba, float* o
 	const sp::CamArgs ca = cam_args_of(&c->acc_cam, c->acc_lens);
 	return multi_frame(c, c->acc_w, c->acc_h, out_rgba, out_mean, [&](sphip_ctx* k, int, size_t n, const sphip_shard& sh) -> int {
 		const sp::AccumArgs p{ (float*)k->acc_sum.p, (uint32_t)c->acc_total };
-		return launch_render(k, k->acc_rays.p, n, &sh, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, k->rgba.p,
-		                     out_mean ? k->accum.p : nullptr, k->own_stream, nullptr, &p, nullptr, c->acc_has_cam ? &ca : nullptr);
+		RenderCall call{ k->acc_rays.p, n, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, k->rgba.p, out_mean ? k->accum.p : nullptr, k->own_stream };
+		call.shard = &sh; call.prog = &p; call.cam = c->acc_has_cam ? &ca : nullptr;
+		return launch_render(k, call);
 	});
 }
 
@@ -1362,9 +1297,7 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 	c->dn_gbuf_ok = false;
 	const int v = pick_variant(flags, c->n_tris);
 	int rc;
-	if ((rc = check_camera_rule(c, flags, v, SPHIP_MODE_PT, cam != nullptr)) || (rc = check_table_rule(c, kSpecRule, flags, v, SPHIP_MODE_PT)) ||
-	    (rc = check_table_rule(c, kSmoothRule, flags, v, SPHIP_MODE_PT)) || (rc = check_table_rule(c, kGlassRule, flags, v, SPHIP_MODE_PT)) ||
-	    (rc = check_table_rule(c, kEnvRule, flags, v, SPHIP_MODE_PT))) return rc;
+	if ((rc = check_feature_rules(c, flags, v, SPHIP_MODE_PT, cam != nullptr))) return rc;
 	if (!c->kids.empty()) {
 		if ((rc = multi_accum_begin(c, rays, cam, w, h, adaptive != nullptr))) return rc;
 	} else {
@@ -1446,7 +1379,7 @@ int gbuffer_dev(sphip_ctx* c, const void* d_rays, size_t n, int flags, void* d_o
 	if ((rc = ensure_classes(c, st)) || (rc = ensure(c, c->dn_hit, n * 8))) return rc;
 	int* idx = (int*)c->dn_hit.p;
 	float* dist = (float*)((char*)c->dn_hit.p + n * 4);
-	if ((rc = launch_render(c, d_rays, n, nullptr, 0, 1, 0, kModeHits, flags, idx, dist, st))) return rc;
+	if ((rc = launch_render(c, RenderCall{ d_rays, n, 1, 0, kModeHits, flags, idx, dist, st }))) return rc;
 	if (smooth)
 		hipLaunchKernelGGL(sp::k_gbuffer_smooth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
 		                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out,
@@ -1852,14 +1785,6 @@ static size_t glass_first_bad(const float* g, size_t n_tris) {
 	return n_tris;
 }
 
-// the zeros that stand in for the specular table of a dielectric render without SPHIP_FLAG_SPECULAR: one row per triangle
-static int ensure_spec_zero(sphip_ctx* c, hipStream_t st) {
-	HIP_TRY(c, hipSetDevice(c->device));
-	if (const int rc = ensure(c, c->spec_zero, c->n_tris * 16)) return rc;
-	HIP_TRY(c, hipMemsetAsync(c->spec_zero.p, 0, c->n_tris * 16, st));
-	return SPHIP_OK;
-}
-
 int sphip_set_dielectric(sphip_t* c, const float* glass) {
 	if (!c) return SPHIP_E_INVALID;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric called before a scene was set");
@@ -1874,7 +1799,7 @@ int sphip_set_dielectric(sphip_t* c, const float* glass) {
 		}
 	}
 	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_glass, sphip_set_dielectric, glass);
-	if (glass) if (const int rc = ensure_spec_zero(c, c->own_stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
+	if (glass) if (const int rc = ensure_zero_rows(c, c->own_stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
 	return set_tri_table(c, c->glass, c->have_glass, glass, 16, hipMemcpyHostToDevice, c->own_stream, true);
 }
 
@@ -1882,7 +1807,7 @@ int sphip_set_dielectric_device(sphip_t* c, const void* d_glass, void* stream) {
 	if (const int rc = single_device_entry(c)) return rc;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric_device called before a scene was set");
 	const bool big = d_glass && c->n_tris >= (size_t)sp::kTransBit;    // refused, and like every call it leaves no table behind
-	if (d_glass && !big) if (const int rc = ensure_spec_zero(c, (hipStream_t)stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
+	if (d_glass && !big) if (const int rc = ensure_zero_rows(c, (hipStream_t)stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
 	const int rc = set_tri_table(c, c->glass, c->have_glass, big ? nullptr : d_glass, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
 	return big ? fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris) : rc;
 }
@@ -1922,7 +1847,9 @@ int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sph
 	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
-	return launch_render(c, d_rays, n_rays, shard, image_width, n_samples, seed, mode, flags, d_out_rgba, d_out_accum, (hipStream_t)stream);
+	RenderCall call{ d_rays, n_rays, n_samples, seed, mode, flags, d_out_rgba, d_out_accum, (hipStream_t)stream };
+	call.shard = shard;
+	return launch_render(c, call);
 }
 
 int sphip_render_device_accum(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
@@ -1934,8 +1861,9 @@ int sphip_render_device_accum(sphip_t* c, const void* d_rays, size_t n_rays, con
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
 	const sp::AccumArgs p{ (float*)d_sum, (uint32_t)sample_base };
-	return launch_render(c, d_rays, n_rays, shard, image_width, n_samples, seed, SPHIP_MODE_PT, flags, d_out_rgba, d_out_mean, (hipStream_t)stream,
-	                     nullptr, &p);
+	RenderCall call{ d_rays, n_rays, n_samples, seed, SPHIP_MODE_PT, flags, d_out_rgba, d_out_mean, (hipStream_t)stream };
+	call.shard = shard; call.prog = &p;
+	return launch_render(c, call);
 }
 
 
@@ -2002,8 +1930,9 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 				if ((rc2 = adapt_step_dev(c, c, n, whole, n_samples, out_mean ? (float*)c->accum.p : nullptr, st))) return rc2;
 			} else {
 				const sp::CamArgs ca = cam_args_of(&c->acc_cam, c->acc_lens);
-				if ((rc2 = launch_render(c, c->acc_rays.p, n, nullptr, c->acc_w, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p,
-				                         out_mean ? c->accum.p : nullptr, st, nullptr, &p, nullptr, c->acc_has_cam ? &ca : nullptr))) return rc2;
+				RenderCall call{ c->acc_rays.p, n, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p, out_mean ? c->accum.p : nullptr, st };
+				call.prog = &p; call.cam = c->acc_has_cam ? &ca : nullptr;
+				if ((rc2 = launch_render(c, call))) return rc2;
 			}
 			if ((rc2 = download_frame(c, n, out_rgba, out_mean, st))) return rc2;
 			c->adp_nact = c->adp_nact_rb;
@@ -2064,8 +1993,9 @@ int sphip_render_camera(sphip_t* c, const sphip_camera* cam, size_t n_samples, u
 	if (out_accum && (rc = ensure(c, c->accum, n * 12))) return rc;
 	if ((rc = launch_viewport(c, cam, c->rays.p, st))) return rc;
 	const sp::CamArgs ca = cam_args_of(cam, c->lens);
-	if ((rc = launch_render(c, c->rays.p, n, nullptr, cam->res_x, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st,
-	                        nullptr, nullptr, nullptr, &ca))) return rc;
+	RenderCall call{ c->rays.p, n, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st };
+	call.cam = &ca;
+	if ((rc = launch_render(c, call))) return rc;
 	if ((rc = download_frame(c, n, out_rgba, out_accum, st))) return rc;
 	c->timed_upload = false;
 	c->timed_download = true;
@@ -2077,7 +2007,9 @@ int sphip_closest_hit_device(sphip_t* c, const void* d_rays, size_t n_rays, cons
 	if (const int rc = single_device_entry(c)) return rc;
 	HIP_TRY(c, hipSetDevice(c->device));
 	c->timed_upload = c->timed_download = false;
-	return launch_render(c, d_rays, n_rays, nullptr, 0, 1, 0, kModeHits, flags, d_out_idx, d_out_dist, (hipStream_t)stream, (const int*)d_src_idx);
+	RenderCall call{ d_rays, n_rays, 1, 0, kModeHits, flags, d_out_idx, d_out_dist, (hipStream_t)stream };
+	call.src = (const int*)d_src_idx;
+	return launch_render(c, call);
 }
 
 int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_samples, uint64_t seed, int mode, int flags,
@@ -2094,7 +2026,7 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 	HIP_TRY(c, hipEventRecord(c->ev_u0, st));
 	HIP_TRY(c, hipMemcpyAsync(c->rays.p, rays, n * 24, hipMemcpyHostToDevice, st));
 	HIP_TRY(c, hipEventRecord(c->ev_u1, st));
-	if ((rc = launch_render(c, c->rays.p, n, nullptr, w, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st))) return rc;
+	if ((rc = launch_render(c, RenderCall{ c->rays.p, n, n_samples, seed, mode, flags, c->rgba.p, out_accum ? c->accum.p : nullptr, st }))) return rc;
 	if ((rc = download_frame(c, n, out_rgba, out_accum, st))) return rc;
 	c->timed_upload = c->timed_download = true;
 	return SPHIP_OK;
