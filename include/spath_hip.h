@@ -79,6 +79,9 @@ enum {
 	SPHIP_FLAG_DIELECTRIC = 0x8000,  /* OPT-IN transparency: dielectric (glass) triangles with Fresnel reflection and refraction from the
 	                                   context's dielectric table (sphip_set_dielectric) for SPHIP_MODE_PT; see "transparency" below.
 	                                   Without the flag the table is ignored. */
+	SPHIP_FLAG_GLOSSY = 0x2000000,   /* OPT-IN glossy reflection: the mirror lobe of SPHIP_FLAG_SPECULAR roughened by the context's roughness
+	                                   table (sphip_set_roughness) for SPHIP_MODE_PT: valid only together with SPHIP_FLAG_SPECULAR; see
+	                                   "glossy reflection" below.  Without the flag the table is ignored. */
 	SPHIP_FLAG_ENVIRONMENT = 0x1000000 /* OPT-IN environment lighting by the context's octahedral radiance map (sphip_set_environment) for
 	                                   SPHIP_MODE_PT: a ray that leaves the scene carries the map's radiance, and NEE|MIS samples the map;
 	                                   see "environment lighting" below.  Without the flag the map is ignored.  (Bits 16..23 are the
@@ -213,7 +216,9 @@ int sphip_plan_shard(size_t width, size_t height, int n_devices, size_t tile_row
  *        8  dielectric     ("transparency" below)                  in f32[8n] dir ns ior entering          out f32[6n] Fr, tir, nt.xyz, c
  *        9  env_lookup     ("environment lighting" below)          in f32[3n] d                            out f32[4n] i, j, r3, valid
  *       10  env_sample     ("environment lighting" below)          in f64[4n] r8 r9 r3 r4                  out f32[6n] i, j, wd.xyz, r3
- *           9 and 10 run against the context's environment map (SPHIP_E_STATE without one) */
+ *           9 and 10 run against the context's environment map (SPHIP_E_STATE without one)
+ *       11  gloss_bounce   ("glossy reflection" below)             in f64[9n] dir.xyz ns.xyz alpha u1 u2 (dir, ns and alpha: f32 values
+ *                                                                  carried in doubles, as what 3 does)      out f32[8n] m.xyz, nd.xyz, g, ok */
 int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void* out);
 
 /* TEST-ONLY: stage 1 of the default scan ALONE -- the conservative reject that decides which (ray, triangle) pairs ever reach
@@ -676,6 +681,56 @@ int sphip_set_environment_device(sphip_t* ctx, const void* d_texels, uint32_t n,
  * This call and sphip_selftest_device what 9 and 10 read the tables on the context's own stream: after sphip_set_environment_device the
  * caller synchronises the stream it gave before calling them (nothing else orders the two streams). */
 int sphip_selftest_env_dump(sphip_t* ctx, uint32_t* n_out, double* out_wt, double* out_rc, double* out_marg, float* out_tpdf, double* out_T_wenv_W);
+
+/* ---- glossy reflection (SPHIP_FLAG_GLOSSY): a per-triangle roughness table beside the scene, 1 f32 per triangle:
+ * the GGX alpha of the triangle's mirror lobe (the lobe of its row of the specular table).  alpha = 0 leaves the lobe the perfect mirror,
+ * bit for bit; alpha > 0 reflects about a microfacet normal drawn from the GGX distribution of visible normals (Heitz 2018) and weights
+ * the sample by the separable Smith term of the outgoing direction, so the weight of a glossy hit is ks g / p <= ks / p: bounded as a
+ * mirror's is.  On a dielectric triangle (ior > 0) the row is ignored: rough glass is out of scope.
+ *
+ * Valid for SPHIP_MODE_PT together with SPHIP_FLAG_SPECULAR, with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with
+ * variants 1, 8 (SPHIP_FLAG_ACCEL) and 16 in both workgroup shapes, with SPHIP_FLAG_SMOOTH, SPHIP_FLAG_DIELECTRIC, SPHIP_FLAG_ENVIRONMENT
+ * and SPHIP_FLAG_CAMERA_SAMPLES on or off, with progressive and adaptive accumulation and denoising (the G-buffer is unchanged), sample
+ * chunks, primary-hit reuse, shards and multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT; with SPHIP_FLAG_NEE alone; with
+ * variants 2, 15 or a retired one; without SPHIP_FLAG_SPECULAR.  SPHIP_E_STATE: the flag without a roughness table.  Hit queries ignore
+ * the flag.  Without the flag every render is bit for bit what it is without a table; with the flag and a table of zeros too.
+ *
+ * The estimator, at hit d of the path of (seed, global pixel, global sample) on triangle i, when the lobe drawn is specular (the lobe
+ * rule of "specular reflection", unchanged), glass[i].w is not positive and al = rough[i] > 0.  dir: the ray; ns: the shading normal
+ * turned against dir, the stored one or smooth shading's; c = dot3(dir, ns).  f32 unless marked, every operation rounded on its own,
+ * nothing fused; dot3 as above, cross3(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x):
+ *   draws:   (u1, u2) = philox_uniforms(seed, pixel, sample, 48 + d)   (streams 0-4, 8-11, 16-19, 24, 25, 32-36, 40-43 are taken)
+ *   frame:   sg = ns.z < 0 ? -1 : 1;  a = -1.0f / (sg + ns.z);  b = (ns.x * ns.y) * a
+ *            t  = (1.0f + (sg * (ns.x * ns.x)) * a,  sg * b,  (-sg) * ns.x)
+ *            bt = (b,  sg + (ns.y * ns.y) * a,  -ns.y)
+ *   view:    v  = (-dot3(dir, t), -dot3(dir, bt), -c)
+ *   stretch: h  = (al v.x, al v.y, v.z);  vh = h / sqrtf(dot3(h, h)) per component
+ *   basis:   l2 = vh.x * vh.x + vh.y * vh.y;  T1 = l2 > 0 ? (-vh.y / sqrtf(l2), vh.x / sqrtf(l2), 0) : (1, 0, 0);  T2 = cross3(vh, T1)
+ *   disk:    r = (float)sqrt(u1) (a double sqrt);  phi = (float)((u2 * pi) * 2.0) (double, as the lens);  (sn, cs) = sincos_glibc(phi)
+ *            p1 = r * cs;  p2 = r * sn;  s = 0.5f * (1.0f + vh.z);  q = 1.0f - p1 * p1;  q = q > 0 ? q : 0
+ *            p2 = (1.0f - s) * sqrtf(q) + s * p2
+ *            z2 = (1.0f - p1 * p1) - p2 * p2;  z = sqrtf(z2 > 0 ? z2 : 0)
+ *            nh = (T1 * p1 + T2 * p2) + vh * z
+ *   normal:  ne = (al nh.x, al nh.y, nh.z > 0 ? nh.z : 0);  ml = ne / sqrtf(dot3(ne, ne));  m = (t * ml.x + bt * ml.y) + ns * ml.z
+ *   bounce:  nd = dir - m * (cm + cm), cm = dot3(dir, m)   (not renormalised, like the mirror's)
+ *   weight:  cl = dot3(nd, ns);  ok = cl > 0;  g = (cl + cl) / (cl + sqrtf(al * al + (1.0f - al * al) * (cl * cl)));  g = g > 1 ? 1 : g
+ * cl stands for the cosine although nd has dir's length, which is unit up to rounding after mirrors and refraction; the last select
+ * keeps g <= 1, and so the weight ks g / p <= ks / p, when that rounding puts cl above 1.
+ *   ending:  the path ends after the hit when !ok: the hit keeps E_d, rec_{d+1} = 0 (g_d counts as 0), nothing more is scanned or
+ *            counted.  On a smooth hit the mirror's two rules apply as well: sm && (!(c < 0) || dot3(nd, n) < 0)
+ *   unwind:  rec_d = E_d + (((ks * rec_{d+1}) * wS) * g_d) per channel; at al = 0 (and after !ok) the mirror's expression with its bits
+ * With SPHIP_FLAG_NEE | SPHIP_FLAG_MIS a glossy hit is a specular hit in every respect: it draws no light sample and traces no shadow
+ * ray, and the next hit or miss counts its emission in full, so both estimators keep one expectation by the mirror's argument. */
+
+/* The context's roughness table: n_tris f32 on the host for the scene last set (NULL clears the table), by the rules of
+ * sphip_set_specular: blocking; accepted by multi-device contexts; cleared by every set_scene; during an accumulation it ends the
+ * accumulation as a set_scene does.  SPHIP_E_STATE without a scene; SPHIP_E_INVALID when a value is not finite or lies outside [0, 1]
+ * (the message names the first such triangle; the table stays as it was). */
+int sphip_set_roughness(sphip_t* ctx, const float* alpha);
+/* The same from a device pointer, by the rules of sphip_set_specular_device: single-device contexts (SPHIP_E_STATE otherwise), ordered by
+ * `stream` alone, and copied.  It does NOT validate the values: a table that breaks the rules above gives undefined images (never
+ * out-of-bounds accesses). */
+int sphip_set_roughness_device(sphip_t* ctx, const void* d_alpha, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

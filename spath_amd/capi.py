@@ -23,6 +23,7 @@ FLAG_SPECULAR = 0x2000      # mirror and mixed diffuse/mirror materials from the
 FLAG_SMOOTH = 0x4000        # smooth shading by the context's per-vertex normals
 FLAG_DIELECTRIC = 0x8000    # transparency: glass triangles from the context's dielectric table
 FLAG_ENVIRONMENT = 0x1000000  # environment lighting by the context's octahedral map
+FLAG_GLOSSY = 0x2000000     # with FLAG_SPECULAR: the mirror lobe roughened by the context's roughness table
 
 
 def flag_chunks(n: int) -> int:
@@ -47,6 +48,7 @@ SYMBOLS = (
     "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
     "sphip_set_dielectric", "sphip_set_dielectric_device",
     "sphip_set_environment", "sphip_set_environment_device", "sphip_selftest_env_dump",
+    "sphip_set_roughness", "sphip_set_roughness_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -216,6 +218,10 @@ def load():
     L.sphip_set_vertex_normals.argtypes = [vp, vp]
     L.sphip_set_vertex_normals_device.restype = C.c_int
     L.sphip_set_vertex_normals_device.argtypes = [vp, vp, vp]
+    L.sphip_set_roughness.restype = C.c_int
+    L.sphip_set_roughness.argtypes = [vp, vp]
+    L.sphip_set_roughness_device.restype = C.c_int
+    L.sphip_set_roughness_device.argtypes = [vp, vp, vp]
     L.sphip_set_dielectric.restype = C.c_int
     L.sphip_set_dielectric.argtypes = [vp, vp]
     L.sphip_set_dielectric_device.restype = C.c_int
@@ -382,6 +388,18 @@ class Context:
             raise ValueError("one dielectric row per triangle of the scene")
         self._check(self._L.sphip_set_dielectric(self._h, glass.ctypes.data), "sphip_set_dielectric")
 
+    def set_roughness(self, alpha):
+        """sphip_set_roughness: the roughness table of FLAG_GLOSSY renders, n_tris f32, the GGX alpha of each triangle's mirror lobe for
+        the scene last set (scene.roughness_table builds one); None clears it.  Every set_scene clears it too."""
+        import numpy as np
+        if alpha is None:
+            self._check(self._L.sphip_set_roughness(self._h, None), "sphip_set_roughness")
+            return
+        alpha = np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
+        if alpha.shape[0] != getattr(self, "_n_tris", alpha.shape[0]):
+            raise ValueError("one roughness value per triangle of the scene")
+        self._check(self._L.sphip_set_roughness(self._h, alpha.ctypes.data), "sphip_set_roughness")
+
     def set_environment(self, texels):
         """sphip_set_environment: the octahedral environment map, (n, n, 3) f32 with texel (i, j) at [j, i] (scene.sky_environment and
         scene.environment_from_latlong build one); None clears it.  set_scene keeps it."""
@@ -421,6 +439,10 @@ class Context:
     def set_dielectric_device(self, d_glass: int, stream: int = 0):
         """sphip_set_dielectric_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_dielectric_device(self._h, d_glass, stream), "sphip_set_dielectric_device")
+
+    def set_roughness_device(self, d_alpha: int, stream: int = 0):
+        """sphip_set_roughness_device: the table from a device pointer (n_tris f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_roughness_device(self._h, d_alpha, stream), "sphip_set_roughness_device")
 
     def set_environment_device(self, d_texels: int, n: int, stream: int = 0):
         """sphip_set_environment_device: the map from a device pointer (n * n * 3 f32, copied in stream order, NOT validated)."""
@@ -561,7 +583,7 @@ class Context:
         return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
-                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6)}
+                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""

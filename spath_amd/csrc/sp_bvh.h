@@ -166,6 +166,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	constexpr bool gls = IsGlass<Acc...>::value;       // transparency (sp_integrator.h GlassArgs, in SpecArgs' place): kTransBit beside kSpecBit
 	constexpr bool env = IsEnv<Acc...>::value;         // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place): a miss carries the map's radiance
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
+	constexpr bool glo = IsGloss<Acc...>::value;       // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -248,6 +249,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					else if (spc && sl) {
 						nd = spec_reflect(dir, ns); hcos[depth] = 0.0f;
 						if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
+						if constexpr (glo) { const float al = rough_table(acc_args...)[bi]; if (al > 0.0f) gloss_hit(a, pixel, s0 + s, depth, al, dir, ns, n, sm, nd, hcos[depth], ended); }
 					} else {
 						double r1, r2;
 						philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
@@ -262,6 +264,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					src = bi;
 					nh = depth + 1;
 					if constexpr (smo) if (ended) alive = false;
+					if constexpr (glo && !smo) if (ended) alive = false;
 				} else {
 					if constexpr (env) Em = env_miss<mis>(env_args(acc_args...).env, dir, depth == 0 || (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);
 					alive = false;
@@ -279,7 +282,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = hD[depth];
 				else if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);
-				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hidx[depth], e, brdf, rec, hcos[depth]);
+				if constexpr (glo) rec = gloss_unwind(glass_table(acc_args...), spec_table(acc_args...), hidx[depth], e, brdf, rec, hcos[depth]);
+				else if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hidx[depth], e, brdf, rec, hcos[depth]);
 				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hidx[depth] & kSpecBit) != 0, e, brdf, rec, hcos[depth]);
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), hcos[depth]), kInvP));
 			}

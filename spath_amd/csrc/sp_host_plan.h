@@ -14,18 +14,18 @@ namespace sp_host {
 // scan = the scan (2 = f32 cylinder filter, sp_cyl_scan.h; 3 = stage 1 on the f16 matrix pipe, sp_cylm_scan.h; 4 = its 512-thread shape)
 struct TwoStage { int R; bool split; int scan; };
 // what a checked render does (check_render): later steps read these, never `flags`.  Every bit but adapt and prog is set in path tracing only
-struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog; };
+struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog, gloss; };
 constexpr uint64_t kChunkTargetBlocks = 262144;         // 256 x the 1024 resident workgroups (measured: profiles/r01_sample_chunks.log)
 constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sample scratch buffer
 
 // THE table of what the two-stage path-tracing kernels park per work slot (sp_scan_kernels.h), buffer by buffer.  work: the path
 // history (5 x int2), the accumulator (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adp_wst: adaptive sampling's S1, S2 (2 doubles);
-// env_M: the miss term of an environment render.  The chunk back-off's estimate and the allocations both read it: a feature that parks
+// env_M: the miss term of an environment render (a glossy render's kernels carry a map, the context's black one if need be).  The chunk back-off's estimate and the allocations both read it: a feature that parks
 // something per slot adds its line here, once
 constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12;
 struct SlotBytes { size_t work, adp_wst, env_M; };
 constexpr SlotBytes slot_bytes(const Features& f) {
-	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env ? kSlotEnvM : 0 };
+	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env || f.gloss ? kSlotEnvM : 0 };
 }
 
 struct LaunchPlan {

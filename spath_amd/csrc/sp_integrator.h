@@ -152,6 +152,16 @@ struct EnvArgs : GlassArgs {
 };
 constexpr uint32_t kEnvStream = 40u;
 
+// glossy reflection (SPHIP_FLAG_GLOSSY, include/spath_hip.h): the scene's roughness table, one float per triangle:
+// the GGX alpha of the triangle's mirror lobe; alpha = 0 leaves the mirror what it is.  It rides IN EnvArgs' PLACE (as EnvArgs rides in
+// GlassArgs'): k_pt<V, MisArgs, GlossArgs, NormArgs, CamArgs>, ...  glass is the scene's table or zeros as in EnvArgs; env is the context's
+// map, or its 1 x 1 black map (T = 0: no entry in the light table, every miss carries 0) when SPHIP_FLAG_ENVIRONMENT is not set.  A
+// glossy hit is a specular hit (kSpecBit) whose weight g rides in the history's cosine slot, which is 0 for every other specular hit
+struct GlossArgs : EnvArgs {
+	const float* rough;        // n_tris
+};
+constexpr uint32_t kGlossStream = 48u;
+
 // smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
 // n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
 // CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
@@ -165,7 +175,8 @@ template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHa
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
-template <typename... Acc> struct IsEnv { static constexpr bool value = PackHas<EnvArgs, Acc...>::value; };
+template <typename... Acc> struct IsGloss { static constexpr bool value = PackHas<GlossArgs, Acc...>::value; };
+template <typename... Acc> struct IsEnv { static constexpr bool value = PackHas<EnvArgs, Acc...>::value || IsGloss<Acc...>::value; };
 template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value || IsEnv<Acc...>::value; };
 template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value || IsGlass<Acc...>::value; };
 // what clears the marks of the path history from a triangle index
@@ -191,6 +202,7 @@ template <typename... P> SP_DEV const EnvMap* env_map(const P&... p) {
 	if constexpr (IsEnv<P...>::value) return &pack_get<EnvArgs>(p...).env;
 	else return nullptr;
 }
+template <typename... P> SP_DEV const float* rough_table(const P&... p) { return pack_get<GlossArgs>(p...).rough; }
 template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
@@ -477,6 +489,79 @@ SP_DEV f3 glass_unwind(const float4* __restrict__ glass, const float4* __restric
 	const float4 g = glass[i];
 	if (g.w > 0.0f) return (id & kTransBit) ? add3(e, mul3(mk3(g.x, g.y, g.z), rec)) : add3(e, rec);
 	return spec_unwind(spec[i], (id & kSpecBit) != 0, e, brdf, rec, ct);
+}
+
+// ---- glossy reflection (include/spath_hip.h "glossy reflection"): one draw from the GGX distribution of visible
+// normals (Heitz 2018) of roughness al > 0 around the shading normal ns (turned against dir), for the uniforms (u1, u2).  f32, every
+// operation rounded on its own, but the disk's radius (a double sqrt) and its angle (double, as the lens).  m: the microfacet normal;
+// nd: dir mirrored about m, not renormalised; g: the separable Smith term G1 of nd, the sample's whole weight beside ks / p.
+// Returns ok: nd is above ns (otherwise the path ends at this hit and g means nothing)
+SP_DEV bool gloss_bounce(f3 dir, f3 ns, float al, double u1, double u2, f3& m, f3& nd, float& g) {
+	const float c = dot3(dir, ns);
+	// frame: a branchless orthonormal basis (t, bt, ns)
+	const float sg = ns.z < 0.0f ? -1.0f : 1.0f;
+	const float a = -1.0f / (sg + ns.z);
+	const float b = (ns.x * ns.y) * a;
+	const f3 t = mk3(1.0f + (sg * (ns.x * ns.x)) * a, sg * b, (-sg) * ns.x);
+	const f3 bt = mk3(b, sg + (ns.y * ns.y) * a, -ns.y);
+	// view: the direction back along the ray in that frame, stretched to the unit-roughness configuration
+	const f3 v = mk3(-dot3(dir, t), -dot3(dir, bt), -c);
+	const f3 h = mk3(al * v.x, al * v.y, v.z);
+	const float hl = __builtin_sqrtf(dot3(h, h));
+	const f3 vh = mk3(h.x / hl, h.y / hl, h.z / hl);
+	// basis: orthogonal to vh
+	const float l2 = vh.x * vh.x + vh.y * vh.y;
+	f3 T1 = mk3(1.0f, 0.0f, 0.0f);
+	if (l2 > 0.0f) { const float l = __builtin_sqrtf(l2); T1 = mk3(-vh.y / l, vh.x / l, 0.0f); }
+	const f3 T2 = cross3(vh, T1);
+	// disk: a uniform point of the unit disk, warped onto the projection of the visible half
+	const float r = (float)__builtin_sqrt(u1);
+	const float phi = (float)((u2 * kPi) * 2.0);
+	float sn, cs;
+	sincos_glibc(phi, &sn, &cs);
+	const float p1 = r * cs;
+	float p2 = r * sn;
+	const float s = 0.5f * (1.0f + vh.z);
+	float q = 1.0f - p1 * p1;
+	q = q > 0.0f ? q : 0.0f;
+	p2 = (1.0f - s) * __builtin_sqrtf(q) + s * p2;
+	const float z2 = (1.0f - p1 * p1) - p2 * p2;
+	const float z = __builtin_sqrtf(z2 > 0.0f ? z2 : 0.0f);
+	const f3 nh = add3(add3(scale3(T1, p1), scale3(T2, p2)), scale3(vh, z));
+	// normal: unstretched, back in the world
+	const f3 ne = mk3(al * nh.x, al * nh.y, nh.z > 0.0f ? nh.z : 0.0f);
+	const float nl = __builtin_sqrtf(dot3(ne, ne));
+	const f3 ml = mk3(ne.x / nl, ne.y / nl, ne.z / nl);
+	m = add3(add3(scale3(t, ml.x), scale3(bt, ml.y)), scale3(ns, ml.z));
+	nd = spec_reflect(dir, m);
+	// weight: cl stands for the cosine although nd has dir's length
+	const float cl = dot3(nd, ns);
+	g = (cl + cl) / (cl + __builtin_sqrtf(al * al + (1.0f - al * al) * (cl * cl)));
+	g = g > 1.0f ? 1.0f : g;                           // a dir a rounding longer than unit gives cl, and so g, a rounding above 1
+	return cl > 0.0f;
+}
+// the bounce of the hit of depth d that took the mirror lobe of a triangle of roughness al > 0 (not an interface): the draw of stream
+// kGlossStream + d; g = 0 with ended when nd is not above ns; sm: the hit is smooth, and the mirror's two ending rules apply as well.
+// NOT inlined, on purpose: a real call keeps the draw's ~200 instructions and its double arithmetic out of the register allocation of
+// the path kernels, which are at their VGPR limit.  Inlined, one instantiation (k_pt_filter<1, false, 3, MisArgs, GlossArgs, NormArgs,
+// CamArgs>) came out with a stage 1 of the default scan that rejected genuine hits
+__device__ __attribute__((noinline)) void gloss_hit(const KArgs& a, uint32_t pixel, uint32_t sample, int depth, float al, f3 dir, f3 ns, f3 n, bool sm, f3& nd, float& g, bool& ended) {
+	double u1, u2;
+	philox_uniforms(a.seed, pixel, sample, kGlossStream + (uint32_t)depth, &u1, &u2);
+	f3 m;
+	const bool ok = gloss_bounce(dir, ns, al, u1, u2, m, nd, g);
+	if (!ok) g = 0.0f;
+	ended = !ok || (sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f));
+}
+// one step of the unwind with a roughness table: glass_unwind's step, scaled once more by g after a glossy hit (a specular hit whose
+// cosine slot ct holds g > 0; a mirror's, an interface's and an ended glossy hit's hold 0)
+SP_DEV f3 gloss_unwind(const float4* __restrict__ glass, const float4* __restrict__ spec, int id, f3 e, f3 brdf, f3 rec, float ct) {
+	const int i = id & ~(kSpecBit | kTransBit);
+	if ((id & kSpecBit) && ct > 0.0f) {
+		const float4 q = spec[i];
+		return add3(e, scale3(scale3(mul3(mk3(q.x, q.y, q.z), rec), 1.0f / q.w), ct));
+	}
+	return glass_unwind(glass, spec, id, e, brdf, rec, ct);
 }
 
 // ---- what the kernels share around the integrator: each is used where the kernel keeps its instructions with it (DESIGN.md

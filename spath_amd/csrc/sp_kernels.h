@@ -210,6 +210,18 @@ __global__ void __launch_bounds__(256) k_selftest_glass(const float* __restrict_
 	w[0] = Fr; w[1] = tir ? 1.0f : 0.0f; w[2] = nt.x; w[3] = nt.y; w[4] = nt.z; w[5] = c;
 }
 
+// what 11: gloss_bounce.  dir ns alpha u1 u2 (the f32 values carried in doubles) -> m.xyz nd.xyz g ok
+__global__ void __launch_bounds__(256) k_selftest_gloss(const double* __restrict__ in, uint32_t n, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const double* q = in + 9 * (size_t)i;
+	f3 m, nd;
+	float g;
+	const bool ok = gloss_bounce(mk3((float)q[0], (float)q[1], (float)q[2]), mk3((float)q[3], (float)q[4], (float)q[5]), (float)q[6], q[7], q[8], m, nd, g);
+	float* w = out + 8 * (size_t)i;
+	w[0] = m.x; w[1] = m.y; w[2] = m.z; w[3] = nd.x; w[4] = nd.y; w[5] = nd.z; w[6] = g; w[7] = ok ? 1.0f : 0.0f;
+}
+
 SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	const uint64_t t = (uint64_t)k / a.tile_px;
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
@@ -352,6 +364,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	static_assert(!gls || VARIANT == 1, "transparency: variant 1 (DESIGN.md section 5.10)");
 	constexpr bool env = IsEnv<Acc...>::value;                   // environment lighting (EnvArgs, in GlassArgs' place): a miss carries the map's radiance
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
+	constexpr bool glo = IsGloss<Acc...>::value;                 // glossy reflection (GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -430,6 +443,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				else if (spc && sl) {
 					nd = spec_reflect(dir, ns);
 					if constexpr (smo) ended = sm && (!(dot3(dir, ns) < 0.0f) || dot3(nd, n) < 0.0f);
+					if constexpr (glo) { const float al = rough_table(acc_args...)[bi]; if (al > 0.0f) gloss_hit(a, pixel, s0 + s, depth, al, dir, ns, n, sm, nd, ct, ended); }
 				} else {
 					double r1, r2;
 					philox_uniforms(a.seed, pixel, s0 + s, (uint32_t)depth, &r1, &r2);
@@ -482,7 +496,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 					if (depth > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, depth == 0 ? L0 : depth == 1 ? L1 : depth == 2 ? L2 : L3);
 				}
-				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), id, e, brdf, rec, ct);
+				if constexpr (glo) rec = gloss_unwind(glass_table(acc_args...), spec_table(acc_args...), id, e, brdf, rec, ct);
+				else if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), id, e, brdf, rec, ct);
 				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id & ~kSpecBit], (id & kSpecBit) != 0, e, brdf, rec, ct);
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), ct), kInvP));            // :67
 			}

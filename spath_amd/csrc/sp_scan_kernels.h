@@ -119,6 +119,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	static_assert(!gls || SCAN >= 3, "transparency: the default scan (DESIGN.md section 5.10)");
 	constexpr bool env = IsEnv<Acc...>::value;               // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place)
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
+	constexpr bool glo = IsGloss<Acc...>::value;             // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place)
 	constexpr int hmask = HistMask<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
@@ -301,6 +302,10 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						if (spc && slr[r]) {
 							nd = spec_reflect(s.dir[r], nadj[r]);
 							if constexpr (smo) ended = smr[r] && (!(dot3(s.dir[r], nadj[r]) < 0.0f) || dot3(nd, ng) < 0.0f);
+							if constexpr (glo) {                     // not on an interface: its bounce follows below
+								const float al = rough_table(acc_args...)[sh.src[r]];
+								if (al > 0.0f && !(glass_table(acc_args...)[sh.src[r]].w > 0.0f)) gloss_hit(a, pixel[r], s0 + smp[r], depth, al, s.dir[r], nadj[r], ng, smr[r], nd, ct, ended);
+							}
 						} else {
 							double r1, r2;
 							philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
@@ -354,6 +359,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					else if (spc && sl) {
 						nd = spec_reflect(s.dir[r], ns);
 						if constexpr (smo) ended = sm && (!(dot3(s.dir[r], ns) < 0.0f) || dot3(nd, n) < 0.0f);
+						if constexpr (glo) { const float al = rough_table(acc_args...)[bi[r]]; if (al > 0.0f) gloss_hit(a, pixel[r], s0 + smp[r], depth, al, s.dir[r], ns, n, sm, nd, ct, ended); }
 					} else {
 						double r1, r2;
 						philox_uniforms(a.seed, pixel[r], s0 + smp[r], (uint32_t)depth, &r1, &r2);
@@ -392,7 +398,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					if (d > 0) e = mk3(0.0f, 0.0f, 0.0f);
 					e = add3(e, mk3(Lp[0], Lp[n_work], Lp[(size_t)2 * n_work]));
 				}
-				if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hc.x, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
+				if constexpr (glo) rec = gloss_unwind(glass_table(acc_args...), spec_table(acc_args...), hc.x, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
+				else if constexpr (gls) rec = glass_unwind(glass_table(acc_args...), spec_table(acc_args...), hc.x, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
 				else if constexpr (spc) rec = spec_unwind(spec_table(acc_args...)[id], (hc.x & kSpecBit) != 0, e, brdf, rec, __uint_as_float((uint32_t)hc.y));
 				else rec = add3(e, scale3(scale3(mul3(brdf, rec), __uint_as_float((uint32_t)hc.y)), kInvP));
 			}

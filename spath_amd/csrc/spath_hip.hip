@@ -133,6 +133,11 @@ struct sphip_ctx {
 	uint32_t env_nee_n = 0;
 	sp_host::LightTable nee_host;                  // the host copy of nee_tab: what the flagged table is made from
 	size_t zero_rows = 0;
+	// ---- glossy reflection (SPHIP_FLAG_GLOSSY): the scene's roughness table, 1 float per triangle, kept and dropped like the specular
+	// table, and the 1 x 1 black map (texel, rc, marg and tpdf all zeros, T = 0) that stands in for the environment map when
+	// SPHIP_FLAG_ENVIRONMENT is not set: it adds no entry to the light table and every miss carries 0
+	DevBuf rough, env_black;
+	bool have_rough = false;
 };
 
 namespace {
@@ -228,6 +233,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->have_spec = false;                          // the specular table belongs to the old scene
 	c->have_vnorm = false;                         // and so do the vertex normals
 	c->have_glass = false;                         // and the dielectric table
+	c->have_rough = false;                         // and the roughness table
 	return SPHIP_OK;
 }
 
@@ -467,6 +473,15 @@ int ensure_zero_rows(sphip_ctx* c, hipStream_t st) {
 	return SPHIP_OK;
 }
 
+// the 1 x 1 black map of a glossy render without SPHIP_FLAG_ENVIRONMENT: zeros, written once per context
+int ensure_black_map(sphip_ctx* c, hipStream_t st) {
+	if (c->env_black.p) return SPHIP_OK;
+	if (const int rc = ensure(c, c->env_black, 256)) return rc;
+	HIP_TRY(c, hipMemsetAsync(c->env_black.p, 0, 256, st));
+	HIP_TRY(c, hipStreamSynchronize(st));          // later renders may come on another stream
+	return SPHIP_OK;
+}
+
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
 // f(args...) with the trailing pack of a path-tracing kernel for the run-time choices, always in the kernels' order: the running
@@ -482,7 +497,7 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
+               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::GlossArgs* glo, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
 			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
@@ -494,6 +509,7 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
 				last();
 			};
+			if constexpr (tables) { if (glo) { tail(*glo); return; } }      // the roughness table carries the map and both tables
 			if constexpr (tables) { if (env) { tail(*env); return; } }      // the environment map carries the dielectric and the specular table
 			if constexpr (tables) { if (gls) { tail(*gls); return; } }      // the dielectric table carries the specular one
 			if constexpr (tables) { if (spc) { tail(*spc); return; } }
@@ -536,13 +552,15 @@ int check_camera_rule(sphip_ctx* c, int flags, int variant, int mode, bool have_
 // the per-triangle tables: specular reflection and smooth shading (5.8; variants 1, 8 and 16 only: 2 and 15 are
 // A/B scans).  Path tracing with the plain estimator or with NEE|MIS, with the feature's variants, once its table is set; the flat pass
 // has no use for them and says so; hit queries ignore the flags
-struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; };
+struct TableRule { int bit; const char* flag; bool (*variant_ok)(int); bool sphip_ctx::*have; const char* needs; int with = 0; const char* with_flag = nullptr; };
 const TableRule kTableRules[] = {
 	{ SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR", variant_carried, &sphip_ctx::have_spec, "a specular table (sphip_set_specular)" },
 	{ SPHIP_FLAG_SMOOTH, "SPHIP_FLAG_SMOOTH", variant_smooth, &sphip_ctx::have_vnorm, "vertex normals (sphip_set_vertex_normals)" },
 	{ SPHIP_FLAG_DIELECTRIC, "SPHIP_FLAG_DIELECTRIC", variant_smooth, &sphip_ctx::have_glass, "a dielectric table (sphip_set_dielectric)" },
 	// environment lighting follows the same rules with the context's map for a table
 	{ SPHIP_FLAG_ENVIRONMENT, "SPHIP_FLAG_ENVIRONMENT", variant_smooth, &sphip_ctx::have_env, "an environment map (sphip_set_environment)" },
+	// glossy reflection roughens the mirror lobe: valid only together with SPHIP_FLAG_SPECULAR, as MIS is with NEE
+	{ SPHIP_FLAG_GLOSSY, "SPHIP_FLAG_GLOSSY", variant_smooth, &sphip_ctx::have_rough, "a roughness table (sphip_set_roughness)", SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR" },
 };
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
@@ -550,6 +568,7 @@ int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, i
 	if ((flags & SPHIP_FLAG_NEE) && !(flags & SPHIP_FLAG_MIS))
 		return fail(c, SPHIP_E_INVALID, "%s works with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, not with SPHIP_FLAG_NEE alone", r.flag);
 	if (!r.variant_ok(variant)) return fail(c, SPHIP_E_INVALID, "%s is not available with kernel variant %d (%s)", r.flag, variant, kVariants[variant].name);
+	if (r.with && !(flags & r.with)) return fail(c, SPHIP_E_INVALID, "%s needs %s", r.flag, r.with_flag);
 	if (!(c->*r.have)) return fail(c, SPHIP_E_STATE, "%s needs %s", r.flag, r.needs);
 	return SPHIP_OK;
 }
@@ -586,7 +605,7 @@ struct Launch {
 	sp::KArgs a{}; sp::ScanSrc src{}; sp::BvhArgs B{}; sp::AdaptArgs ad{}; sp::NormArgs nra{};
 	int2* hist = nullptr; float* acc = nullptr;   // the work buffer's path history and accumulator
 	sp::MisArgs est{};                       // the light table; handed on as NeeArgs or as MisArgs
-	sp::EnvArgs tab{};                       // the per-triangle tables and the map; handed on as SpecArgs, GlassArgs or EnvArgs
+	sp::GlossArgs tab{};                     // the per-triangle tables and the map; handed on as SpecArgs, GlassArgs, EnvArgs or GlossArgs
 };
 
 // ---- step 1, check: refuse what cannot be rendered and name what will be.  The order is behaviour (a call that is wrong twice hears of
@@ -619,13 +638,15 @@ int check_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	// the features are those of path tracing: flat and hit queries ignore the flags.  MIS is a form of NEE
 	auto on = [&](int bit) { return pt && (flags & bit); };
 	const Features f = L.f = { on(SPHIP_FLAG_NEE), on(SPHIP_FLAG_MIS), on(SPHIP_FLAG_SPECULAR), on(SPHIP_FLAG_DIELECTRIC), on(SPHIP_FLAG_ENVIRONMENT),
-	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr };
+	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr, on(SPHIP_FLAG_GLOSSY) };
 	if (f.mis && !f.nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	if (f.nee && (rc = ensure_lights(c, r.st))) return rc;
 	if ((rc = check_feature_rules(c, flags, variant, mode, r.cam != nullptr))) return rc;
 	// environment lighting stands zeros in for either table whose flag is off; under NEE|MIS the estimator reads the flagged light table
-	if (f.env && (!f.spec || !f.glass) && (rc = ensure_zero_rows(c, r.st))) return rc;
+	// and so does glossy reflection for the dielectric table, and its black map for the environment
+	if ((f.env || f.gloss) && (!f.spec || !f.glass) && (rc = ensure_zero_rows(c, r.st))) return rc;
 	if (f.env && f.nee && (rc = ensure_env_lights(c, r.st))) return rc;
+	if (f.gloss && !f.env && (rc = ensure_black_map(c, r.st))) return rc;
 	return SPHIP_OK;
 }
 
@@ -696,6 +717,8 @@ int bind_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	L.tab.spec = (const float4*)(f.spec ? c->spec.p : c->spec_zero.p);
 	L.tab.glass = (const float4*)(f.glass ? c->glass.p : c->spec_zero.p);
 	if (f.env) L.tab.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
+	else if (f.gloss) L.tab.env = sp::EnvMap{ (const float*)c->env_black.p, (const double*)c->env_black.p, (const double*)c->env_black.p, (const float*)c->env_black.p, 0.0, 1u };
+	L.tab.rough = (const float*)c->rough.p;
 	L.nra.vnorm = (const float*)c->vnorm.p;
 	return SPHIP_OK;
 }
@@ -732,10 +755,11 @@ int dispatch_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	}
 	// the pack's carriers: the estimator rides as NeeArgs or MisArgs, the tables as the base of EnvArgs that the flags reach
 	const sp::NeeArgs* ne = f.nee ? &L.est : nullptr;
-	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env ? &L.tab : nullptr;
-	const sp::GlassArgs* gls = f.glass && !f.env ? &L.tab : nullptr;
+	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env && !f.gloss ? &L.tab : nullptr;
+	const sp::GlassArgs* gls = f.glass && !f.env && !f.gloss ? &L.tab : nullptr;
+	const sp::EnvArgs* env = f.env && !f.gloss ? &L.tab : nullptr;
 	const sp::AdaptArgs* adp = f.adapt ? &L.ad : nullptr;
-	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, f.env ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
+	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, env, f.gloss ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, L.B, src_idx, oi, od, p...);
@@ -965,6 +989,7 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	c->have_spec = false;
 	c->have_vnorm = false;
 	c->have_glass = false;
+	c->have_rough = false;
 	return SPHIP_OK;
 }
 
@@ -1753,6 +1778,23 @@ int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) {
 	return big ? fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris) : rc;
 }
 
+int sphip_set_roughness(sphip_t* c, const float* alpha) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_roughness called before a scene was set");
+	if (alpha)
+		for (size_t i = 0; i < c->n_tris; ++i)
+			if (!std::isfinite(alpha[i]) || !(alpha[i] >= 0.0f) || !(alpha[i] <= 1.0f))
+				return fail(c, SPHIP_E_INVALID, "roughness table: triangle %zu has alpha %g (finite, 0 <= alpha <= 1)", i, (double)alpha[i]);
+	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_rough, sphip_set_roughness, alpha);
+	return set_tri_table(c, c->rough, c->have_rough, alpha, 4, hipMemcpyHostToDevice, c->own_stream, true);
+}
+
+int sphip_set_roughness_device(sphip_t* c, const void* d_alpha, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_roughness_device called before a scene was set");
+	return set_tri_table(c, c->rough, c->have_rough, d_alpha, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+}
+
 int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
 	if (!c) return SPHIP_E_INVALID;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals called before a scene was set");
@@ -2034,10 +2076,10 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[11] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32 }, out_b[11] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24 };
-	if (what < 0 || what > 10 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[12] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32, 72 }, out_b[12] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24, 32 };
+	if (what < 0 || what > 11 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
-	if (what >= 9 && !k->have_env) return fail(c, SPHIP_E_STATE, "selftest %d needs an environment map (sphip_set_environment)", what);
+	if ((what == 9 || what == 10) && !k->have_env) return fail(c, SPHIP_E_STATE, "selftest %d needs an environment map (sphip_set_environment)", what);
 	HIP_TRY(c, hipSetDevice(k->device));
 	sp::EnvMap em{};
 	if (what == 10) {                                                // T alone: the tables of the map itself, no scene needed
@@ -2050,7 +2092,8 @@ int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* 
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 10) hipLaunchKernelGGL(sp::k_selftest_env_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, em, (float*)d_out);
+		if (what == 11) hipLaunchKernelGGL(sp::k_selftest_gloss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, (float*)d_out);
+		else if (what == 10) hipLaunchKernelGGL(sp::k_selftest_env_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, em, (float*)d_out);
 		else if (what == 9) hipLaunchKernelGGL(sp::k_selftest_env_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, k->env_n, (float*)d_out);
 		else if (what == 8) hipLaunchKernelGGL(sp::k_selftest_glass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 7) hipLaunchKernelGGL(sp::k_selftest_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);

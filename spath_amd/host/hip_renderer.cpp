@@ -59,6 +59,8 @@ struct hip_r : public basic_renderer {
 	std::vector<float> vnorm;
 	// transparency (set_dielectric): likewise, 4 floats per triangle and SPHIP_FLAG_DIELECTRIC
 	std::vector<float> glass;
+	// glossy reflection (set_roughness): likewise, 1 float per triangle and SPHIP_FLAG_GLOSSY
+	std::vector<float> rough;
 	// environment lighting (set_environment): the map, env_n x env_n x 3 floats, and SPHIP_FLAG_ENVIRONMENT; the library keeps it across
 	// scenes, but it travels with the scene upload like the tables so that one key covers everything a frame depends on
 	std::vector<float> env;
@@ -111,6 +113,10 @@ struct hip_r : public basic_renderer {
 			if (glass.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the dielectric table and the scene differ in size");
 			h = fnv(glass.data(), glass.size() * sizeof(float), h);
 		}
+		if (!rough.empty()) {
+			if (rough.size() != n_tris) throw std::runtime_error("hip_renderer: the roughness table and the scene differ in size");
+			h = fnv(rough.data(), rough.size() * sizeof(float), h);
+		}
 		if (!env.empty()) h = fnv(env.data(), env.size() * sizeof(float), h);
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
@@ -118,6 +124,7 @@ struct hip_r : public basic_renderer {
 			if (!spec.empty()) check(sphip_set_specular(ctx, spec.data()), "set_specular");
 			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
 			if (!glass.empty()) check(sphip_set_dielectric(ctx, glass.data()), "set_dielectric");
+			if (!rough.empty()) check(sphip_set_roughness(ctx, rough.data()), "set_roughness");
 			scene_hash = h; scene_n = n_tris;
 		}
 	}
@@ -190,7 +197,7 @@ struct hip_r : public basic_renderer {
 	int table_flags(const int mode) const {              // the flags of the tables that are set
 		if (mode != SPHIP_MODE_PT) return 0;
 		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0) |
-		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0);
+		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0) | (!rough.empty() ? SPHIP_FLAG_GLOSSY : 0);
 	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
@@ -293,6 +300,14 @@ namespace hip_renderer {
 		if (!p) return;
 		if (glass && n_tris) p->glass.assign(glass, glass + n_tris * 4);
 		else p->glass.clear();
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+	}
+
+	void set_roughness(scene::renderer* r, const float* alpha, size_t n_tris) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (alpha && n_tris) p->rough.assign(alpha, alpha + n_tris);
+		else p->rough.clear();
 		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
 	}
 

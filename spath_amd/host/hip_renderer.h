@@ -50,6 +50,12 @@ namespace hip_renderer {
 	// (render_flat is unchanged).  NULL or n_tris = 0 removes it.  A table the library refuses makes the next frame throw
 	// std::runtime_error, as does one whose size differs from the scene's.  Changing it begins a new progressive accumulation.
 	extern void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris);
+	// glossy reflection (sphip_set_roughness, SPHIP_FLAG_GLOSSY; include/spath_hip.h "glossy reflection"): n_tris GGX alphas (copied)
+	// beside the specular table of the scenes rendered next; while they are set, path-traced frames roughen the mirror lobe by them
+	// (render_flat is unchanged; the library refuses the frame without a specular table).  NULL or n_tris = 0 removes them.  A table the
+	// library refuses makes the next frame throw std::runtime_error, as does one whose size differs from the scene's.  Changing it
+	// begins a new progressive accumulation.
+	extern void set_roughness(scene::renderer* r, const float* alpha, size_t n_tris);
 	// environment lighting (sphip_set_environment, SPHIP_FLAG_ENVIRONMENT; include/spath_hip.h "environment lighting"): an octahedral
 	// radiance map of n x n x 3 floats (copied); while one is set, path-traced frames are lit by it and show it behind the scene
 	// (render_flat is unchanged).  NULL or n = 0 removes it.  A map the library refuses makes the next frame throw std::runtime_error.

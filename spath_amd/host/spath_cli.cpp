@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--env FILE.bin] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -25,6 +25,8 @@
 //   ('SPVN', n, n x {n0.xyz n1.xyz n2.xyz} f32: spath_amd/scene.py write_vertex_normals); path tracing only, not with --nee without --mis
 // --glass FILE.bin: transparency (SPHIP_FLAG_DIELECTRIC) by the dielectric table in FILE.bin, a file of its own beside the scene file
 //   ('SPDI', n, n x {kt.r kt.g kt.b ior} f32: spath_amd/scene.py write_dielectric); path tracing only, not with --nee without --mis
+// --rough FILE.bin: glossy reflection (SPHIP_FLAG_GLOSSY) by the roughness table in FILE.bin, a file of its own beside the scene file
+//   ('SPRG', n, n x {alpha} f32: spath_amd/scene.py write_roughness); needs --spec; the flat pass ignores it; not with --nee without --mis
 // --env FILE.bin: environment lighting (SPHIP_FLAG_ENVIRONMENT) by the octahedral map in FILE.bin, a file of its own ('SPEN', n,
 //   n x n x {r g b} f32: spath_amd/scene.py write_environment); path tracing only, not with --nee without --mis
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
@@ -156,6 +158,7 @@ bool load_table(const char* path, uint32_t magic, size_t row, std::vector<float>
 bool load_specular(const char* path, std::vector<float>& spec) { return load_table(path, 0x50535053u, 4, spec); }
 bool load_normals(const char* path, std::vector<float>& vn) { return load_table(path, 0x4E565053u, 9, vn); }
 bool load_dielectric(const char* path, std::vector<float>& glass) { return load_table(path, 0x49445053u, 4, glass); }
+bool load_roughness(const char* path, std::vector<float>& rough) { return load_table(path, 0x47525053u, 1, rough); }
 
 // an environment map file of spath_amd/scene.py: 'SPEN', n, n * n * 3 f32
 bool load_environment(const char* path, std::vector<float>& env, uint32_t& n) {
@@ -176,7 +179,7 @@ bool load_environment(const char* path, std::vector<float>& env, uint32_t& n) {
 
 int main(int argc, char** argv) {
 	try {
-		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg;
+		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg, rough_arg;
 		bool device_viewport = false;
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
@@ -200,6 +203,7 @@ int main(int argc, char** argv) {
 			else if (k == "--spec") { need(1); spec_arg = argv[++i]; }
 			else if (k == "--normals") { need(1); normals_arg = argv[++i]; }
 			else if (k == "--glass") { need(1); glass_arg = argv[++i]; }
+			else if (k == "--rough") { need(1); rough_arg = argv[++i]; }
 			else if (k == "--env") { need(1); env_arg = argv[++i]; }
 			else if (k == "--w") { need(1); w = std::atoi(argv[++i]); }
 			else if (k == "--h") { need(1); h = std::atoi(argv[++i]); }
@@ -263,6 +267,8 @@ int main(int argc, char** argv) {
 		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
 		if (!env_arg.empty() && mode != "pt") throw std::runtime_error("--env needs --mode pt");
 		if (!env_arg.empty() && nee && !mis) throw std::runtime_error("--env works with the plain estimator and with --mis, not with --nee alone");
+		if (!rough_arg.empty() && spec_arg.empty()) throw std::runtime_error("--rough needs --spec (it roughens the mirror lobe of the specular table)");
+		if (!rough_arg.empty() && nee && !mis) throw std::runtime_error("--rough works with the plain estimator and with --mis, not with --nee alone");
 		std::vector<geom::triangle> tris;
 		std::vector<scene::material> mats;
 		if (scene_arg == "default") default_scene(tris, mats);
@@ -292,6 +298,12 @@ int main(int argc, char** argv) {
 			if (!load_dielectric(glass_arg.c_str(), glass)) throw std::runtime_error("cannot read dielectric file " + glass_arg);
 			if (glass.size() != tris.size() * 4) throw std::runtime_error("the dielectric file " + glass_arg + " and the scene differ in size");
 			hip_renderer::set_dielectric(r.get(), glass.data(), tris.size());
+		}
+		if (!rough_arg.empty()) {
+			std::vector<float> rough;
+			if (!load_roughness(rough_arg.c_str(), rough)) throw std::runtime_error("cannot read roughness file " + rough_arg);
+			if (rough.size() != tris.size()) throw std::runtime_error("the roughness file " + rough_arg + " and the scene differ in size");
+			hip_renderer::set_roughness(r.get(), rough.data(), tris.size());
 		}
 		if (!env_arg.empty()) {
 			std::vector<float> env;

@@ -104,6 +104,14 @@ class HipRenderer(BasicRenderer):
         self._vnorm = None
         self._glass = None
         self._env = None
+        self._rough = None
+
+    def set_roughness(self, alpha):
+        """The roughness table of capi.FLAG_GLOSSY renders ([n_tris] float32, scene.roughness_table; None: no table), like
+        hip_renderer::set_roughness: it goes to the library with the next scene upload and begins a new accumulation, and while one is
+        set every path-traced frame carries capi.FLAG_GLOSSY (render_flat never does); the flag needs a specular table beside it."""
+        self._rough = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1).copy()
+        self._scene_key = None
 
     def set_environment(self, env):
         """The environment map of capi.FLAG_ENVIRONMENT renders ([n, n, 3] float32, scene.sky_environment or
@@ -135,11 +143,12 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC and FLAG_ENVIRONMENT on while their tables or the map
-        are set, and never on the flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT and FLAG_GLOSSY on while their
+        tables or the map are set, and never on the flat pass"""
         if mode == capi.MODE_FLAT:
-            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT)
+            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT | capi.FLAG_GLOSSY)
         flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
+        flags = flags | capi.FLAG_GLOSSY if self._rough is not None else flags
         flags = flags | capi.FLAG_ENVIRONMENT if self._env is not None else flags
         flags = flags | capi.FLAG_DIELECTRIC if self._glass is not None else flags
         return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
@@ -153,7 +162,7 @@ class HipRenderer(BasicRenderer):
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
         key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
                None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()),
-               None if self._env is None else hash(self._env.tobytes()))
+               None if self._env is None else hash(self._env.tobytes()), None if self._rough is None else hash(self._rough.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
             if self._spec is not None:
@@ -162,6 +171,8 @@ class HipRenderer(BasicRenderer):
                 self.ctx.set_vertex_normals(self._vnorm[:n_tris])
             if self._glass is not None:
                 self.ctx.set_dielectric(self._glass[:n_tris])
+            if self._rough is not None:
+                self.ctx.set_roughness(self._rough[:n_tris])
             self.ctx.set_environment(self._env)
             self._scene_key = key
 

@@ -21,6 +21,7 @@ SPEC_MAGIC = 0x50535053   # 'SPSP'
 VNORM_MAGIC = 0x4E565053  # 'SPVN'
 GLASS_MAGIC = 0x49445053  # 'SPDI'
 ENV_MAGIC = 0x4E455053    # 'SPEN'
+ROUGH_MAGIC = 0x47525053  # 'SPRG'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -254,6 +255,30 @@ def write_dielectric(path, glass: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(struct.pack("<II", GLASS_MAGIC, glass.shape[0]))
         f.write(glass.tobytes())
+
+
+def roughness_table(tris: np.ndarray, alpha=0.2, which=None) -> np.ndarray:
+    """A roughness table for capi.Context.set_roughness (include/spath_hip.h, "glossy reflection"): float32 [N], the GGX alpha of each
+    triangle's mirror lobe.  alpha: a scalar or [N] (finite, in [0, 1]); which: the triangles that get the value (an index array or a
+    boolean mask; None = all), every other row is zero (the lobe stays the perfect mirror)."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    n = t.shape[0]
+    sel = np.ones(n, bool) if which is None else np.zeros(n, bool)
+    if which is not None:
+        sel[np.asarray(which)] = True
+    a = np.broadcast_to(np.asarray(alpha, F), (n,)).copy()
+    if not (np.isfinite(a).all() and (a >= 0).all() and (a <= 1).all()):
+        raise ValueError("roughness table: every value finite and in [0, 1]")
+    a[~sel] = 0.0
+    return a
+
+
+def write_roughness(path, alpha: np.ndarray) -> None:
+    """Roughness file read by the headless CLI (--rough), beside the scene file: 'SPRG', n, n float32."""
+    alpha = np.ascontiguousarray(alpha, dtype=F).reshape(-1)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", ROUGH_MAGIC, alpha.shape[0]))
+        f.write(alpha.tobytes())
 
 
 def octahedral_directions(n: int) -> np.ndarray:
