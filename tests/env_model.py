@@ -1,20 +1,14 @@
 """Environment lighting in the numpy model (include/spath_hip.h, "environment lighting"), operation by operation:
-the octahedral lookup and the sample in f32, the importance tables in float64 with numpy's sequential cumsum, and tests/path_model.py's
-loop restated (on top of tests/dielectric_model.py's restatement) with the environment steps: the map's entry of the flagged light
-table, its light sample, and the miss term from which the unwind of a path that left the scene starts.
+the octahedral lookup and the sample in f32, the importance tables in float64 with numpy's sequential cumsum, and the environment
+steps that tests/path_model.py's loop (its `env` map) calls: the map's entry of the flagged light table, its light sample, and the
+miss term from which the unwind of a path that left the scene starts.  The scenes and maps of the replay and their coverage check
+are here too.
 
-env = None means that the steps are not executed and the loop is dielectric_model.samples', which without a dielectric table is
-path_model.samples' (tests/test_env_model.py holds them together, bits and scans); with a map the specular and the dielectric step
-are executed as in the kernels, against the tables given or tables of zeros.
-
-Not a test module: tests/test_hip_environment.py holds the device functions, the table kernels and the path kernels to it at
-tolerance 0."""
+Not a test module: tests/test_hip_environment.py holds the device functions, the table kernels and, through path_model, the path
+kernels to it at tolerance 0."""
 import numpy as np
 
-from oracle import oracle as O
-from dielectric_model import dielectric
-from path_model import (ESTIMATORS, F, INV_P, INV_PI, PI_SQ, TWO_PI, _dot, _philox, _unit_vec, mis_emit, nee_light, shade_normal,
-                        smooth_light_ok, spec_lobe, spec_reflect, spec_unwind, turned_normal)
+from model_primitives import F, INV_PI, PI_SQ, TWO_PI, _dot, _philox
 from spath_amd import scene
 
 MAX_DIST = F(1e12)
@@ -135,7 +129,7 @@ def roundtrip_share(n, count, seed):
     return float(np.mean(~ok | (li != i) | (lj != j)))
 
 
-# ---------------------------------------------------------------------------------------------------------------- the estimator
+# ---------------------------------------------------------------------------------------------------------------- the estimator's steps
 def u_env(sxz, r3, tp):
     """the balance ratio ((kPiSq * sxz) * r3) * tpdf[t], 0 where that is NaN"""
     with np.errstate(invalid="ignore", over="ignore"):
@@ -186,197 +180,6 @@ def env_miss(env, tpdf, d, full, mis):
     opu = F(1) + u_env(np.sqrt(d[:, 0] * d[:, 0] + d[:, 2] * d[:, 2]), r3, tp)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(w[:, None], Le / opu[:, None], Le).astype(F)
-
-
-def samples(rays, tris, mats, seed, s0, n, est, spec=None, vn=None, glass=None, env=None):
-    """dielectric_model.samples with an environment map env [n, n, 3] (None: the flag is not set) -> (rec, scans, info).
-    info: "miss" [5] rays of depth d that left the scene and, of those, "miss_after_spec" straight after a specular or transmitted
-    hit and "miss_weighted" those that MIS weighted; "env_lights" light samples that picked the map and had cos_x > 0, of those
-    "env_unoccluded" and "env_occluded"; "tri_lights" shadow rays towards triangles; "glass" hits on an interface, "spec" hits that
-    took the mirror lobe"""
-    if est not in ESTIMATORS:
-        raise ValueError(f"unknown estimator {est!r}")
-    if est == "nee" and (spec is not None or vn is not None or glass is not None or env is not None):
-        raise ValueError("plain NEE takes no table and no environment map (the library refuses the flags together)")
-    tris = np.ascontiguousarray(tris, F).reshape(-1, 12)
-    mats = np.ascontiguousarray(mats, F).reshape(-1, 6)
-    rays = np.ascontiguousarray(rays, F).reshape(-1, 6)
-    spec = None if spec is None else np.ascontiguousarray(spec, F).reshape(-1, 4)
-    vn = None if vn is None else np.ascontiguousarray(vn, F).reshape(-1, 9)
-    glass = None if glass is None else np.ascontiguousarray(glass, F).reshape(-1, 4)
-    env = None if env is None else np.ascontiguousarray(env, F)
-    if env is not None and glass is None:
-        glass = np.zeros((tris.shape[0], 4), F)                   # the context's table of zeros: ior = 0, no interface
-    if glass is not None and spec is None:
-        spec = np.zeros((tris.shape[0], 4), F)                    # the context's table of zeros: p = 0, wD = 1.0f
-    mis = est == "mis"
-    tab = tpdf = None
-    if est == "plain":
-        light = None
-    elif env is not None:
-        tab = tables(env)
-        part = scene_part(tab, tris, mats)
-        tpdf = part["tpdf"]
-        light = flagged_light_table(tris, mats, part)
-    else:
-        from path_model import light_table
-        light = (scene.light_table if mis else light_table)(tris, mats)
-    tip = light[4] if mis else None
-    nhits = 4 if est == "nee" else 5
-    npix = rays.shape[0]
-    P = npix * n
-    pix = np.repeat(np.arange(npix, dtype=np.uint32), n)
-    smp = np.tile(np.arange(s0, s0 + n, dtype=np.uint32), npix)
-    o, d = rays[pix, :3].copy(), rays[pix, 3:].copy()
-    src = np.full(P, -1, np.int32)
-    alive = np.ones(P, bool)
-    hidx = np.full((nhits, P), -1, np.int64)
-    hct = np.zeros((nhits, P), F)
-    hspec = np.zeros((nhits, P), bool)
-    htrans = np.zeros((nhits, P), bool)
-    E = np.zeros((nhits, P, 3), F)
-    rec = np.zeros((P, 3), F)                                     # the unwind starts from the miss term, 0 for a path that did not leave
-    prev_spec = np.zeros(P, bool)
-    info = {"samples": P, "hits": 0, "miss": [0] * 5, "miss_after_spec": 0, "miss_weighted": 0, "env_lights": 0, "env_unoccluded": 0,
-            "env_occluded": 0, "tri_lights": 0, "glass": 0, "spec": 0}
-    scans = 0
-    for depth in range(nhits):
-        a = np.flatnonzero(alive)
-        if a.size == 0:
-            break
-        scans += a.size
-        idx, dist = O.closest_hits(np.concatenate([o[a], d[a]], 1), tris, src[a])
-        hit = idx >= 0
-        alive[a[~hit]] = False
-        if env is not None:                                       # the miss term
-            m = a[~hit]
-            full = prev_spec[m] if depth > 0 else np.ones(m.size, bool)
-            rec[m] = env_miss(env, tpdf, d[m], full, mis)
-            info["miss"][depth] += m.size
-            info["miss_after_spec"] += int(prev_spec[m].sum()) if depth > 0 else 0
-            if mis:
-                li_, lj_, _, ok_ = lookup(d[m], env.shape[0])
-                info["miss_weighted"] += int((ok_ & ~full & (tpdf[lj_, li_] > F(0))).sum())
-        a, idx, dist = a[hit], idx[hit].astype(np.int64), dist[hit]
-        info["hits"] += a.size
-        ps = prev_spec[a]
-        # 1, 2: the turned normal and the shading normal
-        nrm = turned_normal(tris, idx, d[a])
-        x = o[a] + d[a] * dist[:, None]
-        ns, sm = nrm, None
-        if vn is not None:
-            _, _, ns, sm = shade_normal(o[a], d[a], tris[idx, 0:9], vn[idx], nrm)
-        # 3: the lobe; an interface is a specular hit
-        isg = np.zeros(a.size, bool) if glass is None else glass[idx, 3] > F(0)
-        sl = None if spec is None else spec_lobe(seed, pix[a], smp[a], depth, spec[idx, 3])
-        if glass is not None:
-            sl = sl | isg
-        # 4: the direct term
-        if mis:
-            De = mis_emit(tris, mats, tip, idx, d[a], dist, ~ps if depth > 0 else np.zeros(a.size, bool))
-        else:
-            De = mats[idx, 3:6] if est == "plain" or depth == 0 else np.zeros((a.size, 3), F)
-        if light is not None and depth < 4:
-            L = np.zeros((a.size, 3), F)
-            if light[0].size:
-                with np.errstate(all="ignore"):
-                    ok, wd, tmax, Lc = nee_light(tris, mats, light, seed, pix[a], smp[a], depth, x, ns, idx, mis)
-                is_env = np.zeros(a.size, bool)
-                if env is not None and light[0][-1] < 0:          # the rows whose draw picked the map's entry
-                    r5, _ = _philox(seed, pix[a], smp[a], 16 + depth)
-                    e = np.minimum(np.searchsorted(light[1], r5 * light[3], side="right"), light[0].size - 1)
-                    is_env = light[0][e] < 0
-                    q = np.flatnonzero(is_env)
-                    if q.size:
-                        ok[q], wd[q], tmax[q], Lc[q], _, _ = env_light(env, tab, tpdf, mats, seed, pix[a[q]], smp[a[q]], depth, ns[q], idx[q])
-                if sl is not None:
-                    ok &= ~sl                                               # a specular hit draws no light sample
-                    with np.errstate(divide="ignore", invalid="ignore"):
-                        Lc = Lc * (F(1) / (F(1) - spec[idx, 3]))[:, None]   # L_d wD
-                if sm is not None:
-                    with np.errstate(invalid="ignore"):
-                        ok &= smooth_light_ok(sm, wd, nrm)
-                k = np.flatnonzero(ok)
-                scans += k.size
-                info["env_lights"] += int(is_env[k].sum())
-                info["tri_lights"] += int((~is_env[k]).sum())
-                if k.size:
-                    sidx, sd = O.closest_hits(np.concatenate([x[k], wd[k]], 1), tris, idx[k].astype(np.int32))
-                    vis = ~((sidx >= 0) & (sd < tmax[k]))
-                    info["env_unoccluded"] += int((vis & is_env[k]).sum())
-                    info["env_occluded"] += int((~vis & is_env[k]).sum())
-                    L[k[vis]] = Lc[k[vis]]
-            De = De + L
-        E[depth, a] = De
-        # 5: the bounce
-        nd = np.zeros((a.size, 3), F)
-        ct = np.zeros(a.size, F)
-        ended = np.zeros(a.size, bool)
-        tr = np.zeros(a.size, bool)
-        df = np.arange(a.size)
-        if sl is not None:
-            gl, mr, df = np.flatnonzero(isg), np.flatnonzero(sl & ~isg), np.flatnonzero(~sl)
-            info["spec"] += mr.size
-            nd[mr], c = spec_reflect(d[a[mr]], ns[mr])
-            if sm is not None:
-                ended[mr] = sm[mr] & (~(c < F(0)) | (_dot(nd[mr], nrm[mr]) < F(0)))
-            if gl.size:
-                dg, nsg = d[a[gl]], ns[gl]
-                entering = ~(_dot(tris[idx[gl], 9:12], dg) > F(0))
-                Fr, tir, nt, c = dielectric(dg, nsg, glass[idx[gl], 3], entering)
-                r7, _ = _philox(seed, pix[a[gl]], smp[a[gl]], 32 + depth)
-                with np.errstate(invalid="ignore"):
-                    t = ~tir & (Fr.astype(np.float64) <= r7)                # a NaN Fr reflects
-                nd[gl] = np.where(t[:, None], nt, spec_reflect(dg, nsg)[0])
-                tr[gl] = t
-                info["glass"] += gl.size
-                if sm is not None:
-                    below = _dot(nd[gl], nrm[gl]) < F(0)
-                    ended[gl] = sm[gl] & (~(c < F(0)) | (~t & below) | (t & ~below))
-        if df.size:
-            r1, r2 = _philox(seed, pix[a[df]], smp[a[df]], depth)
-            nd[df] = _unit_vec(ns[df], r1, r2)
-            ct[df] = _dot(nd[df], ns[df])
-            if sm is not None:
-                ended[df] = sm[df] & (_dot(nd[df], nrm[df]) < F(0))
-        hct[depth, a] = ct
-        hidx[depth, a] = idx
-        if sl is not None:
-            hspec[depth, a] = sl
-            htrans[depth, a] = tr
-            prev_spec[a] = sl
-        o[a], d[a], src[a] = x, nd, idx.astype(np.int32)
-        alive[a[ended]] = False
-    # 6: the unwind, one step per hit, backward, from the miss term
-    for depth in range(nhits - 1, -1, -1):
-        h = np.flatnonzero(hidx[depth] >= 0)
-        i = hidx[depth, h]
-        brdf = mats[i, 0:3] * INV_PI
-        if spec is None:
-            rec[h] = E[depth, h] + ((brdf * rec[h]) * hct[depth, h][:, None]) * INV_P
-        else:
-            r = spec_unwind(spec[i], hspec[depth, h], E[depth, h], brdf, rec[h], hct[depth, h])
-            if glass is not None:
-                g = glass[i]
-                with np.errstate(invalid="ignore", over="ignore"):
-                    through = E[depth, h] + np.where(htrans[depth, h][:, None], g[:, 0:3] * rec[h], rec[h])
-                r = np.where((g[:, 3] > F(0))[:, None], through, r).astype(F)
-            rec[h] = r
-    return rec.reshape(npix, n, 3), scans, info
-
-
-def render(rays, tris, mats, n, seed, est, spec=None, vn=None, glass=None, env=None):
-    """-> (rgba [npix, 4] u8, mean [npix, 3] f32, scans, info) of a one-shot render of n samples under `samples`' estimator"""
-    rec, scans, info = samples(rays, tris, mats, seed, 0, n, est, spec, vn, glass, env)
-    acc = np.zeros((rec.shape[0], 3), F)
-    for s in range(n):
-        acc = acc + rec[:, s]
-    mean = acc * F(1.0 / n)
-    c = np.clip(mean, F(0), F(1)) * F(255) + F(0.5)
-    q = np.where(c < 0, 0, np.where(c > 255, 255, c.astype(np.uint32) & 0xFF)).astype(np.uint8)
-    rgba = np.zeros((rec.shape[0], 4), np.uint8)
-    rgba[:, :3] = q
-    return rgba, mean, scans, info
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenes of the tests

@@ -1,8 +1,9 @@
-"""What the estimator tests share on the GPU side (tests/test_hip_nee.py, test_hip_mis.py, test_hip_specular.py, test_hip_smooth.py;
-the helpers also serve test_hip_camera_samples.py, test_hip_adaptive.py, test_hip_progressive.py and test_hip_denoise.py): the
-rays and contexts, the scenes the replay (tests/path_model.py) is held to, the two fixtures, and one check per composition of an
-estimator flag with the rest of the library.  A check takes a context with the feature's tables installed and the flag word; the
-test picks the scene and the flags, closes the context and keeps the asserts that are its own.
+"""What the estimator tests share on the GPU side (tests/test_hip_nee.py, test_hip_mis.py, test_hip_specular.py, test_hip_smooth.py,
+test_hip_dielectric.py, test_hip_environment.py, test_hip_glossy.py; the helpers also serve test_hip_camera_samples.py,
+test_hip_adaptive.py, test_hip_progressive.py and test_hip_denoise.py): the rays, the contexts and their flags, the scenes the
+replay (tests/path_model.py) is held to, the two fixtures, and one check per composition of an estimator flag with the rest of the
+library.  A check takes a context with the feature's tables installed and the flag word; the test picks the scene and the flags,
+closes the context and keeps the asserts that are its own.
 
 Not a test module."""
 import ctypes as C
@@ -35,15 +36,21 @@ def rays(w=W, h=H, moves=MOVES):
     return cam_rays(w, h, moves)[1]
 
 
-def ctx(t, m, spec=None, vn=None, devs=None):
-    """a context (a multi-device one over devs) with the scene and the tables given"""
+def ctx(t, m, spec=None, vn=None, devs=None, glass=None, env=None, rough=None):
+    """a context (a multi-device one over devs) with the scene, the tables and the map given"""
     c = capi.Context(0) if devs is None else capi.Context.multi(devs)
     c.set_scene(t, m)
-    if spec is not None:
-        c.set_specular(spec)
-    if vn is not None:
-        c.set_vertex_normals(vn)
+    for table, setter in ((spec, c.set_specular), (vn, c.set_vertex_normals), (glass, c.set_dielectric), (env, c.set_environment),
+                          (rough, c.set_roughness)):
+        if table is not None:
+            setter(table)
     return c
+
+
+def table_flags(spec=None, vn=None, glass=None, env=None, rough=None):
+    """the flags that turn on the steps of the tables and the map given"""
+    return sum(flag for table, flag in ((spec, capi.FLAG_SPECULAR), (vn, capi.FLAG_SMOOTH), (glass, capi.FLAG_DIELECTRIC),
+                                        (env, capi.FLAG_ENVIRONMENT), (rough, capi.FLAG_GLOSSY)) if table is not None)
 
 
 def same(a, b):

@@ -2,12 +2,12 @@
 kt.r kt.g kt.b ior; a triangle with ior >= 1 is a smooth interface between vacuum and a dielectric that reflects with the Fresnel
 probability and transmits by Snell's law otherwise.
 
-The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/dielectric_model.py, tests/path_model.py's
-loop restated with the dielectric steps).  STATED TOLERANCE: 0 -- images, means and scan counts bit for bit.  The statistical bar (plain
-against NEE|MIS) is the project's: hip_checks.z_grid over 16 seeds x 256 spp at 32 x 32.  The f32 statement is held to float64
+The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/dielectric_model.py's interface in
+tests/path_model.py's loop, its `glass` table).  STATED TOLERANCE: 0 -- images, means and scan counts bit for bit.  The statistical bar
+(plain against NEE|MIS) is the project's: hip_checks.z_grid over 16 seeds x 256 spp at 32 x 32.  The f32 statement is held to float64
 Snell/Fresnel at 2^-16 (test_f32_statement_against_float64 says where the figure comes from).
 
-CPU part: the flag and the symbols; the model against path_model without a table and with a table of zeros; a slab by hand; the f32
+CPU part: the flag and the symbols; the model with a table of zeros against the model without a table; a slab by hand; the f32
 statement against float64; scene.dielectric_table; the coverage of the replay cases; the BVH case's noise accepts.
 GPU part: the selftest; the replay for variants 1 and 16, both estimators; zero table = no flag; both workgroup shapes; the
 compositions; the BVH's parity; one expectation; the error contract; the front ends."""
@@ -65,22 +65,12 @@ def sphere_scene(smooth, mixed):
     return t, m, (s if mixed else None), (vn if smooth else None), g
 
 
-def _case_flags(s, vn):
-    return GLASS | (SPEC if s is not None else 0) | (SMOOTH if vn is not None else 0)
-
-
-def _ctx(t, m, s, vn, g, devs=None):
-    c = hc.ctx(t, m, s, vn, devs)
-    c.set_dielectric(g)
-    return c
-
-
 def _model(smooth, mixed, est):
     """the replay's reference, computed once per case"""
     key = (smooth, mixed, est)
     if key not in _MODEL:
         t, m, s, vn, g = sphere_scene(smooth, mixed)
-        _MODEL[key] = dm.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, g, ("accepts",))
+        _MODEL[key] = path_model.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, g, collect=("accepts",))
     return _MODEL[key]
 
 
@@ -125,27 +115,23 @@ def test_null_context_and_triangle_limit():
 
 
 @pytest.mark.parametrize("tables", ["none", "spec", "vn", "spec+vn"])
-def test_model_is_path_model(tables):
-    """without a dielectric table and with a table of zeros the restated loop is path_model.samples, bits and scans, for every
-    estimator it takes, with and without a specular table and vertex normals: it cannot drift"""
+def test_zero_table_is_no_table(tables):
+    """a dielectric table of zeros (whatever kt) executes the step and changes nothing: the bits, the scans and every counter of the
+    call without the table, for every estimator that takes one, with and without a specular table and vertex normals"""
     t, m, s, vn = hc.smooth_case("diffuse_sphere", True)
     s, vn = (s if "spec" in tables else None), (vn if "vn" in tables else None)
     rays = hc.rays(16, 12)
     z = np.zeros((t.shape[0], 4), F)
     z[:, 0:3] = 0.6                                   # kt alone changes nothing
-    for est in path_model.ESTIMATORS:
-        if est == "nee" and tables != "none":
-            continue
+    for est in sorted(ESTIMATORS):
         want, want_scans, wi = path_model.samples(rays, t, m, 5, 1, 3, est, s, vn)
-        tabs = (None,) if est == "nee" else (None, z)
-        for g in tabs:
-            rec, scans, info = dm.samples(rays, t, m, 5, 1, 3, est, s, vn, g)
-            assert np.array_equal(_bits(rec), _bits(want)) and scans == want_scans, (est, g is None)
-            assert info["glass"] == 0 and all(info[k] == wi[k] for k in wi if k in info), (est, g is None)
+        rec, scans, info = path_model.samples(rays, t, m, 5, 1, 3, est, s, vn, z)
+        assert np.array_equal(_bits(rec), _bits(want)) and scans == want_scans, est
+        assert info["glass"] == 0 and info == wi, est
     # zero dielectric table = zero specular table = no table
     if tables == "none":
         for est in sorted(ESTIMATORS):
-            a = dm.samples(rays, t, m, 5, 1, 3, est, None, None, z)
+            a = path_model.samples(rays, t, m, 5, 1, 3, est, None, None, z)
             b = path_model.samples(rays, t, m, 5, 1, 3, est, np.zeros_like(z))
             assert np.array_equal(_bits(a[0]), _bits(b[0])) and a[1] == b[1], est
 
@@ -157,7 +143,7 @@ def test_slab_by_hand(est):
     through, or once back and forth inside): 0.92307 +- 0.021 at 4096 samples"""
     t, m, g, ray = slab_scene()
     n = 4096
-    rec, scans, info = dm.samples(ray, t, m, 5, 0, n, est, glass=g)
+    rec, scans, info = path_model.samples(ray, t, m, 5, 0, n, est, glass=g)
     want = np.asarray(KT, F) * (np.asarray(KT, F) * m[2, 3:6])
     assert list(want) == [F(0.5), F(0.1875), F(0.75)]
     lit = rec[0].any(1)
@@ -283,9 +269,9 @@ def test_slab_bit_exact(variant, est):
     """the hand scene: W x H copies of the one ray (the pixel keys the draws), image, mean and scans"""
     t, m, g, ray = slab_scene()
     rays = np.ascontiguousarray(np.broadcast_to(ray, (W * H, 6)))
-    want_img, want_mean, want_scans, info = dm.render(rays, t, m, SPP, REPLAY_SEED, est, glass=g)
+    want_img, want_mean, want_scans, info = path_model.render(rays, t, m, SPP, REPLAY_SEED, est, glass=g)
     assert info["transmit"] > 0 and info["emitter_after_glass"] > 0 and info["glass"] > info["transmit"]
-    c = _ctx(t, m, None, None, g)
+    c = hc.ctx(t, m, glass=g)
     img, mean = c.render(rays, W, H, SPP, seed=REPLAY_SEED, flags=GLASS | ESTIMATORS[est] | variant, want_accum=True)
     st = c.stats()
     c.close()
@@ -304,8 +290,8 @@ def test_model_bit_exact(smooth, mixed, variant, est):
     t, m, s, vn, g = sphere_scene(smooth, mixed)
     want_img, want_mean, want_scans, info = _model(smooth, mixed, est)
     _covered(info, smooth)
-    c = _ctx(t, m, s, vn, g)
-    img, mean = c.render(hc.rays(), W, H, SPP, seed=REPLAY_SEED, flags=_case_flags(s, vn) | ESTIMATORS[est] | variant, want_accum=True)
+    c = hc.ctx(t, m, s, vn, glass=g)
+    img, mean = c.render(hc.rays(), W, H, SPP, seed=REPLAY_SEED, flags=hc.table_flags(s, vn, g) | ESTIMATORS[est] | variant, want_accum=True)
     st = c.stats()
     c.close()
     assert st["kernel_variant"] == variant
@@ -326,7 +312,7 @@ def test_zero_table_is_no_flag(variant, tables, est):
     f = ESTIMATORS[est] | variant | (SPEC if s is not None else 0) | (SMOOTH if vn is not None else 0)
     z = np.zeros((t.shape[0], 4), F)
     z[:, 0:3] = 0.7
-    c = _ctx(t, m, s, vn, z)
+    c = hc.ctx(t, m, s, vn, glass=z)
     hc.check_zero_table_is_no_flag(c, f, GLASS)
     c.set_dielectric(scene.dielectric_table(t, which=np.arange(14, t.shape[0])))
     rays = hc.rays()
@@ -341,8 +327,8 @@ def test_both_block_shapes(shape, smooth, est):
     """variant 16 in its 256- and its 512-thread shape: the replay, a progressive and an adaptive split, primary-hit reuse, camera
     samples, and zero table = no flag; the tile size of the stream says which shape ran"""
     t, m, s, vn, g = sphere_scene(smooth, True)
-    c = _ctx(t, m, s, vn, g)
-    hc.check_both_block_shapes(c, shape, ESTIMATORS[est] | 16 | (_case_flags(s, vn) & ~GLASS), GLASS, _model(smooth, True, est)[:3],
+    c = hc.ctx(t, m, s, vn, glass=g)
+    hc.check_both_block_shapes(c, shape, ESTIMATORS[est] | 16 | (hc.table_flags(s, vn, g) & ~GLASS), GLASS, _model(smooth, True, est)[:3],
                                lambda c: c.set_dielectric(np.zeros_like(g)))
     c.close()
 
@@ -352,8 +338,8 @@ def test_both_block_shapes(shape, smooth, est):
 @pytest.mark.parametrize("variant", [16, capi.FLAG_ACCEL, 1])
 def test_progressive_adaptive_denoise(variant, est):
     t, m, s, vn, g = sphere_scene(True, True)
-    f = _case_flags(s, vn) | ESTIMATORS[est] | variant
-    c = _ctx(t, m, s, vn, g)
+    f = hc.table_flags(s, vn, g) | ESTIMATORS[est] | variant
+    c = hc.ctx(t, m, s, vn, glass=g)
     hc.check_progressive_adaptive_denoise(c, f)
     g1 = c.accum_gbuffer()
     c.accum_begin(rays=hc.rays(), w=W, h=H, seed=9, flags=f & ~GLASS, adaptive=(0.3, 0.05, 4))
@@ -371,7 +357,7 @@ def test_camera_samples_and_device_table(variant, est):
     t, m, s, vn, g = sphere_scene(True, True)
     c = hc.ctx(t, m, s, vn)
     hc.set_device_table(c.set_dielectric_device, g)
-    hc.check_camera_samples(c, _case_flags(s, vn) | ESTIMATORS[est] | variant)
+    hc.check_camera_samples(c, hc.table_flags(s, vn, g) | ESTIMATORS[est] | variant)
     c.close()
 
 
@@ -383,15 +369,15 @@ def test_reuse_chunks_multi_device(smooth, est):
     single context's render; sphip_set_dielectric ends a multi-device accumulation"""
     t, m, s, vn, g = sphere_scene(smooth, False)
     r = hc.rays()
-    f = _case_flags(s, vn) | ESTIMATORS[est]
-    c = _ctx(t, m, s, vn, g)
+    f = hc.table_flags(s, vn, g) | ESTIMATORS[est]
+    c = hc.ctx(t, m, s, vn, glass=g)
     want = c.render(r, W, H, SPP, seed=4, flags=f, want_accum=True)
     assert not hc.same(want, c.render(r, W, H, SPP, seed=4, flags=f & ~GLASS, want_accum=True))
     for extra in (capi.FLAG_PRIMARY_REUSE, capi.flag_chunks(1), capi.flag_chunks(4), capi.flag_chunks(3) | capi.FLAG_PRIMARY_REUSE, 1, 1 | capi.FLAG_PRIMARY_REUSE):
         assert hc.same(c.render(r, W, H, SPP, seed=4, flags=f | extra, want_accum=True), want), extra
     c.close()
     for devs in ([0, 0], [0, 0, 0]):
-        mc = _ctx(t, m, s, vn, g, devs)
+        mc = hc.ctx(t, m, s, vn, devs, glass=g)
         got = mc.render(r, W, H, SPP, seed=4, flags=f, want_accum=True)
         mc.accum_begin(rays=r, w=W, h=H, seed=4, flags=f)
         mc.accum_step(1)
@@ -412,8 +398,8 @@ def test_reuse_chunks_multi_device(smooth, est):
 def test_accel_geometric_parity(est):
     """the BVH gives variant 16's image up to its rare rounding-noise accepts: at least 99 % of the pixels"""
     t, m, s, vn, g = sphere_scene(True, True)
-    c = _ctx(t, m, s, vn, g)
-    f = _case_flags(s, vn) | ESTIMATORS[est]
+    c = hc.ctx(t, m, s, vn, glass=g)
+    f = hc.table_flags(s, vn, g) | ESTIMATORS[est]
     b = hc.check_accel_parity(c, f)
     assert c.stats()["kernel_variant"] == 8
     unflagged = c.render(hc.rays(), W, H, SPP, seed=3, flags=(f & ~GLASS) | capi.FLAG_ACCEL, want_accum=True)[1]
@@ -431,8 +417,8 @@ def test_unbiased_plain_vs_mis(smooth, seed0):
     w = h = 32
     rays = hc.rays(w, h)
     seeds = list(range(seed0, seed0 + 16))
-    f = _case_flags(s, vn)
-    c = _ctx(t, m, s, vn, g)
+    f = hc.table_flags(s, vn, g)
+    c = hc.ctx(t, m, s, vn, glass=g)
     a = hc.seeds_means(c, rays, w, h, 256, f | NEE_MIS, seeds)
     b = hc.seeds_means(c, rays, w, h, 256, f, seeds)
     c.close()
@@ -551,7 +537,7 @@ def test_cli_and_adapter(tmp_path):
     w, h = 40, 24
     cam = view.Camera(w, h)
     rays = np.ascontiguousarray(cam.get_viewport(), dtype=F)
-    c = _ctx(t, m, s, vn, g)
+    c = hc.ctx(t, m, s, vn, glass=g)
     glass = c.render(rays, w, h, 8, seed=9, flags=GLASS)
     glass_mis = c.render(rays, w, h, 8, seed=9, flags=GLASS | NEE_MIS)
     glass_all = c.render(rays, w, h, 8, seed=9, flags=GLASS | SPEC | SMOOTH)

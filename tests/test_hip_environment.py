@@ -2,9 +2,9 @@
 device-pointer form, the importance tables the library builds behind both, the two device functions of the octahedral mapping
 (sphip_selftest_device what 9 and 10), and SPHIP_FLAG_ENVIRONMENT in the path kernels.
 
-The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/env_model.py).  STATED TOLERANCE: 0 --
-texel indices, r3, directions, wt, rc, marg, tpdf, T, w_env and W, and the images, means and scans_executed of flagged renders, bit for
-bit.  Without the flag renders with a map set are held to the renders without one, bit for bit."""
+The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/env_model.py's steps in
+tests/path_model.py's loop, its `env` map).  STATED TOLERANCE: 0 -- texel indices, r3, directions, wt, rc, marg, tpdf, T, w_env and W,
+and the images, means and scans_executed of flagged renders, bit for bit.  Without the flag renders with a map set are held to the renders without one, bit for bit."""
 import ctypes as C
 import os
 
@@ -13,6 +13,7 @@ import pytest
 
 import env_model as em
 import hip_checks as hc
+import path_model
 from oracle import oracle as O
 from hip_checks import E_INVALID, E_STATE, ESTIMATORS, H, REPLAY_SEED, SPP, W, _torch_first, shape  # noqa: F401  (fixtures)
 from path_model import F, _bits
@@ -261,24 +262,11 @@ def _replay_scene(name, tables):
     return em.replay_scene(name, tables, hc.mixed_table)
 
 
-def _flags(s, vn, g):
-    return ENV | (capi.FLAG_SPECULAR if s is not None else 0) | (capi.FLAG_SMOOTH if vn is not None else 0) | (capi.FLAG_DIELECTRIC if g is not None else 0)
-
-
-def _ctx(t, m, s, vn, g, env, devs=None):
-    c = hc.ctx(t, m, s, vn, devs)
-    if g is not None:
-        c.set_dielectric(g)
-    if env is not None:
-        c.set_environment(env)
-    return c
-
-
 def _model(name, tables, mp, est):
     key = (name, tables, mp, est)
     if key not in _MODEL:
         t, m, s, vn, g = _replay_scene(name, tables)
-        _MODEL[key] = em.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, g, MAPS[mp])
+        _MODEL[key] = path_model.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, g, MAPS[mp])
     return _MODEL[key]
 
 
@@ -294,7 +282,7 @@ def test_orientation_by_hand():
     t = scene.flat_normals(t)
     m = np.full((1, 6), 0.5, F)
     env = (np.arange(48, dtype=F).reshape(4, 4, 3) + 1) / F(64)
-    c = _ctx(t, m, None, None, None, env)
+    c = hc.ctx(t, m, env=env)
     seen = {}
     for tag, rot in (("ahead", (0.0, 0.0, 0.0)), ("up", (-np.pi / 2, 0.0, 0.0)), ("down", (np.pi / 2, 0.0, 0.0))):
         cam = view.Camera(24, 16)
@@ -318,8 +306,8 @@ def _replay(name, mp, tables, variant, est, shape=None):
     t, m, s, vn, g = _replay_scene(name, tables)
     want_img, want_mean, want_scans, info = _model(name, tables, mp, est)
     em.covered(info, name, tables, est)
-    c = _ctx(t, m, s, vn, g, MAPS[mp])
-    img, mean = c.render(hc.rays(), W, H, SPP, seed=REPLAY_SEED, flags=_flags(s, vn, g) | ESTIMATORS[est] | variant, want_accum=True)
+    c = hc.ctx(t, m, s, vn, glass=g, env=MAPS[mp])
+    img, mean = c.render(hc.rays(), W, H, SPP, seed=REPLAY_SEED, flags=hc.table_flags(s, vn, g) | ENV | ESTIMATORS[est] | variant, want_accum=True)
     st = c.stats()
     if shape is not None:
         assert hc._tiles(c)[1] == shape
@@ -356,7 +344,7 @@ def test_zero_map_is_no_flag(variant, est):
     """an all-zero map: the flagged render is the unflagged one bit for bit, scans included, from rays and from a camera with and without
     camera samples; and a real map matters"""
     t, m = _scene()
-    c = _ctx(t, m, None, None, None, np.zeros((5, 5, 3), F))
+    c = hc.ctx(t, m, env=np.zeros((5, 5, 3), F))
     f = ESTIMATORS[est] | variant
     hc.check_zero_table_is_no_flag(c, f, ENV)
     c.set_environment(scene.sky_environment(64))
@@ -369,8 +357,8 @@ def test_zero_map_is_no_flag(variant, est):
 def test_both_block_shapes(shape, est):
     t, m, s, vn, g = _replay_scene("glass", True)
     env = MAPS["sky64"]
-    c = _ctx(t, m, s, vn, g, env)
-    hc.check_both_block_shapes(c, shape, ESTIMATORS[est] | 16 | (_flags(s, vn, g) & ~ENV), ENV, _model("glass", True, "sky64", est)[:3],
+    c = hc.ctx(t, m, s, vn, glass=g, env=env)
+    hc.check_both_block_shapes(c, shape, ESTIMATORS[est] | 16 | hc.table_flags(s, vn, g), ENV, _model("glass", True, "sky64", est)[:3],
                                lambda c: c.set_environment(np.zeros_like(env)))
     c.close()
 
@@ -379,8 +367,8 @@ def test_both_block_shapes(shape, est):
 @pytest.mark.parametrize("variant", [16, capi.FLAG_ACCEL, 1])
 def test_progressive_adaptive_denoise(variant, est):
     t, m, s, vn, g = _replay_scene("glass", True)
-    f = _flags(s, vn, g) | ESTIMATORS[est] | variant
-    c = _ctx(t, m, s, vn, g, MAPS["sky64"])
+    f = hc.table_flags(s, vn, g) | ENV | ESTIMATORS[est] | variant
+    c = hc.ctx(t, m, s, vn, glass=g, env=MAPS["sky64"])
     hc.check_progressive_adaptive_denoise(c, f)
     g1 = c.accum_gbuffer()
     c.accum_begin(rays=hc.rays(), w=W, h=H, seed=9, flags=f & ~ENV, adaptive=(0.3, 0.05, 4))
@@ -397,8 +385,8 @@ def test_camera_samples_and_device_setter(variant, est):
     import torch
     t, m, s, vn, g = _replay_scene("open", True)
     env = MAPS["sky64"]
-    f = _flags(s, vn, g) | ESTIMATORS[est] | variant
-    c = _ctx(t, m, s, vn, g, env)
+    f = hc.table_flags(s, vn, g) | ENV | ESTIMATORS[est] | variant
+    c = hc.ctx(t, m, s, vn, glass=g, env=env)
     want = c.render(hc.rays(), W, H, SPP, seed=5, flags=f, want_accum=True)
     c.set_environment(None)
     d = torch.from_numpy(env).to("cuda")
@@ -413,20 +401,20 @@ def test_camera_samples_and_device_setter(variant, est):
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
 def test_reuse_chunks_multi_device(est):
     """primary-hit reuse, sample chunks, variant 1 and multi-device contexts give the single context's render; sphip_set_environment ends
-    a multi-device accumulation.  The clauses are hip_checks.check_reuse_chunks_multi_device's, written out because its contexts (hc.ctx)
-    cannot carry a dielectric table or a map"""
+    a multi-device accumulation.  The clauses are hip_checks.check_reuse_chunks_multi_device's, written out because it builds its own
+    contexts, without a dielectric table or a map"""
     t, m, s, vn, g = _replay_scene("glass", False)
     env = MAPS["sky64"]
     r = hc.rays()
-    f = _flags(s, vn, g) | ESTIMATORS[est]
-    c = _ctx(t, m, s, vn, g, env)
+    f = hc.table_flags(s, vn, g) | ENV | ESTIMATORS[est]
+    c = hc.ctx(t, m, s, vn, glass=g, env=env)
     want = c.render(r, W, H, SPP, seed=4, flags=f, want_accum=True)
     assert not hc.same(want, c.render(r, W, H, SPP, seed=4, flags=f & ~ENV, want_accum=True))
     for extra in (capi.FLAG_PRIMARY_REUSE, capi.flag_chunks(1), capi.flag_chunks(4), capi.flag_chunks(3) | capi.FLAG_PRIMARY_REUSE, 1, 1 | capi.FLAG_PRIMARY_REUSE):
         assert hc.same(c.render(r, W, H, SPP, seed=4, flags=f | extra, want_accum=True), want), extra
     c.close()
     for devs in ([0, 0], [0, 0, 0]):
-        mc = _ctx(t, m, s, vn, g, env, devs)
+        mc = hc.ctx(t, m, s, vn, devs, g, env)
         got = mc.render(r, W, H, SPP, seed=4, flags=f, want_accum=True)
         mc.accum_begin(rays=r, w=W, h=H, seed=4, flags=f)
         mc.accum_step(1)
@@ -442,8 +430,8 @@ def test_reuse_chunks_multi_device(est):
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
 def test_accel_parity(est):
     t, m, s, vn, g = _replay_scene("glass", True)
-    c = _ctx(t, m, s, vn, g, MAPS["sky64"])
-    hc.check_accel_parity(c, _flags(s, vn, g) | ESTIMATORS[est])
+    c = hc.ctx(t, m, s, vn, glass=g, env=MAPS["sky64"])
+    hc.check_accel_parity(c, hc.table_flags(s, vn, g) | ENV | ESTIMATORS[est])
     assert c.stats()["kernel_variant"] == 8
     c.close()
 
@@ -451,7 +439,7 @@ def test_accel_parity(est):
 def test_set_scene_keeps_the_map_and_the_flagged_table_follows():
     """after a set_scene the flagged render is the model's for the new scene under the old map"""
     t, m = scene.closed_room(200)
-    c = _ctx(t, m, None, None, None, MAPS["sky64"])
+    c = hc.ctx(t, m, env=MAPS["sky64"])
     c.render(hc.rays(), W, H, 1, seed=1, flags=ENV | hc.NEE_MIS)
     t2, m2, s, vn, g = _replay_scene("open", False)
     c.set_scene(t2, m2)
@@ -507,7 +495,7 @@ def test_one_expectation(case):
     t, m = scene.open_clutter(100) if case == "open_clutter_sky" else em.window_room()
     seeds = range(500, 516) if case == "open_clutter_sky" else range(700, 716)
     r = hc.rays(32, 32)
-    c = _ctx(t, m, None, None, None, MAPS["sky64"])
+    c = hc.ctx(t, m, env=MAPS["sky64"])
     a = _seed_means(c, r, ENV | hc.NEE_MIS, seeds)
     b = _seed_means(c, r, ENV, seeds)
     c.close()
@@ -520,7 +508,7 @@ def test_sun_scene_bound_and_variance():
     lower under NEE|MIS than under the plain estimator"""
     t, m, env = em.sun_scene()
     r = hc.rays(32, 32)
-    c = _ctx(t, m, None, None, None, env)
+    c = hc.ctx(t, m, env=env)
     on = O.closest_hits(r, t, np.full(r.shape[0], -1, np.int32))[0] >= 0
     assert on.sum() > 300
     rho = float(m[:, 0:3].max())
@@ -552,7 +540,7 @@ def test_cli_and_python_renderer(tmp_path):
     scene.write_environment(se, env)
     w, h = 40, 24
     rays = np.ascontiguousarray(view.Camera(w, h).get_viewport(), dtype=F)
-    c = _ctx(t, m, None, None, None, env)
+    c = hc.ctx(t, m, env=env)
     lit = c.render(rays, w, h, 8, seed=9, flags=ENV)
     lit_mis = c.render(rays, w, h, 8, seed=9, flags=ENV | hc.NEE_MIS)
     plain = c.render(rays, w, h, 8, seed=9)

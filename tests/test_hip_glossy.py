@@ -2,13 +2,13 @@
 alpha that roughens the mirror lobe of SPHIP_FLAG_SPECULAR.  A hit that took the lobe of a triangle with alpha > 0 reflects about a
 microfacet normal drawn from the distribution of visible normals and is weighted by the Smith term G1 of the outgoing direction.
 
-The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/glossy_model.py, tests/env_model.py's
-loop restated with the glossy step).  STATED TOLERANCE: 0 -- images, means and scan counts bit for bit.  The statistical bars are the
-project's: hip_checks.z_grid over 16 seeds x 256 spp at 32 x 32 for plain against NEE|MIS, and 5 standard errors of the mean for the
-statement against the float64 quadrature of what it must mean.  The f32 statement is held to a float64 restatement of the same
+The arithmetic is stated operation by operation in the header, so it is replayed in numpy (tests/glossy_model.py's draw in
+tests/path_model.py's loop, its `rough` table).  STATED TOLERANCE: 0 -- images, means and scan counts bit for bit.  The statistical bars
+are the project's: hip_checks.z_grid over 16 seeds x 256 spp at 32 x 32 for plain against NEE|MIS, and 5 standard errors of the mean
+for the statement against the float64 quadrature of what it must mean.  The f32 statement is held to a float64 restatement of the same
 formulas at 2^-6 where cl >= 1/16 (test_f32_statement_against_float64 says where the figure comes from).
 
-CPU part: the flag and the symbols; the model against env_model without a table, with a table of zeros and on rows of zeros; a plane by
+CPU part: the flag and the symbols; the model with a table of zeros and on rows of zeros against the model without a table; a plane by
 hand; the statement against the quadrature; the f32 statement against float64; scene.roughness_table; the coverage of the replay cases.
 GPU part: the selftest; the replay for variants 1, 8 and 16, both estimators; zero table = no flag; both workgroup shapes; the
 compositions; one expectation and the sample bound; the error contract; the front ends."""
@@ -22,6 +22,7 @@ import pytest
 import env_model
 import glossy_model as gm
 import hip_checks as hc
+import path_model
 from hip_checks import E_INVALID, E_STATE, ESTIMATORS, NEE_MIS, REPLAY_SEED, SPP, H, W, _torch_first, shape  # noqa: F401  (fixtures)
 from path_model import F, _bits
 from spath_amd import capi, scene, view
@@ -74,25 +75,18 @@ CASES = ("floor", "mixed", "sphere", "glass", "sky")
 
 
 def _flags(k):
-    return GLOSSY | SPEC | (SMOOTH if k["vn"] is not None else 0) | (GLASS if k["g"] is not None else 0) | (ENV if k["env"] is not None else 0)
+    return hc.table_flags(k["s"], k["vn"], k["g"], k["env"], k["rough"])
 
 
 def _ctx(k, devs=None, rough=True):
-    c = hc.ctx(k["t"], k["m"], k["s"], k["vn"], devs)
-    if k["g"] is not None:
-        c.set_dielectric(k["g"])
-    if k["env"] is not None:
-        c.set_environment(k["env"])
-    if rough:
-        c.set_roughness(k["rough"])
-    return c
+    return hc.ctx(k["t"], k["m"], k["s"], k["vn"], devs, k["g"], k["env"], k["rough"] if rough else None)
 
 
 def _model(name, est):
     """the replay's reference, computed once per case"""
     if (name, est) not in _MODEL:
         k = case(name)
-        _MODEL[name, est] = gm.render(hc.rays(), k["t"], k["m"], SPP, REPLAY_SEED, est, k["s"], k["vn"], k["g"], k["env"], k["rough"])
+        _MODEL[name, est] = path_model.render(hc.rays(), k["t"], k["m"], SPP, REPLAY_SEED, est, k["s"], k["vn"], k["g"], k["env"], k["rough"])
     return _MODEL[name, est]
 
 
@@ -139,25 +133,19 @@ def test_flag_value_and_symbols():
 
 @pytest.mark.parametrize("est", sorted(ESTIMATORS))
 @pytest.mark.parametrize("tables", ["spec", "spec+glass+vn", "spec+env"])
-def test_model_is_env_model(tables, est):
-    """without a roughness table and with a table of zeros the restated loop is env_model.samples (which is dielectric_model's and
-    path_model's where their tables are absent: tests/test_env_model.py), bits and scans, plain and mis, bare and with glass, vertex
-    normals and a map; and rows of zeros among non-zero rows are the mirror: a table that is non-zero only on triangles whose lobe is
-    never specular changes nothing"""
+def test_zero_table_is_no_table(tables, est):
+    """a roughness table of zeros executes the step and changes nothing: the bits and the scans of the call without the table, plain
+    and mis, bare and with glass, vertex normals and a map; and rows of zeros among non-zero rows are the mirror: a table that is
+    non-zero only on triangles whose lobe is never specular changes nothing"""
     k = case("glass" if "glass" in tables else "sky" if "env" in tables else "mixed")
     t, m, s = k["t"], k["m"], k["s"]
     vn = scene.vertex_normals(t, which=np.arange(7, t.shape[0])) if "vn" in tables else None
     r = hc.rays(24, 16)
-    want = env_model.samples(r, t, m, REPLAY_SEED, 0, 2, est, s, vn, k["g"], k["env"])
-    for rough in (None, np.zeros(t.shape[0], F), np.where(s[:, 3] > 0, F(0), F(0.5)).astype(F)):
-        got = gm.samples(r, t, m, REPLAY_SEED, 0, 2, est, s, vn, k["g"], k["env"], rough)
+    want = path_model.samples(r, t, m, REPLAY_SEED, 0, 2, est, s, vn, k["g"], k["env"])
+    for rough in (np.zeros(t.shape[0], F), np.where(s[:, 3] > 0, F(0), F(0.5)).astype(F)):
+        got = path_model.samples(r, t, m, REPLAY_SEED, 0, 2, est, s, vn, k["g"], k["env"], rough)
         assert np.array_equal(_bits(got[0]), _bits(want[0])) and got[1] == want[1]
-        assert got[2]["glossy"] == 0 and (rough is None or got[2]["alpha0"] > 0)
-    # and without any table the three restatements are path_model's
-    import path_model
-    p = path_model.samples(r, t, m, REPLAY_SEED, 0, 2, est)
-    q = gm.samples(r, t, m, REPLAY_SEED, 0, 2, est)
-    assert np.array_equal(_bits(p[0]), _bits(q[0])) and p[1] == q[1]
+        assert got[2]["glossy"] == 0 and got[2]["alpha0"] > 0
 
 
 def test_plane_by_hand():

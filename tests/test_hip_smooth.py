@@ -40,7 +40,7 @@ def _model(name, mixed, est):
     if key not in _MODEL:
         t, m, s, vn = _case(name, mixed)
         fn = []
-        _MODEL[key] = path_model.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, fn, ("accepts",)) + (fn[0],)
+        _MODEL[key] = path_model.render(hc.rays(), t, m, SPP, REPLAY_SEED, est, s, vn, first_ns=fn, collect=("accepts",)) + (fn[0],)
     return _MODEL[key]
 
 
