@@ -82,6 +82,9 @@ enum {
 	SPHIP_FLAG_GLOSSY = 0x2000000,   /* OPT-IN glossy reflection: the mirror lobe of SPHIP_FLAG_SPECULAR roughened by the context's roughness
 	                                   table (sphip_set_roughness) for SPHIP_MODE_PT: valid only together with SPHIP_FLAG_SPECULAR; see
 	                                   "glossy reflection" below.  Without the flag the table is ignored. */
+	SPHIP_FLAG_TEXTURE = 0x4000000,  /* OPT-IN textures: the diffuse reflectance of a hit scaled by the bilinear sample of the context's atlas
+	                                   (sphip_set_texture) at the hit's interpolated UV (sphip_set_uv) for SPHIP_MODE_PT; see "textures"
+	                                   below.  Without the flag both are ignored. */
 	SPHIP_FLAG_ENVIRONMENT = 0x1000000 /* OPT-IN environment lighting by the context's octahedral radiance map (sphip_set_environment) for
 	                                   SPHIP_MODE_PT: a ray that leaves the scene carries the map's radiance, and NEE|MIS samples the map;
 	                                   see "environment lighting" below.  Without the flag the map is ignored.  (Bits 16..23 are the
@@ -218,7 +221,9 @@ int sphip_plan_shard(size_t width, size_t height, int n_devices, size_t tile_row
  *       10  env_sample     ("environment lighting" below)          in f64[4n] r8 r9 r3 r4                  out f32[6n] i, j, wd.xyz, r3
  *           9 and 10 run against the context's environment map (SPHIP_E_STATE without one)
  *       11  gloss_bounce   ("glossy reflection" below)             in f64[9n] dir.xyz ns.xyz alpha u1 u2 (dir, ns and alpha: f32 values
- *                                                                  carried in doubles, as what 3 does)      out f32[8n] m.xyz, nd.xyz, g, ok */
+ *                                                                  carried in doubles, as what 3 does)      out f32[8n] m.xyz, nd.xyz, g, ok
+ *       12  tex_albedo     ("textures" below)                      in f32[21n] pos dir v0 v1 v2 uv0 uv1 uv2  out f32[6n] s, t, c.rgb, textured
+ *           12 runs against the context's atlas (SPHIP_E_STATE without one); c = 1 where the hit is not textured */
 int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void* out);
 
 /* TEST-ONLY: stage 1 of the default scan ALONE -- the conservative reject that decides which (ray, triangle) pairs ever reach
@@ -731,6 +736,52 @@ int sphip_set_roughness(sphip_t* ctx, const float* alpha);
  * `stream` alone, and copied.  It does NOT validate the values: a table that breaks the rules above gives undefined images (never
  * out-of-bounds accesses). */
 int sphip_set_roughness_device(sphip_t* ctx, const void* d_alpha, void* stream);
+
+/* ---- textures (SPHIP_FLAG_TEXTURE): a per-triangle UV table beside the scene, 6 f32 per triangle: s0 t0 s1 t1 s2 t2
+ * for v0 v1 v2, and one atlas on the context, tw x th RGB texels, f32, row-major: texel (i, j) at texels[(j * tw + i) * 3], row 0 at
+ * t = 0.  With the flag the diffuse reflectance of a hit on a textured triangle is albedo = rho * c per channel: rho the material's
+ * reflectance, c the bilinear sample of the atlas at the hit's interpolated UV, with repeat addressing.  albedo replaces rho in exactly
+ * two places: the unwind's brdf_d = albedo * (1 / pi), and the reflectance of the hit in its light sample L_d (a triangle light's and
+ * the map's).  Nothing else reads it: ks, kt, the emittance, the light table, the G-buffer (its albedo and mat stay the material's),
+ * the flat pass and hit queries are unchanged, and so is scans_executed: a texture traces nothing.  A row of the UV table whose six
+ * values all compare equal to 0.0f leaves its triangle untextured (as nine zero normals leave a triangle flat).
+ *
+ * Valid for SPHIP_MODE_PT with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with variants 1, 8 (SPHIP_FLAG_ACCEL) and 16
+ * in both workgroup shapes, with SPHIP_FLAG_SPECULAR, SPHIP_FLAG_GLOSSY, SPHIP_FLAG_DIELECTRIC, SPHIP_FLAG_ENVIRONMENT, SPHIP_FLAG_SMOOTH
+ * and SPHIP_FLAG_CAMERA_SAMPLES on or off, with progressive and adaptive accumulation and denoising, sample chunks, primary-hit reuse,
+ * shards and multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT; with SPHIP_FLAG_NEE alone; with variants 2, 15 or a retired
+ * one.  SPHIP_E_STATE: the flag without a UV table (checked first), or without an atlas.  Hit queries ignore the flag.  Without the
+ * flag every render is bit for bit what it is without a table; with the flag and a table of zeros too.
+ *
+ * The arithmetic at a hit on triangle i by ray (o, dir).  f32, every operation rounded on its own, nothing fused:
+ *   bary:    u, v exactly as smooth shading computes them (geom.h:200-212), for the winning triangle, after the scan
+ *   interp:  w = (1.0f - u) - v;  s = (s0 * w + s1 * u) + s2 * v;  t likewise
+ *            textured iff the row is not all zero and s, t are finite; otherwise albedo = rho: the hit is in every respect what it is
+ *            without the flag
+ *   wrap:    fs = s - floorf(s);  fs = fs < 1.0f ? fs : 0.0f;  ft likewise                       (repeat addressing)
+ *   texel:   x = fs * (float)tw - 0.5f;  x0 = floorf(x);  fx = x - x0;  i0 = (int)x0;  i0 = i0 < 0 ? i0 + tw : i0;
+ *            i1 = i0 + 1 == tw ? 0 : i0 + 1;  y, y0, fy, j0, j1 likewise with th
+ *   lerp:    top = t00 + (t10 - t00) * fx;  bot = t01 + (t11 - t01) * fx;  c = top + (bot - top) * fy   (per channel; tIJ = texel (iI, jJ))
+ *   albedo:  rho * c per channel
+ * Where the four texels of a footprint are equal, c is that texel bit for bit: the lerp form is chosen for that. */
+
+/* The context's atlas: tw x th x 3 f32 on the host (NULL clears it), by the rules of sphip_set_environment: blocking; accepted by
+ * multi-device contexts (every device keeps the atlas); kept across set_scene and needs no scene; during an accumulation it ends the
+ * accumulation as a set_scene does.  SPHIP_E_INVALID when tw or th is 0 or above 4096, or a value is negative or not finite (the message
+ * names the first such texel; the atlas stays as it was). */
+int sphip_set_texture(sphip_t* ctx, const float* texels, uint32_t tw, uint32_t th);
+/* The same from a device pointer, by the rules of sphip_set_environment_device: single-device contexts (SPHIP_E_STATE otherwise),
+ * ordered by `stream` alone, and copied.  It does NOT validate the values: texels that break the rules above give undefined images
+ * (never out-of-bounds accesses). */
+int sphip_set_texture_device(sphip_t* ctx, const void* d_texels, uint32_t tw, uint32_t th, void* stream);
+/* The context's UV table: n_tris * 6 f32 on the host for the scene last set (NULL clears the table), by the rules of
+ * sphip_set_specular: blocking; accepted by multi-device contexts; cleared by every set_scene; during an accumulation it ends the
+ * accumulation as a set_scene does.  SPHIP_E_STATE without a scene; SPHIP_E_INVALID when a value is not finite (the message names the
+ * first such triangle; the table stays as it was). */
+int sphip_set_uv(sphip_t* ctx, const float* uv);
+/* The same from a device pointer, by the rules of sphip_set_specular_device.  It does NOT validate the values: a hit whose
+ * interpolated UV is not finite is untextured (never out-of-bounds accesses). */
+int sphip_set_uv_device(sphip_t* ctx, const void* d_uv, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

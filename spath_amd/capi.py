@@ -24,6 +24,7 @@ FLAG_SMOOTH = 0x4000        # smooth shading by the context's per-vertex normals
 FLAG_DIELECTRIC = 0x8000    # transparency: glass triangles from the context's dielectric table
 FLAG_ENVIRONMENT = 0x1000000  # environment lighting by the context's octahedral map
 FLAG_GLOSSY = 0x2000000     # with FLAG_SPECULAR: the mirror lobe roughened by the context's roughness table
+FLAG_TEXTURE = 0x4000000    # textures: the diffuse reflectance scaled by the context's atlas at the hit's UV
 
 
 def flag_chunks(n: int) -> int:
@@ -49,6 +50,7 @@ SYMBOLS = (
     "sphip_set_dielectric", "sphip_set_dielectric_device",
     "sphip_set_environment", "sphip_set_environment_device", "sphip_selftest_env_dump",
     "sphip_set_roughness", "sphip_set_roughness_device",
+    "sphip_set_texture", "sphip_set_texture_device", "sphip_set_uv", "sphip_set_uv_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 
@@ -222,6 +224,14 @@ def load():
     L.sphip_set_roughness.argtypes = [vp, vp]
     L.sphip_set_roughness_device.restype = C.c_int
     L.sphip_set_roughness_device.argtypes = [vp, vp, vp]
+    L.sphip_set_uv.restype = C.c_int
+    L.sphip_set_uv.argtypes = [vp, vp]
+    L.sphip_set_uv_device.restype = C.c_int
+    L.sphip_set_uv_device.argtypes = [vp, vp, vp]
+    L.sphip_set_texture.restype = C.c_int
+    L.sphip_set_texture.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.sphip_set_texture_device.restype = C.c_int
+    L.sphip_set_texture_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
     L.sphip_set_dielectric.restype = C.c_int
     L.sphip_set_dielectric.argtypes = [vp, vp]
     L.sphip_set_dielectric_device.restype = C.c_int
@@ -400,6 +410,31 @@ class Context:
             raise ValueError("one roughness value per triangle of the scene")
         self._check(self._L.sphip_set_roughness(self._h, alpha.ctypes.data), "sphip_set_roughness")
 
+    def set_uv(self, uv):
+        """sphip_set_uv: the UV table of FLAG_TEXTURE renders, (n_tris, 6) f32: s0 t0 s1 t1 s2 t2 for v0 v1 v2 of each triangle of the
+        scene last set (scene.uv_table and scene.planar_uv build one); a row of zeros leaves its triangle untextured; None clears it.
+        Every set_scene clears it too."""
+        import numpy as np
+        if uv is None:
+            self._check(self._L.sphip_set_uv(self._h, None), "sphip_set_uv")
+            return
+        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 6)
+        if uv.shape[0] != getattr(self, "_n_tris", uv.shape[0]):
+            raise ValueError("one UV row per triangle of the scene")
+        self._check(self._L.sphip_set_uv(self._h, uv.ctypes.data), "sphip_set_uv")
+
+    def set_texture(self, texels):
+        """sphip_set_texture: the atlas of FLAG_TEXTURE renders, (th, tw, 3) f32 with texel (i, j) at [j, i] (scene.checker_texture
+        builds one); None clears it.  set_scene keeps it."""
+        import numpy as np
+        if texels is None:
+            self._check(self._L.sphip_set_texture(self._h, None, 0, 0), "sphip_set_texture")
+            return
+        texels = np.ascontiguousarray(texels, dtype=np.float32)
+        if texels.ndim != 3 or texels.shape[2] != 3:
+            raise ValueError("an atlas is (th, tw, 3)")
+        self._check(self._L.sphip_set_texture(self._h, texels.ctypes.data, texels.shape[1], texels.shape[0]), "sphip_set_texture")
+
     def set_environment(self, texels):
         """sphip_set_environment: the octahedral environment map, (n, n, 3) f32 with texel (i, j) at [j, i] (scene.sky_environment and
         scene.environment_from_latlong build one); None clears it.  set_scene keeps it."""
@@ -443,6 +478,14 @@ class Context:
     def set_roughness_device(self, d_alpha: int, stream: int = 0):
         """sphip_set_roughness_device: the table from a device pointer (n_tris f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_roughness_device(self._h, d_alpha, stream), "sphip_set_roughness_device")
+
+    def set_uv_device(self, d_uv: int, stream: int = 0):
+        """sphip_set_uv_device: the table from a device pointer (n_tris * 6 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_uv_device(self._h, d_uv, stream), "sphip_set_uv_device")
+
+    def set_texture_device(self, d_texels: int, tw: int, th: int, stream: int = 0):
+        """sphip_set_texture_device: the atlas from a device pointer (tw * th * 3 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_texture_device(self._h, d_texels or None, tw, th, stream or None), "sphip_set_texture_device")
 
     def set_environment_device(self, d_texels: int, n: int, stream: int = 0):
         """sphip_set_environment_device: the map from a device pointer (n * n * 3 f32, copied in stream order, NOT validated)."""
@@ -583,7 +626,7 @@ class Context:
         return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
-                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8)}
+                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8), 12: ("float32", 6)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""

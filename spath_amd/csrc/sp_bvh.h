@@ -167,6 +167,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	constexpr bool env = IsEnv<Acc...>::value;         // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place): a miss carries the map's radiance
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;       // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
+	constexpr bool tex = IsTex<Acc...>::value;         // textures (sp_integrator.h TexArgs, in GlossArgs' place): the hit's albedo per depth in hA
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -193,6 +194,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 		float hcos[5];
 		f3 hL[kNeeDepths];
 		f3 hD[kMisDepths];
+		f3 hA[5];                                       // textures: the albedo of hits 0..4
 		int nh = 0;
 		bool alive = valid;
 		f3 Em = mk3(0.0f, 0.0f, 0.0f);                  // environment: what the ray that left the scene carries
@@ -209,6 +211,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					f3 ns = n;                                    // the shading normal
 					bool sm = false, ended = false;               // smooth shading: a bounce below the surface ends the path
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
+					if constexpr (tex) hA[depth] = tex_hit(a, tex_args(acc_args...), bi, o, dir);
 					bool sl = false;                              // specular: this hit takes the mirror lobe
 					float pm = 0.0f;
 					float gi = 0.0f;                              // transparency: the triangle's ior; > 0: an interface, a specular hit
@@ -224,6 +227,17 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 						const bool full = depth == 0 || (spc && (hidx[depth > 0 ? depth - 1 : 0] & kSpecBit) != 0);   // after a mirror bounce e_d counts in full
 						const f3 De = full ? mk3(m[3], m[4], m[5]) : mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
 						f3 Ld = mk3(0.0f, 0.0f, 0.0f);
+						// the light sample of a textured hit takes the hit's albedo.  Two copies of the block: the kernels without TexArgs keep
+						// the lines, and so the instructions, they had before the element existed (tools/listing_diff.py)
+						if constexpr (tex) {
+							if (depth < kNeeDepths && !sl && nee_light<true, env, true>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, ns, bi, wd, tm, Lc, env_map(acc_args...), &hA[depth]) && (!smo || smooth_light_ok(sm, wd, n))) {
+								float sd; int si;
+								scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
+								my_scans++;
+								if (si < 0) Ld = Lc;
+								Ld = scale3(Ld, 1.0f / (1.0f - pm));   // L_d wD
+							}
+						} else
 						if (depth < kNeeDepths && !sl && nee_light<true, env>(a, nee_args(acc_args...), pixel, s0 + s, depth, x, ns, bi, wd, tm, Lc, env_map(acc_args...)) && (!smo || smooth_light_ok(sm, wd, n))) {
 							float sd; int si;
 							scan_bvh(B, x, wd, bi, sd, si, nullptr, nullptr, tm, true);
@@ -278,7 +292,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 			if (depth < nh) {
 				const int id = spc ? hidx[depth] & hmask : hidx[depth];
 				const float* m = a.mats + (size_t)id * 6;
-				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
+				f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
+				if constexpr (tex) brdf = scale3(hA[depth], kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = hD[depth];
 				else if constexpr (nee) e = add3(depth == 0 ? e : mk3(0.0f, 0.0f, 0.0f), hL[depth < kNeeDepths ? depth : 0]);

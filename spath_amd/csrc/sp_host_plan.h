@@ -14,7 +14,7 @@ namespace sp_host {
 // scan = the scan (2 = f32 cylinder filter, sp_cyl_scan.h; 3 = stage 1 on the f16 matrix pipe, sp_cylm_scan.h; 4 = its 512-thread shape)
 struct TwoStage { int R; bool split; int scan; };
 // what a checked render does (check_render): later steps read these, never `flags`.  Every bit but adapt and prog is set in path tracing only
-struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog, gloss; };
+struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog, gloss, tex; };
 constexpr uint64_t kChunkTargetBlocks = 262144;         // 256 x the 1024 resident workgroups (measured: profiles/r01_sample_chunks.log)
 constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sample scratch buffer
 
@@ -22,10 +22,12 @@ constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sampl
 // history (5 x int2), the accumulator (3 floats), then NEE's L[4][3] or MIS's D[5][3]; adp_wst: adaptive sampling's S1, S2 (2 doubles);
 // env_M: the miss term of an environment render (a glossy render's kernels carry a map, the context's black one if need be).  The chunk back-off's estimate and the allocations both read it: a feature that parks
 // something per slot adds its line here, once
-constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12;
-struct SlotBytes { size_t work, adp_wst, env_M; };
+// tex_A: the albedo of hits 0..4 of a textured render, A[5][3] (a textured render's kernels carry a map as a glossy render's do)
+constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12, kSlotTexA = 60;
+struct SlotBytes { size_t work, adp_wst, env_M, tex_A; };
 constexpr SlotBytes slot_bytes(const Features& f) {
-	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env || f.gloss ? kSlotEnvM : 0 };
+	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env || f.gloss || f.tex ? kSlotEnvM : 0,
+	         f.tex ? kSlotTexA : 0 };
 }
 
 struct LaunchPlan {
@@ -69,7 +71,7 @@ LaunchPlan plan_launch(uint64_t n_rays, uint64_t n_samples, uint32_t forced, boo
 			bool asked = false;
 			if (samp_bytes > kChunkMaxBytes) p.chunks = 1;
 			while (p.chunks > 1) {
-				const uint64_t work_bytes = lanes * p.chunks * (p.slot.work + p.slot.adp_wst + p.slot.env_M);
+				const uint64_t work_bytes = lanes * p.chunks * (p.slot.work + p.slot.adp_wst + p.slot.env_M + p.slot.tex_A);
 				const uint64_t need = (samp_bytes > samp_cap ? samp_bytes : 0) + (work_bytes > work_cap ? work_bytes : 0);
 				if (need == 0) break;
 				if (!asked) { asked = true; if ((free_b = free_bytes()) < 0) { p.chunks = 1; break; } }

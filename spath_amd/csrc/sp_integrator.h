@@ -162,6 +162,20 @@ struct GlossArgs : EnvArgs {
 };
 constexpr uint32_t kGlossStream = 48u;
 
+// textures (SPHIP_FLAG_TEXTURE, include/spath_hip.h): the scene's UV table, 6 floats per triangle: s0 t0 s1 t1 s2 t2
+// for v0 v1 v2 (a row of zeros leaves its triangle untextured), and the context's atlas, tw x th RGB texels, texel (i, j) at
+// (j * tw + i) * 3.  It rides IN GlossArgs' PLACE (as GlossArgs rides in EnvArgs'): k_pt<V, MisArgs, TexArgs, NormArgs, CamArgs>, ...
+// spec, glass and rough are the scene's tables or zeros, env the context's map or its black one, as in GlossArgs.  The hit's albedo
+// rho * c (tex_albedo) replaces the material's reflectance in the unwind's brdf and in the light sample, nowhere else.
+// A: the two-stage kernels park the albedo of depth d there, A[(d * 3 + c) * n_work + slot] (12 B per depth and slot)
+struct TexArgs : GlossArgs {
+	const float* uv;           // n_tris * 6
+	const float* atlas;        // tw * th * 3
+	uint32_t tw, th;
+	float* A;                  // two-stage kernels only
+};
+constexpr uint32_t kTexMaxN = 4096;
+
 // smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
 // n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
 // CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
@@ -175,7 +189,8 @@ template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHa
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
-template <typename... Acc> struct IsGloss { static constexpr bool value = PackHas<GlossArgs, Acc...>::value; };
+template <typename... Acc> struct IsTex { static constexpr bool value = PackHas<TexArgs, Acc...>::value; };
+template <typename... Acc> struct IsGloss { static constexpr bool value = PackHas<GlossArgs, Acc...>::value || IsTex<Acc...>::value; };
 template <typename... Acc> struct IsEnv { static constexpr bool value = PackHas<EnvArgs, Acc...>::value || IsGloss<Acc...>::value; };
 template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value || IsEnv<Acc...>::value; };
 template <typename... Acc> struct IsSpec { static constexpr bool value = PackHas<SpecArgs, Acc...>::value || IsGlass<Acc...>::value; };
@@ -203,6 +218,7 @@ template <typename... P> SP_DEV const EnvMap* env_map(const P&... p) {
 	else return nullptr;
 }
 template <typename... P> SP_DEV const float* rough_table(const P&... p) { return pack_get<GlossArgs>(p...).rough; }
+template <typename... P> SP_DEV const TexArgs& tex_args(const P&... p) { return pack_get<TexArgs>(p...); }
 template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
@@ -352,9 +368,11 @@ SP_DEV f3 env_miss(const EnvMap& e, f3 dir, bool full) {
 	return mk3(Le.x / opu, Le.y / opu, Le.z / opu);
 }
 // the light sample that picked the map's entry of the light table, at a hit on triangle src of shading normal n: (r3u, r4u) are the
-// uniforms of stream 8 + d that place a triangle sample.  The shadow ray (x, wd) is unbounded: anything it hits occludes
+// uniforms of stream 8 + d that place a triangle sample.  The shadow ray (x, wd) is unbounded: anything it hits occludes.
+// TEX: the hit's reflectance is *refl, not the material's (textures: tex_albedo)
+template <bool TEX = false>
 SP_DEV bool env_light(const KArgs& a, const EnvMap& e, uint32_t pixel, uint32_t sample, int depth, f3 n, int src, double r3u, double r4u,
-                      f3& wd, float& tmax, f3& L) {
+                      f3& wd, float& tmax, f3& L, const f3* refl = nullptr) {
 	double r8, r9;
 	philox_uniforms(a.seed, pixel, sample, kEnvStream + (uint32_t)depth, &r8, &r9);
 	uint32_t i, j;
@@ -367,7 +385,8 @@ SP_DEV bool env_light(const KArgs& a, const EnvMap& e, uint32_t pixel, uint32_t 
 	const float g = (kTwoPi * cos_x) / (1.0f + env_u(sxz, r3, e.tpdf[t]));
 	tmax = kMaxDist;
 	const float* ms = a.mats + (size_t)src * 6;
-	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(e.texels[t * 3], e.texels[t * 3 + 1], e.texels[t * 3 + 2]), g));
+	if constexpr (TEX) L = mul3(scale3(*refl, kInvPi), scale3(mk3(e.texels[t * 3], e.texels[t * 3 + 1], e.texels[t * 3 + 2]), g));
+	else L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(e.texels[t * 3], e.texels[t * 3 + 1], e.texels[t * 3 + 2]), g));
 	return true;
 }
 
@@ -375,10 +394,11 @@ SP_DEV bool env_light(const KArgs& a, const EnvMap& e, uint32_t pixel, uint32_t 
 // n: the hit triangle's normal as the path uses it (turned against the incoming ray); src: the hit triangle.  Returns whether a
 // shadow ray (x, wd) with the bound tmax is to be traced, and then L = the direct light it carries when nothing occludes it.
 // MIS: L carries the balance heuristic's weight u / (1 + u), and sxz = 0 is no early-out (L is finite).
-// ENV: the table is the flagged one, whose entry of triangle -1 is the environment map *em (env_light)
-template <bool MIS = false, bool ENV = false>
+// ENV: the table is the flagged one, whose entry of triangle -1 is the environment map *em (env_light).
+// TEX: the hit's reflectance is *refl, not the material's (textures: tex_albedo)
+template <bool MIS = false, bool ENV = false, bool TEX = false>
 SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_t sample, int depth, f3 x, f3 n, int src,
-                      f3& wd, float& tmax, f3& L, const EnvMap* em = nullptr) {
+                      f3& wd, float& tmax, f3& L, const EnvMap* em = nullptr, const f3* refl = nullptr) {
 	if (ne.n == 0) return false;
 	double r3, r4, r5, r6;
 	philox_uniforms(a.seed, pixel, sample, 8u + (uint32_t)depth, &r3, &r4);
@@ -392,7 +412,7 @@ SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_
 	}
 	const int li = ne.tri[lo];
 	if (li == src) return false;
-	if constexpr (ENV) if (li < 0) return env_light(a, *em, pixel, sample, depth, n, src, r3, r4, wd, tmax, L);
+	if constexpr (ENV) if (li < 0) return env_light<TEX>(a, *em, pixel, sample, depth, n, src, r3, r4, wd, tmax, L, refl);
 	const float* tv = a.tris + (size_t)li * 12;
 	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
 	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);
@@ -422,7 +442,8 @@ SP_DEV bool nee_light(const KArgs& a, const NeeArgs& ne, uint32_t pixel, uint32_
 	// MIS: g (u / (1 + u)) with u = ((pi^2 sxz) dist2) / (cos_y ipdf): the 1 / dist2 and 1 / sxz factors cancel, g <= 2 pi
 	if constexpr (MIS) g = (kTwoPi * cos_x) / (1.0f + mis_u(sxz, dist2, cos_y, ne.ipdf[lo]));
 	else g = (((cos_x * cos_y) / dist2) * ne.ipdf[lo]) * (kTwoOverPi / sxz);
-	L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
+	if constexpr (TEX) L = mul3(scale3(*refl, kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
+	else L = mul3(scale3(mk3(ms[0], ms[1], ms[2]), kInvPi), scale3(mk3(me[3], me[4], me[5]), g));
 	return true;
 }
 
@@ -562,6 +583,77 @@ SP_DEV f3 gloss_unwind(const float4* __restrict__ glass, const float4* __restric
 		return add3(e, scale3(scale3(mul3(mk3(q.x, q.y, q.z), rec), 1.0f / q.w), ct));
 	}
 	return glass_unwind(glass, spec, id, e, brdf, rec, ct);
+}
+
+// ---- textures (include/spath_hip.h "textures").  f32, every operation rounded on its own.
+// One axis of the bilinear footprint of coordinate s on n texels, repeat addressing: the two texel indices and the weight of the second
+SP_DEV void tex_axis(float s, uint32_t n, int& i0, int& i1, float& fx) {
+	float fs = s - __builtin_floorf(s);
+	fs = fs < 1.0f ? fs : 0.0f;                        // a small negative s rounds s - floorf(s) up to 1
+	const float x = fs * (float)n - 0.5f;
+	const float x0 = __builtin_floorf(x);
+	fx = x - x0;
+	i0 = (int)x0;
+	i0 = i0 < 0 ? i0 + (int)n : i0;
+	i1 = i0 + 1 == (int)n ? 0 : i0 + 1;
+}
+// the bilinear sample of the tw x th atlas at (s, t), both finite.  The lerp form returns a texel bit for bit where the four texels of
+// the footprint are equal
+SP_DEV f3 tex_sample(const float* __restrict__ atlas, uint32_t tw, uint32_t th, float s, float t) {
+	int i0, i1, j0, j1;
+	float fx, fy;
+	tex_axis(s, tw, i0, i1, fx);
+	tex_axis(t, th, j0, j1, fy);
+	const float* p00 = atlas + ((size_t)j0 * tw + (size_t)i0) * 3;
+	const float* p10 = atlas + ((size_t)j0 * tw + (size_t)i1) * 3;
+	const float* p01 = atlas + ((size_t)j1 * tw + (size_t)i0) * 3;
+	const float* p11 = atlas + ((size_t)j1 * tw + (size_t)i1) * 3;
+	float c[3];
+#pragma unroll
+	for (int k = 0; k < 3; ++k) {
+		const float top = p00[k] + (p10[k] - p00[k]) * fx;
+		const float bot = p01[k] + (p11[k] - p01[k]) * fx;
+		c[k] = top + (bot - top) * fy;
+	}
+	return mk3(c[0], c[1], c[2]);
+}
+// the texture's colour c at the hit of ray (o, dir) on the triangle whose vertices are tv[0..8] and whose UV row is uvr[0..5]:
+//   bary:    u, v exactly as shade_normal computes them (geom.h:200-212), for the winning triangle
+//   interp:  w = (1 - u) - v;  s = (s0 w + s1 u) + s2 v;  t likewise
+// Returns whether the hit is textured: the row is not all zero and s, t are finite; otherwise c = 1
+SP_DEV bool tex_lookup(const float* __restrict__ tv, const float* __restrict__ uvr, const float* __restrict__ atlas, uint32_t tw, uint32_t th,
+                       f3 o, f3 dir, float& s, float& t, f3& c) {
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);   // geom.h:200-201
+	const f3 h = cross3(dir, e2);                    // :202
+	const float a = dot3(e1, h);                     // :203
+	const float f = recip_ieee(a);                   // :206
+	const f3 sv = sub3(o, v0);                       // :207
+	const float u = f * dot3(sv, h);                 // :208
+	const f3 q = cross3(sv, e1);                     // :211
+	const float v = f * dot3(dir, q);                // :212
+	const float w = (1.0f - u) - v;
+	s = (uvr[0] * w + uvr[2] * u) + uvr[4] * v;
+	t = (uvr[1] * w + uvr[3] * u) + uvr[5] * v;
+	const bool zero = uvr[0] == 0.0f && uvr[1] == 0.0f && uvr[2] == 0.0f && uvr[3] == 0.0f && uvr[4] == 0.0f && uvr[5] == 0.0f;
+	const bool tex = !zero && fabsf(s) < __builtin_inff() && fabsf(t) < __builtin_inff();
+	c = mk3(1.0f, 1.0f, 1.0f);
+	if (tex) c = tex_sample(atlas, tw, th, s, t);
+	return tex;
+}
+// the albedo of that hit: rho * c per channel, the material's reflectance rho = mat[0..2] itself on an untextured hit.  Called once per
+// hit, after the scan.  NOT inlined, on purpose, as gloss_hit is not: the path kernels are at their VGPR limit
+__device__ __attribute__((noinline)) f3 tex_albedo(const float* __restrict__ tv, const float* __restrict__ uvr, const float* __restrict__ mat,
+                                                   const float* __restrict__ atlas, uint32_t tw, uint32_t th, f3 o, f3 dir) {
+	const f3 rho = mk3(mat[0], mat[1], mat[2]);
+	float s, t;
+	f3 c;
+	if (!tex_lookup(tv, uvr, atlas, tw, th, o, dir, s, t, c)) return rho;
+	return mul3(rho, c);
+}
+// ... for hit triangle bi of a path kernel
+SP_DEV f3 tex_hit(const KArgs& a, const TexArgs& x, int bi, f3 o, f3 dir) {
+	return tex_albedo(a.tris + (size_t)bi * 12, x.uv + (size_t)bi * 6, a.mats + (size_t)bi * 6, x.atlas, x.tw, x.th, o, dir);
 }
 
 // ---- what the kernels share around the integrator: each is used where the kernel keeps its instructions with it (DESIGN.md

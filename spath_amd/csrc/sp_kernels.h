@@ -222,6 +222,18 @@ __global__ void __launch_bounds__(256) k_selftest_gloss(const double* __restrict
 	w[0] = m.x; w[1] = m.y; w[2] = m.z; w[3] = nd.x; w[4] = nd.y; w[5] = nd.z; w[6] = g; w[7] = ok ? 1.0f : 0.0f;
 }
 
+// what 12: tex_lookup, what tex_albedo samples.  pos dir v0 v1 v2 uv0 uv1 uv2 -> s t c.rgb textured
+__global__ void __launch_bounds__(256) k_selftest_tex(const float* __restrict__ in, uint32_t n, const float* __restrict__ atlas, uint32_t tw, uint32_t th, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const float* q = in + 21 * (size_t)i;
+	float s, t;
+	f3 c;
+	const bool tx = tex_lookup(q + 6, q + 15, atlas, tw, th, mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), s, t, c);
+	float* w = out + 6 * (size_t)i;
+	w[0] = s; w[1] = t; w[2] = c.x; w[3] = c.y; w[4] = c.z; w[5] = tx ? 1.0f : 0.0f;
+}
+
 SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	const uint64_t t = (uint64_t)k / a.tile_px;
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
@@ -365,6 +377,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	constexpr bool env = IsEnv<Acc...>::value;                   // environment lighting (EnvArgs, in GlassArgs' place): a miss carries the map's radiance
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;                 // glossy reflection (GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
+	constexpr bool tex = IsTex<Acc...>::value;                   // textures (TexArgs, in GlossArgs' place): the hit's albedo per depth in A0..A4
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -401,6 +414,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 		f3 L0 = mk3(0.0f, 0.0f, 0.0f), L1 = L0, L2 = L0, L3 = L0;   // NEE: direct light sampled at hits 0..3
 		f3 D0 = L0, D1 = L0, D2 = L0, D3 = L0, D4 = L0;             // MIS: D_d = e_d w_b + L_d
 		f3 Em = L0;                                                  // environment: what the ray that left the scene carries
+		f3 A0 = L0, A1 = L0, A2 = L0, A3 = L0, A4 = L0;             // textures: the albedo of hits 0..4
 #pragma unroll 1
 		for (int depth = 0; depth < (mis ? kMisDepths : nee ? kNeeDepths : 5); ++depth) {   // :33 depth >= 5 -> black (NEE: the 5th hit carries nothing)
 			if (!__syncthreads_or(alive ? 1 : 0)) break;   // block-uniform: the LDS scan has barriers
@@ -421,6 +435,11 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				f3 ns = n;                                        // the shading normal
 				bool sm = false;
 				if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
+				[[maybe_unused]] f3 alb;                          // textures: the hit's albedo
+				if constexpr (tex) {
+					alb = tex_hit(a, tex_args(acc_args...), bi, o, dir);
+					if (depth == 0) A0 = alb; else if (depth == 1) A1 = alb; else if (depth == 2) A2 = alb; else if (depth == 3) A3 = alb; else A4 = alb;
+				}
 				bool sl = false;                                  // specular: this hit takes the mirror lobe
 				float pm = 0.0f;
 				float gi = 0.0f;                                  // transparency: the triangle's ior; > 0: an interface, a specular hit
@@ -432,7 +451,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				if constexpr (mis) {
 					if (depth == 0 || (spc && pspec)) { const float* m = a.mats + (size_t)bi * 6; De = mk3(m[3], m[4], m[5]); }
 					else De = mis_emit(a, mis_tipdf(acc_args...), dir, bd, bi);
-					if (depth < kNeeDepths && !sl) sh = nee_light<true, env>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc, env_map(acc_args...));
+					if constexpr (tex) { if (depth < kNeeDepths && !sl) sh = nee_light<true, env, true>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc, env_map(acc_args...), &alb); }
+					else if (depth < kNeeDepths && !sl) sh = nee_light<true, env>(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), ns, bi, wd, tm, Lc, env_map(acc_args...));
 					if constexpr (smo) sh = sh && smooth_light_ok(sm, wd, n);
 					if constexpr (spc) if (sh) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 				} else if constexpr (nee) sh = nee_light(a, nee_args(acc_args...), pixel, s0 + s, depth, add3(o, scale3(dir, bd)), n, bi, wd, tm, Lc);
@@ -489,7 +509,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 			const float ct = depth == 0 ? c0 : depth == 1 ? c1 : depth == 2 ? c2 : depth == 3 ? c3 : c4;
 			if (id >= 0) {
 				const float* m = a.mats + (size_t)(spc ? id & hmask : id) * 6;
-				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                     // :63
+				f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);                           // :63
+				if constexpr (tex) brdf = scale3(depth == 0 ? A0 : depth == 1 ? A1 : depth == 2 ? A2 : depth == 3 ? A3 : A4, kInvPi);
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) e = depth == 0 ? D0 : depth == 1 ? D1 : depth == 2 ? D2 : depth == 3 ? D3 : D4;   // D_d
 				else if constexpr (nee) {                                                   // (e_0 or 0) + L_d

@@ -94,6 +94,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_flat_filter
 // slot stays 8 B per depth, and the unwind (and the next hit's MIS weight) reads the lobe back from there.
 // With a NormArgs (smooth shading, sp_integrator.h) the barycentric coordinates are recomputed for the winning triangle after the
 // scan (shade_normal), never inside its tile loops; a path whose bounce leaves the surface's upper side stops being active.
+// With a TexArgs (textures, sp_integrator.h) the hit's albedo is computed once per hit after the scan (tex_albedo) and parked in
+// TexArgs::A[5][3][n_work] (12 B per depth and slot) for the unwind.
 template <int R, bool SPLIT, int SCAN, typename... Acc>
 __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(const KArgs a, const ScanSrc src2, const unsigned int* __restrict__ bounds,
                                                    int2* __restrict__ hist, float* __restrict__ acc, uint32_t n_work, const Acc... acc_args) {
@@ -120,6 +122,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	constexpr bool env = IsEnv<Acc...>::value;               // environment lighting (sp_integrator.h EnvArgs, in GlassArgs' place)
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;             // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place)
+	constexpr bool tex = IsTex<Acc...>::value;               // textures (sp_integrator.h TexArgs, in GlossArgs' place): the hit's albedo parked in TexArgs::A
 	constexpr int hmask = HistMask<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
@@ -228,6 +231,12 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						f3 ns = n;                                 // the shading normal
 						if constexpr (smo) smr[r] = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
 						nadj[r] = ns;
+						[[maybe_unused]] f3 alb;                   // textures: the hit's albedo, parked for the unwind
+						if constexpr (tex) {
+							alb = tex_hit(a, tex_args(acc_args...), bi[r], s.o[r], s.dir[r]);
+							float* Ap = tex_args(acc_args...).A + (size_t)depth * 3 * n_work + k0 + r * B;
+							Ap[0] = alb.x; Ap[n_work] = alb.y; Ap[(size_t)2 * n_work] = alb.z;
+						}
 						const f3 x = add3(s.o[r], scale3(s.dir[r], bd[r]));
 						f3 wd = s.dir[r], Lc = mk3(0.0f, 0.0f, 0.0f);
 						float tm = kMaxDist;
@@ -246,7 +255,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 								// an interface is a specular hit whatever its row of the specular table: no light sample; its own lobe is drawn
 								// after the shadow scan
 								if constexpr (gls) if (glass_table(acc_args...)[bi[r]].w > 0.0f) slr[r] = true;
-								sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true, env>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc, env_map(acc_args...));
+								if constexpr (tex) sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true, env, true>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc, env_map(acc_args...), &alb);
+								else sh.act[r] = depth < kNeeDepths && !slr[r] && nee_light<true, env>(a, ne, pixel[r], s0 + smp[r], depth, x, ns, bi[r], wd, tm, Lc, env_map(acc_args...));
 								if constexpr (smo) sh.act[r] = sh.act[r] && smooth_light_ok(smr[r], wd, n);
 								if (sh.act[r]) Lc = scale3(Lc, 1.0f / (1.0f - pm));   // L_d wD (a diffuse hit: p < 1)
 							}
@@ -346,6 +356,11 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					f3 ns = n;                                   // the shading normal
 					bool sm = false;
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
+					if constexpr (tex) {                         // the hit's albedo, parked for the unwind
+						const f3 alb = tex_hit(a, tex_args(acc_args...), bi[r], s.o[r], s.dir[r]);
+						float* Ap = tex_args(acc_args...).A + (size_t)depth * 3 * n_work + k0 + r * B;
+						Ap[0] = alb.x; Ap[n_work] = alb.y; Ap[(size_t)2 * n_work] = alb.z;
+					}
 					bool sl = false;
 					float gi = 0.0f;                             // transparency: the triangle's ior; > 0: an interface, a specular hit
 					if constexpr (gls) {
@@ -388,7 +403,11 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 				const int2 hc = hist[(size_t)d * n_work + kw];
 				const int id = spc ? hc.x & hmask : hc.x;
 				const float* m = a.mats + (size_t)id * 6;
-				const f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
+				f3 brdf = scale3(mk3(m[0], m[1], m[2]), kInvPi);
+				if constexpr (tex) {
+					const float* Ap = tex_args(acc_args...).A + (size_t)d * 3 * n_work + kw;
+					brdf = scale3(mk3(Ap[0], Ap[n_work], Ap[(size_t)2 * n_work]), kInvPi);
+				}
 				f3 e = mk3(m[3], m[4], m[5]);
 				if constexpr (mis) {                         // D_d
 					const float* Lp = nee_args(acc_args...).L + (size_t)d * 3 * n_work + kw;

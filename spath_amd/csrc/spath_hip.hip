@@ -138,6 +138,12 @@ struct sphip_ctx {
 	// SPHIP_FLAG_ENVIRONMENT is not set: it adds no entry to the light table and every miss carries 0
 	DevBuf rough, env_black;
 	bool have_rough = false;
+	// ---- textures (SPHIP_FLAG_TEXTURE): the scene's UV table, 6 floats per triangle, kept and dropped like the specular table, and the
+	// atlas tex_w x tex_h x 3 f32, context-level like the environment map: NOT dropped by set_scene; every device of a multi-device
+	// context keeps both.  tex_A: where the two-stage kernels park the albedo per depth
+	DevBuf uv, atlas, tex_A;
+	bool have_uv = false, have_tex = false;
+	uint32_t tex_w = 0, tex_h = 0;
 };
 
 namespace {
@@ -234,6 +240,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->have_vnorm = false;                         // and so do the vertex normals
 	c->have_glass = false;                         // and the dielectric table
 	c->have_rough = false;                         // and the roughness table
+	c->have_uv = false;                            // and the UV table
 	return SPHIP_OK;
 }
 
@@ -463,7 +470,7 @@ int ensure_env_lights(sphip_ctx* c, hipStream_t st) {
 }
 
 // the zeros that stand in for a per-triangle table whose flag is off (the specular table of a dielectric render, either table of an
-// environment render): one float4 row per triangle of the scene.  The dielectric setters call this before they make the device current
+// environment render, the roughness table of a textured one: its first float per triangle): one float4 row per triangle of the scene.  The dielectric setters call this before they make the device current
 int ensure_zero_rows(sphip_ctx* c, hipStream_t st) {
 	if (c->zero_rows == c->n_tris) return SPHIP_OK;
 	HIP_TRY(c, hipSetDevice(c->device));
@@ -497,7 +504,7 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::GlossArgs* glo, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
+               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::GlossArgs* glo, const sp::TexArgs* tex, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
 			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
@@ -509,6 +516,7 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
 				last();
 			};
+			if constexpr (tables) { if (tex) { tail(*tex); return; } }      // the UV table and the atlas carry the roughness table and all it carries
 			if constexpr (tables) { if (glo) { tail(*glo); return; } }      // the roughness table carries the map and both tables
 			if constexpr (tables) { if (env) { tail(*env); return; } }      // the environment map carries the dielectric and the specular table
 			if constexpr (tables) { if (gls) { tail(*gls); return; } }      // the dielectric table carries the specular one
@@ -561,6 +569,9 @@ const TableRule kTableRules[] = {
 	{ SPHIP_FLAG_ENVIRONMENT, "SPHIP_FLAG_ENVIRONMENT", variant_smooth, &sphip_ctx::have_env, "an environment map (sphip_set_environment)" },
 	// glossy reflection roughens the mirror lobe: valid only together with SPHIP_FLAG_SPECULAR, as MIS is with NEE
 	{ SPHIP_FLAG_GLOSSY, "SPHIP_FLAG_GLOSSY", variant_smooth, &sphip_ctx::have_rough, "a roughness table (sphip_set_roughness)", SPHIP_FLAG_SPECULAR, "SPHIP_FLAG_SPECULAR" },
+	// textures need two things, asked for in this order: the scene's UV table and the context's atlas
+	{ SPHIP_FLAG_TEXTURE, "SPHIP_FLAG_TEXTURE", variant_smooth, &sphip_ctx::have_uv, "a UV table (sphip_set_uv)" },
+	{ SPHIP_FLAG_TEXTURE, "SPHIP_FLAG_TEXTURE", variant_smooth, &sphip_ctx::have_tex, "an atlas (sphip_set_texture)" },
 };
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
@@ -605,7 +616,7 @@ struct Launch {
 	sp::KArgs a{}; sp::ScanSrc src{}; sp::BvhArgs B{}; sp::AdaptArgs ad{}; sp::NormArgs nra{};
 	int2* hist = nullptr; float* acc = nullptr;   // the work buffer's path history and accumulator
 	sp::MisArgs est{};                       // the light table; handed on as NeeArgs or as MisArgs
-	sp::GlossArgs tab{};                     // the per-triangle tables and the map; handed on as SpecArgs, GlassArgs, EnvArgs or GlossArgs
+	sp::TexArgs tab{};                       // the per-triangle tables, the map and the atlas; handed on as SpecArgs, GlassArgs, EnvArgs, GlossArgs or TexArgs
 };
 
 // ---- step 1, check: refuse what cannot be rendered and name what will be.  The order is behaviour (a call that is wrong twice hears of
@@ -638,15 +649,17 @@ int check_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	// the features are those of path tracing: flat and hit queries ignore the flags.  MIS is a form of NEE
 	auto on = [&](int bit) { return pt && (flags & bit); };
 	const Features f = L.f = { on(SPHIP_FLAG_NEE), on(SPHIP_FLAG_MIS), on(SPHIP_FLAG_SPECULAR), on(SPHIP_FLAG_DIELECTRIC), on(SPHIP_FLAG_ENVIRONMENT),
-	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr, on(SPHIP_FLAG_GLOSSY) };
+	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr, on(SPHIP_FLAG_GLOSSY),
+	                           on(SPHIP_FLAG_TEXTURE) };
 	if (f.mis && !f.nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	if (f.nee && (rc = ensure_lights(c, r.st))) return rc;
 	if ((rc = check_feature_rules(c, flags, variant, mode, r.cam != nullptr))) return rc;
 	// environment lighting stands zeros in for either table whose flag is off; under NEE|MIS the estimator reads the flagged light table
-	// and so does glossy reflection for the dielectric table, and its black map for the environment
-	if ((f.env || f.gloss) && (!f.spec || !f.glass) && (rc = ensure_zero_rows(c, r.st))) return rc;
+	// and so does glossy reflection for the dielectric table, and its black map for the environment; a textured render does both, and
+	// the zeros are its roughness table too when SPHIP_FLAG_GLOSSY is not set
+	if ((f.env || f.gloss || f.tex) && (!f.spec || !f.glass || (f.tex && !f.gloss)) && (rc = ensure_zero_rows(c, r.st))) return rc;
 	if (f.env && f.nee && (rc = ensure_env_lights(c, r.st))) return rc;
-	if (f.gloss && !f.env && (rc = ensure_black_map(c, r.st))) return rc;
+	if ((f.gloss || f.tex) && !f.env && (rc = ensure_black_map(c, r.st))) return rc;
 	return SPHIP_OK;
 }
 
@@ -692,11 +705,13 @@ int bind_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 		if ((rc = ensure(c, c->work, (size_t)p.n_work * p.slot.work))) return rc;
 		if (p.slot.adp_wst && (rc = ensure(c, c->adp_wst, (size_t)p.n_work * p.slot.adp_wst))) return rc;
 		if (p.slot.env_M && (rc = ensure(c, c->env_M, (size_t)p.n_work * p.slot.env_M))) return rc;
+		if (p.slot.tex_A && (rc = ensure(c, c->tex_A, (size_t)p.n_work * p.slot.tex_A))) return rc;
 		L.hist = (int2*)c->work.p;
 		L.acc = (float*)((char*)c->work.p + (size_t)p.n_work * kSlotHist);
 		L.est.L = (float*)((char*)c->work.p + (size_t)p.n_work * (kSlotHist + kSlotAcc));     // NEE: L[4][3][n_work]; MIS: D[5][3][n_work]
 		L.ad.wst = (double*)c->adp_wst.p;
 		L.tab.M = (float*)c->env_M.p;
+		L.tab.A = (float*)c->tex_A.p;
 	}
 	if (L.ts.scan == 2 && (rc = ensure_cyl(c, r.st))) return rc;
 	L.src.cyl.rec = (const float4*)c->cyl_rec.p; L.src.cyl.hdr = (const uint32_t*)c->cyl_hdr.p;
@@ -717,8 +732,9 @@ int bind_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	L.tab.spec = (const float4*)(f.spec ? c->spec.p : c->spec_zero.p);
 	L.tab.glass = (const float4*)(f.glass ? c->glass.p : c->spec_zero.p);
 	if (f.env) L.tab.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
-	else if (f.gloss) L.tab.env = sp::EnvMap{ (const float*)c->env_black.p, (const double*)c->env_black.p, (const double*)c->env_black.p, (const float*)c->env_black.p, 0.0, 1u };
-	L.tab.rough = (const float*)c->rough.p;
+	else if (f.gloss || f.tex) L.tab.env = sp::EnvMap{ (const float*)c->env_black.p, (const double*)c->env_black.p, (const double*)c->env_black.p, (const float*)c->env_black.p, 0.0, 1u };
+	L.tab.rough = (const float*)(f.gloss ? c->rough.p : c->spec_zero.p);
+	L.tab.uv = (const float*)c->uv.p; L.tab.atlas = (const float*)c->atlas.p; L.tab.tw = c->tex_w; L.tab.th = c->tex_h;
 	L.nra.vnorm = (const float*)c->vnorm.p;
 	return SPHIP_OK;
 }
@@ -755,11 +771,12 @@ int dispatch_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	}
 	// the pack's carriers: the estimator rides as NeeArgs or MisArgs, the tables as the base of EnvArgs that the flags reach
 	const sp::NeeArgs* ne = f.nee ? &L.est : nullptr;
-	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env && !f.gloss ? &L.tab : nullptr;
-	const sp::GlassArgs* gls = f.glass && !f.env && !f.gloss ? &L.tab : nullptr;
-	const sp::EnvArgs* env = f.env && !f.gloss ? &L.tab : nullptr;
+	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
+	const sp::GlassArgs* gls = f.glass && !f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
+	const sp::EnvArgs* env = f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
+	const sp::GlossArgs* glo = f.gloss && !f.tex ? &L.tab : nullptr;
 	const sp::AdaptArgs* adp = f.adapt ? &L.ad : nullptr;
-	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, env, f.gloss ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
+	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, env, glo, f.tex ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, L.B, src_idx, oi, od, p...);
@@ -990,6 +1007,7 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 	c->have_vnorm = false;
 	c->have_glass = false;
 	c->have_rough = false;
+	c->have_uv = false;
 	return SPHIP_OK;
 }
 
@@ -1795,6 +1813,27 @@ int sphip_set_roughness_device(sphip_t* c, const void* d_alpha, void* stream) {
 	return set_tri_table(c, c->rough, c->have_rough, d_alpha, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
 }
 
+int sphip_set_uv(sphip_t* c, const float* uv) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_uv called before a scene was set");
+	if (uv)
+		for (size_t i = 0; i < c->n_tris; ++i)
+			for (int k = 0; k < 6; ++k)
+				if (!std::isfinite(uv[i * 6 + k])) {
+					const float* q = uv + i * 6;
+					return fail(c, SPHIP_E_INVALID, "UV table: triangle %zu has {%g %g, %g %g, %g %g} (every value finite)", i, (double)q[0], (double)q[1],
+					            (double)q[2], (double)q[3], (double)q[4], (double)q[5]);
+				}
+	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_uv, sphip_set_uv, uv);
+	return set_tri_table(c, c->uv, c->have_uv, uv, 24, hipMemcpyHostToDevice, c->own_stream, true);
+}
+
+int sphip_set_uv_device(sphip_t* c, const void* d_uv, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_uv_device called before a scene was set");
+	return set_tri_table(c, c->uv, c->have_uv, d_uv, 24, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+}
+
 int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
 	if (!c) return SPHIP_E_INVALID;
 	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals called before a scene was set");
@@ -1882,6 +1921,52 @@ int sphip_set_environment_device(sphip_t* c, const void* d_texels, uint32_t n, v
 	const bool bad = d_texels && (n == 0 || n > sp::kEnvMaxN);        // refused, and like every call it leaves no map behind
 	const int rc = set_env_map(c, bad ? nullptr : d_texels, n, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
 	return bad ? fail(c, SPHIP_E_INVALID, "environment map: n = %u (1 <= n <= %u)", n, sp::kEnvMaxN) : rc;
+}
+
+// the atlas of a single-device context from src (tw * th * 3 f32), or no atlas with src == nullptr; sync: src is borrowed host memory
+static int set_atlas(sphip_ctx* c, const void* src, uint32_t tw, uint32_t th, hipMemcpyKind kind, hipStream_t st, bool sync) {
+	c->acc_stale = c->acc_on;                      // the running sum was rendered under the old atlas
+	c->have_tex = false;
+	if (!src) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	const size_t bytes = (size_t)tw * th * 12;
+	if (const int rc = ensure(c, c->atlas, bytes)) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->atlas.p, src, bytes, kind, st));
+	if (sync) HIP_TRY(c, hipStreamSynchronize(st));
+	c->tex_w = tw; c->tex_h = th;
+	c->have_tex = true;
+	return SPHIP_OK;
+}
+
+int sphip_set_texture(sphip_t* c, const float* texels, uint32_t tw, uint32_t th) {
+	if (!c) return SPHIP_E_INVALID;
+	if (texels) {
+		if (tw == 0 || tw > sp::kTexMaxN || th == 0 || th > sp::kTexMaxN)
+			return fail(c, SPHIP_E_INVALID, "atlas: %u x %u texels (1 <= tw, th <= %u)", tw, th, sp::kTexMaxN);
+		const size_t cnt = (size_t)tw * th * 3;
+		for (size_t k = 0; k < cnt; ++k)
+			if (!std::isfinite(texels[k]) || !(texels[k] >= 0.0f))
+				return fail(c, SPHIP_E_INVALID, "atlas: texel (%zu, %zu) has component %zu = %g (every value finite and >= 0)", (k / 3) % tw, (k / 3) / tw,
+				            k % 3, (double)texels[k]);
+	}
+	if (c->kids.empty()) return set_atlas(c, texels, tw, th, hipMemcpyHostToDevice, c->own_stream, true);
+	c->acc_stale = c->acc_on;
+	c->have_tex = false;
+	for (sphip_ctx* k : c->kids)                                   // the texels were validated above, once
+		if (const int rc = set_atlas(k, texels, tw, th, hipMemcpyHostToDevice, k->own_stream, true)) {   // a device that refuses leaves no device with an atlas: they must never differ
+			for (sphip_ctx* q : c->kids) q->have_tex = false;
+			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+		}
+	c->have_tex = texels != nullptr;
+	c->tex_w = texels ? tw : 0; c->tex_h = texels ? th : 0;
+	return SPHIP_OK;
+}
+
+int sphip_set_texture_device(sphip_t* c, const void* d_texels, uint32_t tw, uint32_t th, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	const bool bad = d_texels && (tw == 0 || tw > sp::kTexMaxN || th == 0 || th > sp::kTexMaxN);   // refused, and like every call it leaves no atlas behind
+	const int rc = set_atlas(c, bad ? nullptr : d_texels, tw, th, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return bad ? fail(c, SPHIP_E_INVALID, "atlas: %u x %u texels (1 <= tw, th <= %u)", tw, th, sp::kTexMaxN) : rc;
 }
 
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
@@ -2076,10 +2161,11 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[12] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32, 72 }, out_b[12] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24, 32 };
-	if (what < 0 || what > 11 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[13] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32, 72, 84 }, out_b[13] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24, 32, 24 };
+	if (what < 0 || what > 12 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
 	if ((what == 9 || what == 10) && !k->have_env) return fail(c, SPHIP_E_STATE, "selftest %d needs an environment map (sphip_set_environment)", what);
+	if (what == 12 && !k->have_tex) return fail(c, SPHIP_E_STATE, "selftest %d needs an atlas (sphip_set_texture)", what);
 	HIP_TRY(c, hipSetDevice(k->device));
 	sp::EnvMap em{};
 	if (what == 10) {                                                // T alone: the tables of the map itself, no scene needed
@@ -2092,7 +2178,8 @@ int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* 
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 11) hipLaunchKernelGGL(sp::k_selftest_gloss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, (float*)d_out);
+		if (what == 12) hipLaunchKernelGGL(sp::k_selftest_tex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (const float*)k->atlas.p, k->tex_w, k->tex_h, (float*)d_out);
+		else if (what == 11) hipLaunchKernelGGL(sp::k_selftest_gloss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 10) hipLaunchKernelGGL(sp::k_selftest_env_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, em, (float*)d_out);
 		else if (what == 9) hipLaunchKernelGGL(sp::k_selftest_env_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, k->env_n, (float*)d_out);
 		else if (what == 8) hipLaunchKernelGGL(sp::k_selftest_glass, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (float*)d_out);

@@ -65,13 +65,17 @@ struct hip_r : public basic_renderer {
 	// scenes, but it travels with the scene upload like the tables so that one key covers everything a frame depends on
 	std::vector<float> env;
 	uint32_t env_n;
+	// textures (set_texture, set_uv): the atlas, tex_w x tex_h x 3 floats, travels like the map; the UV table, 6 floats per triangle,
+	// like the tables; SPHIP_FLAG_TEXTURE while both are set
+	std::vector<float> tex, uv;
+	uint32_t tex_w, tex_h;
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
-	                                                                   cam_samples(false), env_n(0) {
+	                                                                   cam_samples(false), env_n(0), tex_w(0), tex_h(0) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
 		std::memset(&lens, 0, sizeof lens);
 		std::memset(&acc_lens, 0, sizeof acc_lens);
@@ -118,6 +122,11 @@ struct hip_r : public basic_renderer {
 			h = fnv(rough.data(), rough.size() * sizeof(float), h);
 		}
 		if (!env.empty()) h = fnv(env.data(), env.size() * sizeof(float), h);
+		if (!uv.empty()) {
+			if (uv.size() != n_tris * 6) throw std::runtime_error("hip_renderer: the UV table and the scene differ in size");
+			h = fnv(uv.data(), uv.size() * sizeof(float), h);
+		}
+		if (!tex.empty()) { h = fnv(&tex_w, sizeof tex_w, h); h = fnv(tex.data(), tex.size() * sizeof(float), h); }
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
 			check(sphip_set_environment(ctx, env.empty() ? 0 : env.data(), env_n), "set_environment");
@@ -125,6 +134,8 @@ struct hip_r : public basic_renderer {
 			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
 			if (!glass.empty()) check(sphip_set_dielectric(ctx, glass.data()), "set_dielectric");
 			if (!rough.empty()) check(sphip_set_roughness(ctx, rough.data()), "set_roughness");
+			check(sphip_set_texture(ctx, tex.empty() ? 0 : tex.data(), tex_w, tex_h), "set_texture");
+			if (!uv.empty()) check(sphip_set_uv(ctx, uv.data()), "set_uv");
 			scene_hash = h; scene_n = n_tris;
 		}
 	}
@@ -197,7 +208,8 @@ struct hip_r : public basic_renderer {
 	int table_flags(const int mode) const {              // the flags of the tables that are set
 		if (mode != SPHIP_MODE_PT) return 0;
 		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0) |
-		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0) | (!rough.empty() ? SPHIP_FLAG_GLOSSY : 0);
+		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0) | (!rough.empty() ? SPHIP_FLAG_GLOSSY : 0) |
+		       (!tex.empty() && !uv.empty() ? SPHIP_FLAG_TEXTURE : 0);
 	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
@@ -308,6 +320,22 @@ namespace hip_renderer {
 		if (!p) return;
 		if (alpha && n_tris) p->rough.assign(alpha, alpha + n_tris);
 		else p->rough.clear();
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+	}
+
+	void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (texels && tw && th) { p->tex.assign(texels, texels + (size_t)tw * th * 3); p->tex_w = tw; p->tex_h = th; }
+		else { p->tex.clear(); p->tex_w = p->tex_h = 0; }
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the atlas (or none) with it
+	}
+
+	void set_uv(scene::renderer* r, const float* uv, size_t n_tris) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		if (!p) return;
+		if (uv && n_tris) p->uv.assign(uv, uv + n_tris * 6);
+		else p->uv.clear();
 		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
 	}
 

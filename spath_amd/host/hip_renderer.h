@@ -56,6 +56,13 @@ namespace hip_renderer {
 	// library refuses makes the next frame throw std::runtime_error, as does one whose size differs from the scene's.  Changing it
 	// begins a new progressive accumulation.
 	extern void set_roughness(scene::renderer* r, const float* alpha, size_t n_tris);
+	// textures (sphip_set_texture, sphip_set_uv, SPHIP_FLAG_TEXTURE; include/spath_hip.h "textures"): an atlas of tw x th x 3 floats and
+	// a UV table of n_tris x 6 floats (both copied); while both are set, path-traced frames scale the diffuse reflectance of every hit
+	// by the atlas at the hit's UV (render_flat is unchanged).  NULL or a zero size removes either.  An atlas or a table the library
+	// refuses makes the next frame throw std::runtime_error, as does a table whose size differs from the scene's.  Changing either
+	// begins a new progressive accumulation.
+	extern void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th);
+	extern void set_uv(scene::renderer* r, const float* uv, size_t n_tris);
 	// environment lighting (sphip_set_environment, SPHIP_FLAG_ENVIRONMENT; include/spath_hip.h "environment lighting"): an octahedral
 	// radiance map of n x n x 3 floats (copied); while one is set, path-traced frames are lit by it and show it behind the scene
 	// (render_flat is unchanged).  NULL or n = 0 removes it.  A map the library refuses makes the next frame throw std::runtime_error.

@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--tex FILE.bin --uv FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -27,6 +27,9 @@
 //   ('SPDI', n, n x {kt.r kt.g kt.b ior} f32: spath_amd/scene.py write_dielectric); path tracing only, not with --nee without --mis
 // --rough FILE.bin: glossy reflection (SPHIP_FLAG_GLOSSY) by the roughness table in FILE.bin, a file of its own beside the scene file
 //   ('SPRG', n, n x {alpha} f32: spath_amd/scene.py write_roughness); needs --spec; the flat pass ignores it; not with --nee without --mis
+// --tex FILE.bin --uv FILE.bin: textures (SPHIP_FLAG_TEXTURE) by the atlas in the first file (u32 tw, u32 th, then tw x th x {r g b} f32:
+//   spath_amd/scene.py write_texture) and the UV table in the second (n_tris x {s0 t0 s1 t1 s2 t2} f32, no header: write_uv); both or
+//   neither; the flat pass ignores them; not with --nee without --mis
 // --env FILE.bin: environment lighting (SPHIP_FLAG_ENVIRONMENT) by the octahedral map in FILE.bin, a file of its own ('SPEN', n,
 //   n x n x {r g b} f32: spath_amd/scene.py write_environment); path tracing only, not with --nee without --mis
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
@@ -177,9 +180,35 @@ bool load_environment(const char* path, std::vector<float>& env, uint32_t& n) {
 
 } // namespace
 
+// an atlas file of spath_amd/scene.py: u32 tw, u32 th, tw * th * 3 f32
+bool load_texture(const char* path, std::vector<float>& tex, uint32_t& tw, uint32_t& th) {
+	FILE* f = std::fopen(path, "rb");
+	if (!f) return false;
+	uint32_t hdr[2] = { 0, 0 };
+	bool ok = std::fread(hdr, 4, 2, f) == 2 && hdr[0] >= 1 && hdr[0] <= 4096 && hdr[1] >= 1 && hdr[1] <= 4096;
+	if (ok) {
+		tw = hdr[0]; th = hdr[1];
+		tex.resize((size_t)tw * th * 3);
+		ok = std::fread(tex.data(), sizeof(float), tex.size(), f) == tex.size();
+	}
+	std::fclose(f);
+	return ok;
+}
+
+// a UV file of spath_amd/scene.py: n_tris * 6 f32, no header
+bool load_uv(const char* path, size_t n_tris, std::vector<float>& uv) {
+	FILE* f = std::fopen(path, "rb");
+	if (!f) return false;
+	uv.resize(n_tris * 6);
+	char extra;
+	const bool ok = std::fread(uv.data(), sizeof(float), uv.size(), f) == uv.size() && std::fread(&extra, 1, 1, f) == 0;
+	std::fclose(f);
+	return ok;
+}
+
 int main(int argc, char** argv) {
 	try {
-		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg, rough_arg;
+		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg, rough_arg, tex_arg, uv_arg;
 		bool device_viewport = false;
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
@@ -205,6 +234,8 @@ int main(int argc, char** argv) {
 			else if (k == "--glass") { need(1); glass_arg = argv[++i]; }
 			else if (k == "--rough") { need(1); rough_arg = argv[++i]; }
 			else if (k == "--env") { need(1); env_arg = argv[++i]; }
+			else if (k == "--tex") { need(1); tex_arg = argv[++i]; }
+			else if (k == "--uv") { need(1); uv_arg = argv[++i]; }
 			else if (k == "--w") { need(1); w = std::atoi(argv[++i]); }
 			else if (k == "--h") { need(1); h = std::atoi(argv[++i]); }
 			else if (k == "--spp") { need(1); spp = (size_t)std::atoll(argv[++i]); }
@@ -267,6 +298,8 @@ int main(int argc, char** argv) {
 		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
 		if (!env_arg.empty() && mode != "pt") throw std::runtime_error("--env needs --mode pt");
 		if (!env_arg.empty() && nee && !mis) throw std::runtime_error("--env works with the plain estimator and with --mis, not with --nee alone");
+		if (tex_arg.empty() != uv_arg.empty()) throw std::runtime_error("--tex and --uv go together (the atlas and the UV table)");
+		if (!tex_arg.empty() && nee && !mis) throw std::runtime_error("--tex works with the plain estimator and with --mis, not with --nee alone");
 		if (!rough_arg.empty() && spec_arg.empty()) throw std::runtime_error("--rough needs --spec (it roughens the mirror lobe of the specular table)");
 		if (!rough_arg.empty() && nee && !mis) throw std::runtime_error("--rough works with the plain estimator and with --mis, not with --nee alone");
 		std::vector<geom::triangle> tris;
@@ -304,6 +337,14 @@ int main(int argc, char** argv) {
 			if (!load_roughness(rough_arg.c_str(), rough)) throw std::runtime_error("cannot read roughness file " + rough_arg);
 			if (rough.size() != tris.size()) throw std::runtime_error("the roughness file " + rough_arg + " and the scene differ in size");
 			hip_renderer::set_roughness(r.get(), rough.data(), tris.size());
+		}
+		if (!tex_arg.empty()) {
+			std::vector<float> tex, uv;
+			uint32_t tw = 0, th = 0;
+			if (!load_texture(tex_arg.c_str(), tex, tw, th)) throw std::runtime_error("cannot read atlas file " + tex_arg);
+			if (!load_uv(uv_arg.c_str(), tris.size(), uv)) throw std::runtime_error("cannot read UV file " + uv_arg + " (n_tris x 6 floats for this scene)");
+			hip_renderer::set_texture(r.get(), tex.data(), tw, th);
+			hip_renderer::set_uv(r.get(), uv.data(), tris.size());
 		}
 		if (!env_arg.empty()) {
 			std::vector<float> env;

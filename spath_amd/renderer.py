@@ -105,6 +105,21 @@ class HipRenderer(BasicRenderer):
         self._glass = None
         self._env = None
         self._rough = None
+        self._tex = None
+        self._uv = None
+
+    def set_texture(self, texels):
+        """The atlas of capi.FLAG_TEXTURE renders ([th, tw, 3] float32, scene.checker_texture; None: no atlas), like
+        hip_renderer::set_texture: it goes to the library with the next scene upload and begins a new accumulation, and while an atlas
+        and a UV table (set_uv) are both set every path-traced frame carries capi.FLAG_TEXTURE (render_flat never does)."""
+        self._tex = None if texels is None else np.ascontiguousarray(texels, dtype=np.float32).copy()
+        self._scene_key = None
+
+    def set_uv(self, uv):
+        """The UV table of capi.FLAG_TEXTURE renders ([n_tris, 6] float32, scene.uv_table or scene.planar_uv; None: no table), like
+        hip_renderer::set_uv: see set_texture."""
+        self._uv = None if uv is None else np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 6).copy()
+        self._scene_key = None
 
     def set_roughness(self, alpha):
         """The roughness table of capi.FLAG_GLOSSY renders ([n_tris] float32, scene.roughness_table; None: no table), like
@@ -143,12 +158,14 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT and FLAG_GLOSSY on while their
-        tables or the map are set, and never on the flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY and FLAG_TEXTURE on
+        while their tables, the map or the atlas are set, and never on the flat pass"""
         if mode == capi.MODE_FLAT:
-            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT | capi.FLAG_GLOSSY)
+            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT | capi.FLAG_GLOSSY |
+                                  capi.FLAG_TEXTURE)
         flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
         flags = flags | capi.FLAG_GLOSSY if self._rough is not None else flags
+        flags = flags | capi.FLAG_TEXTURE if self._tex is not None and self._uv is not None else flags
         flags = flags | capi.FLAG_ENVIRONMENT if self._env is not None else flags
         flags = flags | capi.FLAG_DIELECTRIC if self._glass is not None else flags
         return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
@@ -162,7 +179,8 @@ class HipRenderer(BasicRenderer):
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
         key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
                None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()),
-               None if self._env is None else hash(self._env.tobytes()), None if self._rough is None else hash(self._rough.tobytes()))
+               None if self._env is None else hash(self._env.tobytes()), None if self._rough is None else hash(self._rough.tobytes()),
+               None if self._tex is None else (self._tex.shape, hash(self._tex.tobytes())), None if self._uv is None else hash(self._uv.tobytes()))
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
             if self._spec is not None:
@@ -173,7 +191,10 @@ class HipRenderer(BasicRenderer):
                 self.ctx.set_dielectric(self._glass[:n_tris])
             if self._rough is not None:
                 self.ctx.set_roughness(self._rough[:n_tris])
+            if self._uv is not None:
+                self.ctx.set_uv(self._uv[:n_tris])
             self.ctx.set_environment(self._env)
+            self.ctx.set_texture(self._tex)
             self._scene_key = key
 
     def _begin_rule(self):

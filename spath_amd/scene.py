@@ -281,6 +281,60 @@ def write_roughness(path, alpha: np.ndarray) -> None:
         f.write(alpha.tobytes())
 
 
+def checker_texture(tw: int = 16, th: int = 16, cell: int = 4, a=(0.9, 0.9, 0.9), b=(0.2, 0.2, 0.2)) -> np.ndarray:
+    """A checkerboard atlas for capi.Context.set_texture (include/spath_hip.h, "textures"): float32 [th, tw, 3] indexed [j, i], cells of
+    cell x cell texels coloured a where (i // cell + j // cell) is even and b where it is odd."""
+    if not (1 <= tw <= 4096 and 1 <= th <= 4096 and cell >= 1):
+        raise ValueError("checker texture: 1 <= tw, th <= 4096 and cell >= 1")
+    i, j = np.meshgrid(np.arange(tw), np.arange(th))
+    odd = ((i // cell + j // cell) & 1).astype(bool)
+    tex = np.where(odd[..., None], np.asarray(b, F), np.asarray(a, F)).astype(F)
+    if not (np.isfinite(tex).all() and (tex >= 0).all()):
+        raise ValueError("checker texture: every value finite and >= 0")
+    return np.ascontiguousarray(tex)
+
+
+def uv_table(tris: np.ndarray, uv=(0.0, 0.0, 1.0, 0.0, 0.0, 1.0), which=None) -> np.ndarray:
+    """A UV table for capi.Context.set_uv (include/spath_hip.h, "textures"): float32 [N, 6], s0 t0 s1 t1 s2 t2 for v0 v1 v2.  uv: one
+    row for all or [N, 6] (finite); which: the triangles that get their row (an index array or a boolean mask; None = all), every other
+    row is zero (the triangle stays untextured)."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    n = t.shape[0]
+    sel = np.ones(n, bool) if which is None else np.zeros(n, bool)
+    if which is not None:
+        sel[np.asarray(which)] = True
+    rows = np.broadcast_to(np.asarray(uv, F).reshape(-1, 6), (n, 6)).copy()
+    if not np.isfinite(rows).all():
+        raise ValueError("UV table: every value finite")
+    rows[~sel] = 0.0
+    return rows
+
+
+def planar_uv(tris: np.ndarray, origin=(0.0, 0.0, 0.0), s_axis=(1.0, 0.0, 0.0), t_axis=(0.0, 0.0, 1.0), which=None) -> np.ndarray:
+    """The UV table of a planar projection: vertex p gets s = (p - origin) . s_axis, t = (p - origin) . t_axis (float64, rounded once),
+    so one repeat of the atlas covers 1 / |axis| world units.  which as in uv_table."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    p = t[:, :9].reshape(-1, 3, 3).astype(np.float64) - np.asarray(origin, np.float64)
+    rows = np.stack([p @ np.asarray(s_axis, np.float64), p @ np.asarray(t_axis, np.float64)], axis=2).reshape(-1, 6)
+    return uv_table(t, rows.astype(F), which)
+
+
+def write_texture(path, texels: np.ndarray) -> None:
+    """Atlas file read by the headless CLI (--tex): u32 tw, u32 th, then th x tw x {r g b} float32."""
+    texels = np.ascontiguousarray(texels, dtype=F)
+    if texels.ndim != 3 or texels.shape[2] != 3:
+        raise ValueError("an atlas is (th, tw, 3)")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", texels.shape[1], texels.shape[0]))
+        f.write(texels.tobytes())
+
+
+def write_uv(path, uv: np.ndarray) -> None:
+    """UV file read by the headless CLI (--uv), beside the scene file: n_tris x 6 float32, no header."""
+    with open(path, "wb") as f:
+        f.write(np.ascontiguousarray(uv, dtype=F).reshape(-1, 6).tobytes())
+
+
 def octahedral_directions(n: int) -> np.ndarray:
     """The unit directions of the texel centres of an n x n octahedral environment map (include/spath_hip.h, "environment lighting"):
     float64 [n, n, 3] indexed [j, i], texel (i, j) centred at (a, b) = (-1 + (2 i + 1) / n, -1 + (2 j + 1) / n), +y at the centre of the
