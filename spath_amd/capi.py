@@ -53,6 +53,15 @@ SYMBOLS = (
     "sphip_set_texture", "sphip_set_texture_device", "sphip_set_uv", "sphip_set_uv_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
+# the per-triangle tables of a scene: (the X of sphip_set_X and sphip_set_X_device, floats per triangle, the ValueError of a table
+# whose rows are not the scene's triangles)
+TRI_TABLES = (
+    ("specular", 4, "one specular row per triangle of the scene"),
+    ("vertex_normals", 9, "one row of vertex normals per triangle of the scene"),
+    ("dielectric", 4, "one dielectric row per triangle of the scene"),
+    ("roughness", 1, "one roughness value per triangle of the scene"),
+    ("uv", 6, "one UV row per triangle of the scene"),
+)
 
 
 class Shard(C.Structure):
@@ -212,30 +221,14 @@ def load():
     L.sphip_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.sphip_camera_rays_device.restype = C.c_int
     L.sphip_camera_rays_device.argtypes = [vp, C.POINTER(CameraArgs), C.c_uint64, C.c_uint32, vp, vp]
-    L.sphip_set_specular.restype = C.c_int
-    L.sphip_set_specular.argtypes = [vp, vp]
-    L.sphip_set_specular_device.restype = C.c_int
-    L.sphip_set_specular_device.argtypes = [vp, vp, vp]
-    L.sphip_set_vertex_normals.restype = C.c_int
-    L.sphip_set_vertex_normals.argtypes = [vp, vp]
-    L.sphip_set_vertex_normals_device.restype = C.c_int
-    L.sphip_set_vertex_normals_device.argtypes = [vp, vp, vp]
-    L.sphip_set_roughness.restype = C.c_int
-    L.sphip_set_roughness.argtypes = [vp, vp]
-    L.sphip_set_roughness_device.restype = C.c_int
-    L.sphip_set_roughness_device.argtypes = [vp, vp, vp]
-    L.sphip_set_uv.restype = C.c_int
-    L.sphip_set_uv.argtypes = [vp, vp]
-    L.sphip_set_uv_device.restype = C.c_int
-    L.sphip_set_uv_device.argtypes = [vp, vp, vp]
+    for name, _, _ in TRI_TABLES:
+        host, dev = getattr(L, "sphip_set_" + name), getattr(L, "sphip_set_" + name + "_device")
+        host.restype = dev.restype = C.c_int
+        host.argtypes, dev.argtypes = [vp, vp], [vp, vp, vp]
     L.sphip_set_texture.restype = C.c_int
     L.sphip_set_texture.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.sphip_set_texture_device.restype = C.c_int
     L.sphip_set_texture_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
-    L.sphip_set_dielectric.restype = C.c_int
-    L.sphip_set_dielectric.argtypes = [vp, vp]
-    L.sphip_set_dielectric_device.restype = C.c_int
-    L.sphip_set_dielectric_device.argtypes = [vp, vp, vp]
     L.sphip_set_environment.restype = C.c_int
     L.sphip_set_environment.argtypes = [vp, vp, C.c_uint32]
     L.sphip_set_environment_device.restype = C.c_int
@@ -362,66 +355,46 @@ class Context:
         self._check(self._L.sphip_set_scene(self._h, tris.ctypes.data, mats.ctypes.data, tris.shape[0]), "sphip_set_scene")
         self._n_tris = tris.shape[0]
 
+    def _set_table(self, name, rows):
+        """sphip_set_<name> of TRI_TABLES: rows as (n_tris, floats) f32 for the scene last set, or None to clear the table."""
+        import numpy as np
+        what = "sphip_set_" + name
+        if rows is not None:
+            floats, mismatch = next(t[1:] for t in TRI_TABLES if t[0] == name)
+            rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, floats)
+            if rows.shape[0] != getattr(self, "_n_tris", rows.shape[0]):
+                raise ValueError(mismatch)
+        self._check(getattr(self._L, what)(self._h, None if rows is None else rows.ctypes.data), what)
+
+    def _set_table_device(self, name, d_rows, stream):
+        what = "sphip_set_" + name + "_device"
+        self._check(getattr(self._L, what)(self._h, d_rows, stream), what)
+
     def set_specular(self, spec):
         """sphip_set_specular: the specular table of FLAG_SPECULAR renders, (n_tris, 4) f32 rows ks.r, ks.g, ks.b, p for the scene last
         set (scene.specular_table builds one); None clears it.  Every set_scene clears it too."""
-        import numpy as np
-        if spec is None:
-            self._check(self._L.sphip_set_specular(self._h, None), "sphip_set_specular")
-            return
-        spec = np.ascontiguousarray(spec, dtype=np.float32).reshape(-1, 4)
-        if spec.shape[0] != getattr(self, "_n_tris", spec.shape[0]):
-            raise ValueError("one specular row per triangle of the scene")
-        self._check(self._L.sphip_set_specular(self._h, spec.ctypes.data), "sphip_set_specular")
+        self._set_table("specular", spec)
 
     def set_vertex_normals(self, vn):
         """sphip_set_vertex_normals: the per-vertex normals of FLAG_SMOOTH renders, (n_tris, 9) f32 rows n0.xyz n1.xyz n2.xyz for the
         scene last set (scene.vertex_normals builds them); None clears them.  Every set_scene clears them too."""
-        import numpy as np
-        if vn is None:
-            self._check(self._L.sphip_set_vertex_normals(self._h, None), "sphip_set_vertex_normals")
-            return
-        vn = np.ascontiguousarray(vn, dtype=np.float32).reshape(-1, 9)
-        if vn.shape[0] != getattr(self, "_n_tris", vn.shape[0]):
-            raise ValueError("one row of vertex normals per triangle of the scene")
-        self._check(self._L.sphip_set_vertex_normals(self._h, vn.ctypes.data), "sphip_set_vertex_normals")
+        self._set_table("vertex_normals", vn)
 
     def set_dielectric(self, glass):
         """sphip_set_dielectric: the dielectric table of FLAG_DIELECTRIC renders, (n_tris, 4) f32 rows kt.r, kt.g, kt.b, ior for the
         scene last set (scene.dielectric_table builds one); None clears it.  Every set_scene clears it too."""
-        import numpy as np
-        if glass is None:
-            self._check(self._L.sphip_set_dielectric(self._h, None), "sphip_set_dielectric")
-            return
-        glass = np.ascontiguousarray(glass, dtype=np.float32).reshape(-1, 4)
-        if glass.shape[0] != getattr(self, "_n_tris", glass.shape[0]):
-            raise ValueError("one dielectric row per triangle of the scene")
-        self._check(self._L.sphip_set_dielectric(self._h, glass.ctypes.data), "sphip_set_dielectric")
+        self._set_table("dielectric", glass)
 
     def set_roughness(self, alpha):
         """sphip_set_roughness: the roughness table of FLAG_GLOSSY renders, n_tris f32, the GGX alpha of each triangle's mirror lobe for
         the scene last set (scene.roughness_table builds one); None clears it.  Every set_scene clears it too."""
-        import numpy as np
-        if alpha is None:
-            self._check(self._L.sphip_set_roughness(self._h, None), "sphip_set_roughness")
-            return
-        alpha = np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
-        if alpha.shape[0] != getattr(self, "_n_tris", alpha.shape[0]):
-            raise ValueError("one roughness value per triangle of the scene")
-        self._check(self._L.sphip_set_roughness(self._h, alpha.ctypes.data), "sphip_set_roughness")
+        self._set_table("roughness", alpha)
 
     def set_uv(self, uv):
         """sphip_set_uv: the UV table of FLAG_TEXTURE renders, (n_tris, 6) f32: s0 t0 s1 t1 s2 t2 for v0 v1 v2 of each triangle of the
         scene last set (scene.uv_table and scene.planar_uv build one); a row of zeros leaves its triangle untextured; None clears it.
         Every set_scene clears it too."""
-        import numpy as np
-        if uv is None:
-            self._check(self._L.sphip_set_uv(self._h, None), "sphip_set_uv")
-            return
-        uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 6)
-        if uv.shape[0] != getattr(self, "_n_tris", uv.shape[0]):
-            raise ValueError("one UV row per triangle of the scene")
-        self._check(self._L.sphip_set_uv(self._h, uv.ctypes.data), "sphip_set_uv")
+        self._set_table("uv", uv)
 
     def set_texture(self, texels):
         """sphip_set_texture: the atlas of FLAG_TEXTURE renders, (th, tw, 3) f32 with texel (i, j) at [j, i] (scene.checker_texture
@@ -465,23 +438,23 @@ class Context:
 
     def set_specular_device(self, d_spec: int, stream: int = 0):
         """sphip_set_specular_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
-        self._check(self._L.sphip_set_specular_device(self._h, d_spec, stream), "sphip_set_specular_device")
+        self._set_table_device("specular", d_spec, stream)
 
     def set_vertex_normals_device(self, d_vn: int, stream: int = 0):
         """sphip_set_vertex_normals_device: the normals from a device pointer (n_tris * 9 f32, copied in stream order, NOT validated)."""
-        self._check(self._L.sphip_set_vertex_normals_device(self._h, d_vn, stream), "sphip_set_vertex_normals_device")
+        self._set_table_device("vertex_normals", d_vn, stream)
 
     def set_dielectric_device(self, d_glass: int, stream: int = 0):
         """sphip_set_dielectric_device: the table from a device pointer (n_tris * 4 f32, copied in stream order, NOT validated)."""
-        self._check(self._L.sphip_set_dielectric_device(self._h, d_glass, stream), "sphip_set_dielectric_device")
+        self._set_table_device("dielectric", d_glass, stream)
 
     def set_roughness_device(self, d_alpha: int, stream: int = 0):
         """sphip_set_roughness_device: the table from a device pointer (n_tris f32, copied in stream order, NOT validated)."""
-        self._check(self._L.sphip_set_roughness_device(self._h, d_alpha, stream), "sphip_set_roughness_device")
+        self._set_table_device("roughness", d_alpha, stream)
 
     def set_uv_device(self, d_uv: int, stream: int = 0):
         """sphip_set_uv_device: the table from a device pointer (n_tris * 6 f32, copied in stream order, NOT validated)."""
-        self._check(self._L.sphip_set_uv_device(self._h, d_uv, stream), "sphip_set_uv_device")
+        self._set_table_device("uv", d_uv, stream)
 
     def set_texture_device(self, d_texels: int, tw: int, th: int, stream: int = 0):
         """sphip_set_texture_device: the atlas from a device pointer (tw * th * 3 f32, copied in stream order, NOT validated)."""

@@ -14,6 +14,7 @@
 #include "sp_denoise.h"
 #include "sp_environment.h"
 #include "sp_host_plan.h"
+#include "sp_host_tables.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,7 +31,7 @@
 #include <vector>
 
 namespace {
-using namespace sp_host;       // the launch plan and the light tables: what needs no device (sp_host_plan.h)
+using namespace sp_host;       // the launch plan, the light tables, the rules of the per-triangle tables: what needs no device (sp_host_*.h)
 
 thread_local std::string g_create_error;
 
@@ -108,17 +109,22 @@ struct sphip_ctx {
 	sphip_lens acc_lens{};
 	sphip_camera acc_cam{};
 	bool acc_has_cam = false;
-	// ---- specular reflection (SPHIP_FLAG_SPECULAR): the scene's specular table, 4 floats per triangle (every device of a multi-device
-	// context keeps the whole table, like the scene); dropped by every set_scene
-	DevBuf spec;
-	bool have_spec = false;
-	// ---- smooth shading (SPHIP_FLAG_SMOOTH): the scene's vertex normals, 9 floats per triangle, kept and dropped like the specular table
-	DevBuf vnorm;
-	bool have_vnorm = false;
-	// ---- transparency (SPHIP_FLAG_DIELECTRIC): the scene's dielectric table, 4 floats per triangle, kept and dropped like the specular
-	// table, and the table of zeros that stands in for the specular table when SPHIP_FLAG_SPECULAR is not set (sized with the scene)
-	DevBuf glass, spec_zero;
-	bool have_glass = false;
+	// ---- the per-triangle tables of the scene (sp_host_tables.h: kTriTables; kTableSlots below names each one's members).  One rule for
+	// all: a table belongs to the scene last set and is kept like it, so every set_scene drops it (drop_tables); every device of a
+	// multi-device context keeps the whole table; a render reads it while its flag is set.  What is particular to each:
+	//   spec   SPHIP_FLAG_SPECULAR    4 floats per triangle
+	//   vnorm  SPHIP_FLAG_SMOOTH      9 floats per triangle
+	//   glass  SPHIP_FLAG_DIELECTRIC  4 floats per triangle; setting it allocates spec_zero (ensure_zero_rows)
+	//   rough  SPHIP_FLAG_GLOSSY      1 float per triangle
+	//   uv     SPHIP_FLAG_TEXTURE     6 floats per triangle; rendered with the context's atlas (below)
+	DevBuf spec, vnorm, glass, rough, uv;
+	bool have_spec = false, have_vnorm = false, have_glass = false, have_rough = false, have_uv = false;
+	// what stands in for a table or a map whose flag is off: spec_zero, a float4 of zeros for each of the scene's first zero_rows triangles
+	// (the specular table of a dielectric render, either table of an environment render, the roughness table of a textured one), and
+	// env_black, the 1 x 1 black map (texel, rc, marg and tpdf all zeros, T = 0) of a glossy render without SPHIP_FLAG_ENVIRONMENT: it adds
+	// no entry to the light table and every miss carries 0
+	DevBuf spec_zero, env_black;
+	size_t zero_rows = 0;
 	// ---- environment lighting (sp_environment.h): the octahedral map env_n x env_n x 3 f32 and its importance tables wt, rc, marg (double),
 	// built on the device by both setters; every device of a multi-device context keeps them.  NOT dropped by set_scene: the map does not
 	// depend on the triangles.  What does (env_T read back, w_env, W and tpdf: ensure_env_lights) is rebuilt on first use after either changes
@@ -128,21 +134,14 @@ struct sphip_ctx {
 	double env_T = 0.0, env_wenv = 0.0, env_W = 0.0;
 	// SPHIP_FLAG_ENVIRONMENT: the flagged light table (the triangle entries under the total W that includes w_env, then the map's entry;
 	// laid out like nee_tab), built by ensure_env_lights from the host copy of the unflagged one; without an entry it is nee_tab itself.
-	// env_M: where the two-stage kernels park the miss term.  zero_rows: the triangles that spec_zero holds zeros for
+	// env_M: where the two-stage kernels park the miss term
 	DevBuf env_tab, env_M;
 	uint32_t env_nee_n = 0;
 	sp_host::LightTable nee_host;                  // the host copy of nee_tab: what the flagged table is made from
-	size_t zero_rows = 0;
-	// ---- glossy reflection (SPHIP_FLAG_GLOSSY): the scene's roughness table, 1 float per triangle, kept and dropped like the specular
-	// table, and the 1 x 1 black map (texel, rc, marg and tpdf all zeros, T = 0) that stands in for the environment map when
-	// SPHIP_FLAG_ENVIRONMENT is not set: it adds no entry to the light table and every miss carries 0
-	DevBuf rough, env_black;
-	bool have_rough = false;
-	// ---- textures (SPHIP_FLAG_TEXTURE): the scene's UV table, 6 floats per triangle, kept and dropped like the specular table, and the
-	// atlas tex_w x tex_h x 3 f32, context-level like the environment map: NOT dropped by set_scene; every device of a multi-device
-	// context keeps both.  tex_A: where the two-stage kernels park the albedo per depth
-	DevBuf uv, atlas, tex_A;
-	bool have_uv = false, have_tex = false;
+	// ---- textures (SPHIP_FLAG_TEXTURE): the atlas tex_w x tex_h x 3 f32, context-level like the environment map: NOT dropped by
+	// set_scene; every device of a multi-device context keeps it.  tex_A: where the two-stage kernels park the albedo per depth
+	DevBuf atlas, tex_A;
+	bool have_tex = false;
 	uint32_t tex_w = 0, tex_h = 0;
 };
 
@@ -164,6 +163,17 @@ int fail(sphip_ctx* c, int code, const char* fmt, ...) {
 		if (e_ != hipSuccess)                                                                    \
 			return fail((c), SPHIP_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
 	} while (0)
+
+// where table k of kTriTables lives in a context
+struct TableSlot { DevBuf sphip_ctx::*buf; bool sphip_ctx::*have; };
+const TableSlot kTableSlots[kTriTableCount] = {
+	{ &sphip_ctx::spec, &sphip_ctx::have_spec }, { &sphip_ctx::vnorm, &sphip_ctx::have_vnorm }, { &sphip_ctx::glass, &sphip_ctx::have_glass },
+	{ &sphip_ctx::rough, &sphip_ctx::have_rough }, { &sphip_ctx::uv, &sphip_ctx::have_uv },
+};
+static_assert(kTriTables[kTabSpecular].max_tris == (size_t)sp::kSpecBit && kTriTables[kTabDielectric].max_tris == (size_t)sp::kTransBit,
+              "the triangle limits of sp_host_tables.h are the path history's marker bits");
+// every table belongs to the scene that is being replaced
+void drop_tables(sphip_ctx* c) { for (const TableSlot& s : kTableSlots) c->*s.have = false; }
 
 // the guard of the device-pointer entry points: a context, and a single-device one
 int single_device_entry(sphip_ctx* c) {
@@ -236,11 +246,7 @@ int repack(sphip_ctx* c, hipStream_t st) {
 	c->nee_valid = false;
 	c->env_lights_valid = false;                   // w_env and tpdf follow the scene; the map itself stays
 	c->zero_rows = 0;
-	c->have_spec = false;                          // the specular table belongs to the old scene
-	c->have_vnorm = false;                         // and so do the vertex normals
-	c->have_glass = false;                         // and the dielectric table
-	c->have_rough = false;                         // and the roughness table
-	c->have_uv = false;                            // and the UV table
+	drop_tables(c);
 	return SPHIP_OK;
 }
 
@@ -470,7 +476,7 @@ int ensure_env_lights(sphip_ctx* c, hipStream_t st) {
 }
 
 // the zeros that stand in for a per-triangle table whose flag is off (the specular table of a dielectric render, either table of an
-// environment render, the roughness table of a textured one: its first float per triangle): one float4 row per triangle of the scene.  The dielectric setters call this before they make the device current
+// environment render, the roughness table of a textured one: its first float per triangle): one float4 row per triangle of the scene.  put_table calls this before it makes the device current
 int ensure_zero_rows(sphip_ctx* c, hipStream_t st) {
 	if (c->zero_rows == c->n_tris) return SPHIP_OK;
 	HIP_TRY(c, hipSetDevice(c->device));
@@ -1003,41 +1009,69 @@ int multi_set_scene(sphip_ctx* c, const float* tris, const float* mats, size_t n
 		if (rcs[(size_t)r]) return fail(c, rcs[(size_t)r], "device %d: %s", c->kids[(size_t)r]->device, c->kids[(size_t)r]->err.c_str());
 	c->n_tris = n_tris;
 	c->have_scene = true;
-	c->have_spec = false;
-	c->have_vnorm = false;
-	c->have_glass = false;
-	c->have_rough = false;
-	c->have_uv = false;
+	drop_tables(c);
 	return SPHIP_OK;
 }
 
-// One per-triangle table of the scene (the specular table, the vertex normals) on a single-device context: bytes_per_tri per triangle
-// from src, or no table with src == nullptr.  sync: src is borrowed host memory and must not outlive the call.
-int set_tri_table(sphip_ctx* c, DevBuf& buf, bool& have, const void* src, size_t bytes_per_tri, hipMemcpyKind kind, hipStream_t st, bool sync) {
+// What every device of a multi-device context keeps whole (a per-triangle table, the map, the atlas): set_child on each child, `have`
+// being the context's flag for it and present whether the call sets one.  A device that refuses leaves no device with one: they must
+// never differ.
+template <typename SetChild>
+int set_on_every_device(sphip_ctx* c, bool sphip_ctx::*have, bool present, SetChild&& set_child) {
+	c->acc_stale = c->acc_on;
+	c->*have = false;
+	for (sphip_ctx* k : c->kids)
+		if (const int rc = set_child(k)) {
+			for (sphip_ctx* q : c->kids) q->*have = false;
+			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
+		}
+	c->*have = present;
+	return SPHIP_OK;
+}
+
+// Table `id` of kTriTables on one device (a single-device context, or a child): its floats per triangle from src, or no table with
+// src == nullptr.  sync: src is borrowed host memory and must not outlive the call.
+int put_table(sphip_ctx* c, int id, const void* src, hipMemcpyKind kind, hipStream_t st, bool sync) {
+	DevBuf& buf = c->*kTableSlots[id].buf;
+	bool& have = c->*kTableSlots[id].have;
+	const size_t bytes = c->n_tris * (size_t)kTriTables[id].floats * 4;
 	c->acc_stale = c->acc_on;                      // the running sum was rendered with the old table
 	have = false;
 	if (!src) return SPHIP_OK;
-	HIP_TRY(c, hipSetDevice(c->device));
 	int rc;
-	if ((rc = ensure(c, buf, c->n_tris * bytes_per_tri))) return rc;
-	HIP_TRY(c, hipMemcpyAsync(buf.p, src, c->n_tris * bytes_per_tri, kind, st));
+	if (kTriTables[id].zero_rows && (rc = ensure_zero_rows(c, st))) return rc;
+	HIP_TRY(c, hipSetDevice(c->device));
+	if ((rc = ensure(c, buf, bytes))) return rc;
+	HIP_TRY(c, hipMemcpyAsync(buf.p, src, bytes, kind, st));
 	if (sync) HIP_TRY(c, hipStreamSynchronize(st));
 	have = true;
 	return SPHIP_OK;
 }
 
-// ... and on a multi-device context: every device keeps the whole table (child_set: the entry point, for a child).  A device that refuses
-// leaves no device with a table: they must never differ.
-int multi_set_tri_table(sphip_ctx* c, bool sphip_ctx::*have, int (*child_set)(sphip_t*, const float*), const float* src) {
-	c->acc_stale = c->acc_on;
-	c->*have = false;
-	for (sphip_ctx* k : c->kids)
-		if (const int rc = child_set(k, src)) {
-			for (sphip_ctx* q : c->kids) q->*have = false;
-			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-		}
-	c->*have = src != nullptr;
-	return SPHIP_OK;
+// sphip_set_X: in this order the context, the scene, the triangle limit, the rows (a refusal so far leaves the old table in place), then
+// the table on the device or, validated once here, on every device
+int set_table(sphip_ctx* c, int id, const float* src) {
+	if (!c) return SPHIP_E_INVALID;
+	const TriTable& t = kTriTables[id];
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "%s called before a scene was set", t.setter);
+	if (src) {
+		if (t.max_tris && c->n_tris >= t.max_tris) return fail(c, SPHIP_E_INVALID, t.too_large, c->n_tris);
+		const size_t bad = first_bad_row(t, src, c->n_tris);
+		if (bad < c->n_tris) return fail(c, SPHIP_E_INVALID, "%s", bad_row_message(t, src, bad).c_str());
+	}
+	if (c->kids.empty()) return put_table(c, id, src, hipMemcpyHostToDevice, c->own_stream, true);
+	return set_on_every_device(c, kTableSlots[id].have, src != nullptr,
+	                           [&](sphip_ctx* k) { return put_table(k, id, src, hipMemcpyHostToDevice, k->own_stream, true); });
+}
+
+// sphip_set_X_device: the rows are not validated; a scene beyond the triangle limit is refused, and like every call it leaves no table behind
+int set_table_device(sphip_ctx* c, int id, const void* d_src, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	const TriTable& t = kTriTables[id];
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "%s_device called before a scene was set", t.setter);
+	const bool big = d_src && t.max_tris && c->n_tris >= t.max_tris;
+	const int rc = put_table(c, id, big ? nullptr : d_src, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return big ? fail(c, SPHIP_E_INVALID, t.too_large, c->n_tris) : rc;
 }
 
 // The tail of the host-pointer paths: n pixels of c->rgba (and, with out_f, the float triples of c->accum) to the caller, timed for
@@ -1761,157 +1795,33 @@ int sphip_set_scene_device(sphip_t* c, const void* d_tris, const void* d_mats, s
 	return repack(c, st);
 }
 
-// the first triangle of a specular table that breaks the rules (finite, ks >= 0, 0 <= p <= 1), or n_tris
-static size_t spec_first_bad(const float* spec, size_t n_tris) {
-	for (size_t i = 0; i < n_tris; ++i) {
-		const float* q = spec + i * 4;
-		for (int k = 0; k < 4; ++k) if (!std::isfinite(q[k]) || !(q[k] >= 0.0f)) return i;
-		if (!(q[3] <= 1.0f)) return i;
-	}
-	return n_tris;
-}
+// the per-triangle tables: kTriTables (sp_host_tables.h) says what differs between them, set_table and set_table_device do the work
+int sphip_set_specular(sphip_t* c, const float* spec) { return set_table(c, kTabSpecular, spec); }
+int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) { return set_table_device(c, kTabSpecular, d_spec, stream); }
+int sphip_set_vertex_normals(sphip_t* c, const float* vn) { return set_table(c, kTabVertexNormals, vn); }
+int sphip_set_vertex_normals_device(sphip_t* c, const void* d_vn, void* stream) { return set_table_device(c, kTabVertexNormals, d_vn, stream); }
+int sphip_set_dielectric(sphip_t* c, const float* glass) { return set_table(c, kTabDielectric, glass); }
+int sphip_set_dielectric_device(sphip_t* c, const void* d_glass, void* stream) { return set_table_device(c, kTabDielectric, d_glass, stream); }
+int sphip_set_roughness(sphip_t* c, const float* alpha) { return set_table(c, kTabRoughness, alpha); }
+int sphip_set_roughness_device(sphip_t* c, const void* d_alpha, void* stream) { return set_table_device(c, kTabRoughness, d_alpha, stream); }
+int sphip_set_uv(sphip_t* c, const float* uv) { return set_table(c, kTabUv, uv); }
+int sphip_set_uv_device(sphip_t* c, const void* d_uv, void* stream) { return set_table_device(c, kTabUv, d_uv, stream); }
 
-int sphip_set_specular(sphip_t* c, const float* spec) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_specular called before a scene was set");
-	if (spec) {
-		// kSpecBit marks a mirror bounce in the path history: triangle indices must stay below it
-		if (c->n_tris >= (size_t)sp::kSpecBit) return fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris);
-		const size_t bad = spec_first_bad(spec, c->n_tris);
-		if (bad < c->n_tris) {
-			const float* q = spec + bad * 4;
-			return fail(c, SPHIP_E_INVALID, "specular table: triangle %zu has {ks %g %g %g, p %g} (every value finite, ks >= 0, 0 <= p <= 1)", bad,
-			            (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
-		}
-	}
-	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_spec, sphip_set_specular, spec);
-	return set_tri_table(c, c->spec, c->have_spec, spec, 16, hipMemcpyHostToDevice, c->own_stream, true);
-}
-
-int sphip_set_specular_device(sphip_t* c, const void* d_spec, void* stream) {
-	if (const int rc = single_device_entry(c)) return rc;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_specular_device called before a scene was set");
-	const bool big = d_spec && c->n_tris >= (size_t)sp::kSpecBit;      // refused, and like every call it leaves no table behind
-	const int rc = set_tri_table(c, c->spec, c->have_spec, big ? nullptr : d_spec, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
-	return big ? fail(c, SPHIP_E_INVALID, "a specular table needs a scene of fewer than 2^30 triangles (this one has %zu)", c->n_tris) : rc;
-}
-
-int sphip_set_roughness(sphip_t* c, const float* alpha) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_roughness called before a scene was set");
-	if (alpha)
-		for (size_t i = 0; i < c->n_tris; ++i)
-			if (!std::isfinite(alpha[i]) || !(alpha[i] >= 0.0f) || !(alpha[i] <= 1.0f))
-				return fail(c, SPHIP_E_INVALID, "roughness table: triangle %zu has alpha %g (finite, 0 <= alpha <= 1)", i, (double)alpha[i]);
-	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_rough, sphip_set_roughness, alpha);
-	return set_tri_table(c, c->rough, c->have_rough, alpha, 4, hipMemcpyHostToDevice, c->own_stream, true);
-}
-
-int sphip_set_roughness_device(sphip_t* c, const void* d_alpha, void* stream) {
-	if (const int rc = single_device_entry(c)) return rc;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_roughness_device called before a scene was set");
-	return set_tri_table(c, c->rough, c->have_rough, d_alpha, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
-}
-
-int sphip_set_uv(sphip_t* c, const float* uv) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_uv called before a scene was set");
-	if (uv)
-		for (size_t i = 0; i < c->n_tris; ++i)
-			for (int k = 0; k < 6; ++k)
-				if (!std::isfinite(uv[i * 6 + k])) {
-					const float* q = uv + i * 6;
-					return fail(c, SPHIP_E_INVALID, "UV table: triangle %zu has {%g %g, %g %g, %g %g} (every value finite)", i, (double)q[0], (double)q[1],
-					            (double)q[2], (double)q[3], (double)q[4], (double)q[5]);
-				}
-	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_uv, sphip_set_uv, uv);
-	return set_tri_table(c, c->uv, c->have_uv, uv, 24, hipMemcpyHostToDevice, c->own_stream, true);
-}
-
-int sphip_set_uv_device(sphip_t* c, const void* d_uv, void* stream) {
-	if (const int rc = single_device_entry(c)) return rc;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_uv_device called before a scene was set");
-	return set_tri_table(c, c->uv, c->have_uv, d_uv, 24, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
-}
-
-int sphip_set_vertex_normals(sphip_t* c, const float* vn) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals called before a scene was set");
-	if (vn) {
-		for (size_t i = 0; i < c->n_tris; ++i)
-			for (int k = 0; k < 9; ++k)
-				if (!std::isfinite(vn[i * 9 + k])) {
-					const float* q = vn + i * 9;
-					return fail(c, SPHIP_E_INVALID, "vertex normals: triangle %zu has {%g %g %g, %g %g %g, %g %g %g} (every value finite)", i, (double)q[0],
-					            (double)q[1], (double)q[2], (double)q[3], (double)q[4], (double)q[5], (double)q[6], (double)q[7], (double)q[8]);
-				}
-	}
-	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_vnorm, sphip_set_vertex_normals, vn);
-	return set_tri_table(c, c->vnorm, c->have_vnorm, vn, 36, hipMemcpyHostToDevice, c->own_stream, true);
-}
-
-int sphip_set_vertex_normals_device(sphip_t* c, const void* d_vn, void* stream) {
-	if (const int rc = single_device_entry(c)) return rc;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_vertex_normals_device called before a scene was set");
-	return set_tri_table(c, c->vnorm, c->have_vnorm, d_vn, 36, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
-}
-
-// the first row of a dielectric table that breaks the rules (finite, kt >= 0, ior 0 or >= 1), or n_tris
-static size_t glass_first_bad(const float* g, size_t n_tris) {
-	for (size_t i = 0; i < n_tris; ++i) {
-		const float* q = g + i * 4;
-		for (int k = 0; k < 4; ++k) if (!std::isfinite(q[k]) || !(q[k] >= 0.0f)) return i;
-		if (q[3] != 0.0f && !(q[3] >= 1.0f)) return i;
-	}
-	return n_tris;
-}
-
-int sphip_set_dielectric(sphip_t* c, const float* glass) {
-	if (!c) return SPHIP_E_INVALID;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric called before a scene was set");
-	if (glass) {
-		// kTransBit marks a transmitted bounce in the path history: triangle indices must stay below it
-		if (c->n_tris >= (size_t)sp::kTransBit) return fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris);
-		const size_t bad = glass_first_bad(glass, c->n_tris);
-		if (bad < c->n_tris) {
-			const float* q = glass + bad * 4;
-			return fail(c, SPHIP_E_INVALID, "dielectric table: triangle %zu has {kt %g %g %g, ior %g} (every value finite, kt >= 0, ior 0 or >= 1)", bad,
-			            (double)q[0], (double)q[1], (double)q[2], (double)q[3]);
-		}
-	}
-	if (!c->kids.empty()) return multi_set_tri_table(c, &sphip_ctx::have_glass, sphip_set_dielectric, glass);
-	if (glass) if (const int rc = ensure_zero_rows(c, c->own_stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
-	return set_tri_table(c, c->glass, c->have_glass, glass, 16, hipMemcpyHostToDevice, c->own_stream, true);
-}
-
-int sphip_set_dielectric_device(sphip_t* c, const void* d_glass, void* stream) {
-	if (const int rc = single_device_entry(c)) return rc;
-	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_set_dielectric_device called before a scene was set");
-	const bool big = d_glass && c->n_tris >= (size_t)sp::kTransBit;    // refused, and like every call it leaves no table behind
-	if (d_glass && !big) if (const int rc = ensure_zero_rows(c, (hipStream_t)stream)) { c->have_glass = false; c->acc_stale = c->acc_on; return rc; }
-	const int rc = set_tri_table(c, c->glass, c->have_glass, big ? nullptr : d_glass, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
-	return big ? fail(c, SPHIP_E_INVALID, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)", c->n_tris) : rc;
+// the texels of a host-pointer image, w x h x {r g b}: every value finite and >= 0
+static int check_texels(sphip_ctx* c, const char* noun, const float* texels, uint32_t w, uint32_t h) {
+	const size_t count = (size_t)w * h * 3, bad = first_bad_texel(texels, count);
+	return bad < count ? fail(c, SPHIP_E_INVALID, "%s", bad_texel_message(noun, texels, bad, w).c_str()) : SPHIP_OK;
 }
 
 int sphip_set_environment(sphip_t* c, const float* texels, uint32_t n) {
 	if (!c) return SPHIP_E_INVALID;
 	if (texels) {
 		if (n == 0 || n > sp::kEnvMaxN) return fail(c, SPHIP_E_INVALID, "environment map: n = %u (1 <= n <= %u)", n, sp::kEnvMaxN);
-		const size_t cnt = (size_t)n * n * 3;
-		for (size_t k = 0; k < cnt; ++k)
-			if (!std::isfinite(texels[k]) || !(texels[k] >= 0.0f))
-				return fail(c, SPHIP_E_INVALID, "environment map: texel (%zu, %zu) has component %zu = %g (every value finite and >= 0)", (k / 3) % n, (k / 3) / n,
-				            k % 3, (double)texels[k]);
+		if (const int rc = check_texels(c, "environment map", texels, n, n)) return rc;
 	}
 	if (c->kids.empty()) return set_env_map(c, texels, n, hipMemcpyHostToDevice, c->own_stream, true);
-	c->acc_stale = c->acc_on;
-	c->have_env = false;
-	for (sphip_ctx* k : c->kids)                                   // the texels were validated above, once
-		if (const int rc = set_env_map(k, texels, n, hipMemcpyHostToDevice, k->own_stream, true)) {   // a device that refuses leaves no device with a map: they must never differ
-			for (sphip_ctx* q : c->kids) q->have_env = false;
-			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-		}
-	c->have_env = texels != nullptr;
+	if (const int rc = set_on_every_device(c, &sphip_ctx::have_env, texels != nullptr,        // the texels were validated above, once
+	                                       [&](sphip_ctx* k) { return set_env_map(k, texels, n, hipMemcpyHostToDevice, k->own_stream, true); })) return rc;
 	c->env_n = texels ? n : 0;
 	return SPHIP_OK;
 }
@@ -1943,21 +1853,11 @@ int sphip_set_texture(sphip_t* c, const float* texels, uint32_t tw, uint32_t th)
 	if (texels) {
 		if (tw == 0 || tw > sp::kTexMaxN || th == 0 || th > sp::kTexMaxN)
 			return fail(c, SPHIP_E_INVALID, "atlas: %u x %u texels (1 <= tw, th <= %u)", tw, th, sp::kTexMaxN);
-		const size_t cnt = (size_t)tw * th * 3;
-		for (size_t k = 0; k < cnt; ++k)
-			if (!std::isfinite(texels[k]) || !(texels[k] >= 0.0f))
-				return fail(c, SPHIP_E_INVALID, "atlas: texel (%zu, %zu) has component %zu = %g (every value finite and >= 0)", (k / 3) % tw, (k / 3) / tw,
-				            k % 3, (double)texels[k]);
+		if (const int rc = check_texels(c, "atlas", texels, tw, th)) return rc;
 	}
 	if (c->kids.empty()) return set_atlas(c, texels, tw, th, hipMemcpyHostToDevice, c->own_stream, true);
-	c->acc_stale = c->acc_on;
-	c->have_tex = false;
-	for (sphip_ctx* k : c->kids)                                   // the texels were validated above, once
-		if (const int rc = set_atlas(k, texels, tw, th, hipMemcpyHostToDevice, k->own_stream, true)) {   // a device that refuses leaves no device with an atlas: they must never differ
-			for (sphip_ctx* q : c->kids) q->have_tex = false;
-			return fail(c, rc, "device %d: %s", k->device, k->err.c_str());
-		}
-	c->have_tex = texels != nullptr;
+	if (const int rc = set_on_every_device(c, &sphip_ctx::have_tex, texels != nullptr,        // the texels were validated above, once
+	                                       [&](sphip_ctx* k) { return set_atlas(k, texels, tw, th, hipMemcpyHostToDevice, k->own_stream, true); })) return rc;
 	c->tex_w = texels ? tw : 0; c->tex_h = texels ? th : 0;
 	return SPHIP_OK;
 }

@@ -21,6 +21,31 @@ namespace {
 static_assert(sizeof(geom::triangle) == 48 && sizeof(geom::ray) == 24 && sizeof(scene::material) == 24 && sizeof(scene::RGBA) == 4,
               "the C ABI takes the reference's packed structs as plain float arrays");
 
+// What a frame depends on beside the triangles and the materials: the per-triangle tables and the two context-level images, in the
+// order in which they follow the scene to the library.  One rule for all: kept by its setter (hip_renderer::set_X), it joins the scene's
+// key and goes to the library with every scene upload (sphip_set_scene clears the tables; the library keeps the images across scenes,
+// but they travel like the tables so that one key covers everything); while everything that carries a flag is set, path-traced frames
+// carry that flag.
+enum part_id { P_ENV, P_SPEC, P_VNORM, P_GLASS, P_ROUGH, P_TEX, P_UV, N_PARTS };
+int set_env_image(sphip_t* c, const float* texels, uint32_t n, uint32_t) { return sphip_set_environment(c, texels, n); }
+struct part_rule {
+	const char* what;                                                // the call, as check() names it
+	int flag;
+	size_t floats;                                                   // per triangle; 0: an image of w x h x 3 floats
+	const char* noun;                                                // of a table, for the size check
+	int (*set_table)(sphip_t*, const float*);
+	int (*set_image)(sphip_t*, const float*, uint32_t, uint32_t);
+};
+const part_rule part_rules[N_PARTS] = {
+	{ "set_environment", SPHIP_FLAG_ENVIRONMENT, 0, 0, 0, set_env_image },
+	{ "set_specular", SPHIP_FLAG_SPECULAR, 4, "specular table", sphip_set_specular, 0 },
+	{ "set_vertex_normals", SPHIP_FLAG_SMOOTH, 9, "vertex normals", sphip_set_vertex_normals, 0 },
+	{ "set_dielectric", SPHIP_FLAG_DIELECTRIC, 4, "dielectric table", sphip_set_dielectric, 0 },
+	{ "set_roughness", SPHIP_FLAG_GLOSSY, 1, "roughness table", sphip_set_roughness, 0 },
+	{ "set_texture", SPHIP_FLAG_TEXTURE, 0, 0, 0, sphip_set_texture },
+	{ "set_uv", SPHIP_FLAG_TEXTURE, 6, "UV table", sphip_set_uv, 0 },
+};
+
 struct hip_r : public basic_renderer {
 	sphip_t* ctx;
 	std::string desc;
@@ -52,30 +77,15 @@ struct hip_r : public basic_renderer {
 	// the lens is the context's, and the one an accumulation was begun with joins its key
 	bool cam_samples;
 	sphip_lens lens, acc_lens;
-	// specular reflection (set_specular): the table goes to the library with every scene upload (sphip_set_scene clears it) and joins
-	// the scene's key; while there is one, path-traced frames carry SPHIP_FLAG_SPECULAR
-	std::vector<float> spec;
-	// smooth shading (set_vertex_normals): likewise, 9 floats per triangle and SPHIP_FLAG_SMOOTH
-	std::vector<float> vnorm;
-	// transparency (set_dielectric): likewise, 4 floats per triangle and SPHIP_FLAG_DIELECTRIC
-	std::vector<float> glass;
-	// glossy reflection (set_roughness): likewise, 1 float per triangle and SPHIP_FLAG_GLOSSY
-	std::vector<float> rough;
-	// environment lighting (set_environment): the map, env_n x env_n x 3 floats, and SPHIP_FLAG_ENVIRONMENT; the library keeps it across
-	// scenes, but it travels with the scene upload like the tables so that one key covers everything a frame depends on
-	std::vector<float> env;
-	uint32_t env_n;
-	// textures (set_texture, set_uv): the atlas, tex_w x tex_h x 3 floats, travels like the map; the UV table, 6 floats per triangle,
-	// like the tables; SPHIP_FLAG_TEXTURE while both are set
-	std::vector<float> tex, uv;
-	uint32_t tex_w, tex_h;
+	struct part { std::vector<float> v; uint32_t w, h; part() : w(0), h(0) {} };      // empty: not set; w, h: an image's size
+	part parts[N_PARTS];
 
 	// ids == 0: every visible GPU of the node (or the list in SPATH_HIP_DEVICES) behind this one renderer object: the frame is
 	// dealt to them as interleaved pixel-row tiles and reassembled on the first (include/spath_hip.h: sphip_create_multi)
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
-	                                                                   cam_samples(false), env_n(0), tex_w(0), tex_h(0) {
+	                                                                   cam_samples(false) {
 		std::memset(&acc_camera, 0, sizeof acc_camera);
 		std::memset(&lens, 0, sizeof lens);
 		std::memset(&acc_lens, 0, sizeof acc_lens);
@@ -105,37 +115,22 @@ struct hip_r : public basic_renderer {
 	void upload_scene(const geom::triangle* tris, const scene::material* mats, const size_t n_tris) {
 		unsigned long long h = fnv(tris, n_tris * sizeof(geom::triangle), 1469598103934665603ull);
 		h = fnv(mats, n_tris * sizeof(scene::material), h);
-		if (!spec.empty()) {
-			if (spec.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the specular table and the scene differ in size");
-			h = fnv(spec.data(), spec.size() * sizeof(float), h);
+		for (int i = 0; i < N_PARTS; ++i) {
+			const part& q = parts[i];
+			if (q.v.empty()) continue;
+			if (part_rules[i].floats && q.v.size() != n_tris * part_rules[i].floats)
+				throw std::runtime_error(std::string("hip_renderer: the ") + part_rules[i].noun + " and the scene differ in size");
+			h = fnv(&q.w, sizeof q.w, h);
+			h = fnv(q.v.data(), q.v.size() * sizeof(float), h);
 		}
-		if (!vnorm.empty()) {
-			if (vnorm.size() != n_tris * 9) throw std::runtime_error("hip_renderer: the vertex normals and the scene differ in size");
-			h = fnv(vnorm.data(), vnorm.size() * sizeof(float), h);
-		}
-		if (!glass.empty()) {
-			if (glass.size() != n_tris * 4) throw std::runtime_error("hip_renderer: the dielectric table and the scene differ in size");
-			h = fnv(glass.data(), glass.size() * sizeof(float), h);
-		}
-		if (!rough.empty()) {
-			if (rough.size() != n_tris) throw std::runtime_error("hip_renderer: the roughness table and the scene differ in size");
-			h = fnv(rough.data(), rough.size() * sizeof(float), h);
-		}
-		if (!env.empty()) h = fnv(env.data(), env.size() * sizeof(float), h);
-		if (!uv.empty()) {
-			if (uv.size() != n_tris * 6) throw std::runtime_error("hip_renderer: the UV table and the scene differ in size");
-			h = fnv(uv.data(), uv.size() * sizeof(float), h);
-		}
-		if (!tex.empty()) { h = fnv(&tex_w, sizeof tex_w, h); h = fnv(tex.data(), tex.size() * sizeof(float), h); }
 		if (h != scene_hash || n_tris != scene_n) {
 			check(sphip_set_scene(ctx, (const float*)tris, (const float*)mats, n_tris), "set_scene");
-			check(sphip_set_environment(ctx, env.empty() ? 0 : env.data(), env_n), "set_environment");
-			if (!spec.empty()) check(sphip_set_specular(ctx, spec.data()), "set_specular");
-			if (!vnorm.empty()) check(sphip_set_vertex_normals(ctx, vnorm.data()), "set_vertex_normals");
-			if (!glass.empty()) check(sphip_set_dielectric(ctx, glass.data()), "set_dielectric");
-			if (!rough.empty()) check(sphip_set_roughness(ctx, rough.data()), "set_roughness");
-			check(sphip_set_texture(ctx, tex.empty() ? 0 : tex.data(), tex_w, tex_h), "set_texture");
-			if (!uv.empty()) check(sphip_set_uv(ctx, uv.data()), "set_uv");
+			for (int i = 0; i < N_PARTS; ++i) {
+				const part& q = parts[i];
+				const float* p = q.v.empty() ? 0 : q.v.data();
+				if (part_rules[i].set_image) check(part_rules[i].set_image(ctx, p, q.w, q.h), part_rules[i].what);     // sent, or cleared, every time
+				else if (p) check(part_rules[i].set_table(ctx, p), part_rules[i].what);
+			}
 			scene_hash = h; scene_n = n_tris;
 		}
 	}
@@ -205,11 +200,11 @@ struct hip_r : public basic_renderer {
 		have_stats = sphip_get_stats(ctx, &stats) == SPHIP_OK;
 	}
 
-	int table_flags(const int mode) const {              // the flags of the tables that are set
+	int table_flags(const int mode) const {              // the flags whose tables and images are all set
 		if (mode != SPHIP_MODE_PT) return 0;
-		return (!spec.empty() ? SPHIP_FLAG_SPECULAR : 0) | (!vnorm.empty() ? SPHIP_FLAG_SMOOTH : 0) | (!glass.empty() ? SPHIP_FLAG_DIELECTRIC : 0) |
-		       (!env.empty() ? SPHIP_FLAG_ENVIRONMENT : 0) | (!rough.empty() ? SPHIP_FLAG_GLOSSY : 0) |
-		       (!tex.empty() && !uv.empty() ? SPHIP_FLAG_TEXTURE : 0);
+		int on = 0, off = 0;
+		for (int i = 0; i < N_PARTS; ++i) (parts[i].v.empty() ? off : on) |= part_rules[i].flag;
+		return on & ~off;                                             // SPHIP_FLAG_TEXTURE needs both the atlas and the UV table
 	}
 
 	void frame(const view::viewport& vp, const geom::triangle* tris, const scene::material* mats, const size_t n_tris,
@@ -299,61 +294,24 @@ namespace hip_renderer {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) p->cam_samples = on;
 	}
 
-	void set_specular(scene::renderer* r, const float* spec, size_t n_tris) {
+	// one part from the caller's `count` floats (copied), or none with src == NULL or count == 0
+	static void keep(scene::renderer* r, part_id id, const float* src, size_t count, uint32_t w = 0, uint32_t h = 0) {
 		hip_r* p = dynamic_cast<hip_r*>(r);
 		if (!p) return;
-		if (spec && n_tris) p->spec.assign(spec, spec + n_tris * 4);
-		else p->spec.clear();
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
+		hip_r::part& q = p->parts[id];
+		if (src && count) { q.v.assign(src, src + count); q.w = w; q.h = h; }
+		else { q.v.clear(); q.w = q.h = 0; }
+		p->scene_n = 0;                    // the next frame uploads the scene again, and the table, map or atlas (or none) with it
 	}
+	static void keep_table(scene::renderer* r, part_id id, const float* rows, size_t n_tris) { keep(r, id, rows, n_tris * part_rules[id].floats); }
 
-	void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (glass && n_tris) p->glass.assign(glass, glass + n_tris * 4);
-		else p->glass.clear();
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
-	}
-
-	void set_roughness(scene::renderer* r, const float* alpha, size_t n_tris) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (alpha && n_tris) p->rough.assign(alpha, alpha + n_tris);
-		else p->rough.clear();
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
-	}
-
-	void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (texels && tw && th) { p->tex.assign(texels, texels + (size_t)tw * th * 3); p->tex_w = tw; p->tex_h = th; }
-		else { p->tex.clear(); p->tex_w = p->tex_h = 0; }
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the atlas (or none) with it
-	}
-
-	void set_uv(scene::renderer* r, const float* uv, size_t n_tris) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (uv && n_tris) p->uv.assign(uv, uv + n_tris * 6);
-		else p->uv.clear();
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the table (or none) with it
-	}
-
-	void set_environment(scene::renderer* r, const float* texels, uint32_t n) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (texels && n) { p->env.assign(texels, texels + (size_t)n * n * 3); p->env_n = n; }
-		else { p->env.clear(); p->env_n = 0; }
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the map (or none) with it
-	}
-
-	void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris) {
-		hip_r* p = dynamic_cast<hip_r*>(r);
-		if (!p) return;
-		if (vn && n_tris) p->vnorm.assign(vn, vn + n_tris * 9);
-		else p->vnorm.clear();
-		p->scene_n = 0;                    // the next frame uploads the scene again, and the normals (or none) with it
-	}
+	void set_specular(scene::renderer* r, const float* spec, size_t n_tris) { keep_table(r, P_SPEC, spec, n_tris); }
+	void set_vertex_normals(scene::renderer* r, const float* vn, size_t n_tris) { keep_table(r, P_VNORM, vn, n_tris); }
+	void set_dielectric(scene::renderer* r, const float* glass, size_t n_tris) { keep_table(r, P_GLASS, glass, n_tris); }
+	void set_roughness(scene::renderer* r, const float* alpha, size_t n_tris) { keep_table(r, P_ROUGH, alpha, n_tris); }
+	void set_uv(scene::renderer* r, const float* uv, size_t n_tris) { keep_table(r, P_UV, uv, n_tris); }
+	void set_environment(scene::renderer* r, const float* texels, uint32_t n) { keep(r, P_ENV, texels, (size_t)n * n * 3, n, n); }
+	void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th) { keep(r, P_TEX, texels, (size_t)tw * th * 3, tw, th); }
 
 	void set_lens(scene::renderer* r, float aperture, float focus_dist) {
 		hip_r* p = dynamic_cast<hip_r*>(r);

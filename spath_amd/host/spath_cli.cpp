@@ -145,7 +145,7 @@ bool load_scene(const char* path, std::vector<geom::triangle>& t, std::vector<sc
 	return ok;
 }
 
-// a per-triangle table file of spath_amd/scene.py: magic, n, n rows of `row` floats ('SPSP': 4, 'SPVN': 9)
+// a per-triangle table file of spath_amd/scene.py: magic, n, n rows of `row` floats (main's table_files lists them)
 bool load_table(const char* path, uint32_t magic, size_t row, std::vector<float>& tab) {
 	FILE* f = std::fopen(path, "rb");
 	if (!f) return false;
@@ -158,10 +158,6 @@ bool load_table(const char* path, uint32_t magic, size_t row, std::vector<float>
 	std::fclose(f);
 	return ok;
 }
-bool load_specular(const char* path, std::vector<float>& spec) { return load_table(path, 0x50535053u, 4, spec); }
-bool load_normals(const char* path, std::vector<float>& vn) { return load_table(path, 0x4E565053u, 9, vn); }
-bool load_dielectric(const char* path, std::vector<float>& glass) { return load_table(path, 0x49445053u, 4, glass); }
-bool load_roughness(const char* path, std::vector<float>& rough) { return load_table(path, 0x47525053u, 1, rough); }
 
 // an environment map file of spath_amd/scene.py: 'SPEN', n, n * n * 3 f32
 bool load_environment(const char* path, std::vector<float>& env, uint32_t& n) {
@@ -314,29 +310,19 @@ int main(int argc, char** argv) {
 		hip_renderer::set_nee(r.get(), nee);
 		if (mis) hip_renderer::set_mis(r.get(), true);
 		hip_renderer::set_camera_samples(r.get(), aa);
-		if (!spec_arg.empty()) {
-			std::vector<float> spec;
-			if (!load_specular(spec_arg.c_str(), spec)) throw std::runtime_error("cannot read specular file " + spec_arg);
-			if (spec.size() != tris.size() * 4) throw std::runtime_error("the specular file " + spec_arg + " and the scene differ in size");
-			hip_renderer::set_specular(r.get(), spec.data(), tris.size());
-		}
-		if (!normals_arg.empty()) {
-			std::vector<float> vn;
-			if (!load_normals(normals_arg.c_str(), vn)) throw std::runtime_error("cannot read vertex-normal file " + normals_arg);
-			if (vn.size() != tris.size() * 9) throw std::runtime_error("the vertex-normal file " + normals_arg + " and the scene differ in size");
-			hip_renderer::set_vertex_normals(r.get(), vn.data(), tris.size());
-		}
-		if (!glass_arg.empty()) {
-			std::vector<float> glass;
-			if (!load_dielectric(glass_arg.c_str(), glass)) throw std::runtime_error("cannot read dielectric file " + glass_arg);
-			if (glass.size() != tris.size() * 4) throw std::runtime_error("the dielectric file " + glass_arg + " and the scene differ in size");
-			hip_renderer::set_dielectric(r.get(), glass.data(), tris.size());
-		}
-		if (!rough_arg.empty()) {
-			std::vector<float> rough;
-			if (!load_roughness(rough_arg.c_str(), rough)) throw std::runtime_error("cannot read roughness file " + rough_arg);
-			if (rough.size() != tris.size()) throw std::runtime_error("the roughness file " + rough_arg + " and the scene differ in size");
-			hip_renderer::set_roughness(r.get(), rough.data(), tris.size());
+		// the table files that carry a magic ('SPSP', 'SPVN', 'SPDI', 'SPRG'): the argument, the magic, floats per triangle, the noun, the setter
+		const struct { const std::string& arg; uint32_t magic; size_t row; const char* noun; void (*set)(scene::renderer*, const float*, size_t); } table_files[] = {
+			{ spec_arg, 0x50535053u, 4, "specular", hip_renderer::set_specular },
+			{ normals_arg, 0x4E565053u, 9, "vertex-normal", hip_renderer::set_vertex_normals },
+			{ glass_arg, 0x49445053u, 4, "dielectric", hip_renderer::set_dielectric },
+			{ rough_arg, 0x47525053u, 1, "roughness", hip_renderer::set_roughness },
+		};
+		for (const auto& t : table_files) {
+			if (t.arg.empty()) continue;
+			std::vector<float> tab;
+			if (!load_table(t.arg.c_str(), t.magic, t.row, tab)) throw std::runtime_error(std::string("cannot read ") + t.noun + " file " + t.arg);
+			if (tab.size() != tris.size() * t.row) throw std::runtime_error(std::string("the ") + t.noun + " file " + t.arg + " and the scene differ in size");
+			t.set(r.get(), tab.data(), tris.size());
 		}
 		if (!tex_arg.empty()) {
 			std::vector<float> tex, uv;

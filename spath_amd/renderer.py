@@ -20,6 +20,17 @@ from .view import Camera
 
 
 NEVER_STOP = (0.0, 0.0, 0xFFFFFFFF)    # an adaptive rule that never stops a pixel (min_samples = UINT32_MAX)
+# What HipRenderer keeps beside the triangles and sends with every scene upload, in upload order: (name, floats per triangle or None for a
+# context-level image, the flag of a path-traced frame, the capi.Context setter).  A flag is on while everything that lists it is set.
+PARTS = (
+    ("spec", 4, capi.FLAG_SPECULAR, "set_specular"),
+    ("vnorm", 9, capi.FLAG_SMOOTH, "set_vertex_normals"),
+    ("glass", 4, capi.FLAG_DIELECTRIC, "set_dielectric"),
+    ("rough", 1, capi.FLAG_GLOSSY, "set_roughness"),
+    ("uv", 6, capi.FLAG_TEXTURE, "set_uv"),
+    ("env", None, capi.FLAG_ENVIRONMENT, "set_environment"),
+    ("tex", None, capi.FLAG_TEXTURE, "set_texture"),
+)
 
 
 class Bitmap:
@@ -100,75 +111,71 @@ class HipRenderer(BasicRenderer):
         self._scene_key = None
         self._accum_key = None
         self.last_stats = None
-        self._spec = None
-        self._vnorm = None
-        self._glass = None
-        self._env = None
-        self._rough = None
-        self._tex = None
-        self._uv = None
+        self._parts = {name: None for name, _, _, _ in PARTS}
+
+    def _set_part(self, name, data):
+        """keep a copy of a table ([n_tris, floats]) or an image (as given), or None; the next frame uploads the scene again"""
+        floats = next(p[1] for p in PARTS if p[0] == name)
+        if data is not None:
+            data = np.ascontiguousarray(data, dtype=np.float32)
+            data = (data if floats is None else data.reshape(-1, floats)).copy()
+        self._parts[name] = data
+        self._scene_key = None
 
     def set_texture(self, texels):
         """The atlas of capi.FLAG_TEXTURE renders ([th, tw, 3] float32, scene.checker_texture; None: no atlas), like
         hip_renderer::set_texture: it goes to the library with the next scene upload and begins a new accumulation, and while an atlas
         and a UV table (set_uv) are both set every path-traced frame carries capi.FLAG_TEXTURE (render_flat never does)."""
-        self._tex = None if texels is None else np.ascontiguousarray(texels, dtype=np.float32).copy()
-        self._scene_key = None
+        self._set_part("tex", texels)
 
     def set_uv(self, uv):
         """The UV table of capi.FLAG_TEXTURE renders ([n_tris, 6] float32, scene.uv_table or scene.planar_uv; None: no table), like
         hip_renderer::set_uv: see set_texture."""
-        self._uv = None if uv is None else np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 6).copy()
-        self._scene_key = None
+        self._set_part("uv", uv)
 
     def set_roughness(self, alpha):
         """The roughness table of capi.FLAG_GLOSSY renders ([n_tris] float32, scene.roughness_table; None: no table), like
         hip_renderer::set_roughness: it goes to the library with the next scene upload and begins a new accumulation, and while one is
         set every path-traced frame carries capi.FLAG_GLOSSY (render_flat never does); the flag needs a specular table beside it."""
-        self._rough = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1).copy()
-        self._scene_key = None
+        self._set_part("rough", alpha)
 
     def set_environment(self, env):
         """The environment map of capi.FLAG_ENVIRONMENT renders ([n, n, 3] float32, scene.sky_environment or
         scene.environment_from_latlong; None: no map), like hip_renderer::set_environment: it goes to the library with the next scene
         upload and begins a new accumulation, and while one is set every path-traced frame carries capi.FLAG_ENVIRONMENT (render_flat
         never does)."""
-        self._env = None if env is None else np.ascontiguousarray(env, dtype=np.float32).copy()
-        self._scene_key = None
+        self._set_part("env", env)
 
     def set_dielectric(self, glass):
         """The dielectric table of capi.FLAG_DIELECTRIC renders ([n_tris, 4] float32, scene.dielectric_table; None: no table), like
         hip_renderer::set_dielectric: it goes to the library with the next scene upload and begins a new accumulation, and while one
         is set every path-traced frame carries capi.FLAG_DIELECTRIC (render_flat never does)."""
-        self._glass = None if glass is None else np.ascontiguousarray(glass, dtype=np.float32).reshape(-1, 4).copy()
-        self._scene_key = None
+        self._set_part("glass", glass)
 
     def set_vertex_normals(self, vn):
         """The per-vertex normals of capi.FLAG_SMOOTH renders ([n_tris, 9] float32, scene.vertex_normals; None: none), like
         hip_renderer::set_vertex_normals: they go to the library with the next scene upload and begin a new accumulation, and while
         they are set every path-traced frame carries capi.FLAG_SMOOTH (render_flat never does)."""
-        self._vnorm = None if vn is None else np.ascontiguousarray(vn, dtype=np.float32).reshape(-1, 9).copy()
-        self._scene_key = None
+        self._set_part("vnorm", vn)
 
     def set_specular(self, spec):
         """The specular table of capi.FLAG_SPECULAR renders ([n_tris, 4] float32, scene.specular_table; None: no table), like
         hip_renderer::set_specular: it goes to the library with the next scene upload and begins a new accumulation, and while one is
         set every path-traced frame carries capi.FLAG_SPECULAR (render_flat never does).  Without a table the flags are the caller's."""
-        self._spec = None if spec is None else np.ascontiguousarray(spec, dtype=np.float32).reshape(-1, 4).copy()
-        self._scene_key = None
+        self._set_part("spec", spec)
 
     def _flags(self, mode):
         """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY and FLAG_TEXTURE on
         while their tables, the map or the atlas are set, and never on the flat pass"""
+        on = off = 0
+        for name, _, flag, _ in PARTS:
+            if self._parts[name] is None:
+                off |= flag
+            else:
+                on |= flag
         if mode == capi.MODE_FLAT:
-            return self.flags & ~(capi.FLAG_SPECULAR | capi.FLAG_SMOOTH | capi.FLAG_DIELECTRIC | capi.FLAG_ENVIRONMENT | capi.FLAG_GLOSSY |
-                                  capi.FLAG_TEXTURE)
-        flags = self.flags | capi.FLAG_SPECULAR if self._spec is not None else self.flags
-        flags = flags | capi.FLAG_GLOSSY if self._rough is not None else flags
-        flags = flags | capi.FLAG_TEXTURE if self._tex is not None and self._uv is not None else flags
-        flags = flags | capi.FLAG_ENVIRONMENT if self._env is not None else flags
-        flags = flags | capi.FLAG_DIELECTRIC if self._glass is not None else flags
-        return flags | capi.FLAG_SMOOTH if self._vnorm is not None else flags
+            return self.flags & ~(on | off)
+        return self.flags | (on & ~off)
 
     def get_description(self) -> str:
         return self.ctx.description
@@ -177,24 +184,16 @@ class HipRenderer(BasicRenderer):
         tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 12)[:n_tris]
         mats = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 6)[:n_tris]
         # the reference's GPU peer re-uploads every frame (cl_renderer.cpp:210-214); upload only on change
-        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes()), None if self._spec is None else hash(self._spec.tobytes()),
-               None if self._vnorm is None else hash(self._vnorm.tobytes()), None if self._glass is None else hash(self._glass.tobytes()),
-               None if self._env is None else hash(self._env.tobytes()), None if self._rough is None else hash(self._rough.tobytes()),
-               None if self._tex is None else (self._tex.shape, hash(self._tex.tobytes())), None if self._uv is None else hash(self._uv.tobytes()))
+        key = (n_tris, hash(tris.tobytes()), hash(mats.tobytes())) + tuple(None if a is None else (a.shape, hash(a.tobytes()))
+                                                                           for a in self._parts.values())
         if key != self._scene_key:
             self.ctx.set_scene(tris, mats)
-            if self._spec is not None:
-                self.ctx.set_specular(self._spec[:n_tris])
-            if self._vnorm is not None:
-                self.ctx.set_vertex_normals(self._vnorm[:n_tris])
-            if self._glass is not None:
-                self.ctx.set_dielectric(self._glass[:n_tris])
-            if self._rough is not None:
-                self.ctx.set_roughness(self._rough[:n_tris])
-            if self._uv is not None:
-                self.ctx.set_uv(self._uv[:n_tris])
-            self.ctx.set_environment(self._env)
-            self.ctx.set_texture(self._tex)
+            for name, floats, _, setter in PARTS:
+                a = self._parts[name]
+                if floats is None:
+                    getattr(self.ctx, setter)(a)               # an image is the context's: sent, or cleared, every time
+                elif a is not None:
+                    getattr(self.ctx, setter)(a[:n_tris])
             self._scene_key = key
 
     def _begin_rule(self):

@@ -222,12 +222,17 @@ def specular_table(tris: np.ndarray, mats: np.ndarray, ks=0.0, which=None, p=Non
     return spec
 
 
+def _write_table(path, magic: int, rows: np.ndarray, width: int) -> None:
+    """The 'magic, n, rows' file of a per-triangle table: u32 magic, u32 n, then n x width float32."""
+    rows = np.ascontiguousarray(rows, dtype=F).reshape(-1, width)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<II", magic, rows.shape[0]))
+        f.write(rows.tobytes())
+
+
 def write_specular(path, spec: np.ndarray) -> None:
     """Specular file read by the headless CLI (--spec), beside the scene file: 'SPSP', n, n * 4 float32."""
-    spec = np.ascontiguousarray(spec, dtype=F).reshape(-1, 4)
-    with open(path, "wb") as f:
-        f.write(struct.pack("<II", SPEC_MAGIC, spec.shape[0]))
-        f.write(spec.tobytes())
+    _write_table(path, SPEC_MAGIC, spec, 4)
 
 
 def dielectric_table(tris: np.ndarray, ior=1.5, kt=1.0, which=None) -> np.ndarray:
@@ -251,10 +256,7 @@ def dielectric_table(tris: np.ndarray, ior=1.5, kt=1.0, which=None) -> np.ndarra
 
 def write_dielectric(path, glass: np.ndarray) -> None:
     """Dielectric file read by the headless CLI (--glass), beside the scene file: 'SPDI', n, n * 4 float32."""
-    glass = np.ascontiguousarray(glass, dtype=F).reshape(-1, 4)
-    with open(path, "wb") as f:
-        f.write(struct.pack("<II", GLASS_MAGIC, glass.shape[0]))
-        f.write(glass.tobytes())
+    _write_table(path, GLASS_MAGIC, glass, 4)
 
 
 def roughness_table(tris: np.ndarray, alpha=0.2, which=None) -> np.ndarray:
@@ -275,10 +277,7 @@ def roughness_table(tris: np.ndarray, alpha=0.2, which=None) -> np.ndarray:
 
 def write_roughness(path, alpha: np.ndarray) -> None:
     """Roughness file read by the headless CLI (--rough), beside the scene file: 'SPRG', n, n float32."""
-    alpha = np.ascontiguousarray(alpha, dtype=F).reshape(-1)
-    with open(path, "wb") as f:
-        f.write(struct.pack("<II", ROUGH_MAGIC, alpha.shape[0]))
-        f.write(alpha.tobytes())
+    _write_table(path, ROUGH_MAGIC, alpha, 1)
 
 
 def checker_texture(tw: int = 16, th: int = 16, cell: int = 4, a=(0.9, 0.9, 0.9), b=(0.2, 0.2, 0.2)) -> np.ndarray:
@@ -438,10 +437,7 @@ def vertex_normals(tris: np.ndarray, crease_deg: float = 180.0, which=None) -> n
 
 def write_vertex_normals(path, vn: np.ndarray) -> None:
     """Vertex-normal file read by the headless CLI (--normals), beside the scene file: 'SPVN', n, n * 9 float32."""
-    vn = np.ascontiguousarray(vn, dtype=F).reshape(-1, 9)
-    with open(path, "wb") as f:
-        f.write(struct.pack("<II", VNORM_MAGIC, vn.shape[0]))
-        f.write(vn.tobytes())
+    _write_table(path, VNORM_MAGIC, vn, 9)
 
 
 def icosphere(subdiv: int, centre=(0.0, 0.0, 0.0), radius: float = 1.0, material=(0.8, 0.8, 0.8, 0.0, 0.0, 0.0)):

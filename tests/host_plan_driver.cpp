@@ -1,11 +1,18 @@
-// The stand-alone program of tests/test_host_plan.py: spath_amd/csrc/sp_host_plan.h under a host compiler and its sanitizers.
+// The stand-alone program of tests/test_host_plan.py and tests/test_host_tables.py: spath_amd/csrc/sp_host_plan.h and sp_host_tables.h
+// under a host compiler and its sanitizers.
 //   host_plan_driver plan n_rays n_samples forced pt R split scan bthreads features samp_cap work_cap free
 //       prints the LaunchPlan as "name=value" words; features: bit k = member k of sp_host::Features; free: what the free-memory
 //       callable reports (negative: it cannot tell); "asked" is how often it was called
 //   host_plan_driver lights in out
 //       in:  u64 n_tris, f64 W_env (0: no flagged table), f32 tris[n_tris * 12], f32 mats[n_tris * 6]
 //       out: i64 bad_tri (-1: none), i64 bad_comp, then per table (the unflagged one, the flagged one if W_env > 0) u64 n, f64 W, the blob
+//   host_plan_driver table name n_tris value...
+//       the rows of the table called `name` in kTriTables (n_tris x its floats values, as strtof reads them: "nan", "-inf"): prints
+//       first_bad_row (n_tris: every row passes), then on a line of its own bad_row_message for that row if there is one
+//   host_plan_driver texels noun w h value...
+//       an image of w x h x 3 values: prints first_bad_texel (w * h * 3: every texel passes), then bad_texel_message if there is one
 #include "sp_host_plan.h"
+#include "sp_host_tables.h"
 
 #include <cinttypes>
 #include <cstdio>
@@ -59,9 +66,40 @@ static int lights(const char* in_path, const char* out_path) {
 	return fclose(out) == 0 && ok ? 0 : 3;
 }
 
+static std::vector<float> values(int n, char** v) {
+	std::vector<float> x((size_t)n);
+	for (int k = 0; k < n; ++k) x[(size_t)k] = strtof(v[k], nullptr);
+	return x;
+}
+
+static int table(int argc, char** v) {
+	const size_t n_tris = (size_t)strtoull(v[1], nullptr, 10);
+	for (const TriTable& t : kTriTables) {
+		if (strcmp(t.name, v[0]) || (size_t)(argc - 2) != n_tris * (size_t)t.floats) continue;
+		const std::vector<float> rows = values(argc - 2, v + 2);
+		const size_t bad = first_bad_row(t, rows.data(), n_tris);
+		printf("%zu\n", bad);
+		if (bad < n_tris) printf("%s\n", bad_row_message(t, rows.data(), bad).c_str());
+		return 0;
+	}
+	return 2;
+}
+
+static int texels(int argc, char** v) {
+	const size_t w = (size_t)strtoull(v[1], nullptr, 10), h = (size_t)strtoull(v[2], nullptr, 10), count = w * h * 3;
+	if ((size_t)(argc - 3) != count) return 2;
+	const std::vector<float> x = values(argc - 3, v + 3);
+	const size_t bad = first_bad_texel(x.data(), count);
+	printf("%zu\n", bad);
+	if (bad < count) printf("%s\n", bad_texel_message(v[0], x.data(), bad, w).c_str());
+	return 0;
+}
+
 int main(int argc, char** argv) {
 	if (argc == 14 && !strcmp(argv[1], "plan")) return plan(argv + 2);
 	if (argc == 4 && !strcmp(argv[1], "lights")) return lights(argv[2], argv[3]);
-	fprintf(stderr, "usage: host_plan_driver plan <12 numbers> | lights <in> <out>\n");
+	if (argc >= 4 && !strcmp(argv[1], "table")) return table(argc - 2, argv + 2);
+	if (argc >= 5 && !strcmp(argv[1], "texels")) return texels(argc - 2, argv + 2);
+	fprintf(stderr, "usage: host_plan_driver plan <12 numbers> | lights <in> <out> | table <name> <n_tris> <values> | texels <noun> <w> <h> <values>\n");
 	return 2;
 }

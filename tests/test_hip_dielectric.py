@@ -110,8 +110,14 @@ def test_null_context_and_triangle_limit():
     src = open(os.path.join(ROOT, "spath_amd", "csrc", "sp_integrator.h")).read()
     assert "constexpr int kTransBit = 0x20000000;" in src and "constexpr int kSpecBit = 0x40000000;" in src
     assert b"a dielectric table needs a scene of fewer than 2^29 triangles" in open(capi.LIB_PATH, "rb").read()
+    # the limit is the dielectric row's max_tris (sp_host_tables.h), held to the bit when the library is compiled, and both forms of
+    # the one setter check it
+    rows = open(os.path.join(ROOT, "spath_amd", "csrc", "sp_host_tables.h")).read()
+    assert '(size_t)1 << 29, "a dielectric table needs a scene of fewer than 2^29 triangles (this one has %zu)"' in rows
     host = open(os.path.join(ROOT, "spath_amd", "csrc", "spath_hip.hip")).read()
-    assert host.count("c->n_tris >= (size_t)sp::kTransBit") == 2          # both forms of the setter
+    import re
+    assert re.search(r"static_assert\([^;]*kTriTables\[kTabDielectric\]\.max_tris == \(size_t\)sp::kTransBit", host)
+    assert host.count("c->n_tris >= t.max_tris") == 2                     # set_table and set_table_device
 
 
 @pytest.mark.parametrize("tables", ["none", "spec", "vn", "spec+vn"])

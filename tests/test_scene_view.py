@@ -60,3 +60,18 @@ def test_scene_file_roundtrip(tmp_path):
     scene.write_scene(p, t, m)
     t2, m2 = scene.read_scene(p)
     assert np.array_equal(t, t2) and np.array_equal(m, m2)
+
+
+def test_table_files_are_magic_count_rows(tmp_path):
+    """write_specular / write_vertex_normals / write_dielectric / write_roughness: u32 magic ('SPSP', 'SPVN', 'SPDI', 'SPRG' read as a
+    little-endian word), u32 n, then the n rows as little-endian f32, nothing else.  The expected bytes are packed here, value by value."""
+    import struct
+    for write, magic, width in ((scene.write_specular, b"SPSP", 4), (scene.write_vertex_normals, b"SPVN", 9),
+                                (scene.write_dielectric, b"SPDI", 4), (scene.write_roughness, b"SPRG", 1)):
+        rows = [[0.125 * (3 * i + k) - 1.0 for k in range(width)] for i in range(5)]
+        want = magic + struct.pack("<I", 5) + b"".join(struct.pack("<f", x) for row in rows for x in row)
+        path = str(tmp_path / "table.bin")
+        write(path, np.asarray(rows, np.float64))                       # any dtype and any shape with n * width values
+        assert open(path, "rb").read() == want, write.__name__
+        write(path, np.asarray(rows, np.float32).reshape(-1))
+        assert open(path, "rb").read() == want, write.__name__
