@@ -85,6 +85,9 @@ enum {
 	SPHIP_FLAG_TEXTURE = 0x4000000,  /* OPT-IN textures: the diffuse reflectance of a hit scaled by the bilinear sample of the context's atlas
 	                                   (sphip_set_texture) at the hit's interpolated UV (sphip_set_uv) for SPHIP_MODE_PT; see "textures"
 	                                   below.  Without the flag both are ignored. */
+	SPHIP_FLAG_NORMAL_MAP = 0x8000000, /* OPT-IN normal mapping: the shading normal of a hit replaced by the tangent-space normal of the
+	                                   context's normal map (sphip_set_normal_map) at the hit's interpolated UV (sphip_set_uv) for
+	                                   SPHIP_MODE_PT; see "normal mapping" below.  Without the flag the map is ignored. */
 	SPHIP_FLAG_ENVIRONMENT = 0x1000000 /* OPT-IN environment lighting by the context's octahedral radiance map (sphip_set_environment) for
 	                                   SPHIP_MODE_PT: a ray that leaves the scene carries the map's radiance, and NEE|MIS samples the map;
 	                                   see "environment lighting" below.  Without the flag the map is ignored.  (Bits 16..23 are the
@@ -782,6 +785,60 @@ int sphip_set_uv(sphip_t* ctx, const float* uv);
 /* The same from a device pointer, by the rules of sphip_set_specular_device.  It does NOT validate the values: a hit whose
  * interpolated UV is not finite is untextured (never out-of-bounds accesses). */
 int sphip_set_uv_device(sphip_t* ctx, const void* d_uv, void* stream);
+
+/* ---- normal mapping (SPHIP_FLAG_NORMAL_MAP): one normal map on the context, nw x nh RGB texels, f32, laid out like the
+ * atlas: texel (i, j) at texels[(j * nw + i) * 3], row 0 at t = 0.  A texel holds a tangent-space vector (x, y, z) as signed floats (NOT
+ * the 0..1 encoding of image files: decoding is the host's job), x along increasing s, y along increasing t, z along the surface normal.
+ * The map is addressed by the scene's UV table (sphip_set_uv) and sampled as the atlas is, with the wrap, texel and lerp steps of
+ * "textures" unchanged.  With the flag every hit of a path replaces its shading normal ns by the map's normal in the hit's tangent frame,
+ * and is from there on a smooth hit (sm = true) in every rule of "smooth shading": the diffuse, mirror, glossy and glass bounces, the
+ * light sample's cosine and its guard against the stored normal, and the ending rules all read ns and sm as they do under
+ * SPHIP_FLAG_SMOOTH.  Emitters keep their stored normal; scans_executed is unchanged: a map traces nothing.
+ *
+ * Valid for SPHIP_MODE_PT with the plain estimator and with SPHIP_FLAG_NEE | SPHIP_FLAG_MIS, with variants 1, 8 (SPHIP_FLAG_ACCEL) and 16
+ * in both workgroup shapes, with every material and lighting flag (SPHIP_FLAG_SPECULAR, SPHIP_FLAG_GLOSSY, SPHIP_FLAG_DIELECTRIC,
+ * SPHIP_FLAG_ENVIRONMENT, SPHIP_FLAG_SMOOTH, SPHIP_FLAG_TEXTURE) and SPHIP_FLAG_CAMERA_SAMPLES on or off, with progressive and adaptive
+ * accumulation and denoising, sample chunks, primary-hit reuse, shards and multi-device contexts.  SPHIP_E_INVALID: with SPHIP_MODE_FLAT;
+ * with SPHIP_FLAG_NEE alone; with variants 2, 15 or a retired one.  SPHIP_E_STATE: the flag without a UV table (checked first), or
+ * without a normal map.  Hit queries ignore the flag.
+ *
+ * The step runs at a hit on triangle i by ray (o, dir), after smooth shading's.  n: the stored normal turned against dir; ns, sm: what
+ * smooth shading left (n, false on a flat triangle or without SPHIP_FLAG_SMOOTH); s0 t0 s1 t1 s2 t2: the triangle's UV row.  f32, every
+ * operation rounded on its own, nothing fused; dot3 and cross3 as above:
+ *   bary:    u, v exactly as smooth shading and textures compute them;  w = (1.0f - u) - v
+ *            s = (s0 * w + s1 * u) + s2 * v;  t likewise                                         (textures' interp)
+ *   texel:   m = the bilinear sample of the map at (s, t)                                        (wrap, texel, lerp of "textures")
+ *   frame:   e1 = v1 - v0;  e2 = v2 - v0
+ *            ds1 = s1 - s0;  ds2 = s2 - s0;  dt1 = t1 - t0;  dt2 = t2 - t0
+ *            det = ds1 * dt2 - ds2 * dt1;  sg = det < 0 ? -1.0f : 1.0f
+ *            T = (e1 * dt2 - e2 * dt1) * sg;  B = (e2 * ds1 - e1 * ds2) * sg                     (per component)
+ *            Tp = T - ns * dot3(ns, T);  lt = dot3(Tp, Tp);  Tn = Tp / sqrtf(lt)                 (per component, IEEE)
+ *            C = cross3(ns, Tn);  h = dot3(C, B) < 0 ? -1.0f : 1.0f;  Bn = C * h
+ *   normal:  p = (Tn * m.x + Bn * m.y) + ns * m.z;  lp = dot3(p, p);  np = p / sqrtf(lp)
+ * The hit is perturbed (ns = np, sm = true) iff all of these hold: the UV row is not all zero and s, t are finite (textures' rule);
+ * det > 0 || det < 0;  lt > 0 and finite;  not (m.x == 0 && m.y == 0);  m.z > 0;  lp > 0 and finite;  dot3(np, n) > 0;
+ * dot3(dir, np) < 0.  Otherwise ns and sm stay what smooth shading left, and the hit is in every respect what it is without the flag.
+ *   - A map of (0, 0, 1) everywhere, or a row of zero UVs, is "no flag" bit for bit.
+ *   - The last two guards fall back to the unmapped normal; they do not end the path, so a steep texel seen at a grazing angle gives no
+ *     black fringe.
+ *   - On a back-face hit ns already points to the ray's side: the bump keeps its x, y and inverts its depth.
+ * Both estimators keep one expectation by smooth shading's argument: ns is a function of the hit and the incoming ray, identical in
+ * the plain and the NEE|MIS path.
+ * G-buffer: with the flag sphip_gbuffer_device and sphip_accum_gbuffer store the perturbed ns of the primary ray where they store ns or n
+ * without it; dist, albedo and mat are unchanged.
+ * sphip_selftest_device what 13 (nmap_normal): in f32[30 n] = pos dir v0 v1 v2 n0 n1 n2 uv0 uv1 uv2, out f32[6 n] = s, t, ns.xyz,
+ * perturbed (0/1), against the context's map (SPHIP_E_STATE without one); the stored normal is the flat normal of the vertices, as in
+ * what 7. */
+
+/* The context's normal map: nw x nh x 3 f32 on the host (NULL clears it), by the rules of sphip_set_texture: blocking; accepted by
+ * multi-device contexts (every device keeps the map); kept across set_scene and needs no scene; during an accumulation it ends the
+ * accumulation as a set_scene does.  SPHIP_E_INVALID when nw or nh is 0 or above 4096, or a value is not finite (negative values are
+ * legal; the message names the first such texel; the map stays as it was). */
+int sphip_set_normal_map(sphip_t* ctx, const float* texels, uint32_t nw, uint32_t nh);
+/* The same from a device pointer, by the rules of sphip_set_texture_device: single-device contexts (SPHIP_E_STATE otherwise), ordered by
+ * `stream` alone, and copied.  It does NOT validate the values: texels that break the rule above give undefined images (never
+ * out-of-bounds accesses). */
+int sphip_set_normal_map_device(sphip_t* ctx, const void* d_texels, uint32_t nw, uint32_t nh, void* stream);
 
 /* Blocks until the last render on this context has finished, then reports its figures. */
 int sphip_get_stats(sphip_t* ctx, sphip_stats* out);

@@ -25,6 +25,7 @@ FLAG_DIELECTRIC = 0x8000    # transparency: glass triangles from the context's d
 FLAG_ENVIRONMENT = 0x1000000  # environment lighting by the context's octahedral map
 FLAG_GLOSSY = 0x2000000     # with FLAG_SPECULAR: the mirror lobe roughened by the context's roughness table
 FLAG_TEXTURE = 0x4000000    # textures: the diffuse reflectance scaled by the context's atlas at the hit's UV
+FLAG_NORMAL_MAP = 0x8000000  # normal mapping: the shading normal from the context's normal map at the hit's UV
 
 
 def flag_chunks(n: int) -> int:
@@ -51,6 +52,7 @@ SYMBOLS = (
     "sphip_set_environment", "sphip_set_environment_device", "sphip_selftest_env_dump",
     "sphip_set_roughness", "sphip_set_roughness_device",
     "sphip_set_texture", "sphip_set_texture_device", "sphip_set_uv", "sphip_set_uv_device",
+    "sphip_set_normal_map", "sphip_set_normal_map_device",
 )
 GATHER_NONE, GATHER_RCCL, GATHER_PEER = 0, 1, 2
 # the per-triangle tables of a scene: (the X of sphip_set_X and sphip_set_X_device, floats per triangle, the ValueError of a table
@@ -229,6 +231,10 @@ def load():
     L.sphip_set_texture.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.sphip_set_texture_device.restype = C.c_int
     L.sphip_set_texture_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
+    L.sphip_set_normal_map.restype = C.c_int
+    L.sphip_set_normal_map.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.sphip_set_normal_map_device.restype = C.c_int
+    L.sphip_set_normal_map_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
     L.sphip_set_environment.restype = C.c_int
     L.sphip_set_environment.argtypes = [vp, vp, C.c_uint32]
     L.sphip_set_environment_device.restype = C.c_int
@@ -456,6 +462,22 @@ class Context:
         """sphip_set_uv_device: the table from a device pointer (n_tris * 6 f32, copied in stream order, NOT validated)."""
         self._set_table_device("uv", d_uv, stream)
 
+    def set_normal_map(self, texels):
+        """sphip_set_normal_map: the normal map of FLAG_NORMAL_MAP renders, (nh, nw, 3) f32 with texel (i, j) at [j, i], each a signed
+        tangent-space vector (scene.normal_map_from_height and scene.decode_normal_map build one); None clears it.  set_scene keeps it."""
+        import numpy as np
+        if texels is None:
+            self._check(self._L.sphip_set_normal_map(self._h, None, 0, 0), "sphip_set_normal_map")
+            return
+        texels = np.ascontiguousarray(texels, dtype=np.float32)
+        if texels.ndim != 3 or texels.shape[2] != 3:
+            raise ValueError("a normal map is (nh, nw, 3)")
+        self._check(self._L.sphip_set_normal_map(self._h, texels.ctypes.data, texels.shape[1], texels.shape[0]), "sphip_set_normal_map")
+
+    def set_normal_map_device(self, d_texels: int, nw: int, nh: int, stream: int = 0):
+        """sphip_set_normal_map_device: the map from a device pointer (nw * nh * 3 f32, copied in stream order, NOT validated)."""
+        self._check(self._L.sphip_set_normal_map_device(self._h, d_texels or None, nw, nh, stream or None), "sphip_set_normal_map_device")
+
     def set_texture_device(self, d_texels: int, tw: int, th: int, stream: int = 0):
         """sphip_set_texture_device: the atlas from a device pointer (tw * th * 3 f32, copied in stream order, NOT validated)."""
         self._check(self._L.sphip_set_texture_device(self._h, d_texels or None, tw, th, stream or None), "sphip_set_texture_device")
@@ -599,7 +621,8 @@ class Context:
         return (out, rgb) if want_rgb else out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
-                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8), 12: ("float32", 6)}
+                    7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8), 12: ("float32", 6),
+                    13: ("float32", 6)}
 
     def selftest(self, what: int, inp, n: int):
         """sphip_selftest_device (test-only): one device function of the path on n caller-supplied inputs."""

@@ -168,6 +168,8 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;       // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
 	constexpr bool tex = IsTex<Acc...>::value;         // textures (sp_integrator.h TexArgs, in GlossArgs' place): the hit's albedo per depth in hA
+	constexpr bool nmp = IsNmap<Acc...>::value;        // normal mapping (sp_integrator.h NmapArgs, in TexArgs' place, always with NormArgs): ns from the map
+	static_assert(!nmp || smo, "a normal-mapped pack carries NormArgs (DESIGN.md section 5.16)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -211,6 +213,7 @@ __global__ void __launch_bounds__(256) k_accel(const KArgs a, const BvhArgs B, c
 					f3 ns = n;                                    // the shading normal
 					bool sm = false, ended = false;               // smooth shading: a bounce below the surface ends the path
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
+					if constexpr (nmp) nmap_hit(a, nmap_args(acc_args...), bi, o, dir, n, ns, sm);
 					if constexpr (tex) hA[depth] = tex_hit(a, tex_args(acc_args...), bi, o, dir);
 					bool sl = false;                              // specular: this hit takes the mirror lobe
 					float pm = 0.0f;

@@ -32,6 +32,11 @@ SP_DEV void gbuffer_entry(const float* __restrict__ rays, const int* __restrict_
 			const f3 o = mk3(rays[(size_t)p * 6], rays[(size_t)p * 6 + 1], rays[(size_t)p * 6 + 2]);
 			const f3 ng = nn;
 			(void)shade_normal(tris + (size_t)i * 12, norm_table(norm...) + (size_t)i * 9, o, dir, ng, nn);
+			if constexpr (IsNmap<Norm...>::value) {                    // normal mapping: NormArgs, NmapArgs (k_gbuffer_nmap)
+				const NmapArgs& x = pack_get<NmapArgs>(norm...);
+				const float4 r = nmap_normal(tris + (size_t)i * 12, x.uv + (size_t)i * 6, x.nmap, x.nw, x.nh, o, dir, ng, nn);
+				nn = mk3(r.x, r.y, r.z);
+			}
 		}
 		const float* m = mats + (size_t)i * 6;
 		g0 = make_float4(nn.x, nn.y, nn.z, dist[p]);
@@ -49,6 +54,12 @@ __global__ void __launch_bounds__(256) k_gbuffer_smooth(const float* __restrict_
                                                         const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
                                                         uint32_t n, float4* __restrict__ out, const NormArgs norm) {
 	gbuffer_entry(rays, idx, dist, tris, mats, cls, n, out, norm);
+}
+// normal mapping: the perturbed shading normal of the primary ray; norm's table is the scene's vertex normals or zeros
+__global__ void __launch_bounds__(256) k_gbuffer_nmap(const float* __restrict__ rays, const int* __restrict__ idx, const float* __restrict__ dist,
+                                                      const float* __restrict__ tris, const float* __restrict__ mats, const int* __restrict__ cls,
+                                                      uint32_t n, float4* __restrict__ out, const NormArgs norm, const NmapArgs nmap) {
+	gbuffer_entry(rays, idx, dist, tris, mats, cls, n, out, norm, nmap);
 }
 
 SP_DEV void dn_emit(uint32_t p, float r, float g, float b, uint32_t* __restrict__ rgba, float* __restrict__ rgb) {

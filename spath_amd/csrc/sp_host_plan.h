@@ -14,7 +14,7 @@ namespace sp_host {
 // scan = the scan (2 = f32 cylinder filter, sp_cyl_scan.h; 3 = stage 1 on the f16 matrix pipe, sp_cylm_scan.h; 4 = its 512-thread shape)
 struct TwoStage { int R; bool split; int scan; };
 // what a checked render does (check_render): later steps read these, never `flags`.  Every bit but adapt and prog is set in path tracing only
-struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog, gloss, tex; };
+struct Features { bool nee, mis, spec, glass, env, smooth, cam, adapt, prog, gloss, tex, nmap; };
 constexpr uint64_t kChunkTargetBlocks = 262144;         // 256 x the 1024 resident workgroups (measured: profiles/r01_sample_chunks.log)
 constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sample scratch buffer
 
@@ -26,8 +26,8 @@ constexpr uint64_t kChunkMaxBytes = 16ull << 30;         // cap of the per-sampl
 constexpr size_t kSlotHist = 40, kSlotAcc = 12, kSlotNeeL = 48, kSlotMisD = 60, kSlotAdaptWst = 16, kSlotEnvM = 12, kSlotTexA = 60;
 struct SlotBytes { size_t work, adp_wst, env_M, tex_A; };
 constexpr SlotBytes slot_bytes(const Features& f) {
-	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env || f.gloss || f.tex ? kSlotEnvM : 0,
-	         f.tex ? kSlotTexA : 0 };
+	return { kSlotHist + kSlotAcc + (f.mis ? kSlotMisD : f.nee ? kSlotNeeL : 0), f.adapt ? kSlotAdaptWst : 0, f.env || f.gloss || f.tex || f.nmap ? kSlotEnvM : 0,
+	         f.tex || f.nmap ? kSlotTexA : 0 };     // a normal-mapped render's kernels are textured ones (NmapArgs is a TexArgs)
 }
 
 struct LaunchPlan {

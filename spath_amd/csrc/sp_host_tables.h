@@ -1,5 +1,5 @@
 // The per-triangle scene tables of libspath_hip.so as data, and the checks of what a host-pointer setter is handed: rows of a table,
-// texels of a context-level image (the environment map, the atlas).  No HIP, like sp_host_plan.h: a host compiler builds this header
+// texels of a context-level image (the environment map, the atlas, the normal map).  No HIP, like sp_host_plan.h: a host compiler builds this header
 // alone, and tests/test_host_tables.py holds every rule and every message to literals.  spath_hip.hip is its one user; its generic
 // setters (set_table, set_table_device) walk kTriTables, so a new table is one row here, where it lives in a context (kTableSlots
 // there) and a pair of one-line entry points.
@@ -70,6 +70,18 @@ inline size_t first_bad_texel(const float* texels, size_t count) {
 inline std::string bad_texel_message(const char* noun, const float* texels, size_t k, size_t width) {
 	char buf[512];
 	snprintf(buf, sizeof buf, "%s: texel (%zu, %zu) has component %zu = %g (every value finite and >= 0)", noun, (k / 3) % width, (k / 3) / width, k % 3,
+	         (double)texels[k]);
+	return buf;
+}
+
+// ... of an image whose values are signed (the normal map): the first float that is not finite, or count
+inline size_t first_nonfinite_texel(const float* texels, size_t count) {
+	for (size_t k = 0; k < count; ++k) if (!std::isfinite(texels[k])) return k;
+	return count;
+}
+inline std::string nonfinite_texel_message(const char* noun, const float* texels, size_t k, size_t width) {
+	char buf[512];
+	snprintf(buf, sizeof buf, "%s: texel (%zu, %zu) has component %zu = %g (every value finite)", noun, (k / 3) % width, (k / 3) / width, k % 3,
 	         (double)texels[k]);
 	return buf;
 }

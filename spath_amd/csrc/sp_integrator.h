@@ -176,6 +176,17 @@ struct TexArgs : GlossArgs {
 };
 constexpr uint32_t kTexMaxN = 4096;
 
+// normal mapping (SPHIP_FLAG_NORMAL_MAP, include/spath_hip.h): the context's normal map, nw x nh RGB texels holding a
+// tangent-space vector (x, y, z) as signed floats, texel (i, j) at (j * nw + i) * 3, addressed by the UV table of TexArgs.  It rides IN
+// TexArgs' PLACE (as TexArgs rides in GlossArgs'), and ALWAYS with a NormArgs behind it: k_pt<V, MisArgs, NmapArgs, NormArgs, CamArgs>, ...
+// Without SPHIP_FLAG_TEXTURE the atlas is the context's 1 x 1 white texel (rho * 1.0f = rho), without SPHIP_FLAG_SMOOTH the vertex normals
+// are a table of zeros (every triangle flat); the other tables as in TexArgs.  Each hit's shading normal is replaced by the map's normal
+// in the hit's tangent frame (nmap_normal), and the hit is then a smooth one in every rule.  Nothing is parked per depth
+struct NmapArgs : TexArgs {
+	const float* nmap;         // nw * nh * 3
+	uint32_t nw, nh;
+};
+
 // smooth shading (SPHIP_FLAG_SMOOTH, include/spath_hip.h): the scene's vertex normals, 9 floats per triangle:
 // n0.xyz n1.xyz n2.xyz for v0 v1 v2.  It rides after the specular table, before the camera: k_pt<V, MisArgs, SpecArgs, NormArgs,
 // CamArgs>, ...  Every hit shades with the interpolated normal of shade_normal; a row of zeros leaves its triangle flat.
@@ -189,7 +200,8 @@ template <typename... Acc> struct IsAdapt { static constexpr bool value = PackHa
 template <typename... Acc> struct IsMis { static constexpr bool value = PackHas<MisArgs, Acc...>::value; };
 template <typename... Acc> struct IsNee { static constexpr bool value = PackHas<NeeArgs, Acc...>::value || IsMis<Acc...>::value; };
 template <typename... Acc> struct IsCam { static constexpr bool value = PackHas<CamArgs, Acc...>::value; };
-template <typename... Acc> struct IsTex { static constexpr bool value = PackHas<TexArgs, Acc...>::value; };
+template <typename... Acc> struct IsNmap { static constexpr bool value = PackHas<NmapArgs, Acc...>::value; };
+template <typename... Acc> struct IsTex { static constexpr bool value = PackHas<TexArgs, Acc...>::value || IsNmap<Acc...>::value; };
 template <typename... Acc> struct IsGloss { static constexpr bool value = PackHas<GlossArgs, Acc...>::value || IsTex<Acc...>::value; };
 template <typename... Acc> struct IsEnv { static constexpr bool value = PackHas<EnvArgs, Acc...>::value || IsGloss<Acc...>::value; };
 template <typename... Acc> struct IsGlass { static constexpr bool value = PackHas<GlassArgs, Acc...>::value || IsEnv<Acc...>::value; };
@@ -219,6 +231,7 @@ template <typename... P> SP_DEV const EnvMap* env_map(const P&... p) {
 }
 template <typename... P> SP_DEV const float* rough_table(const P&... p) { return pack_get<GlossArgs>(p...).rough; }
 template <typename... P> SP_DEV const TexArgs& tex_args(const P&... p) { return pack_get<TexArgs>(p...); }
+template <typename... P> SP_DEV const NmapArgs& nmap_args(const P&... p) { return pack_get<NmapArgs>(p...); }
 template <typename... P> SP_DEV const float* norm_table(const P&... p) { return pack_get<NormArgs>(p...).vnorm; }
 template <typename... P> SP_DEV const float* mis_tipdf(const P&... p) { return pack_get<MisArgs>(p...).tipdf; }
 // local pixel of launch ray k (k < n_rays): k itself, or the active list's entry
@@ -654,6 +667,52 @@ __device__ __attribute__((noinline)) f3 tex_albedo(const float* __restrict__ tv,
 // ... for hit triangle bi of a path kernel
 SP_DEV f3 tex_hit(const KArgs& a, const TexArgs& x, int bi, f3 o, f3 dir) {
 	return tex_albedo(a.tris + (size_t)bi * 12, x.uv + (size_t)bi * 6, a.mats + (size_t)bi * 6, x.atlas, x.tw, x.th, o, dir);
+}
+
+// ---- normal mapping (include/spath_hip.h "normal mapping").  f32, every operation rounded on its own.
+// The shading normal of the hit of ray (o, dir) on the triangle whose vertices are tv[0..8] and whose UV row is uvr[0..5]; n is the stored
+// normal turned against dir, ns what shade_normal left.
+//   bary, s, t, texel:  tex_lookup on the map: m = the bilinear sample at the hit's (s, t)
+//   frame:   e1 = v1 - v0;  e2 = v2 - v0;  ds1 = s1 - s0;  ds2 = s2 - s0;  dt1 = t1 - t0;  dt2 = t2 - t0
+//            det = ds1 dt2 - ds2 dt1;  sg = det < 0 ? -1 : 1;  T = (e1 dt2 - e2 dt1) sg;  B = (e2 ds1 - e1 ds2) sg
+//            Tp = T - ns dot3(ns, T);  lt = dot3(Tp, Tp);  Tn = Tp / sqrtf(lt);  C = cross3(ns, Tn);  h = dot3(C, B) < 0 ? -1 : 1;  Bn = C h
+//   normal:  p = (Tn m.x + Bn m.y) + ns m.z;  lp = dot3(p, p);  np = p / sqrtf(lp)
+// Returns {np, 1} where the hit is perturbed: a textured row, det != 0, lt and lp > 0 and finite, m not (0, 0, z), m.z > 0, np on n's
+// side and against dir; {ns, 0} otherwise.  Called once per hit, after shade_normal.  NOT inlined, on purpose, as tex_albedo is not
+__device__ __attribute__((noinline)) float4 nmap_normal(const float* __restrict__ tv, const float* __restrict__ uvr, const float* __restrict__ nmap,
+                                                        uint32_t nw, uint32_t nh, f3 o, f3 dir, f3 n, f3 ns) {
+	float s, t;
+	f3 m;
+	const float4 keep = make_float4(ns.x, ns.y, ns.z, 0.0f);
+	if (!tex_lookup(tv, uvr, nmap, nw, nh, o, dir, s, t, m)) return keep;
+	const f3 v0 = mk3(tv[0], tv[1], tv[2]);
+	const f3 e1 = sub3(mk3(tv[3], tv[4], tv[5]), v0), e2 = sub3(mk3(tv[6], tv[7], tv[8]), v0);
+	const float ds1 = uvr[2] - uvr[0], ds2 = uvr[4] - uvr[0], dt1 = uvr[3] - uvr[1], dt2 = uvr[5] - uvr[1];
+	const float det = ds1 * dt2 - ds2 * dt1;
+	if (!(det > 0.0f || det < 0.0f)) return keep;
+	if ((m.x == 0.0f && m.y == 0.0f) || !(m.z > 0.0f)) return keep;
+	const float sg = det < 0.0f ? -1.0f : 1.0f;
+	const f3 T = scale3(sub3(scale3(e1, dt2), scale3(e2, dt1)), sg), B = scale3(sub3(scale3(e2, ds1), scale3(e1, ds2)), sg);
+	const f3 Tp = sub3(T, scale3(ns, dot3(ns, T)));
+	const float lt = dot3(Tp, Tp);
+	if (!(lt > 0.0f && lt < __builtin_inff())) return keep;
+	const float l = __builtin_sqrtf(lt);
+	const f3 Tn = mk3(Tp.x / l, Tp.y / l, Tp.z / l);
+	const f3 C = cross3(ns, Tn);
+	const f3 Bn = scale3(C, dot3(C, B) < 0.0f ? -1.0f : 1.0f);
+	const f3 p = add3(add3(scale3(Tn, m.x), scale3(Bn, m.y)), scale3(ns, m.z));
+	const float lp = dot3(p, p);
+	if (!(lp > 0.0f && lp < __builtin_inff())) return keep;
+	const float q = __builtin_sqrtf(lp);
+	const f3 np = mk3(p.x / q, p.y / q, p.z / q);
+	if (!(dot3(np, n) > 0.0f) || !(dot3(dir, np) < 0.0f)) return keep;
+	return make_float4(np.x, np.y, np.z, 1.0f);
+}
+// ... for hit triangle bi of a path kernel: ns and sm as shade_normal left them become the hit's
+SP_DEV void nmap_hit(const KArgs& a, const NmapArgs& x, int bi, f3 o, f3 dir, f3 n, f3& ns, bool& sm) {
+	const float4 r = nmap_normal(a.tris + (size_t)bi * 12, x.uv + (size_t)bi * 6, x.nmap, x.nw, x.nh, o, dir, n, ns);
+	ns = mk3(r.x, r.y, r.z);
+	sm = sm || r.w != 0.0f;
 }
 
 // ---- what the kernels share around the integrator: each is used where the kernel keeps its instructions with it (DESIGN.md

@@ -234,6 +234,25 @@ __global__ void __launch_bounds__(256) k_selftest_tex(const float* __restrict__ 
 	w[0] = s; w[1] = t; w[2] = c.x; w[3] = c.y; w[4] = c.z; w[5] = tx ? 1.0f : 0.0f;
 }
 
+// what 13: nmap_normal after shade_normal.  pos dir v0 v1 v2 n0 n1 n2 uv0 uv1 uv2 -> s t ns.xyz perturbed; the stored normal as in what 7
+__global__ void __launch_bounds__(256) k_selftest_nmap(const float* __restrict__ in, uint32_t n, const float* __restrict__ nmap, uint32_t nw, uint32_t nh, float* __restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i >= n) return;
+	const float* q = in + 30 * (size_t)i;
+	const f3 o = mk3(q[0], q[1], q[2]), dir = mk3(q[3], q[4], q[5]), v0 = mk3(q[6], q[7], q[8]);
+	const f3 c = cross3(sub3(mk3(q[9], q[10], q[11]), v0), sub3(mk3(q[12], q[13], q[14]), v0));
+	const float l = __builtin_sqrtf(dot3(c, c));
+	f3 nn = mk3(c.x / l, c.y / l, c.z / l);
+	if (dot3(nn, dir) > 0.0f) nn = scale3(nn, -1.0f);
+	f3 ns, m;
+	float s, t;
+	(void)shade_normal(q + 6, q + 15, o, dir, nn, ns);
+	(void)tex_lookup(q + 6, q + 24, nmap, nw, nh, o, dir, s, t, m);
+	const float4 r = nmap_normal(q + 6, q + 24, nmap, nw, nh, o, dir, nn, ns);
+	float* w = out + 6 * (size_t)i;
+	w[0] = s; w[1] = t; w[2] = r.x; w[3] = r.y; w[4] = r.z; w[5] = r.w;
+}
+
 SP_DEV uint64_t shard_pixel(const KArgs& a, uint32_t k) {
 	const uint64_t t = (uint64_t)k / a.tile_px;
 	return a.pixel_base + t * a.tile_stride_px + ((uint64_t)k - t * a.tile_px);
@@ -378,6 +397,8 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;                 // glossy reflection (GlossArgs, in EnvArgs' place): the weight g in the mirror hit's cosine slot
 	constexpr bool tex = IsTex<Acc...>::value;                   // textures (TexArgs, in GlossArgs' place): the hit's albedo per depth in A0..A4
+	constexpr bool nmp = IsNmap<Acc...>::value;                  // normal mapping (NmapArgs, in TexArgs' place, always with NormArgs): ns from the map
+	static_assert(!nmp || smo, "a normal-mapped pack carries NormArgs (DESIGN.md section 5.16)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	const uint32_t pk = adapt ? local_px(kk, acc_args...) : kk;   // where the pixel's running sums live (valid rays)
 	const uint32_t pixel = (uint32_t)shard_pixel(a, pk);
@@ -435,6 +456,7 @@ __global__ void __launch_bounds__(256) k_pt(const KArgs a, const Acc... acc_args
 				f3 ns = n;                                        // the shading normal
 				bool sm = false;
 				if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi * 12, norm_table(acc_args...) + (size_t)bi * 9, o, dir, n, ns);
+				if constexpr (nmp) nmap_hit(a, nmap_args(acc_args...), bi, o, dir, n, ns, sm);
 				[[maybe_unused]] f3 alb;                          // textures: the hit's albedo
 				if constexpr (tex) {
 					alb = tex_hit(a, tex_args(acc_args...), bi, o, dir);

@@ -123,6 +123,8 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 	static_assert(!env || mis || !nee, "environment lighting: plain or NEE|MIS (DESIGN.md section 5.11)");
 	constexpr bool glo = IsGloss<Acc...>::value;             // glossy reflection (sp_integrator.h GlossArgs, in EnvArgs' place)
 	constexpr bool tex = IsTex<Acc...>::value;               // textures (sp_integrator.h TexArgs, in GlossArgs' place): the hit's albedo parked in TexArgs::A
+	constexpr bool nmp = IsNmap<Acc...>::value;              // normal mapping (sp_integrator.h NmapArgs, in TexArgs' place, always with NormArgs): ns from the map
+	static_assert(!nmp || smo, "a normal-mapped pack carries NormArgs (DESIGN.md section 5.16)");
 	constexpr int hmask = HistMask<Acc...>::value;
 	uint32_t pixel[R];
 #pragma unroll
@@ -230,6 +232,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 						if (dot3(n, s.dir[r]) > 0.0f) n = scale3(n, -1.0f);
 						f3 ns = n;                                 // the shading normal
 						if constexpr (smo) smr[r] = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
+						if constexpr (nmp) nmap_hit(a, nmap_args(acc_args...), bi[r], s.o[r], s.dir[r], n, ns, smr[r]);
 						nadj[r] = ns;
 						[[maybe_unused]] f3 alb;                   // textures: the hit's albedo, parked for the unwind
 						if constexpr (tex) {
@@ -356,6 +359,7 @@ __global__ void __launch_bounds__(scan_block<SCAN>(), SP_PT_WAVES) k_pt_filter(c
 					f3 ns = n;                                   // the shading normal
 					bool sm = false;
 					if constexpr (smo) sm = shade_normal(a.tris + (size_t)bi[r] * 12, norm_table(acc_args...) + (size_t)bi[r] * 9, s.o[r], s.dir[r], n, ns);
+					if constexpr (nmp) nmap_hit(a, nmap_args(acc_args...), bi[r], s.o[r], s.dir[r], n, ns, sm);
 					if constexpr (tex) {                         // the hit's albedo, parked for the unwind
 						const f3 alb = tex_hit(a, tex_args(acc_args...), bi[r], s.o[r], s.dir[r]);
 						float* Ap = tex_args(acc_args...).A + (size_t)depth * 3 * n_work + k0 + r * B;

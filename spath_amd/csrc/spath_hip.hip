@@ -143,6 +143,13 @@ struct sphip_ctx {
 	DevBuf atlas, tex_A;
 	bool have_tex = false;
 	uint32_t tex_w = 0, tex_h = 0;
+	// ---- normal mapping (SPHIP_FLAG_NORMAL_MAP): the map nmap_w x nmap_h x 3 f32 (signed tangent-space vectors), kept like the atlas.  What
+	// stands in when SPHIP_FLAG_SMOOTH or SPHIP_FLAG_TEXTURE is off: vnorm_zero, 9 floats of zeros for each of the scene's first
+	// vnorm_zero_rows triangles (every triangle flat), and tex_white, the 1 x 1 white atlas (rho * 1.0f = rho)
+	DevBuf nmap, vnorm_zero, tex_white;
+	bool have_nmap = false;
+	uint32_t nmap_w = 0, nmap_h = 0;
+	size_t vnorm_zero_rows = 0;
 };
 
 namespace {
@@ -495,6 +502,26 @@ int ensure_black_map(sphip_ctx* c, hipStream_t st) {
 	return SPHIP_OK;
 }
 
+// the stand-ins of a normal-mapped render (sphip_ctx): the zero vertex normals of the scene's triangles ...
+int ensure_zero_vnorm(sphip_ctx* c, hipStream_t st) {
+	if (c->vnorm_zero_rows == c->n_tris && c->vnorm_zero.p) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	if (const int rc = ensure(c, c->vnorm_zero, c->n_tris * 36)) return rc;
+	HIP_TRY(c, hipMemsetAsync(c->vnorm_zero.p, 0, c->n_tris * 36, st));
+	HIP_TRY(c, hipStreamSynchronize(st));          // later renders may come on another stream; once per scene
+	c->vnorm_zero_rows = c->n_tris;
+	return SPHIP_OK;
+}
+// ... and the 1 x 1 white atlas, written once per context
+int ensure_white_texel(sphip_ctx* c, hipStream_t st) {
+	if (c->tex_white.p) return SPHIP_OK;
+	static const float one[3] = { 1.0f, 1.0f, 1.0f };
+	if (const int rc = ensure(c, c->tex_white, 256)) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->tex_white.p, one, sizeof one, hipMemcpyHostToDevice, st));
+	HIP_TRY(c, hipStreamSynchronize(st));          // later renders may come on another stream
+	return SPHIP_OK;
+}
+
 constexpr int kModeHits = 2;   // internal: sphip_closest_hit_device
 
 // f(args...) with the trailing pack of a path-tracing kernel for the run-time choices, always in the kernels' order: the running
@@ -510,7 +537,7 @@ void with_accum(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, F&& f) {
 }
 template <typename F>
 void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::NeeArgs* ne, const sp::MisArgs* me, const sp::SpecArgs* spc,
-               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::GlossArgs* glo, const sp::TexArgs* tex, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
+               const sp::GlassArgs* gls, const sp::EnvArgs* env, const sp::GlossArgs* glo, const sp::TexArgs* tex, const sp::NmapArgs* nmp, const sp::NormArgs* nrm, const sp::CamArgs* cam, F&& f) {
 	with_accum(prog, ad, [&](const auto&... acc) {
 		auto est = [&](const auto&... e) {
 			constexpr bool tables = sizeof...(e) == 0 || sp::IsMis<std::decay_t<decltype(e)>...>::value;
@@ -519,9 +546,14 @@ void with_pack(const sp::AccumArgs* prog, const sp::AdaptArgs* ad, const sp::Nee
 					if (cam) f(acc..., e..., t..., u..., *cam);
 					else f(acc..., e..., t..., u...);
 				};
-				if constexpr (tables) { if (nrm) { last(*nrm); return; } }
-				last();
+				// a normal-mapped pack always carries vertex normals (the scene's or zeros): its packs without NormArgs are not built
+				if constexpr (sp::IsNmap<std::decay_t<decltype(t)>...>::value) last(*nrm);
+				else {
+					if constexpr (tables) { if (nrm) { last(*nrm); return; } }
+					last();
+				}
 			};
+			if constexpr (tables) { if (nmp) { tail(*nmp); return; } }      // the normal map carries the UV table, the atlas and all they carry
 			if constexpr (tables) { if (tex) { tail(*tex); return; } }      // the UV table and the atlas carry the roughness table and all it carries
 			if constexpr (tables) { if (glo) { tail(*glo); return; } }      // the roughness table carries the map and both tables
 			if constexpr (tables) { if (env) { tail(*env); return; } }      // the environment map carries the dielectric and the specular table
@@ -578,6 +610,9 @@ const TableRule kTableRules[] = {
 	// textures need two things, asked for in this order: the scene's UV table and the context's atlas
 	{ SPHIP_FLAG_TEXTURE, "SPHIP_FLAG_TEXTURE", variant_smooth, &sphip_ctx::have_uv, "a UV table (sphip_set_uv)" },
 	{ SPHIP_FLAG_TEXTURE, "SPHIP_FLAG_TEXTURE", variant_smooth, &sphip_ctx::have_tex, "an atlas (sphip_set_texture)" },
+	// normal mapping likewise: the scene's UV table, then the context's normal map
+	{ SPHIP_FLAG_NORMAL_MAP, "SPHIP_FLAG_NORMAL_MAP", variant_smooth, &sphip_ctx::have_uv, "a UV table (sphip_set_uv)" },
+	{ SPHIP_FLAG_NORMAL_MAP, "SPHIP_FLAG_NORMAL_MAP", variant_smooth, &sphip_ctx::have_nmap, "a normal map (sphip_set_normal_map)" },
 };
 int check_table_rule(sphip_ctx* c, const TableRule& r, int flags, int variant, int mode) {
 	if (mode == kModeHits || !(flags & r.bit)) return SPHIP_OK;
@@ -622,7 +657,7 @@ struct Launch {
 	sp::KArgs a{}; sp::ScanSrc src{}; sp::BvhArgs B{}; sp::AdaptArgs ad{}; sp::NormArgs nra{};
 	int2* hist = nullptr; float* acc = nullptr;   // the work buffer's path history and accumulator
 	sp::MisArgs est{};                       // the light table; handed on as NeeArgs or as MisArgs
-	sp::TexArgs tab{};                       // the per-triangle tables, the map and the atlas; handed on as SpecArgs, GlassArgs, EnvArgs, GlossArgs or TexArgs
+	sp::NmapArgs tab{};                      // the per-triangle tables, the map, the atlas and the normal map; handed on as SpecArgs, GlassArgs, EnvArgs, GlossArgs, TexArgs or NmapArgs
 };
 
 // ---- step 1, check: refuse what cannot be rendered and name what will be.  The order is behaviour (a call that is wrong twice hears of
@@ -656,16 +691,20 @@ int check_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	auto on = [&](int bit) { return pt && (flags & bit); };
 	const Features f = L.f = { on(SPHIP_FLAG_NEE), on(SPHIP_FLAG_MIS), on(SPHIP_FLAG_SPECULAR), on(SPHIP_FLAG_DIELECTRIC), on(SPHIP_FLAG_ENVIRONMENT),
 	                           on(SPHIP_FLAG_SMOOTH), on(SPHIP_FLAG_CAMERA_SAMPLES), r.adapt != nullptr, r.prog != nullptr, on(SPHIP_FLAG_GLOSSY),
-	                           on(SPHIP_FLAG_TEXTURE) };
+	                           on(SPHIP_FLAG_TEXTURE), on(SPHIP_FLAG_NORMAL_MAP) };
 	if (f.mis && !f.nee) return fail(c, SPHIP_E_INVALID, "SPHIP_FLAG_MIS needs SPHIP_FLAG_NEE");
 	if (f.nee && (rc = ensure_lights(c, r.st))) return rc;
 	if ((rc = check_feature_rules(c, flags, variant, mode, r.cam != nullptr))) return rc;
 	// environment lighting stands zeros in for either table whose flag is off; under NEE|MIS the estimator reads the flagged light table
 	// and so does glossy reflection for the dielectric table, and its black map for the environment; a textured render does both, and
 	// the zeros are its roughness table too when SPHIP_FLAG_GLOSSY is not set
-	if ((f.env || f.gloss || f.tex) && (!f.spec || !f.glass || (f.tex && !f.gloss)) && (rc = ensure_zero_rows(c, r.st))) return rc;
+	// a normal-mapped render is a textured one with these stand-ins, and its own: zero vertex normals and the white texel
+	const bool tx = f.tex || f.nmap;
+	if ((f.env || f.gloss || tx) && (!f.spec || !f.glass || (tx && !f.gloss)) && (rc = ensure_zero_rows(c, r.st))) return rc;
 	if (f.env && f.nee && (rc = ensure_env_lights(c, r.st))) return rc;
-	if ((f.gloss || f.tex) && !f.env && (rc = ensure_black_map(c, r.st))) return rc;
+	if ((f.gloss || tx) && !f.env && (rc = ensure_black_map(c, r.st))) return rc;
+	if (f.nmap && !f.smooth && (rc = ensure_zero_vnorm(c, r.st))) return rc;
+	if (f.nmap && !f.tex && (rc = ensure_white_texel(c, r.st))) return rc;
 	return SPHIP_OK;
 }
 
@@ -738,10 +777,12 @@ int bind_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	L.tab.spec = (const float4*)(f.spec ? c->spec.p : c->spec_zero.p);
 	L.tab.glass = (const float4*)(f.glass ? c->glass.p : c->spec_zero.p);
 	if (f.env) L.tab.env = sp::EnvMap{ (const float*)c->env_tex.p, (const double*)c->env_rc.p, (const double*)c->env_marg.p, (const float*)c->env_tpdf.p, c->env_T, c->env_n };
-	else if (f.gloss || f.tex) L.tab.env = sp::EnvMap{ (const float*)c->env_black.p, (const double*)c->env_black.p, (const double*)c->env_black.p, (const float*)c->env_black.p, 0.0, 1u };
+	else if (f.gloss || f.tex || f.nmap) L.tab.env = sp::EnvMap{ (const float*)c->env_black.p, (const double*)c->env_black.p, (const double*)c->env_black.p, (const float*)c->env_black.p, 0.0, 1u };
 	L.tab.rough = (const float*)(f.gloss ? c->rough.p : c->spec_zero.p);
 	L.tab.uv = (const float*)c->uv.p; L.tab.atlas = (const float*)c->atlas.p; L.tab.tw = c->tex_w; L.tab.th = c->tex_h;
-	L.nra.vnorm = (const float*)c->vnorm.p;
+	if (f.nmap && !f.tex) { L.tab.atlas = (const float*)c->tex_white.p; L.tab.tw = L.tab.th = 1u; }
+	L.tab.nmap = (const float*)c->nmap.p; L.tab.nw = c->nmap_w; L.tab.nh = c->nmap_h;
+	L.nra.vnorm = (const float*)(f.nmap && !f.smooth ? c->vnorm_zero.p : c->vnorm.p);
 	return SPHIP_OK;
 }
 
@@ -777,12 +818,13 @@ int dispatch_render(sphip_ctx* c, const RenderCall& r, Launch& L) {
 	}
 	// the pack's carriers: the estimator rides as NeeArgs or MisArgs, the tables as the base of EnvArgs that the flags reach
 	const sp::NeeArgs* ne = f.nee ? &L.est : nullptr;
-	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
-	const sp::GlassArgs* gls = f.glass && !f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
-	const sp::EnvArgs* env = f.env && !f.gloss && !f.tex ? &L.tab : nullptr;
-	const sp::GlossArgs* glo = f.gloss && !f.tex ? &L.tab : nullptr;
+	const bool tx = f.tex || f.nmap;
+	const sp::SpecArgs* spc = f.spec && !f.glass && !f.env && !f.gloss && !tx ? &L.tab : nullptr;
+	const sp::GlassArgs* gls = f.glass && !f.env && !f.gloss && !tx ? &L.tab : nullptr;
+	const sp::EnvArgs* env = f.env && !f.gloss && !tx ? &L.tab : nullptr;
+	const sp::GlossArgs* glo = f.gloss && !tx ? &L.tab : nullptr;
 	const sp::AdaptArgs* adp = f.adapt ? &L.ad : nullptr;
-	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, env, glo, f.tex ? &L.tab : nullptr, f.smooth ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
+	auto pt_pack = [&](auto&& fn) { with_pack(r.prog, adp, ne, f.mis ? &L.est : nullptr, spc, gls, env, glo, f.tex && !f.nmap ? &L.tab : nullptr, f.nmap ? &L.tab : nullptr, f.smooth || f.nmap ? &L.nra : nullptr, f.cam ? r.cam : nullptr, fn); };
 	// k_accel in mode M (0 flat, 1 path tracing, 2 hits); the exact-only kernels of variant 1 (rpl_sload) or 2 (rpl_lds)
 	auto accel = [&](auto mode_c, const int* src_idx, int* oi, float* od, const auto&... p) {
 		hipLaunchKernelGGL((sp::k_accel<decltype(mode_c)::value, std::decay_t<decltype(p)>...>), grid, block, 0, st, a, L.B, src_idx, oi, od, p...);
@@ -1452,12 +1494,22 @@ int gbuffer_dev(sphip_ctx* c, const void* d_rays, size_t n, int flags, void* d_o
 	if (n == 0 || n > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n_rays %zu out of range", n);
 	const bool smooth = (flags & SPHIP_FLAG_SMOOTH) != 0;  // the normals are the path's shading normals
 	if (smooth && !c->have_vnorm) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_SMOOTH needs vertex normals (sphip_set_vertex_normals)");
+	const bool nmap = (flags & SPHIP_FLAG_NORMAL_MAP) != 0;   // ... perturbed by the normal map
+	if (nmap && !c->have_uv) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_NORMAL_MAP needs a UV table (sphip_set_uv)");
+	if (nmap && !c->have_nmap) return fail(c, SPHIP_E_STATE, "SPHIP_FLAG_NORMAL_MAP needs a normal map (sphip_set_normal_map)");
 	int rc;
+	if (nmap && !smooth && (rc = ensure_zero_vnorm(c, st))) return rc;
 	if ((rc = ensure_classes(c, st)) || (rc = ensure(c, c->dn_hit, n * 8))) return rc;
 	int* idx = (int*)c->dn_hit.p;
 	float* dist = (float*)((char*)c->dn_hit.p + n * 4);
 	if ((rc = launch_render(c, RenderCall{ d_rays, n, 1, 0, kModeHits, flags, idx, dist, st }))) return rc;
-	if (smooth)
+	if (nmap) {
+		sp::NmapArgs x{};
+		x.uv = (const float*)c->uv.p; x.nmap = (const float*)c->nmap.p; x.nw = c->nmap_w; x.nh = c->nmap_h;
+		hipLaunchKernelGGL(sp::k_gbuffer_nmap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
+		                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out,
+		                   sp::NormArgs{ (const float*)(smooth ? c->vnorm.p : c->vnorm_zero.p) }, x);
+	} else if (smooth)
 		hipLaunchKernelGGL(sp::k_gbuffer_smooth, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)d_rays, (const int*)idx,
 		                   (const float*)dist, (const float*)c->tris.p, (const float*)c->mats.p, (const int*)c->dn_cls.p, (uint32_t)n, (float4*)d_out,
 		                   sp::NormArgs{ (const float*)c->vnorm.p });
@@ -1869,6 +1921,43 @@ int sphip_set_texture_device(sphip_t* c, const void* d_texels, uint32_t tw, uint
 	return bad ? fail(c, SPHIP_E_INVALID, "atlas: %u x %u texels (1 <= tw, th <= %u)", tw, th, sp::kTexMaxN) : rc;
 }
 
+// the normal map of a single-device context from src (nw * nh * 3 f32), or no map with src == nullptr; sync: src is borrowed host memory
+static int set_nmap(sphip_ctx* c, const void* src, uint32_t nw, uint32_t nh, hipMemcpyKind kind, hipStream_t st, bool sync) {
+	c->acc_stale = c->acc_on;                      // the running sum was rendered under the old map
+	c->have_nmap = false;
+	if (!src) return SPHIP_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	const size_t bytes = (size_t)nw * nh * 12;
+	if (const int rc = ensure(c, c->nmap, bytes)) return rc;
+	HIP_TRY(c, hipMemcpyAsync(c->nmap.p, src, bytes, kind, st));
+	if (sync) HIP_TRY(c, hipStreamSynchronize(st));
+	c->nmap_w = nw; c->nmap_h = nh;
+	c->have_nmap = true;
+	return SPHIP_OK;
+}
+
+int sphip_set_normal_map(sphip_t* c, const float* texels, uint32_t nw, uint32_t nh) {
+	if (!c) return SPHIP_E_INVALID;
+	if (texels) {
+		if (nw == 0 || nw > sp::kTexMaxN || nh == 0 || nh > sp::kTexMaxN)
+			return fail(c, SPHIP_E_INVALID, "normal map: %u x %u texels (1 <= nw, nh <= %u)", nw, nh, sp::kTexMaxN);
+		const size_t count = (size_t)nw * nh * 3, bad = first_nonfinite_texel(texels, count);    // negative values are legal here
+		if (bad < count) return fail(c, SPHIP_E_INVALID, "%s", nonfinite_texel_message("normal map", texels, bad, nw).c_str());
+	}
+	if (c->kids.empty()) return set_nmap(c, texels, nw, nh, hipMemcpyHostToDevice, c->own_stream, true);
+	if (const int rc = set_on_every_device(c, &sphip_ctx::have_nmap, texels != nullptr,       // the texels were validated above, once
+	                                       [&](sphip_ctx* k) { return set_nmap(k, texels, nw, nh, hipMemcpyHostToDevice, k->own_stream, true); })) return rc;
+	c->nmap_w = texels ? nw : 0; c->nmap_h = texels ? nh : 0;
+	return SPHIP_OK;
+}
+
+int sphip_set_normal_map_device(sphip_t* c, const void* d_texels, uint32_t nw, uint32_t nh, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	const bool bad = d_texels && (nw == 0 || nw > sp::kTexMaxN || nh == 0 || nh > sp::kTexMaxN);   // refused, and like every call it leaves no map behind
+	const int rc = set_nmap(c, bad ? nullptr : d_texels, nw, nh, hipMemcpyDeviceToDevice, (hipStream_t)stream, false);
+	return bad ? fail(c, SPHIP_E_INVALID, "normal map: %u x %u texels (1 <= nw, nh <= %u)", nw, nh, sp::kTexMaxN) : rc;
+}
+
 int sphip_render_device(sphip_t* c, const void* d_rays, size_t n_rays, const sphip_shard* shard, size_t image_width,
                         size_t n_samples, uint64_t seed, int mode, int flags, void* d_out_rgba, void* d_out_accum, void* stream) {
 	if (const int rc = single_device_entry(c)) return rc;
@@ -2061,11 +2150,12 @@ int sphip_render(sphip_t* c, const float* rays, size_t w, size_t h, size_t n_sam
 
 int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* out) {
 	if (!c) return SPHIP_E_INVALID;
-	static const size_t in_b[13] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32, 72, 84 }, out_b[13] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24, 32, 24 };
-	if (what < 0 || what > 12 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
+	static const size_t in_b[14] = { 4, 4, 20, 40, 60, 12, 48, 96, 32, 12, 32, 72, 84, 120 }, out_b[14] = { 8, 4, 16, 12, 4, 4, 8, 24, 24, 16, 24, 32, 24, 24 };
+	if (what < 0 || what > 13 || !in || !out || n == 0 || n > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad selftest arguments (what=%d n=%zu)", what, n);
 	sphip_ctx* k = c->kids.empty() ? c : c->kids[0];
 	if ((what == 9 || what == 10) && !k->have_env) return fail(c, SPHIP_E_STATE, "selftest %d needs an environment map (sphip_set_environment)", what);
 	if (what == 12 && !k->have_tex) return fail(c, SPHIP_E_STATE, "selftest %d needs an atlas (sphip_set_texture)", what);
+	if (what == 13 && !k->have_nmap) return fail(c, SPHIP_E_STATE, "selftest %d needs a normal map (sphip_set_normal_map)", what);
 	HIP_TRY(c, hipSetDevice(k->device));
 	sp::EnvMap em{};
 	if (what == 10) {                                                // T alone: the tables of the map itself, no scene needed
@@ -2078,7 +2168,8 @@ int sphip_selftest_device(sphip_t* c, int what, const void* in, size_t n, void* 
 	hipError_t e = hipMalloc(&d_out, n * out_b[what]);
 	if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_b[what], hipMemcpyHostToDevice);
 	if (e == hipSuccess) {
-		if (what == 12) hipLaunchKernelGGL(sp::k_selftest_tex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (const float*)k->atlas.p, k->tex_w, k->tex_h, (float*)d_out);
+		if (what == 13) hipLaunchKernelGGL(sp::k_selftest_nmap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (const float*)k->nmap.p, k->nmap_w, k->nmap_h, (float*)d_out);
+		else if (what == 12) hipLaunchKernelGGL(sp::k_selftest_tex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, (const float*)k->atlas.p, k->tex_w, k->tex_h, (float*)d_out);
 		else if (what == 11) hipLaunchKernelGGL(sp::k_selftest_gloss, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, (float*)d_out);
 		else if (what == 10) hipLaunchKernelGGL(sp::k_selftest_env_sample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const double*)d_in, (uint32_t)n, em, (float*)d_out);
 		else if (what == 9) hipLaunchKernelGGL(sp::k_selftest_env_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->own_stream, (const float*)d_in, (uint32_t)n, k->env_n, (float*)d_out);

@@ -21,12 +21,12 @@ namespace {
 static_assert(sizeof(geom::triangle) == 48 && sizeof(geom::ray) == 24 && sizeof(scene::material) == 24 && sizeof(scene::RGBA) == 4,
               "the C ABI takes the reference's packed structs as plain float arrays");
 
-// What a frame depends on beside the triangles and the materials: the per-triangle tables and the two context-level images, in the
+// What a frame depends on beside the triangles and the materials: the per-triangle tables and the three context-level images, in the
 // order in which they follow the scene to the library.  One rule for all: kept by its setter (hip_renderer::set_X), it joins the scene's
 // key and goes to the library with every scene upload (sphip_set_scene clears the tables; the library keeps the images across scenes,
 // but they travel like the tables so that one key covers everything); while everything that carries a flag is set, path-traced frames
 // carry that flag.
-enum part_id { P_ENV, P_SPEC, P_VNORM, P_GLASS, P_ROUGH, P_TEX, P_UV, N_PARTS };
+enum part_id { P_ENV, P_SPEC, P_VNORM, P_GLASS, P_ROUGH, P_TEX, P_NMAP, P_UV, N_PARTS };
 int set_env_image(sphip_t* c, const float* texels, uint32_t n, uint32_t) { return sphip_set_environment(c, texels, n); }
 struct part_rule {
 	const char* what;                                                // the call, as check() names it
@@ -43,7 +43,8 @@ const part_rule part_rules[N_PARTS] = {
 	{ "set_dielectric", SPHIP_FLAG_DIELECTRIC, 4, "dielectric table", sphip_set_dielectric, 0 },
 	{ "set_roughness", SPHIP_FLAG_GLOSSY, 1, "roughness table", sphip_set_roughness, 0 },
 	{ "set_texture", SPHIP_FLAG_TEXTURE, 0, 0, 0, sphip_set_texture },
-	{ "set_uv", SPHIP_FLAG_TEXTURE, 6, "UV table", sphip_set_uv, 0 },
+	{ "set_normal_map", SPHIP_FLAG_NORMAL_MAP, 0, 0, 0, sphip_set_normal_map },
+	{ "set_uv", SPHIP_FLAG_TEXTURE | SPHIP_FLAG_NORMAL_MAP, 6, "UV table", sphip_set_uv, 0 },      // the one UV table addresses the atlas and the normal map
 };
 
 struct hip_r : public basic_renderer {
@@ -312,6 +313,7 @@ namespace hip_renderer {
 	void set_uv(scene::renderer* r, const float* uv, size_t n_tris) { keep_table(r, P_UV, uv, n_tris); }
 	void set_environment(scene::renderer* r, const float* texels, uint32_t n) { keep(r, P_ENV, texels, (size_t)n * n * 3, n, n); }
 	void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th) { keep(r, P_TEX, texels, (size_t)tw * th * 3, tw, th); }
+	void set_normal_map(scene::renderer* r, const float* texels, uint32_t nw, uint32_t nh) { keep(r, P_NMAP, texels, (size_t)nw * nh * 3, nw, nh); }
 
 	void set_lens(scene::renderer* r, float aperture, float focus_dist) {
 		hip_r* p = dynamic_cast<hip_r*>(r);

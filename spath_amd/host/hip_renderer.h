@@ -63,6 +63,11 @@ namespace hip_renderer {
 	// begins a new progressive accumulation.
 	extern void set_texture(scene::renderer* r, const float* texels, uint32_t tw, uint32_t th);
 	extern void set_uv(scene::renderer* r, const float* uv, size_t n_tris);
+	// normal mapping (sphip_set_normal_map, SPHIP_FLAG_NORMAL_MAP; include/spath_hip.h "normal mapping"): a map of nw x nh x 3 floats, signed
+	// tangent-space vectors (copied), addressed by the UV table of set_uv; while a map and a UV table are both set, path-traced frames
+	// shade every hit with the map's normal (render_flat is unchanged).  NULL or a zero size removes it.  A map the library refuses makes
+	// the next frame throw std::runtime_error.  Changing it begins a new progressive accumulation.
+	extern void set_normal_map(scene::renderer* r, const float* texels, uint32_t nw, uint32_t nh);
 	// environment lighting (sphip_set_environment, SPHIP_FLAG_ENVIRONMENT; include/spath_hip.h "environment lighting"): an octahedral
 	// radiance map of n x n x 3 floats (copied); while one is set, path-traced frames are lit by it and show it behind the scene
 	// (render_flat is unchanged).  NULL or n = 0 removes it.  A map the library refuses makes the next frame throw std::runtime_error.

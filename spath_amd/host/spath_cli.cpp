@@ -4,7 +4,7 @@
 // '+'/'-' -> --spp, 'p' -> --mode.  The image goes to a binary PPM or a raw RGBA file.
 //
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
-//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--tex FILE.bin --uv FILE.bin] [--out image.ppm|image.rgba] [--frames n]
+//             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--tex FILE.bin --uv FILE.bin] [--nmap FILE.bin --uv FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
@@ -30,6 +30,9 @@
 // --tex FILE.bin --uv FILE.bin: textures (SPHIP_FLAG_TEXTURE) by the atlas in the first file (u32 tw, u32 th, then tw x th x {r g b} f32:
 //   spath_amd/scene.py write_texture) and the UV table in the second (n_tris x {s0 t0 s1 t1 s2 t2} f32, no header: write_uv); both or
 //   neither; the flat pass ignores them; not with --nee without --mis
+// --nmap FILE.bin --uv FILE.bin: normal mapping (SPHIP_FLAG_NORMAL_MAP) by the map in the first file ('SPNM', u32 nw, u32 nh, then
+//   nw x nh x {x y z} f32, signed: spath_amd/scene.py write_normal_map) over the UV table of --uv, which --tex shares; the flat pass
+//   ignores it; not with --nee without --mis
 // --env FILE.bin: environment lighting (SPHIP_FLAG_ENVIRONMENT) by the octahedral map in FILE.bin, a file of its own ('SPEN', n,
 //   n x n x {r g b} f32: spath_amd/scene.py write_environment); path tracing only, not with --nee without --mis
 // --out: .ppm (binary P6), .png (8-bit RGB, stored deflate blocks: no compression library needed), anything else = raw RGBA8
@@ -191,6 +194,21 @@ bool load_texture(const char* path, std::vector<float>& tex, uint32_t& tw, uint3
 	return ok;
 }
 
+// a normal map file of spath_amd/scene.py: 'SPNM', then an atlas file's layout
+bool load_normal_map(const char* path, std::vector<float>& map, uint32_t& nw, uint32_t& nh) {
+	FILE* f = std::fopen(path, "rb");
+	if (!f) return false;
+	uint32_t hdr[3] = { 0, 0, 0 };
+	bool ok = std::fread(hdr, 4, 3, f) == 3 && hdr[0] == 0x4D4E5053u && hdr[1] >= 1 && hdr[1] <= 4096 && hdr[2] >= 1 && hdr[2] <= 4096;
+	if (ok) {
+		nw = hdr[1]; nh = hdr[2];
+		map.resize((size_t)nw * nh * 3);
+		ok = std::fread(map.data(), sizeof(float), map.size(), f) == map.size();
+	}
+	std::fclose(f);
+	return ok;
+}
+
 // a UV file of spath_amd/scene.py: n_tris * 6 f32, no header
 bool load_uv(const char* path, size_t n_tris, std::vector<float>& uv) {
 	FILE* f = std::fopen(path, "rb");
@@ -204,7 +222,7 @@ bool load_uv(const char* path, size_t n_tris, std::vector<float>& uv) {
 
 int main(int argc, char** argv) {
 	try {
-		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg, rough_arg, tex_arg, uv_arg;
+		std::string scene_arg = "default", mode = "pt", out_path, spec_arg, normals_arg, glass_arg, env_arg, rough_arg, tex_arg, uv_arg, nmap_arg;
 		bool device_viewport = false;
 		std::vector<int> devices;                                    // empty: one GPU (hip_renderer::get: device 0 or SPATH_HIP_DEVICES)
 		bool all_gpus = false;
@@ -232,6 +250,7 @@ int main(int argc, char** argv) {
 			else if (k == "--env") { need(1); env_arg = argv[++i]; }
 			else if (k == "--tex") { need(1); tex_arg = argv[++i]; }
 			else if (k == "--uv") { need(1); uv_arg = argv[++i]; }
+			else if (k == "--nmap") { need(1); nmap_arg = argv[++i]; }
 			else if (k == "--w") { need(1); w = std::atoi(argv[++i]); }
 			else if (k == "--h") { need(1); h = std::atoi(argv[++i]); }
 			else if (k == "--spp") { need(1); spp = (size_t)std::atoll(argv[++i]); }
@@ -294,7 +313,9 @@ int main(int argc, char** argv) {
 		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
 		if (!env_arg.empty() && mode != "pt") throw std::runtime_error("--env needs --mode pt");
 		if (!env_arg.empty() && nee && !mis) throw std::runtime_error("--env works with the plain estimator and with --mis, not with --nee alone");
-		if (tex_arg.empty() != uv_arg.empty()) throw std::runtime_error("--tex and --uv go together (the atlas and the UV table)");
+		if (!nmap_arg.empty() && uv_arg.empty()) throw std::runtime_error("--nmap needs --uv (the UV table addresses the normal map)");
+		if (!nmap_arg.empty() && nee && !mis) throw std::runtime_error("--nmap works with the plain estimator and with --mis, not with --nee alone");
+		if (tex_arg.empty() != uv_arg.empty() && (nmap_arg.empty() || !tex_arg.empty())) throw std::runtime_error("--tex and --uv go together (the atlas and the UV table)");
 		if (!tex_arg.empty() && nee && !mis) throw std::runtime_error("--tex works with the plain estimator and with --mis, not with --nee alone");
 		if (!rough_arg.empty() && spec_arg.empty()) throw std::runtime_error("--rough needs --spec (it roughens the mirror lobe of the specular table)");
 		if (!rough_arg.empty() && nee && !mis) throw std::runtime_error("--rough works with the plain estimator and with --mis, not with --nee alone");
@@ -325,11 +346,20 @@ int main(int argc, char** argv) {
 			t.set(r.get(), tab.data(), tris.size());
 		}
 		if (!tex_arg.empty()) {
-			std::vector<float> tex, uv;
+			std::vector<float> tex;
 			uint32_t tw = 0, th = 0;
 			if (!load_texture(tex_arg.c_str(), tex, tw, th)) throw std::runtime_error("cannot read atlas file " + tex_arg);
-			if (!load_uv(uv_arg.c_str(), tris.size(), uv)) throw std::runtime_error("cannot read UV file " + uv_arg + " (n_tris x 6 floats for this scene)");
 			hip_renderer::set_texture(r.get(), tex.data(), tw, th);
+		}
+		if (!nmap_arg.empty()) {
+			std::vector<float> map;
+			uint32_t nw = 0, nh = 0;
+			if (!load_normal_map(nmap_arg.c_str(), map, nw, nh)) throw std::runtime_error("cannot read normal map file " + nmap_arg);
+			hip_renderer::set_normal_map(r.get(), map.data(), nw, nh);
+		}
+		if (!uv_arg.empty()) {
+			std::vector<float> uv;
+			if (!load_uv(uv_arg.c_str(), tris.size(), uv)) throw std::runtime_error("cannot read UV file " + uv_arg + " (n_tris x 6 floats for this scene)");
 			hip_renderer::set_uv(r.get(), uv.data(), tris.size());
 		}
 		if (!env_arg.empty()) {

@@ -27,9 +27,10 @@ PARTS = (
     ("vnorm", 9, capi.FLAG_SMOOTH, "set_vertex_normals"),
     ("glass", 4, capi.FLAG_DIELECTRIC, "set_dielectric"),
     ("rough", 1, capi.FLAG_GLOSSY, "set_roughness"),
-    ("uv", 6, capi.FLAG_TEXTURE, "set_uv"),
+    ("uv", 6, capi.FLAG_TEXTURE | capi.FLAG_NORMAL_MAP, "set_uv"),         # the one UV table addresses the atlas and the normal map
     ("env", None, capi.FLAG_ENVIRONMENT, "set_environment"),
     ("tex", None, capi.FLAG_TEXTURE, "set_texture"),
+    ("nmap", None, capi.FLAG_NORMAL_MAP, "set_normal_map"),
 )
 
 
@@ -128,8 +129,15 @@ class HipRenderer(BasicRenderer):
         and a UV table (set_uv) are both set every path-traced frame carries capi.FLAG_TEXTURE (render_flat never does)."""
         self._set_part("tex", texels)
 
+    def set_normal_map(self, texels):
+        """The normal map of capi.FLAG_NORMAL_MAP renders ([nh, nw, 3] float32 of signed tangent-space vectors,
+        scene.normal_map_from_height or scene.decode_normal_map; None: no map), like hip_renderer::set_normal_map: it goes to the
+        library with the next scene upload and begins a new accumulation, and while a map and a UV table (set_uv) are both set every
+        path-traced frame carries capi.FLAG_NORMAL_MAP (render_flat never does)."""
+        self._set_part("nmap", texels)
+
     def set_uv(self, uv):
-        """The UV table of capi.FLAG_TEXTURE renders ([n_tris, 6] float32, scene.uv_table or scene.planar_uv; None: no table), like
+        """The UV table of capi.FLAG_TEXTURE and capi.FLAG_NORMAL_MAP renders ([n_tris, 6] float32, scene.uv_table or scene.planar_uv; None: no table), like
         hip_renderer::set_uv: see set_texture."""
         self._set_part("uv", uv)
 
@@ -165,8 +173,8 @@ class HipRenderer(BasicRenderer):
         self._set_part("spec", spec)
 
     def _flags(self, mode):
-        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY and FLAG_TEXTURE on
-        while their tables, the map or the atlas are set, and never on the flat pass"""
+        """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY, FLAG_TEXTURE and
+        FLAG_NORMAL_MAP on while their tables, the maps or the atlas are set, and never on the flat pass"""
         on = off = 0
         for name, _, flag, _ in PARTS:
             if self._parts[name] is None:

@@ -328,6 +328,51 @@ def write_texture(path, texels: np.ndarray) -> None:
         f.write(texels.tobytes())
 
 
+def normal_map_from_height(height, strength: float = 1.0) -> np.ndarray:
+    """A normal map for capi.Context.set_normal_map (include/spath_hip.h, "normal mapping") from a height field [nh, nw] indexed
+    [j, i]: central differences with repeat wrap, dx = (h[j, i + 1] - h[j, i - 1]) / 2 and dy likewise along j (per texel), and the
+    unit vector of (-strength dx, -strength dy, 1) in float64, rounded once: float32 [nh, nw, 3] with z > 0; a constant height gives
+    (0, 0, 1) exactly."""
+    h = np.asarray(height, np.float64)
+    if h.ndim != 2 or not (1 <= h.shape[0] <= 4096 and 1 <= h.shape[1] <= 4096) or not np.isfinite(h).all():
+        raise ValueError("normal map: a finite height field [nh, nw], 1 <= nw, nh <= 4096")
+    dx = (np.roll(h, -1, axis=1) - np.roll(h, 1, axis=1)) / 2.0
+    dy = (np.roll(h, -1, axis=0) - np.roll(h, 1, axis=0)) / 2.0
+    v = np.stack([-float(strength) * dx, -float(strength) * dy, np.ones_like(h)], axis=2)
+    return np.ascontiguousarray((v / np.sqrt((v * v).sum(axis=2, keepdims=True))).astype(F))
+
+
+def decode_normal_map(rgb01) -> np.ndarray:
+    """The signed vectors of a normal map stored in the 0..1 encoding of image files: 2 c - 1 per component, float32 [nh, nw, 3]."""
+    c = np.asarray(rgb01, F)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("a normal map is (nh, nw, 3)")
+    return np.ascontiguousarray(F(2.0) * c - F(1.0))
+
+
+def write_normal_map(path, texels: np.ndarray) -> None:
+    """Normal map file read by the headless CLI (--nmap): 'SPNM', u32 nw, u32 nh, then nh x nw x {x y z} float32 (the atlas file's layout
+    behind a magic of its own)."""
+    texels = np.ascontiguousarray(texels, dtype=F)
+    if texels.ndim != 3 or texels.shape[2] != 3:
+        raise ValueError("a normal map is (nh, nw, 3)")
+    with open(path, "wb") as f:
+        f.write(b"SPNM" + struct.pack("<II", texels.shape[1], texels.shape[0]))
+        f.write(texels.tobytes())
+
+
+def read_normal_map(path) -> np.ndarray:
+    """The float32 [nh, nw, 3] texels of a file written by write_normal_map."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:4] != b"SPNM" or len(raw) < 12:
+        raise ValueError("not a normal map file")
+    nw, nh = struct.unpack("<II", raw[4:12])
+    if len(raw) != 12 + nw * nh * 12:
+        raise ValueError("normal map file: size and header differ")
+    return np.frombuffer(raw, F, offset=12).reshape(nh, nw, 3).copy()
+
+
 def write_uv(path, uv: np.ndarray) -> None:
     """UV file read by the headless CLI (--uv), beside the scene file: n_tris x 6 float32, no header."""
     with open(path, "wb") as f:
