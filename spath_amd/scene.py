@@ -22,6 +22,7 @@ VNORM_MAGIC = 0x4E565053  # 'SPVN'
 GLASS_MAGIC = 0x49445053  # 'SPDI'
 ENV_MAGIC = 0x4E455053    # 'SPEN'
 ROUGH_MAGIC = 0x47525053  # 'SPRG'
+LAMP_MAGIC = 0x414C5053   # 'SPLA'
 
 
 def flat_normals(tris: np.ndarray) -> np.ndarray:
@@ -187,6 +188,181 @@ def light_table(tris: np.ndarray, mats: np.ndarray):
     tipdf = np.zeros(t.shape[0], F)
     tipdf[tri] = ipdf
     return tri, np.array(cdf, np.float64), ipdf, W, tipdf
+
+
+LAMP_POINT, LAMP_SPOT, LAMP_SUN = 0, 1, 2
+LAMP_MAX_ROWS = 65536
+
+
+def _unit(v, what):
+    v = np.asarray(v, np.float64).reshape(3)
+    ln = float(np.sqrt((v * v).sum()))
+    if not (np.isfinite(v).all() and ln > 0.0):
+        raise ValueError(f"{what}: a finite direction of positive length")
+    return (v / ln).astype(F)
+
+
+def point_lamp(position, intensity) -> np.ndarray:
+    """A point light for lamp_table: float32 [12], kind 0 at `position` with the radiant intensity
+    (per steradian) `intensity`, a scalar or an rgb triple."""
+    row = np.zeros(12, F)
+    row[0] = LAMP_POINT
+    row[1:4] = np.asarray(position, F).reshape(3)
+    row[4:7] = np.broadcast_to(np.asarray(intensity, F), (3,))
+    return row
+
+
+def spot_lamp(position, direction, intensity, inner_deg: float = 20.0, outer_deg: float = 30.0) -> np.ndarray:
+    """A spot light for lamp_table: float32 [12], kind 1 at `position`, its cone around `direction` (normalised here, in float64,
+    rounded once), radiant intensity `intensity` on the axis, full inside the half-angle inner_deg and none outside outer_deg
+    (degrees, 0 <= inner < outer <= 180); the row holds their cosines, float32(cos(radians))."""
+    if not 0.0 <= float(inner_deg) < float(outer_deg) <= 180.0:
+        raise ValueError("spot lamp: 0 <= inner_deg < outer_deg <= 180")
+    row = np.zeros(12, F)
+    row[0] = LAMP_SPOT
+    row[1:4] = np.asarray(position, F).reshape(3)
+    row[4:7] = np.broadcast_to(np.asarray(intensity, F), (3,))
+    row[7:10] = _unit(direction, "spot lamp")
+    row[10] = F(max(-1.0, min(1.0, np.cos(np.radians(float(inner_deg))))))
+    row[11] = F(max(-1.0, min(1.0, np.cos(np.radians(float(outer_deg))))))
+    if not row[11] < row[10]:
+        raise ValueError("spot lamp: the two cosines coincide in float32")
+    return row
+
+
+def sun_lamp(direction, irradiance) -> np.ndarray:
+    """A sun for lamp_table: float32 [12], kind 2, its light travelling along `direction` (normalised here; not the vertical: x and z
+    must not both be 0) with `irradiance` on a plane facing it, a scalar or an rgb triple."""
+    row = np.zeros(12, F)
+    row[0] = LAMP_SUN
+    row[4:7] = np.broadcast_to(np.asarray(irradiance, F), (3,))
+    row[7:10] = _unit(direction, "sun lamp")
+    if row[7] == 0 and row[9] == 0:
+        raise ValueError("sun lamp: a vertical sun (a.x == 0 and a.z == 0) lights nothing finitely")
+    return row
+
+
+LAMP_FIELDS = ("kind", "p.x", "p.y", "p.z", "c.r", "c.g", "c.b", "a.x", "a.y", "a.z", "ci", "co")
+LAMP_AXIS_TOL = float(F(1e-3))
+# the rules of a lamp row, in the order in which a row that breaks several hears of them
+LAMP_RULES = ("ok", "non_finite", "negative", "kind", "axis", "cone", "vertical", "must_be_zero")
+
+
+def check_lamp_row(q):
+    """THE rules of a lamp row -> (rule, field): the first rule of LAMP_RULES that q [12] breaks and the first
+    float that breaks it; ("ok", -1) for a valid row.  Every value finite; c >= 0; kind 0, 1 or 2; the axis of a spot or a sun a unit
+    vector (its squared length, in double, within 1e-3 of 1); a spot's -1 <= co < ci <= 1; no vertical sun (a.x == 0 and a.z == 0);
+    a point's a, ci, co and a sun's p, ci, co zero."""
+    q = np.asarray(q, F).reshape(12)
+    for k in range(12):
+        if not np.isfinite(q[k]):
+            return "non_finite", k
+    for k in (4, 5, 6):
+        if not q[k] >= 0:
+            return "negative", k
+    if float(q[0]) not in (0.0, 1.0, 2.0):
+        return "kind", 0
+    kind = int(q[0])
+    if kind != LAMP_POINT:
+        a = q[7:10].astype(np.float64)
+        if not abs(((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) - 1.0) <= LAMP_AXIS_TOL:
+            return "axis", 7
+    if kind == LAMP_SPOT and not (q[11] >= -1 and q[11] < q[10] and q[10] <= 1):
+        return "cone", 10
+    if kind == LAMP_SUN and q[7] == 0 and q[9] == 0:
+        return "vertical", 7
+    for k in {LAMP_POINT: range(7, 12), LAMP_SPOT: (), LAMP_SUN: (1, 2, 3, 10, 11)}[kind]:
+        if q[k] != 0:
+            return "must_be_zero", k
+    return "ok", -1
+
+
+def lamp_row_message(q, row: int, rule: str, field: int) -> str:
+    """What a setter says of row number `row`, q [12], that breaks `rule` at float `field`: the row, the offending values as %g prints
+    them, and the rule."""
+    v = [float(x) for x in np.asarray(q, F).reshape(12)]
+    if rule == "non_finite":
+        return "lamp table: row %d has %s = %g (every value finite)" % (row, LAMP_FIELDS[field], v[field])
+    if rule == "negative":
+        return "lamp table: row %d has c {%g %g %g} (c >= 0)" % (row, v[4], v[5], v[6])
+    if rule == "kind":
+        return "lamp table: row %d has kind %g (0 point, 1 spot, 2 sun)" % (row, v[0])
+    if rule == "axis":
+        return "lamp table: row %d has axis {%g %g %g} (a unit vector: |dot(a, a) - 1| <= 1e-3)" % (row, v[7], v[8], v[9])
+    if rule == "cone":
+        return "lamp table: row %d has {ci %g, co %g} (-1 <= co < ci <= 1)" % (row, v[10], v[11])
+    if rule == "vertical":
+        return ("lamp table: row %d is a sun with axis {%g %g %g} (a.x and a.z must not both be 0: a vertical sun lights nothing finitely)"
+                % (row, v[7], v[8], v[9]))
+    if rule == "must_be_zero":
+        return "lamp table: row %d (%s) has %s = %g (must be 0 for this kind)" % (row, "point" if v[0] == 0 else "sun", LAMP_FIELDS[field], v[field])
+    raise ValueError(f"no message for rule {rule!r}")
+
+
+def lamp_table(*rows) -> np.ndarray:
+    """The lamp table from rows of point_lamp, spot_lamp and sun_lamp (or [12] arrays, or [k, 12] blocks):
+    float32 [n, 12] of at most 65536 rows, every row checked by check_lamp_row; the ValueError of the first row that breaks a rule is
+    lamp_row_message's."""
+    tab = np.concatenate([np.asarray(r, F).reshape(-1, 12) for r in rows]) if rows else np.zeros((0, 12), F)
+    if tab.shape[0] > LAMP_MAX_ROWS:
+        raise ValueError("lamp table: %d rows (at most %d)" % (tab.shape[0], LAMP_MAX_ROWS))
+    for k, q in enumerate(tab):
+        rule, field = check_lamp_row(q)
+        if rule != "ok":
+            raise ValueError(lamp_row_message(q, k, rule, field))
+    return np.ascontiguousarray(tab)
+
+
+def scene_R2(tris: np.ndarray) -> float:
+    """A quarter of the squared diagonal of the bounding box of the scene's vertices, in double from the f32 values: the R2 of the
+    environment map's weight and of a sun lamp's."""
+    v = np.asarray(tris, F).reshape(-1, 12)[:, :9].reshape(-1, 3)
+    ext = v.max(0).astype(np.float64) - v.min(0).astype(np.float64)
+    return float(0.25 * ((ext[0] * ext[0] + ext[1] * ext[1]) + ext[2] * ext[2]))
+
+
+def lamp_weights(tris: np.ndarray, lamps: np.ndarray) -> np.ndarray:
+    """The weight of every lamp row in the light table's units, float64 [n]: with Csum = ((double)c.r + c.g) + c.b, a point 4 Csum, a
+    spot (2 (1 - (double)co)) Csum, a sun R2 Csum (scene_R2)."""
+    q = np.asarray(lamps, F).reshape(-1, 12)
+    c = q[:, 4:7].astype(np.float64)
+    cs = (c[:, 0] + c[:, 1]) + c[:, 2]
+    R2 = scene_R2(tris)
+    return np.where(q[:, 0] == LAMP_POINT, 4.0 * cs, np.where(q[:, 0] == LAMP_SPOT, (2.0 * (1.0 - q[:, 11].astype(np.float64))) * cs, R2 * cs))
+
+
+def lamp_light_table(tris: np.ndarray, mats: np.ndarray, lamps: np.ndarray, w_env: float = 0.0):
+    """The light table of a render with lamps, in numpy:
+    -> (tri, cdf, ipdf, W, tipdf) like light_table.  The triangle entries of light_table, then every lamp of positive finite weight
+    in row order (row k as triangle -2 - k), then, with w_env > 0 (the weight of an environment map's entry), triangle -1 last; W is
+    the running double sum over all of them; ipdf = float32(W / Esum) for a triangle, float32(W / w) for a lamp, 0 for the map."""
+    t = np.asarray(tris, F).reshape(-1, 12)
+    m = np.asarray(mats, F).reshape(-1, 6)
+    tri, cdf, _, W, _ = light_table(t, m)
+    tri, cdf = list(tri), list(cdf)
+    n_tri = len(tri)
+    lw = []
+    for k, w in enumerate(lamp_weights(t, lamps)):
+        if not (w > 0.0 and np.isfinite(w)):
+            continue
+        W = W + float(w)
+        tri.append(-2 - k), cdf.append(W), lw.append(float(w))
+    if w_env > 0.0:
+        W = W + float(w_env)
+        tri.append(-1), cdf.append(W)
+    tri = np.array(tri, np.int64)
+    e = m[tri[:n_tri], 3:6].astype(np.float64)
+    ipdf = np.zeros(tri.size, F)
+    ipdf[:n_tri] = (W / ((e[:, 0] + e[:, 1]) + e[:, 2])).astype(F)
+    ipdf[n_tri:n_tri + len(lw)] = (W / np.array(lw, np.float64)).astype(F)
+    tipdf = np.zeros(t.shape[0], F)
+    tipdf[tri[:n_tri]] = ipdf[:n_tri]
+    return tri, np.array(cdf, np.float64), ipdf, W, tipdf
+
+
+def write_lamps(path, lamps: np.ndarray) -> None:
+    """Lamp file, in the format of the other table files: 'SPLA', n, n * 12 float32."""
+    _write_table(path, LAMP_MAGIC, lamps, 12)
 
 
 def specular_table(tris: np.ndarray, mats: np.ndarray, ks=0.0, which=None, p=None) -> np.ndarray:
