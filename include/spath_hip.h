@@ -381,6 +381,82 @@ int  sphip_accum_gbuffer(sphip_t* ctx, void* out_gbuf);
  * filtered on the first device. */
 int  sphip_accum_denoise(sphip_t* ctx, const sphip_denoise* p, uint8_t* out_rgba, float* out_rgb /* or NULL */);
 
+/* ---- temporal reprojection: the step SVGF-style pipelines put in front of the a-trous filter.  When the camera
+ * moves, the previous view's accumulated radiance (a mean and a per-pixel history count: how many samples the mean stands for) is
+ * resampled at the new view's primary hits and blended with the new view's samples, so that an accumulation survives the move.  A
+ * post-process like the denoiser: it leaves the scans, the sums and every render as they are.  Every operation is an f32 + - * /
+ * (IEEE division), a comparison, a select or a float-to-int floor in the order below, nothing fused, so the output is reproducible bit
+ * for bit; dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z.
+ *
+ * Inputs: the current view's rays and G-buffer (sphip_viewport_device of the new camera, sphip_gbuffer_device of those rays), the
+ * previous view's rays, G-buffer, mean and history count, and the previous camera `prev`.  Host constants of `prev`, formed exactly as
+ * sphip_viewport_device forms them (src/view.h:101-108): x_max, x_step, h_x, y_max, y_step, h_y; xo = x_max - h_x, yo = y_max - h_y (f32).
+ *
+ * Reprojection of the current pixel p = y * w + x, G-buffer entry (n_p, dist_p, mat_p), primary ray (o_p, d_p):
+ *   1. mat_p < 0 (a miss): mean 0, history 0.
+ *   2. P = o_p + d_p * dist_p per component (one multiply, one add).
+ *   3. v = P - prev.pos per component.  The inverse of rel_move (src/view.h:54-68,83-85: rel_move = rY(rX(.))), rY's first:
+ *        a = (v.x * cos_y + v.z * -sin_y,  v.y,  v.x * sin_y + v.z * cos_y)
+ *        c = (a.x,  a.y * cos_x + a.z * sin_x,  a.y * -sin_x + a.z * cos_x)
+ *      The reference's rays leave the view plane z = 0 towards (px, py, focal): the eye is (0, 0, -focal).  No history unless c.z > 0.
+ *        qz = c.z + focal;  sx = (c.x * focal) / qz;  sy = (c.y * focal) / qz
+ *   4. fx = (xo - sx) / x_step;  fy = (yo - sy) / y_step  (the inverse of src/view.h:111).  No history when fx or fy is not finite.
+ *      x0 = floor(fx);  tx = fx - x0;  ux = 1 - tx;  y0, ty, uy likewise.
+ *   5. The taps q = (x0 + a, y0 + b), visited b, then a, over {0, 1}; wb = (a ? tx : ux) * (b ? ty : uy).  A tap counts only when all of
+ *      these hold, tested in this order (nothing of a tap is read before the first):
+ *        0 <= x0 + a < w and 0 <= y0 + b < h;   wb > 0;   hist_q > 0;   mat_q == mat_p;   dot3(n_p, n_q) >= normal_min;
+ *        |dot3(P_q - P, n_p)| <= plane_tol * dist_p,  P_q = o_q + d_q * dist_q of the PREVIOUS view's ray and G-buffer entry q
+ *   6. Sums from 0, in tap order:  W += wb;  C.rgb += wb * mean_q.rgb (per channel);  Hs += wb * hist_q.
+ *      !(W > 0): mean 0, history 0.  Else mean = C / W per channel;  hist = Hs / W;  hist = hist > max_history ? max_history : hist.
+ *
+ * Blend of a history (hm, h) with the running sum s of n new samples, per channel:
+ *      h == 0:  s * (float)(1.0 / n)  -- what every render and accumulation step writes, so a pixel without history is bit for bit the
+ *               plain accumulation's;   else  (h * hm + s) / (h + (float)n)
+ * RGBA8 through vec3::clamp and scene::vec3_RGBA, as the render's.  The history that a blended accumulation of n samples hands to the
+ * next reprojection is (that blend, h + (float)n); the cap max_history applies in step 6 alone.
+ *
+ * What it is not: the history is an unbiased estimate of the new pixel only where the first hit is diffuse.  Mirrors, glass, glossy
+ * highlights and depth of field depend on the view and lag by up to max_history samples; the bilinear resampling blurs across
+ * irradiance gradients.  There is no per-material rejection. */
+typedef struct {
+	float    max_history;   /* >= 0, finite: cap of the per-pixel history count (0: no history is taken over) */
+	float    normal_min;    /* in [-1, 1]: a tap counts only when dot3(n_p, n_q) >= normal_min */
+	float    plane_tol;     /* >= 0, finite: a tap counts only when |dot3(P_q - P, n_p)| <= plane_tol * dist_p */
+	uint32_t reserved;      /* must be 0 */
+} sphip_reproject;
+
+/* the calibrated defaults */
+void sphip_reproject_defaults(sphip_reproject* out);
+/* Steps 1-6 for the w*h pixels of the current view.  Device pointers: rays w*h*6 f32, G-buffers w*h*32 B (16-byte aligned),
+ * d_mean_prev / d_out_mean w*h*3 f32, d_hist_prev / d_out_hist w*h f32; the outputs overlap no input.  Stateless; needs no scene;
+ * asynchronous on `stream`; single-device contexts (SPHIP_E_STATE otherwise).  SPHIP_E_INVALID: a NULL pointer, w or h 0 or >= 2^30,
+ * cam_prev->res_x/res_y differing from w/h, a parameter out of its range or not finite, reserved != 0. */
+int sphip_reproject_device(sphip_t* ctx, const sphip_reproject* p, const sphip_camera* cam_prev, size_t w, size_t h,
+                           const void* d_rays_cur, const void* d_gbuf_cur, const void* d_rays_prev, const void* d_gbuf_prev,
+                           const void* d_mean_prev, const void* d_hist_prev, void* d_out_mean, void* d_out_hist, void* stream);
+/* The blend for n pixels: d_sum n*3 f32 (the raw sum of n_samples > 0 samples, as sphip_render_device_accum keeps it), d_hist_mean n*3 f32
+ * and d_hist n f32 (both NULL: no pixel has a history); d_out_rgba n*4 u8 and d_out_mean n*3 f32, either may be NULL, not both.
+ * Stateless, asynchronous, single-device contexts like the call above. */
+int sphip_temporal_resolve_device(sphip_t* ctx, size_t n, const void* d_sum, uint32_t n_samples, const void* d_hist_mean, const void* d_hist,
+                                  void* d_out_rgba, void* d_out_mean, void* stream);
+/* Moves the current accumulation to the view cam_new and keeps what it has gathered as history.  Needs a live accumulation that was
+ * begun with `cam` (not rays), is plain (not adaptive), lives on a single-device context and has taken at least one step.  The call
+ * turns that accumulation (with its own history, if it has one) into a (mean, history count) pair, reuses the old view's cached
+ * G-buffer (building it if no call has yet), generates the new view's rays and G-buffer, reprojects, and begins a new accumulation for
+ * cam_new with the old flags and lens and the given seed, with the reprojected history attached.  After it sphip_accum_step returns
+ * the blend (*total_out counts the new samples only), sphip_accum_denoise filters the blended mean (without wl, as for any plain
+ * accumulation), sphip_accum_gbuffer is the new view's, and the call may be repeated any number of times.  sphip_accum_begin and
+ * sphip_accum_begin_adaptive drop the history.  Pass a seed other than the history's: the same seed at the same view draws the same
+ * samples again, which adds nothing.  Blocking.
+ * A refusal changes nothing (the next step is what it would have been).  SPHIP_E_STATE: no accumulation, one ended by a setter or a
+ * set_scene, one begun with rays, an adaptive one, a multi-device context, or before the first step.  SPHIP_E_INVALID: a NULL
+ * argument, cam_new->res_x/res_y differing from the accumulation's, a parameter out of its range or not finite, reserved != 0.
+ * A call that fails on the device (SPHIP_E_DEVICE) ends the accumulation, as a failing step does (begin again). */
+int sphip_accum_reproject(sphip_t* ctx, const sphip_camera* cam_new, uint64_t seed, const sphip_reproject* p);
+/* The per-pixel history counts of the current accumulation in image order (all 0 for one without history).  Blocking; SPHIP_E_STATE when
+ * no accumulation has been begun. */
+int sphip_accum_history(sphip_t* ctx, float* out_hist /* w*h */);
+
 /* ---- next-event estimation (SPHIP_FLAG_NEE): at each of the first four surface hits of a path, one light
  * sample and one shadow ray.  Valid for SPHIP_MODE_PT on every render and accumulation entry point and with the variants 1,
  * 2, 8 (SPHIP_FLAG_ACCEL), 15 and 16, every one the library carries (a retired number is SPHIP_E_INVALID with or without the flag); flat and hit queries ignore it.

@@ -45,6 +45,7 @@ SYMBOLS = (
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
+    "sphip_reproject_defaults", "sphip_reproject_device", "sphip_temporal_resolve_device", "sphip_accum_reproject", "sphip_accum_history",
     "sphip_set_lens", "sphip_camera_rays_device",
     "sphip_set_specular", "sphip_set_specular_device",
     "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
@@ -118,6 +119,35 @@ class Denoise(C.Structure):
 
     def as_dict(self):
         return {"iterations": self.iterations, "normal_log2": self.normal_log2, "sigma_depth": self.sigma_depth, "sigma_lum": self.sigma_lum}
+
+
+class Reproject(C.Structure):
+    """sphip_reproject: parameters of temporal reprojection (include/spath_hip.h)."""
+    _fields_ = [("max_history", C.c_float), ("normal_min", C.c_float), ("plane_tol", C.c_float), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls):
+        d = cls()
+        load().sphip_reproject_defaults(C.byref(d))
+        return d
+
+    @classmethod
+    def make(cls, params=None):
+        """None: the library's defaults; a Reproject as is; a (max_history, normal_min, plane_tol) tuple; a dict overrides some of
+        the defaults."""
+        if isinstance(params, cls):
+            return params
+        if isinstance(params, (tuple, list)):
+            return cls(*[float(x) for x in params], 0)
+        d = cls.defaults()
+        for k, v in (params or {}).items():
+            if k not in ("max_history", "normal_min", "plane_tol", "reserved"):
+                raise ValueError(f"unknown reproject parameter {k!r}")
+            setattr(d, k, v)
+        return d
+
+    def as_dict(self):
+        return {"max_history": self.max_history, "normal_min": self.normal_min, "plane_tol": self.plane_tol}
 
 
 def gbuffer_dtype():
@@ -219,6 +249,16 @@ def load():
     L.sphip_accum_gbuffer.argtypes = [vp, vp]
     L.sphip_accum_denoise.restype = C.c_int
     L.sphip_accum_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp]
+    L.sphip_reproject_defaults.restype = None
+    L.sphip_reproject_defaults.argtypes = [C.POINTER(Reproject)]
+    L.sphip_reproject_device.restype = C.c_int
+    L.sphip_reproject_device.argtypes = [vp, C.POINTER(Reproject), C.POINTER(CameraArgs), sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sphip_temporal_resolve_device.restype = C.c_int
+    L.sphip_temporal_resolve_device.argtypes = [vp, sz, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.sphip_accum_reproject.restype = C.c_int
+    L.sphip_accum_reproject.argtypes = [vp, C.POINTER(CameraArgs), C.c_uint64, C.POINTER(Reproject)]
+    L.sphip_accum_history.restype = C.c_int
+    L.sphip_accum_history.argtypes = [vp, vp]
     L.sphip_set_lens.restype = C.c_int
     L.sphip_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.sphip_camera_rays_device.restype = C.c_int
@@ -619,6 +659,39 @@ class Context:
         self._check(self._L.sphip_accum_denoise(self._h, C.byref(p), out.ctypes.data if w * h else None,
                                                 rgb.ctypes.data if want_rgb and w * h else None), "sphip_accum_denoise")
         return (out, rgb) if want_rgb else out
+
+    # temporal reprojection -------------------------------------------------------------------
+    def reproject_device(self, params, cam_prev, w: int, h: int, d_rays_cur: int, d_gbuf_cur: int, d_rays_prev: int, d_gbuf_prev: int,
+                         d_mean_prev: int, d_hist_prev: int, d_out_mean: int, d_out_hist: int, stream: int = 0):
+        """The previous view's (mean, history count) resampled at the current view's primary hits (device pointers; asynchronous).
+        cam_prev: the previous view's view.Camera or CameraArgs; params as for Reproject.make."""
+        p = Reproject.make(params)
+        ca = cam_prev if isinstance(cam_prev, CameraArgs) or cam_prev is None else CameraArgs.from_camera(cam_prev)
+        self._check(self._L.sphip_reproject_device(self._h, C.byref(p), C.byref(ca) if ca is not None else None, w, h, d_rays_cur or None,
+                                                   d_gbuf_cur or None, d_rays_prev or None, d_gbuf_prev or None, d_mean_prev or None,
+                                                   d_hist_prev or None, d_out_mean or None, d_out_hist or None, stream or None),
+                    "sphip_reproject_device")
+
+    def temporal_resolve_device(self, n: int, d_sum: int, n_samples: int, d_out_rgba: int = 0, d_out_mean: int = 0, *, d_hist_mean: int = 0,
+                                d_hist: int = 0, stream: int = 0):
+        """The blend of the running sum of n_samples samples with a history (none: the plain resolve) on device pointers; asynchronous."""
+        self._check(self._L.sphip_temporal_resolve_device(self._h, n, d_sum or None, n_samples, d_hist_mean or None, d_hist or None,
+                                                          d_out_rgba or None, d_out_mean or None, stream or None), "sphip_temporal_resolve_device")
+
+    def accum_reproject(self, cam_new, seed, params=None):
+        """Moves the current accumulation to the view cam_new (view.Camera) and keeps what it has gathered as history; pass a seed other
+        than the history's.  params as for Reproject.make."""
+        p = Reproject.make(params)
+        ca = cam_new if isinstance(cam_new, CameraArgs) or cam_new is None else CameraArgs.from_camera(cam_new)
+        self._check(self._L.sphip_accum_reproject(self._h, C.byref(ca) if ca is not None else None, seed, C.byref(p)), "sphip_accum_reproject")
+
+    def accum_history(self):
+        """-> the per-pixel history counts of the current accumulation, float32 [w*h] (all 0 without a history)."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        out = np.zeros(w * h, dtype=np.float32)
+        self._check(self._L.sphip_accum_history(self._h, out.ctypes.data if w * h else None), "sphip_accum_history")
+        return out
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
                     7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8), 12: ("float32", 6),

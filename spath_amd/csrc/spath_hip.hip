@@ -12,6 +12,7 @@
 #include "sp_bvh_build.h"
 #include "sp_adaptive.h"
 #include "sp_denoise.h"
+#include "sp_reproject.h"
 #include "sp_environment.h"
 #include "sp_host_plan.h"
 #include "sp_host_tables.h"
@@ -109,6 +110,11 @@ struct sphip_ctx {
 	sphip_lens acc_lens{};
 	sphip_camera acc_cam{};
 	bool acc_has_cam = false;
+	// ---- temporal reprojection (sp_reproject.h, sphip_accum_reproject): the history attached to the current accumulation (the reprojected
+	// mean and count per pixel), and what a reprojection reads of the view it leaves: its rays, G-buffer, blended mean and count
+	// (rp_pmean doubles as the blended mean sphip_accum_denoise filters).  Every one is written whole before it is read.
+	DevBuf rp_hmean, rp_hist, rp_prays, rp_pgbuf, rp_pmean, rp_phist;
+	bool acc_hist_on = false;                     // dropped by every accumulation begin
 	// ---- the per-triangle tables of the scene (sp_host_tables.h: kTriTables; kTableSlots below names each one's members).  One rule for
 	// all: a table belongs to the scene last set and is kept like it, so every set_scene drops it (drop_tables); every device of a
 	// multi-device context keeps the whole table; a render reads it while its flag is set.  What is particular to each:
@@ -1413,6 +1419,7 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the camera's %ux%u", w, h, cam->res_x, cam->res_y);
 	c->acc_on = false;                             // a begin that fails leaves no accumulation behind
 	c->adp_on = false;
+	c->acc_hist_on = false;
 	c->dn_gbuf_ok = false;
 	const int v = pick_variant(flags, c->n_tris);
 	int rc;
@@ -1449,6 +1456,51 @@ int accum_begin(sphip_t* c, const float* rays, const sphip_camera* cam, size_t w
 // Denoising (sp_denoise.h; include/spath_hip.h: sphip_denoise): a G-buffer of the primary hits and an edge-aware a-trous
 // filter, a post-process that leaves the scans, the sums and the raw image as they are.
 // =====================================================================================================================
+
+// the blend of sp_reproject.h for n pixels: the sum of `total` samples and a history (hist == nullptr: none) -> RGBA8 and mean (either may
+// be nullptr).  after_render: the launch closes the kernel time of the render it follows.
+int temporal_resolve_dev(sphip_ctx* c, size_t n, const void* sum, uint64_t total, const void* hmean, const void* hist, void* rgba, void* mean,
+                         hipStream_t st, bool after_render) {
+	const float inv_n = (float)(1.0 / (double)(total ? total : 1));    // as launch_render forms it
+	hipLaunchKernelGGL(sp::k_temporal_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)sum, inv_n, (float)total,
+	                   (const float*)hmean, (const float*)hist, (uint32_t)n, (uint32_t*)rgba, (float*)mean);
+	HIP_TRY(c, hipGetLastError());
+	if (after_render) {
+		HIP_TRY(c, hipEventRecord(c->ev_k1, st));
+		c->stats.n_launches += 1;
+	}
+	return SPHIP_OK;
+}
+
+int check_reproject(sphip_ctx* c, const sphip_reproject* P) {
+	if (!P) return fail(c, SPHIP_E_INVALID, "null sphip_reproject");
+	if (!std::isfinite(P->max_history) || P->max_history < 0.0f || !(P->normal_min >= -1.0f && P->normal_min <= 1.0f) ||
+	    !std::isfinite(P->plane_tol) || P->plane_tol < 0.0f || P->reserved != 0)
+		return fail(c, SPHIP_E_INVALID, "bad sphip_reproject {max_history %g, normal_min %g, plane_tol %g, reserved %u}: max_history and plane_tol "
+		            "finite and >= 0, normal_min in [-1, 1], reserved 0", (double)P->max_history, (double)P->normal_min, (double)P->plane_tol, P->reserved);
+	return SPHIP_OK;
+}
+
+// steps 1-6 of "temporal reprojection" (include/spath_hip.h) on device pointers; the arguments are checked by the callers
+int reproject_dev(sphip_ctx* c, const sphip_reproject* P, const sphip_camera* prev, size_t w, size_t h, const void* rays_cur, const void* gbuf_cur,
+                  const void* rays_prev, const void* gbuf_prev, const void* mean_prev, const void* hist_prev, void* out_mean, void* out_hist,
+                  hipStream_t st) {
+	const sp::ViewArgs v = view_args(prev);
+	sp::ReprojArgs A{};
+	A.rays_cur = (const float*)rays_cur; A.gbuf_cur = (const float4*)gbuf_cur;
+	A.rays_prev = (const float*)rays_prev; A.gbuf_prev = (const float4*)gbuf_prev;
+	A.mean_prev = (const float*)mean_prev; A.hist_prev = (const float*)hist_prev;
+	A.out_mean = (float*)out_mean; A.out_hist = (float*)out_hist;
+	A.w = (uint32_t)w; A.h = (uint32_t)h; A.n = (uint32_t)(w * h);
+	A.px = v.px; A.py = v.py; A.pz = v.pz;
+	A.cos_y = v.cos_y; A.sin_y = v.sin_y; A.cos_x = v.cos_x; A.sin_x = v.sin_x; A.focal = v.focal;
+	A.xo = v.x_max - v.h_x_step; A.x_step = v.x_step;
+	A.yo = v.y_max - v.h_y_step; A.y_step = v.y_step;
+	A.max_history = P->max_history; A.normal_min = P->normal_min; A.plane_tol = P->plane_tol;
+	hipLaunchKernelGGL(sp::k_reproject, dim3((unsigned)((w * h + 255) / 256)), dim3(256), 0, st, A);
+	HIP_TRY(c, hipGetLastError());
+	return SPHIP_OK;
+}
 
 int check_denoise(sphip_ctx* c, const sphip_denoise* P) {
 	if (!P) return fail(c, SPHIP_E_INVALID, "null sphip_denoise");
@@ -1584,7 +1636,12 @@ int accum_denoise_dev(sphip_ctx* c, sphip_ctx* k, const sphip_denoise* P, const 
 	uint32_t* rgba = (uint32_t*)k->rgba.p;
 	float* rgb = want_rgb ? (float*)k->accum.p : nullptr;
 	const bool k0 = P->iterations == 0;
-	if (!have4) {
+	if (!have4 && c->acc_hist_on) {                    // a reprojected history (single-device, plain): the blended mean, no variance
+		if ((rc = temporal_resolve_dev(k, n, c->acc_sum.p, c->acc_total, c->rp_hmean.p, c->rp_hist.p, nullptr, c->rp_pmean.p, st, false))) return rc;
+		hipLaunchKernelGGL(sp::k_dn_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->rp_pmean.p, (const float*)nullptr,
+		                   (uint32_t)n, (float4*)c->dn_a.p, k0 ? rgba : nullptr, k0 ? rgb : nullptr);
+		k->stats.n_launches += 2;
+	} else if (!have4) {
 		hipLaunchKernelGGL(sp::k_dn_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->acc_sum.p,
 		                   c->adp_on ? (const uint32_t*)c->adp_cnt.p : nullptr, (uint32_t)c->acc_total, c->adp_on ? (const double*)c->adp_s12.p : nullptr,
 		                   (uint32_t)n, (float4*)c->dn_a.p, k0 ? rgba : nullptr, k0 ? rgb : nullptr);
@@ -2049,6 +2106,9 @@ int sphip_accum_step(sphip_t* c, size_t n_samples, uint8_t* out_rgba, float* out
 				RenderCall call{ c->acc_rays.p, n, n_samples, c->acc_seed, SPHIP_MODE_PT, c->acc_flags, c->rgba.p, out_mean ? c->accum.p : nullptr, st };
 				call.prog = &p; call.cam = c->acc_has_cam ? &ca : nullptr;
 				if ((rc2 = launch_render(c, call))) return rc2;
+				// a reprojected history: the frame is the blend of it with the sum (sp_reproject.h); pixels without one keep their bits
+				if (c->acc_hist_on && (rc2 = temporal_resolve_dev(c, n, c->acc_sum.p, c->acc_total + n_samples, c->rp_hmean.p, c->rp_hist.p,
+				                                                  c->rgba.p, out_mean ? c->accum.p : nullptr, st, true))) return rc2;
 			}
 			if ((rc2 = download_frame(c, n, out_rgba, out_mean, st))) return rc2;
 			c->adp_nact = c->adp_nact_rb;
@@ -2432,6 +2492,109 @@ int sphip_accum_denoise(sphip_t* c, const sphip_denoise* P, uint8_t* out_rgba, f
 	}
 	if (rc) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return rc; }
 	c->timed_upload = c->timed_download = false;
+	return SPHIP_OK;
+}
+
+void sphip_reproject_defaults(sphip_reproject* out) {
+	if (!out) return;
+	std::memset(out, 0, sizeof *out);
+	out->max_history = 32.0f;      // calibrated with tools/reproject_calibrate.py
+	out->normal_min = 0.5f;
+	out->plane_tol = 0.1f;
+}
+
+int sphip_reproject_device(sphip_t* c, const sphip_reproject* P, const sphip_camera* cam_prev, size_t w, size_t h, const void* d_rays_cur,
+                           const void* d_gbuf_cur, const void* d_rays_prev, const void* d_gbuf_prev, const void* d_mean_prev, const void* d_hist_prev,
+                           void* d_out_mean, void* d_out_hist, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if ((rc = check_reproject(c, P))) return rc;
+	if ((rc = single_device_entry(c))) return rc;
+	if (!cam_prev || !d_rays_cur || !d_gbuf_cur || !d_rays_prev || !d_gbuf_prev || !d_mean_prev || !d_hist_prev || !d_out_mean || !d_out_hist)
+		return fail(c, SPHIP_E_INVALID, "null camera, input or output pointer");
+	if (w == 0 || h == 0 || w >= (1u << 30) || h >= (1u << 30) || w * h > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "bad image size (w=%zu h=%zu)", w, h);
+	if (cam_prev->res_x != w || cam_prev->res_y != h)
+		return fail(c, SPHIP_E_INVALID, "w x h = %zux%zu differs from the previous camera's %ux%u", w, h, cam_prev->res_x, cam_prev->res_y);
+	if (((uintptr_t)d_gbuf_cur | (uintptr_t)d_gbuf_prev) & 15u) return fail(c, SPHIP_E_INVALID, "a G-buffer pointer is not 16-byte aligned");
+	HIP_TRY(c, hipSetDevice(c->device));
+	return reproject_dev(c, P, cam_prev, w, h, d_rays_cur, d_gbuf_cur, d_rays_prev, d_gbuf_prev, d_mean_prev, d_hist_prev, d_out_mean, d_out_hist,
+	                     (hipStream_t)stream);
+}
+
+int sphip_temporal_resolve_device(sphip_t* c, size_t n, const void* d_sum, uint32_t n_samples, const void* d_hist_mean, const void* d_hist,
+                                  void* d_out_rgba, void* d_out_mean, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	if (!d_sum || (!d_out_rgba && !d_out_mean)) return fail(c, SPHIP_E_INVALID, "null sum pointer, or no output");
+	if ((d_hist_mean == nullptr) != (d_hist == nullptr)) return fail(c, SPHIP_E_INVALID, "a history is both its mean and its count, or neither");
+	if (n == 0 || n > 0xffffffffull || n_samples == 0) return fail(c, SPHIP_E_INVALID, "n = %zu pixels of %u samples: both must be positive", n, n_samples);
+	HIP_TRY(c, hipSetDevice(c->device));
+	return temporal_resolve_dev(c, n, d_sum, n_samples, d_hist_mean, d_hist, d_out_rgba, d_out_mean, (hipStream_t)stream, false);
+}
+
+int sphip_accum_reproject(sphip_t* c, const sphip_camera* cam_new, uint64_t seed, const sphip_reproject* P) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if (!cam_new) return fail(c, SPHIP_E_INVALID, "null camera");
+	if ((rc = check_reproject(c, P))) return rc;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "sphip_accum_reproject needs a single-device context (sphip_create)");
+	if (!c->acc_on) return fail(c, SPHIP_E_STATE, "sphip_accum_reproject called with no accumulation begun");
+	if (c->acc_stale) return fail(c, SPHIP_E_STATE, "the scene changed since sphip_accum_begin: begin a new accumulation");
+	if (!c->acc_has_cam) return fail(c, SPHIP_E_STATE, "sphip_accum_reproject needs an accumulation begun with a camera, not with rays");
+	if (c->adp_on) return fail(c, SPHIP_E_STATE, "sphip_accum_reproject needs a plain accumulation, not an adaptive one");
+	if (c->acc_total == 0) return fail(c, SPHIP_E_STATE, "sphip_accum_reproject needs an accumulation with at least one step");
+	if (cam_new->res_x != c->acc_w || cam_new->res_y != c->acc_h)
+		return fail(c, SPHIP_E_INVALID, "the camera's %ux%u differs from the accumulation's %zux%zu", cam_new->res_x, cam_new->res_y, c->acc_w, c->acc_h);
+	if (c->acc_w >= (1u << 30) || c->acc_h >= (1u << 30)) return fail(c, SPHIP_E_INVALID, "image too wide or tall to reproject");
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	const size_t w = c->acc_w, h = c->acc_h, n = w * h;
+	auto body = [&]() -> int {
+		int r;
+		if ((r = ensure(c, c->rp_hmean, n * 12)) || (r = ensure(c, c->rp_hist, n * 4)) || (r = ensure(c, c->rp_prays, n * 24)) ||
+		    (r = ensure(c, c->rp_pgbuf, n * 32)) || (r = ensure(c, c->rp_pmean, n * 12)) || (r = ensure(c, c->rp_phist, n * 4)) ||
+		    (r = ensure(c, c->dn_gbuf, n * 32))) return r;
+		// the view being left: its G-buffer (cached, or built now), its rays, and the accumulation as a (mean, count) pair
+		if (!c->dn_gbuf_ok && (r = gbuffer_dev(c, c->acc_rays.p, n, c->acc_flags, c->dn_gbuf.p, st))) return r;
+		HIP_TRY(c, hipMemcpyAsync(c->rp_pgbuf.p, c->dn_gbuf.p, n * 32, hipMemcpyDeviceToDevice, st));
+		HIP_TRY(c, hipMemcpyAsync(c->rp_prays.p, c->acc_rays.p, n * 24, hipMemcpyDeviceToDevice, st));
+		hipLaunchKernelGGL(sp::k_history, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->acc_sum.p,
+		                   (float)(1.0 / (double)c->acc_total), (float)c->acc_total, c->acc_hist_on ? (const float*)c->rp_hmean.p : nullptr,
+		                   c->acc_hist_on ? (const float*)c->rp_hist.p : nullptr, (uint32_t)n, (float*)c->rp_pmean.p, (float*)c->rp_phist.p);
+		HIP_TRY(c, hipGetLastError());
+		// the new view: rays over the old ones, G-buffer over the old one, then the history the steps to come blend with
+		c->dn_gbuf_ok = false;
+		if ((r = launch_viewport(c, cam_new, c->acc_rays.p, st)) || (r = gbuffer_dev(c, c->acc_rays.p, n, c->acc_flags, c->dn_gbuf.p, st))) return r;
+		c->dn_gbuf_ok = true;
+		if ((r = reproject_dev(c, P, &c->acc_cam, w, h, c->acc_rays.p, c->dn_gbuf.p, c->rp_prays.p, c->rp_pgbuf.p, c->rp_pmean.p, c->rp_phist.p,
+		                       c->rp_hmean.p, c->rp_hist.p, st))) return r;
+		HIP_TRY(c, hipStreamSynchronize(st));
+		return SPHIP_OK;
+	};
+	if ((rc = body())) {                           // the old view's state is partly overwritten: nothing can continue from it
+		(void)hipStreamSynchronize(st); (void)hipGetLastError();
+		c->acc_on = false;
+		return rc;
+	}
+	c->acc_cam = *cam_new;
+	c->acc_seed = seed;
+	c->acc_total = 0;                              // the next step's sample_base: the sum buffer's contents are not read
+	c->acc_hist_on = true;
+	c->timed_upload = c->timed_download = false;
+	return SPHIP_OK;
+}
+
+int sphip_accum_history(sphip_t* c, float* out_hist) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->acc_on) return fail(c, SPHIP_E_STATE, "sphip_accum_history called with no accumulation begun");
+	if (!out_hist) return fail(c, SPHIP_E_INVALID, "null history output");
+	const size_t n = c->acc_w * c->acc_h;
+	if (!c->acc_hist_on) {
+		std::fill(out_hist, out_hist + n, 0.0f);
+		return SPHIP_OK;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipMemcpyAsync(out_hist, c->rp_hist.p, n * 4, hipMemcpyDeviceToHost, c->own_stream));
+	HIP_TRY(c, hipStreamSynchronize(c->own_stream));
 	return SPHIP_OK;
 }
 

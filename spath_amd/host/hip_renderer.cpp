@@ -78,6 +78,11 @@ struct hip_r : public basic_renderer {
 	// the lens is the context's, and the one an accumulation was begun with joins its key
 	bool cam_samples;
 	sphip_lens lens, acc_lens;
+	// temporal reprojection (set_reproject) of the progressive mode on the camera path: a camera move keeps the accumulation as history
+	// (sphip_accum_reproject) where it would begin anew; rp_moves: the moves reprojected so far, which key the seeds of the new samples
+	bool rp_on;
+	sphip_reproject rp;
+	unsigned long long rp_moves;
 	struct part { std::vector<float> v; uint32_t w, h; part() : w(0), h(0) {} };      // empty: not set; w, h: an image's size
 	part parts[N_PARTS];
 
@@ -86,7 +91,8 @@ struct hip_r : public basic_renderer {
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
-	                                                                   cam_samples(false) {
+	                                                                   cam_samples(false), rp_on(false), rp_moves(0) {
+		std::memset(&rp, 0, sizeof rp);
 		std::memset(&acc_camera, 0, sizeof acc_camera);
 		std::memset(&lens, 0, sizeof lens);
 		std::memset(&acc_lens, 0, sizeof acc_lens);
@@ -155,7 +161,7 @@ struct hip_r : public basic_renderer {
 	void begin(const float* rays, const sphip_camera* cam, size_t w, size_t h, int flags) {
 		have_raw = false;
 		if (adp.rel_error >= 0.0) check(sphip_accum_begin_adaptive(ctx, rays, cam, w, h, seed, flags, &adp), "accum_begin_adaptive");
-		else if (dn_on) {
+		else if (dn_on && !rp_on) {                // with reprojection on the accumulation stays plain: the filter runs without the variance
 			sphip_adaptive never;                 // the variance for the filter, the image of a plain accumulation
 			std::memset(&never, 0, sizeof never);
 			never.min_samples = 0xffffffffu;
@@ -185,8 +191,18 @@ struct hip_r : public basic_renderer {
 		const sphip_camera c = camera_args();
 		const int f = (cam_samples ? (flags | SPHIP_FLAG_CAMERA_SAMPLES) : flags) | table_flags(mode);
 		if (progressive && mode == SPHIP_MODE_PT) {
-			if (!(same_accumulation(c.res_x, c.res_y, f) && acc_cam && std::memcmp(&c, &acc_camera, sizeof c) == 0 &&
-			      std::memcmp(&lens, &acc_lens, sizeof lens) == 0)) {
+			const bool same = same_accumulation(c.res_x, c.res_y, f) && acc_cam && std::memcmp(&lens, &acc_lens, sizeof lens) == 0;
+			if (same && std::memcmp(&c, &acc_camera, sizeof c) == 0) {
+				// the view stands still: the accumulation goes on
+			} else if (same && rp_on && adp.rel_error < 0.0) {
+				// only the camera moved (set_delta_mov / set_delta_rot / set_delta_focal): the accumulation becomes the new view's history
+				acc_live = false;
+				have_raw = false;
+				++rp_moves;
+				check(sphip_accum_reproject(ctx, &c, seed + rp_moves, &rp), "accum_reproject");
+				acc_live = true;
+				acc_camera = c;
+			} else {
 				acc_live = false;
 				begin(0, &c, c.res_x, c.res_y, f);
 				begun(c.res_x, c.res_y, true, f);
@@ -332,12 +348,23 @@ namespace hip_renderer {
 
 	void set_adaptive(scene::renderer* r, double t, double floor, unsigned min_samples) {
 		if (hip_r* p = dynamic_cast<hip_r*>(r)) {
+			if (t >= 0.0 && p->rp_on) throw std::runtime_error("hip_renderer: set_adaptive: sphip_accum_reproject needs a plain accumulation, not an adaptive one");
 			p->adp.rel_error = t < 0.0 ? -1.0 : t;
 			p->adp.floor = floor;
 			p->adp.min_samples = min_samples;
 			p->adp.reserved = 0;
 			p->acc_live = false;
 		}
+	}
+
+	void set_reproject(scene::renderer* r, const sphip_reproject* p) {
+		hip_r* q = dynamic_cast<hip_r*>(r);
+		if (!q) return;
+		if (p && q->adp.rel_error >= 0.0)          // what the library answers to sphip_accum_reproject on an adaptive accumulation
+			throw std::runtime_error("hip_renderer: set_reproject: sphip_accum_reproject needs a plain accumulation, not an adaptive one");
+		if (q->rp_on != (p != 0) && q->dn_on) q->acc_live = false;     // the rule the accumulation begins with changes
+		q->rp_on = p != 0;
+		if (p) q->rp = *p;
 	}
 
 	void set_denoise(scene::renderer* r, const sphip_denoise* p) {

@@ -88,6 +88,14 @@ namespace hip_renderer {
 	// adaptive rule the accumulation is begun with one that never stops a pixel (min_samples = UINT32_MAX), so that the filter has
 	// the variance; the raw image is bit-identical to a plain accumulation's.  NULL turns it off (the default).
 	extern void set_denoise(scene::renderer* r, const sphip_denoise* p);
+	// Temporal reprojection of the progressive mode (include/spath_hip.h: sphip_accum_reproject): with p != NULL (copied), a camera move
+	// (set_delta_mov / set_delta_rot / set_delta_focal) between two render_own_viewport frames no longer begins a new accumulation: the
+	// old view's accumulation is reprojected into the new view and blended with its samples, drawn under seed + the number of moves
+	// reprojected so far.  Every other cause still begins anew: a scene, table or image change, a resize, the lens, the seed, the flags,
+	// the adaptive rule, and render() (the caller's rays carry no camera).  With denoising on, the accumulation is plain and the filter
+	// runs without the variance.  Refused (std::runtime_error with the library's message) while an adaptive rule is set, as set_adaptive
+	// is while this is on.  NULL turns it off (the default).
+	extern void set_reproject(scene::renderer* r, const sphip_reproject* p);
 	// the raw (not denoised) image of the last progressive step with denoising on; NULL if r is not a hip renderer or there is none
 	extern const scene::bitmap* raw_bitmap(scene::renderer* r);
 	// per-pixel sample counts (w*h, image order) and active pixels of the current accumulation; false if r is not a hip renderer

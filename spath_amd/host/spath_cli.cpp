@@ -6,7 +6,12 @@
 //   spath_cli [--scene default|FILE.bin] [--w 640 --h 480] [--spp 128] [--mode pt|flat]
 //             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--tex FILE.bin --uv FILE.bin] [--nmap FILE.bin --uv FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
-//              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]]
+//              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]
+//              [--reproject [MAXH[,NMIN[,PTOL]]] --then-move X,Y,Z[,RX,RY] [--spp-after K] [--first-out FILE]]]
+// --reproject [MAXH[,NMIN[,PTOL]]] --then-move X,Y,Z[,RX,RY]: with --progressive (and the device-generated viewport), temporal
+//   reprojection (include/spath_hip.h: sphip_accum_reproject; the library's defaults for what is left out): after the --spp samples of
+//   the last frame the camera moves by X,Y,Z and turns by RX,RY, the accumulation is reprojected into the new view and --spp-after K
+//   (default: one step) more samples are blended with it; --out is then that image, --first-out FILE the first view's
 // --progressive n: render the --spp samples of a frame as progressive steps of n samples (the last takes the remainder), the way
 //   a viewer refines a still view; prints every step, and the final image is byte-identical to the one rendered in one go
 // --adaptive T[,FLOOR[,MIN]]: with --progressive, stop converged pixels after each step (include/spath_hip.h: sphip_adaptive;
@@ -234,7 +239,12 @@ int main(int argc, char** argv) {
 		double adp_t = -1.0, adp_floor = 0.1;                        // --adaptive defaults: FLOOR 0.1, MIN 8
 		unsigned adp_min = 8;
 		std::string counts_path, raw_path;
-		bool denoise = false;
+		bool denoise = false, reproject = false, then_move = false;
+		sphip_reproject rp;
+		sphip_reproject_defaults(&rp);
+		float mv[5] = { 0, 0, 0, 0, 0 };
+		size_t spp_after = 0;
+		std::string first_path;
 		sphip_denoise dn;
 		sphip_denoise_defaults(&dn);
 		unsigned long long seed = 1;
@@ -299,6 +309,35 @@ int main(int argc, char** argv) {
 				}
 			}
 			else if (k == "--raw-out") { need(1); raw_path = argv[++i]; }
+			else if (k == "--reproject") {
+				reproject = true;
+				if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {     // optional MAXH[,NMIN[,PTOL]]
+					const char* p = argv[++i];
+					char* e = 0;
+					rp.max_history = std::strtof(p, &e);
+					if (e == p) throw std::runtime_error("bad --reproject value (MAXH[,NMIN[,PTOL]])");
+					if (*e == ',') { p = e + 1; rp.normal_min = std::strtof(p, &e); if (e == p) throw std::runtime_error("bad --reproject NMIN"); }
+					if (*e == ',') { p = e + 1; rp.plane_tol = std::strtof(p, &e); if (e == p) throw std::runtime_error("bad --reproject PTOL"); }
+					if (*e) throw std::runtime_error("bad --reproject value (MAXH[,NMIN[,PTOL]])");
+				}
+			}
+			else if (k == "--then-move") {
+				need(1);
+				then_move = true;
+				const char* p = argv[++i];
+				int got = 0;
+				for (; got < 5; ++got) {
+					char* e = 0;
+					mv[got] = std::strtof(p, &e);
+					if (e == p) throw std::runtime_error("bad --then-move value (X,Y,Z[,RX,RY])");
+					p = e;
+					if (*p != ',') { ++got; break; }
+					++p;
+				}
+				if (*p || (got != 3 && got != 5)) throw std::runtime_error("bad --then-move value (X,Y,Z[,RX,RY])");
+			}
+			else if (k == "--spp-after") { need(1); spp_after = (size_t)std::atoll(argv[++i]); }
+			else if (k == "--first-out") { need(1); first_path = argv[++i]; }
 			else if (k == "--frames") { need(1); frames = std::atoi(argv[++i]); }
 			else if (k == "--out") { need(1); out_path = argv[++i]; }
 			else if (k == "--device-viewport") device_viewport = true;
@@ -311,6 +350,10 @@ int main(int argc, char** argv) {
 		}
 		if (denoise && !(progressive && mode == "pt")) throw std::runtime_error("--denoise needs --progressive n and --mode pt");
 		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
+		if (reproject != then_move) throw std::runtime_error("--reproject and --then-move go together");
+		if (reproject && !(progressive && mode == "pt")) throw std::runtime_error("--reproject needs --progressive n and --mode pt");
+		if ((spp_after || !first_path.empty()) && !reproject) throw std::runtime_error("--spp-after and --first-out need --reproject");
+		if (reproject) device_viewport = true;                          // the reprojection needs the camera
 		if (!env_arg.empty() && mode != "pt") throw std::runtime_error("--env needs --mode pt");
 		if (!env_arg.empty() && nee && !mis) throw std::runtime_error("--env works with the plain estimator and with --mis, not with --nee alone");
 		if (!nmap_arg.empty() && uv_arg.empty()) throw std::runtime_error("--nmap needs --uv (the UV table addresses the normal map)");
@@ -374,6 +417,7 @@ int main(int argc, char** argv) {
 		if (!counts_path.empty() && !(progressive && mode == "pt")) throw std::runtime_error("--counts-out needs --progressive n and --mode pt");
 		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);
 		hip_renderer::set_denoise(r.get(), denoise ? &dn : 0);
+		hip_renderer::set_reproject(r.get(), reproject ? &rp : 0);       // throws with --adaptive: the library's refusal
 		std::printf("Current renderer: %s [%d device(s)]\n", r->get_description(), hip_renderer::device_count(r.get()));     // main.cpp:30-32
 		for (size_t k = 0; k < moves.size(); ++k) {
 			if (moves[k].first == 'm') r->set_delta_mov(moves[k].second);
@@ -425,6 +469,20 @@ int main(int argc, char** argv) {
 			}
 			std::fclose(o);
 		};
+		if (reproject) {                                                // the camera moves, the accumulation follows it
+			if (!first_path.empty()) write_image(first_path, bmp);
+			r->set_delta_mov(geom::vec3(mv[0], mv[1], mv[2]));
+			if (mv[3] != 0.0f || mv[4] != 0.0f) r->set_delta_rot(geom::vec3(mv[3], mv[4], 0));
+			const size_t more = spp_after ? spp_after : progressive;
+			for (size_t done = 0, step = 0; done < more; ++step) {
+				const size_t n = std::min(progressive, more - done);
+				hip_renderer::render_own_viewport(r.get(), tris.data(), mats.data(), tris.size(), n, bmp, false);
+				done += n;
+				double kms = 0;
+				hip_renderer::last_stats(r.get(), &kms, 0);
+				std::printf("  after the move, step %zu: %zu spp (%zu new so far), kernel %.3f ms\n", step, n, done, kms);
+			}
+		}
 		if (!out_path.empty()) write_image(out_path, bmp);
 		if (!raw_path.empty()) {
 			const scene::bitmap* raw = hip_renderer::raw_bitmap(r.get());

@@ -109,6 +109,8 @@ class HipRenderer(BasicRenderer):
             raise ValueError("denoising needs progressive=True")
         self.denoise = None if denoise is False or denoise is None else capi.Denoise.make(None if denoise is True else denoise)
         self.raw_bitmap = Bitmap()
+        self.reproject = None                                  # set_reproject
+        self._moves = 0
         self._scene_key = None
         self._accum_key = None
         self.last_stats = None
@@ -172,6 +174,23 @@ class HipRenderer(BasicRenderer):
         set every path-traced frame carries capi.FLAG_SPECULAR (render_flat never does).  Without a table the flags are the caller's."""
         self._set_part("spec", spec)
 
+    def set_reproject(self, params=True):
+        """Temporal reprojection of the progressive mode, like hip_renderer::set_reproject: with params True (the library's defaults), a
+        capi.Reproject, a (max_history, normal_min, plane_tol) tuple or a dict of its fields, a camera move (set_delta_mov /
+        set_delta_rot / set_delta_focal) between two render_own_viewport frames no longer begins a new accumulation: the old view's
+        accumulation is reprojected into the new view (capi.Context.accum_reproject) and blended with its samples, drawn under seed +
+        the number of moves reprojected so far.  Every other cause still begins anew: a scene, table or image change, a resize, the
+        seed, the flags, and render() (the caller's rays carry no camera).  With denoising on, the accumulation is plain and the
+        filter runs without the variance.  Refused with the library's message while an adaptive rule is set.  None or False: off."""
+        if params is None or params is False:
+            self.reproject = None
+            return
+        if not self.progressive:
+            raise ValueError("temporal reprojection needs progressive=True")
+        if self.adaptive is not None:
+            raise capi.SpathHipError("sphip_accum_reproject failed [-3]: sphip_accum_reproject needs a plain accumulation, not an adaptive one")
+        self.reproject = capi.Reproject.make(None if params is True else params)
+
     def _flags(self, mode):
         """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY, FLAG_TEXTURE and
         FLAG_NORMAL_MAP on while their tables, the maps or the atlas are set, and never on the flat pass"""
@@ -205,16 +224,20 @@ class HipRenderer(BasicRenderer):
             self._scene_key = key
 
     def _begin_rule(self):
-        if self.adaptive is None and self.denoise is not None:
+        if self.adaptive is None and self.denoise is not None and self.reproject is None:
             return NEVER_STOP
         return self.adaptive
 
-    def _accum_step(self, key, begin, n_samples, out):
+    def _accum_step(self, key, begin, n_samples, out, move=None):
         if self.denoise is not None:
-            key = key + ("denoise",)                           # the rule it begins with; the parameters apply to any step
+            key = key + ("denoise", self.reproject is not None)   # the rule it begins with; the parameters apply to any step
         if key != self._accum_key:
-            self._accum_key = None
-            begin()
+            old, self._accum_key = self._accum_key, None
+            # move: only the camera (key[1], at an unchanged resolution) differs from the live accumulation's key
+            if move is not None and old is not None and old[0] == key[0] == "cam" and old[2:] == key[2:]:
+                move()
+            else:
+                begin()
             self._accum_key = key
         try:
             out.values, _ = self.ctx.accum_step(n_samples)
@@ -255,9 +278,13 @@ class HipRenderer(BasicRenderer):
         if self.progressive and not flat:
             ca = capi.CameraArgs.from_camera(self.vc)
             flags = self._flags(capi.MODE_PT)
-            key = ("cam", bytes(ca), self._scene_key, self.seed, flags, self.adaptive)
+            key = ("cam", bytes(ca), (ca.res_x, ca.res_y), self._scene_key, self.seed, flags, self.adaptive)
+
+            def move():
+                self._moves += 1
+                self.ctx.accum_reproject(self.vc, self.seed + self._moves, self.reproject)
             self._accum_step(key, lambda: self.ctx.accum_begin(cam=self.vc, seed=self.seed, flags=flags, adaptive=self._begin_rule()),
-                             max(int(n_samples), 1), out)
+                             max(int(n_samples), 1), out, move if self.reproject is not None and self.adaptive is None else None)
             return
         out.values = self.ctx.render_camera(self.vc, max(int(n_samples), 1), seed=self.seed, mode=capi.MODE_FLAT if flat else capi.MODE_PT,
                                             flags=self._flags(capi.MODE_FLAT if flat else capi.MODE_PT))
