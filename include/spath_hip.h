@@ -140,7 +140,7 @@ int  sphip_create(int device_id, sphip_t** out);
  *   A device may be listed more than once (several shards on one GPU: how a one-GPU box exercises this path).
  *   SPATH_HIP_GATHER=rccl|peer overrides the choice of exchange.
  * The host-pointer entry points (sphip_set_scene, sphip_render, sphip_render_camera, sphip_accum_begin, sphip_accum_step,
- * sphip_accum_gbuffer, sphip_accum_denoise, sphip_get_stats, sphip_description, sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
+ * sphip_accum_gbuffer, sphip_accum_denoise, sphip_accum_display, sphip_get_stats, sphip_description, sphip_destroy) accept such a context; the device-pointer entry points need a single-device context (SPHIP_E_STATE). */
 int  sphip_create_multi(const int* device_ids, int n_devices, sphip_t** out);
 int  sphip_device_count(const sphip_t* ctx);        /* devices behind ctx (1 for sphip_create) */
 void sphip_destroy(sphip_t* ctx);
@@ -456,6 +456,88 @@ int sphip_accum_reproject(sphip_t* ctx, const sphip_camera* cam_new, uint64_t se
 /* The per-pixel history counts of the current accumulation in image order (all 0 for one without history).  Blocking; SPHIP_E_STATE when
  * no accumulation has been begun. */
 int sphip_accum_history(sphip_t* ctx, float* out_hist /* w*h */);
+
+/* ---- display transform: the last stage of the viewer pipeline.  Every render, step, denoise and blend above
+ * ends in vec3::clamp and scene::vec3_RGBA: a linear clamp to [0, 1] and * 255 + 0.5, which is the reference's and right for its closed
+ * room, and which shows an HDR sky, a small bright emitter or a lamp as a white sheet.  This stage turns a mean image (f32 rgb radiance)
+ * into pixels the way a viewer expects: an exposure (given, or metered from the image), a tone curve, then the linear or the sRGB
+ * encoding.  A post-process over the mean: it touches no scan, no integrator and no sum.  On the device every operation is an f32
+ * + - * / (IEEE division), a comparison, a select, a bit cast or an integer operation in the order below, nothing fused, so the output is
+ * reproducible bit for bit; bits(x) is the f32's bit pattern as a u32.
+ *
+ * Luminance:  lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *
+ * Histogram (metering): 2048 u32 bins over the pixels of the mean.  With l = lum(c): a pixel with !(l > 0) (zero, negative, NaN) counts in
+ * bin 0, any other in bin bits(l) >> 20 (+inf: bin 2040).  The bin is the f32 exponent and the top three mantissa bits: a logarithmic
+ * histogram, eight bins per octave, without a transcendental function; a sum of integers, the same in whatever order it is formed.
+ *
+ * Exposure from a histogram: host arithmetic in double, in this order.  The valid bins are b = 8 .. 2039 (bin 0, the denormals' bins 1 .. 7
+ * and infinity's are ignored), and a valid bin stands for the level
+ *     L[b] = (double)((int)(b >> 3) - 127) + ((double)(b & 7) + 0.5) / 8.0
+ * the piecewise-linear (Mitchell) log2 of the bin's centre, exact in double.  N = the pixels in valid bins; N == 0: exposure 1.
+ *     lo = (u64)((double)low * (double)N);   hi = N - (u64)((1.0 - (double)high) * (double)N);   hi <= lo: lo = 0, hi = N
+ * The valid pixels are ranked 0 .. N-1 in ascending bin order; bins in ascending order, `part` = the number of the bin's pixels whose rank
+ * lies in [lo, hi):  M += part;  S += (double)part * L[b]  (M a u64, S a double from 0.0).  Then
+ *     mean = S / (double)M;   x = -mean clamped to [-126, 126];   f = floor(x);   E = (float)((double)key * ldexp(1.0 + (x - f), (int)f))
+ * ldexp of 1 + frac is the exact inverse of L, so no log2 or exp2 of any libm is called.  The metered level lies within Mitchell's
+ * 0.086 of a true log-average (about 6 % in exposure).
+ *
+ * Transform of a pixel c with exposure E:  v = c * E per channel, then the curve
+ *     SPHIP_CURVE_CLAMP     v
+ *     SPHIP_CURVE_REINHARD  extended Reinhard on luminance with white point w:  l = lum(v);  !(l > 0): v;  else
+ *                           s = (1.0f + l / (w * w)) / (1.0f + l);  v = v * s per channel  (l = w maps to luminance 1, up to rounding)
+ *     SPHIP_CURVE_FILMIC    Narkowicz's fit of the ACES curve, per channel x:
+ *                           (x * ((2.51f * x) + 0.03f)) / ((x * ((2.43f * x) + 0.59f)) + 0.14f)
+ * then vec3::clamp (x > 1 ? 1 : (x < 0 ? 0 : x), which lets a NaN through): this triple is the float output, display-linear.  Then
+ *     SPHIP_ENCODE_LINEAR   scene::vec3_RGBA, as every render
+ *     SPHIP_ENCODE_SRGB     the code of a channel x = the number of k in 1 .. 255 with x >= T[k] (an 8-step binary search; a NaN is 0),
+ *                           T[k] = the f32 nearest to the inverse sRGB transfer function at (k - 0.5) / 255.  The 255 values are literals
+ *                           (spath_amd/csrc/sp_srgb_table.h, sphip_srgb_thresholds): the table is the contract, no pow is evaluated
+ * Alpha is 0.  A non-finite input goes where IEEE arithmetic takes it (inf / inf is a NaN under either curve, shown as 0).
+ * With E = 1, SPHIP_CURVE_CLAMP and SPHIP_ENCODE_LINEAR the RGBA8 is, bit for bit, what every render and step writes for that mean. */
+enum { SPHIP_CURVE_CLAMP = 0, SPHIP_CURVE_REINHARD = 1, SPHIP_CURVE_FILMIC = 2 };
+enum { SPHIP_ENCODE_LINEAR = 0, SPHIP_ENCODE_SRGB = 1 };
+typedef struct {
+	float    exposure;     /* > 0, finite: E when the call does not meter */
+	float    white;        /* > 0, finite: Reinhard's white point w (read by that curve only) */
+	uint32_t curve;        /* SPHIP_CURVE_* */
+	uint32_t encode;       /* SPHIP_ENCODE_* */
+	uint32_t reserved[2];  /* must be 0 */
+} sphip_display;
+typedef struct {
+	float    key;          /* > 0, finite: the level the metered log-average is mapped to */
+	float    low, high;    /* 0 <= low < high <= 1: the rank window, as fractions of the valid pixels */
+	uint32_t reserved;     /* must be 0 */
+} sphip_metering;
+
+/* curve FILMIC, encode SRGB, exposure 1, white 4; key 0.18, low 0.5, high 0.95: conventions, not measurements */
+void sphip_display_defaults(sphip_display* out);
+void sphip_metering_defaults(sphip_metering* out);
+/* T[1] .. T[255] into out[0] .. out[254]; needs no GPU */
+void sphip_srgb_thresholds(float out[255]);
+/* The histogram of the n pixels of d_mean (n*3 f32) into d_out_hist (2048 u32; zeroed by the call on the same stream).  Device pointers;
+ * stateless; needs no scene; asynchronous on `stream`; single-device contexts (SPHIP_E_STATE otherwise).  SPHIP_E_INVALID: a NULL
+ * pointer, n == 0 or n >= 2^32. */
+int  sphip_luminance_histogram_device(sphip_t* ctx, size_t n, const void* d_mean, void* d_out_hist /* 2048 u32 */, void* stream);
+/* "Exposure from a histogram" above for a host copy of the 2048 bins.  Host only, no context, no GPU.  SPHIP_E_INVALID (*exposure_out
+ * untouched): a NULL pointer, key not finite or not > 0, low or high outside [0, 1], low >= high, reserved != 0. */
+int  sphip_exposure_from_histogram(const uint32_t* hist, const sphip_metering* m, float* exposure_out);
+/* The transform of the n pixels of d_mean with E = p->exposure: d_out_rgba n*4 u8, d_out_rgb n*3 f32 or NULL; the outputs overlap no
+ * input.  Pointers that are all 16-byte aligned move four pixels per lane as whole vectors; any alignment gives the same bytes.
+ * Stateless, asynchronous, single-device contexts like the histogram.  SPHIP_E_INVALID: a NULL p, d_mean or d_out_rgba, n == 0 or
+ * n >= 2^32, exposure or white not finite or not > 0, an unknown curve or encoding, reserved != 0. */
+int  sphip_display_device(sphip_t* ctx, const sphip_display* p, size_t n, const void* d_mean, void* d_out_rgba, void* d_out_rgb /* or NULL */,
+                          void* stream);
+/* Shows the current accumulation without altering it.  The input is the mean sphip_accum_step would return -- plain, adaptive (each
+ * pixel from its own count) or blended with a history after sphip_accum_reproject -- or, with dn, the output of sphip_accum_denoise(dn)
+ * (which builds and caches the G-buffer on first use, as that call does; without dn no G-buffer is built or read).  With m that image
+ * is metered first and E is the metered exposure; without, p->exposure.  *exposure_out (may be NULL) = the E that was used.  Blocking;
+ * host outputs (out_rgb may be NULL: the display-linear float).  Multi-device contexts are accepted as by sphip_accum_denoise, with the
+ * bytes of one device.  A refusal changes nothing.  SPHIP_E_INVALID: a NULL p or out_rgba, a bad *p, *m or *dn (as the calls above and
+ * sphip_accum_denoise refuse them).  SPHIP_E_STATE: exactly where sphip_accum_denoise returns it. */
+int  sphip_accum_display(sphip_t* ctx, const sphip_display* p, const sphip_metering* m /* NULL: p->exposure as given */,
+                         const sphip_denoise* dn /* NULL: the raw mean */, uint8_t* out_rgba, float* out_rgb /* or NULL */,
+                         float* exposure_out /* or NULL */);
 
 /* ---- next-event estimation (SPHIP_FLAG_NEE): at each of the first four surface hits of a path, one light
  * sample and one shadow ray.  Valid for SPHIP_MODE_PT on every render and accumulation entry point and with the variants 1,

@@ -46,6 +46,8 @@ SYMBOLS = (
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
     "sphip_denoise_defaults", "sphip_gbuffer_device", "sphip_denoise_device", "sphip_accum_gbuffer", "sphip_accum_denoise",
     "sphip_reproject_defaults", "sphip_reproject_device", "sphip_temporal_resolve_device", "sphip_accum_reproject", "sphip_accum_history",
+    "sphip_display_defaults", "sphip_metering_defaults", "sphip_srgb_thresholds", "sphip_luminance_histogram_device",
+    "sphip_exposure_from_histogram", "sphip_display_device", "sphip_accum_display",
     "sphip_set_lens", "sphip_camera_rays_device",
     "sphip_set_specular", "sphip_set_specular_device",
     "sphip_set_vertex_normals", "sphip_set_vertex_normals_device",
@@ -148,6 +150,95 @@ class Reproject(C.Structure):
 
     def as_dict(self):
         return {"max_history": self.max_history, "normal_min": self.normal_min, "plane_tol": self.plane_tol}
+
+
+CURVE_CLAMP, CURVE_REINHARD, CURVE_FILMIC = 0, 1, 2
+ENCODE_LINEAR, ENCODE_SRGB = 0, 1
+CURVES = {"clamp": CURVE_CLAMP, "reinhard": CURVE_REINHARD, "filmic": CURVE_FILMIC}
+LUM_BINS = 2048
+
+
+class Display(C.Structure):
+    """sphip_display: exposure, tone curve and encoding of the display transform (include/spath_hip.h)."""
+    _fields_ = [("exposure", C.c_float), ("white", C.c_float), ("curve", C.c_uint32), ("encode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def defaults(cls):
+        d = cls()
+        load().sphip_display_defaults(C.byref(d))
+        return d
+
+    @classmethod
+    def make(cls, params=None):
+        """None: the library's defaults; a Display as is; a dict overrides some of the defaults (exposure, white, curve -- a CURVE_*
+        or its name --, encode -- an ENCODE_*, or "srgb" / "linear")."""
+        if isinstance(params, cls):
+            return params
+        d = cls.defaults()
+        for k, v in (params or {}).items():
+            if k not in ("exposure", "white", "curve", "encode"):
+                raise ValueError(f"unknown display parameter {k!r}")
+            if k == "curve" and isinstance(v, str):
+                v = CURVES[v]
+            if k == "encode" and isinstance(v, str):
+                v = {"linear": ENCODE_LINEAR, "srgb": ENCODE_SRGB}[v]
+            setattr(d, k, v)
+        return d
+
+    def as_dict(self):
+        return {"exposure": self.exposure, "white": self.white, "curve": self.curve, "encode": self.encode}
+
+
+class Metering(C.Structure):
+    """sphip_metering: the key and the rank window of auto exposure (include/spath_hip.h)."""
+    _fields_ = [("key", C.c_float), ("low", C.c_float), ("high", C.c_float), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls):
+        d = cls()
+        load().sphip_metering_defaults(C.byref(d))
+        return d
+
+    @classmethod
+    def make(cls, params=None):
+        """None: the library's defaults; a Metering as is; a (key, low, high) tuple; a dict overrides some of the defaults."""
+        if isinstance(params, cls):
+            return params
+        if isinstance(params, (tuple, list)):
+            return cls(*[float(x) for x in params], 0)
+        d = cls.defaults()
+        for k, v in (params or {}).items():
+            if k not in ("key", "low", "high", "reserved"):
+                raise ValueError(f"unknown metering parameter {k!r}")
+            setattr(d, k, v)
+        return d
+
+    def as_dict(self):
+        return {"key": self.key, "low": self.low, "high": self.high}
+
+
+def srgb_thresholds():
+    """-> T[1] .. T[255] of the sRGB encoding, float32[255] (sphip_srgb_thresholds; needs no GPU)."""
+    import numpy as np
+    out = np.zeros(255, dtype=np.float32)
+    load().sphip_srgb_thresholds(out.ctypes.data)
+    return out
+
+
+def exposure_from_histogram(hist, metering=None):
+    """sphip_exposure_from_histogram: the exposure the 2048-bin luminance histogram `hist` meters (host only; metering as for
+    Metering.make)."""
+    import numpy as np
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    if hist.shape != (LUM_BINS,):
+        raise ValueError("a luminance histogram has 2048 bins")
+    m = Metering.make(metering)
+    e = C.c_float(0.0)
+    L = load()
+    rc = L.sphip_exposure_from_histogram(hist.ctypes.data, C.byref(m), C.byref(e))
+    if rc != 0:
+        raise SpathHipError(f"sphip_exposure_from_histogram failed [{rc}]: {L.sphip_last_error(None).decode()}")
+    return e.value
 
 
 def gbuffer_dtype():
@@ -259,6 +350,20 @@ def load():
     L.sphip_accum_reproject.argtypes = [vp, C.POINTER(CameraArgs), C.c_uint64, C.POINTER(Reproject)]
     L.sphip_accum_history.restype = C.c_int
     L.sphip_accum_history.argtypes = [vp, vp]
+    L.sphip_display_defaults.restype = None
+    L.sphip_display_defaults.argtypes = [C.POINTER(Display)]
+    L.sphip_metering_defaults.restype = None
+    L.sphip_metering_defaults.argtypes = [C.POINTER(Metering)]
+    L.sphip_srgb_thresholds.restype = None
+    L.sphip_srgb_thresholds.argtypes = [vp]
+    L.sphip_luminance_histogram_device.restype = C.c_int
+    L.sphip_luminance_histogram_device.argtypes = [vp, sz, vp, vp, vp]
+    L.sphip_exposure_from_histogram.restype = C.c_int
+    L.sphip_exposure_from_histogram.argtypes = [vp, C.POINTER(Metering), C.POINTER(C.c_float)]
+    L.sphip_display_device.restype = C.c_int
+    L.sphip_display_device.argtypes = [vp, C.POINTER(Display), sz, vp, vp, vp, vp]
+    L.sphip_accum_display.restype = C.c_int
+    L.sphip_accum_display.argtypes = [vp, C.POINTER(Display), C.POINTER(Metering), C.POINTER(Denoise), vp, vp, C.POINTER(C.c_float)]
     L.sphip_set_lens.restype = C.c_int
     L.sphip_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.sphip_camera_rays_device.restype = C.c_int
@@ -692,6 +797,35 @@ class Context:
         out = np.zeros(w * h, dtype=np.float32)
         self._check(self._L.sphip_accum_history(self._h, out.ctypes.data if w * h else None), "sphip_accum_history")
         return out
+
+    # display transform ------------------------------------------------------------------------
+    def luminance_histogram_device(self, n: int, d_mean: int, d_out_hist: int, stream: int = 0):
+        """The 2048-bin luminance histogram of the n pixels of d_mean (n*3 f32) into d_out_hist (2048 u32); asynchronous."""
+        self._check(self._L.sphip_luminance_histogram_device(self._h, n, d_mean or None, d_out_hist or None, stream or None),
+                    "sphip_luminance_histogram_device")
+
+    def display_device(self, n: int, d_mean: int, d_out_rgba: int, *, d_out_rgb: int = 0, params=None, stream: int = 0):
+        """Exposure, tone curve and encoding of n pixels on device pointers; params as for Display.make; asynchronous."""
+        p = Display.make(params)
+        self._check(self._L.sphip_display_device(self._h, C.byref(p), n, d_mean or None, d_out_rgba or None, d_out_rgb or None, stream or None),
+                    "sphip_display_device")
+
+    def accum_display(self, params=None, metering=None, denoise=None, want_rgb=False):
+        """The current accumulation through the display transform (it is not altered) -> (img, exposure) or (img, rgb, exposure).
+        metering: None = params' exposure as given, True = the default window, else as for Metering.make; denoise: None = the raw
+        mean, True = the default filter, else as for Denoise.make."""
+        import numpy as np
+        w, h = getattr(self, "_accum_shape", (0, 0))
+        p = Display.make(params)
+        m = None if metering is None or metering is False else Metering.make(None if metering is True else metering)
+        dn = None if denoise is None or denoise is False else Denoise.make(None if denoise is True else denoise)
+        out = np.zeros((w * h, 4), dtype=np.uint8)
+        rgb = np.zeros((w * h, 3), dtype=np.float32) if want_rgb else None
+        e = C.c_float(0.0)
+        self._check(self._L.sphip_accum_display(self._h, C.byref(p), C.byref(m) if m is not None else None, C.byref(dn) if dn is not None else None,
+                                                out.ctypes.data if w * h else None, rgb.ctypes.data if want_rgb and w * h else None, C.byref(e)),
+                    "sphip_accum_display")
+        return (out, rgb, e.value) if want_rgb else (out, e.value)
 
     SELFTEST_OUT = {0: ("float32", 2), 1: ("float32", 1), 2: ("float64", 2), 3: ("float32", 3), 4: ("float32", 1), 5: ("uint32", 1), 6: ("float32", 2),
                     7: ("float32", 6), 8: ("float32", 6), 9: ("float32", 4), 10: ("float32", 6), 11: ("float32", 8), 12: ("float32", 6),

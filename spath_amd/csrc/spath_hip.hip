@@ -13,6 +13,7 @@
 #include "sp_adaptive.h"
 #include "sp_denoise.h"
 #include "sp_reproject.h"
+#include "sp_display.h"
 #include "sp_environment.h"
 #include "sp_host_plan.h"
 #include "sp_host_tables.h"
@@ -115,6 +116,9 @@ struct sphip_ctx {
 	// (rp_pmean doubles as the blended mean sphip_accum_denoise filters).  Every one is written whole before it is read.
 	DevBuf rp_hmean, rp_hist, rp_prays, rp_pgbuf, rp_pmean, rp_phist;
 	bool acc_hist_on = false;                     // dropped by every accumulation begin
+	// ---- display transform (sp_display.h, sphip_accum_display): the luminance histogram of a metered call and the display-linear float
+	// output; scratch of one call, nothing another call reads
+	DevBuf dp_hist, dp_rgb;
 	// ---- the per-triangle tables of the scene (sp_host_tables.h: kTriTables; kTableSlots below names each one's members).  One rule for
 	// all: a table belongs to the scene last set and is kept like it, so every set_scene drops it (drop_tables); every device of a
 	// multi-device context keeps the whole table; a render reads it while its flag is set.  What is particular to each:
@@ -1622,14 +1626,20 @@ int dn_clock_start(sphip_ctx* c, hipStream_t st) {
 
 // sphip_accum_denoise on a single-device context (k == c), or on the first device of a multi-device one with the frame's
 // mean/variance (image order) already in c->dn_a.  d_rays: the frame's rays (for a G-buffer build).  Leaves the outputs in
-// k->rgba / k->accum.
+// k->rgba / k->accum.  P == nullptr (sphip_accum_display without a filter): the mean itself, and no G-buffer is built or read.
+// That path is this function's K = 0 form taken as it is, so that the display shows exactly the mean a filter would be given: it still
+// writes the float4 pack into dn_a and a linear-clamp RGBA8 into k->rgba, neither of which the display tail reads (it overwrites
+// k->rgba) -- about 20 B per pixel of stores beside the 12 B the tail needs, the price of one preparation of the mean instead of two.
 int accum_denoise_dev(sphip_ctx* c, sphip_ctx* k, const sphip_denoise* P, const void* d_rays, bool have4, bool use_var, bool want_rgb,
                       hipStream_t st) {
 	const size_t w = c->acc_w, h = c->acc_h, n = w * h;
+	const sphip_denoise raw{};                         // K = 0: the input itself
+	const bool filter = P != nullptr;
+	if (!filter) P = &raw;
 	int rc;
-	if ((rc = ensure(c, c->dn_gbuf, n * 32)) || (rc = ensure(c, c->dn_a, n * 16)) || (rc = ensure(c, c->dn_b, n * 16)) ||
+	if ((filter && (rc = ensure(c, c->dn_gbuf, n * 32))) || (rc = ensure(c, c->dn_a, n * 16)) || (rc = ensure(c, c->dn_b, n * 16)) ||
 	    (rc = ensure(k, k->rgba, n * 4)) || (want_rgb && (rc = ensure(k, k->accum, n * 12)))) return rc;
-	const bool build = !c->dn_gbuf_ok;
+	const bool build = filter && !c->dn_gbuf_ok;
 	if (build) {
 		if ((rc = gbuffer_dev(k, d_rays, n, c->acc_flags, c->dn_gbuf.p, st))) return rc;
 	} else if ((rc = dn_clock_start(k, st))) return rc;
@@ -1660,12 +1670,16 @@ int accum_denoise_dev(sphip_ctx* c, sphip_ctx* k, const sphip_denoise* P, const 
 
 // sphip_accum_denoise on a multi-device context: every device turns its shard's state into {mean, var}; the frame is put together in
 // image order on the host (and, for a G-buffer build, the rays with it), uploaded to the first device and filtered there -- the
-// per-pixel values do not depend on the sharding, so the bytes are those of a single-device context
-int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba, float* out_rgb) {
+// per-pixel values do not depend on the sharding, so the bytes are those of a single-device context.  P == nullptr: the mean itself.
+// post (sphip_accum_display): the display tail that follows on the first device, from root->accum (always written then) into root->rgba
+// and, with out_rgb, root->dp_rgb
+struct DisplayTail { const sphip_display* p; const sphip_metering* m; float* exposure_used; };
+int display_tail(sphip_ctx* k, const sphip_display* p, const sphip_metering* m, size_t n, bool want_rgb, hipStream_t st, float* exposure_used);
+int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba, float* out_rgb, const DisplayTail* post = nullptr) {
 	const int g = (int)c->kids.size();
 	const RowPlan plan(c->acc_w, c->acc_h, g, (size_t)plan_tile_rows(c->acc_h, g));
 	const size_t npix = plan.npix;
-	const bool need_rays = !c->dn_gbuf_ok;
+	const bool need_rays = P != nullptr && !c->dn_gbuf_ok;
 	sphip_ctx* root = c->kids[0];
 	auto body = [&]() -> int {
 		std::vector<float4> img4(npix);
@@ -1692,11 +1706,12 @@ int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba,
 		HIP_TRY(c, hipEventRecord(c->ev_g0, rs));
 		HIP_TRY(c, hipMemcpyAsync(c->dn_a.p, img4.data(), npix * 16, hipMemcpyHostToDevice, rs));
 		if (need_rays) HIP_TRY(c, hipMemcpyAsync(c->dn_rays.p, rays.data(), npix * 24, hipMemcpyHostToDevice, rs));
-		if ((rc = accum_denoise_dev(c, root, P, c->dn_rays.p, true, c->adp_on, out_rgb != nullptr, rs)))
+		if ((rc = accum_denoise_dev(c, root, P, c->dn_rays.p, true, c->adp_on, out_rgb != nullptr || post != nullptr, rs)) ||
+		    (post && (rc = display_tail(root, post->p, post->m, npix, out_rgb != nullptr, rs, post->exposure_used))))
 			return fail(c, rc, "device %d: %s", root->device, root->err.c_str());
 		HIP_TRY(c, hipEventRecord(c->ev_g1, rs));
 		HIP_TRY(c, hipMemcpyAsync(out_rgba, root->rgba.p, npix * 4, hipMemcpyDeviceToHost, rs));
-		if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, root->accum.p, npix * 12, hipMemcpyDeviceToHost, rs));
+		if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, post ? root->dp_rgb.p : root->accum.p, npix * 12, hipMemcpyDeviceToHost, rs));
 		HIP_TRY(c, hipStreamSynchronize(rs));          // img4 and rays are locals
 		root->timed_upload = root->timed_download = false;
 		c->have_render = true;
@@ -1707,6 +1722,107 @@ int multi_accum_denoise(sphip_ctx* c, const sphip_denoise* P, uint8_t* out_rgba,
 	const int rc = body();
 	if (rc) drain_all(c);
 	return rc;
+}
+
+// =====================================================================================================================
+// Display transform (sp_display.h; include/spath_hip.h: sphip_display): metering by a luminance histogram, then exposure, a tone
+// curve and the encoding in one pass over a mean image.  A post-process: it reads a mean and writes pixels, nothing else.
+// =====================================================================================================================
+
+const uint32_t kSrgbBits[255] = { SP_SRGB_THRESHOLD_BITS };
+
+int check_display(sphip_ctx* c, const sphip_display* p) {
+	if (!p) return fail(c, SPHIP_E_INVALID, "null sphip_display");
+	if (!std::isfinite(p->exposure) || !(p->exposure > 0.0f) || !std::isfinite(p->white) || !(p->white > 0.0f) || p->curve > SPHIP_CURVE_FILMIC ||
+	    p->encode > SPHIP_ENCODE_SRGB || p->reserved[0] || p->reserved[1])
+		return fail(c, SPHIP_E_INVALID, "bad sphip_display {exposure %g, white %g, curve %u, encode %u, reserved %u %u}: exposure and white finite "
+		            "and > 0, curve 0..2, encode 0..1, reserved 0", (double)p->exposure, (double)p->white, p->curve, p->encode, p->reserved[0], p->reserved[1]);
+	return SPHIP_OK;
+}
+
+int check_metering(sphip_ctx* c, const sphip_metering* m) {
+	if (!m) return fail(c, SPHIP_E_INVALID, "null sphip_metering");
+	if (!std::isfinite(m->key) || !(m->key > 0.0f) || !(m->low >= 0.0f && m->low <= 1.0f) || !(m->high >= 0.0f && m->high <= 1.0f) ||
+	    !(m->low < m->high) || m->reserved != 0)
+		return fail(c, SPHIP_E_INVALID, "bad sphip_metering {key %g, low %g, high %g, reserved %u}: key finite and > 0, 0 <= low < high <= 1, "
+		            "reserved 0", (double)m->key, (double)m->low, (double)m->high, m->reserved);
+	return SPHIP_OK;
+}
+
+// "exposure from a histogram" of include/spath_hip.h: double, bins in ascending order, no libm beyond floor and ldexp (both exact)
+float exposure_from_histogram(const uint32_t* hist, const sphip_metering* m) {
+	uint64_t N = 0;
+	for (uint32_t b = 8; b < 2040; ++b) N += hist[b];
+	if (N == 0) return 1.0f;
+	uint64_t lo = (uint64_t)((double)m->low * (double)N);
+	uint64_t hi = N - (uint64_t)((1.0 - (double)m->high) * (double)N);
+	if (hi <= lo) { lo = 0; hi = N; }
+	uint64_t M = 0, cum = 0;
+	double S = 0.0;
+	for (uint32_t b = 8; b < 2040; ++b) {
+		const uint64_t first = cum, last = cum + hist[b];          // the bin holds the ranks [first, last)
+		cum = last;
+		const uint64_t a = first > lo ? first : lo, z = last < hi ? last : hi;
+		if (z <= a) continue;
+		const uint64_t part = z - a;
+		const double L = (double)((int)(b >> 3) - 127) + ((double)(b & 7u) + 0.5) / 8.0;
+		M += part;
+		S += (double)part * L;
+	}
+	const double mean = S / (double)M;
+	double x = -mean;
+	x = x < -126.0 ? -126.0 : (x > 126.0 ? 126.0 : x);
+	const double f = std::floor(x);
+	return (float)((double)m->key * std::ldexp(1.0 + (x - f), (int)f));
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// the histogram of n pixels of d_mean into d_hist (2048 u32, zeroed here on the same stream)
+int histogram_dev(sphip_ctx* c, size_t n, const void* d_mean, void* d_hist, hipStream_t st) {
+	HIP_TRY(c, hipMemsetAsync(d_hist, 0, sp::kLumBins * sizeof(uint32_t), st));
+	const uint32_t nq = (uint32_t)(n / 4 + (n % 4 ? 1 : 0));
+	const uint32_t blocks = std::min<uint32_t>((nq + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(sp::k_lum_histogram, dim3(blocks), dim3(256), 0, st, (const float*)d_mean, (uint32_t)n, nq, aligned16(d_mean) ? 1u : 0u,
+	                   (uint32_t*)d_hist);
+	HIP_TRY(c, hipGetLastError());
+	return SPHIP_OK;
+}
+
+// the transform of n pixels with the exposure given (p's own, or the metered one)
+int display_dev(sphip_ctx* c, const sphip_display* p, float exposure, size_t n, const void* d_mean, void* d_rgba, void* d_rgb, hipStream_t st) {
+	sp::DisplayArgs A{};
+	A.mean = (const float*)d_mean; A.rgba = (uint32_t*)d_rgba; A.rgb = (float*)d_rgb;
+	A.n = (uint32_t)n;
+	A.exposure = exposure;
+	A.w2 = p->white * p->white;
+	A.curve = p->curve; A.encode = p->encode;
+	A.vec = aligned16(d_mean) && aligned16(d_rgba) && aligned16(d_rgb) ? 1u : 0u;
+	const size_t nq = n / 4 + (n % 4 ? 1 : 0);
+	hipLaunchKernelGGL(sp::k_display, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, A);
+	HIP_TRY(c, hipGetLastError());
+	return SPHIP_OK;
+}
+
+// what sphip_accum_display does after the mean stands in k->accum (n pixels, k's device current): meter it (m != nullptr: one read-back
+// of the 8 KB histogram), then the transform into k->rgba and, with want_rgb, k->dp_rgb.  Closes the call's kernel time.
+int display_tail(sphip_ctx* k, const sphip_display* p, const sphip_metering* m, size_t n, bool want_rgb, hipStream_t st, float* exposure_used) {
+	int rc;
+	float E = p->exposure;
+	if (m) {
+		uint32_t hist[sp::kLumBins];
+		if ((rc = ensure(k, k->dp_hist, sizeof hist)) || (rc = histogram_dev(k, n, k->accum.p, k->dp_hist.p, st))) return rc;
+		HIP_TRY(k, hipMemcpyAsync(hist, k->dp_hist.p, sizeof hist, hipMemcpyDeviceToHost, st));
+		HIP_TRY(k, hipStreamSynchronize(st));
+		E = exposure_from_histogram(hist, m);
+		k->stats.n_launches += 1;
+	}
+	if (want_rgb && (rc = ensure(k, k->dp_rgb, n * 12))) return rc;
+	if ((rc = display_dev(k, p, E, n, k->accum.p, k->rgba.p, want_rgb ? k->dp_rgb.p : nullptr, st))) return rc;
+	HIP_TRY(k, hipEventRecord(k->ev_k1, st));
+	k->stats.n_launches += 1;
+	*exposure_used = E;
+	return SPHIP_OK;
 }
 
 } // namespace
@@ -2595,6 +2711,85 @@ int sphip_accum_history(sphip_t* c, float* out_hist) {
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, hipMemcpyAsync(out_hist, c->rp_hist.p, n * 4, hipMemcpyDeviceToHost, c->own_stream));
 	HIP_TRY(c, hipStreamSynchronize(c->own_stream));
+	return SPHIP_OK;
+}
+
+void sphip_display_defaults(sphip_display* out) {
+	if (!out) return;
+	std::memset(out, 0, sizeof *out);
+	out->exposure = 1.0f;          // conventions, not measurements
+	out->white = 4.0f;
+	out->curve = SPHIP_CURVE_FILMIC;
+	out->encode = SPHIP_ENCODE_SRGB;
+}
+
+void sphip_metering_defaults(sphip_metering* out) {
+	if (!out) return;
+	std::memset(out, 0, sizeof *out);
+	out->key = 0.18f;              // conventions as well: middle grey, the median to the 95th percentile
+	out->low = 0.5f;
+	out->high = 0.95f;
+}
+
+void sphip_srgb_thresholds(float out[255]) {
+	if (out) std::memcpy(out, kSrgbBits, sizeof kSrgbBits);
+}
+
+int sphip_exposure_from_histogram(const uint32_t* hist, const sphip_metering* m, float* exposure_out) {
+	if (!hist || !exposure_out) return fail(nullptr, SPHIP_E_INVALID, "null histogram or output pointer");
+	if (const int rc = check_metering(nullptr, m)) return rc;
+	*exposure_out = exposure_from_histogram(hist, m);
+	return SPHIP_OK;
+}
+
+int sphip_luminance_histogram_device(sphip_t* c, size_t n, const void* d_mean, void* d_out_hist, void* stream) {
+	if (const int rc = single_device_entry(c)) return rc;
+	if (!d_mean || !d_out_hist) return fail(c, SPHIP_E_INVALID, "null mean or histogram pointer");
+	if (n == 0 || n > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n = %zu pixels out of range", n);
+	HIP_TRY(c, hipSetDevice(c->device));
+	return histogram_dev(c, n, d_mean, d_out_hist, (hipStream_t)stream);
+}
+
+int sphip_display_device(sphip_t* c, const sphip_display* p, size_t n, const void* d_mean, void* d_out_rgba, void* d_out_rgb, void* stream) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if ((rc = check_display(c, p))) return rc;
+	if ((rc = single_device_entry(c))) return rc;
+	if (!d_mean || !d_out_rgba) return fail(c, SPHIP_E_INVALID, "null mean or output pointer");
+	if (n == 0 || n > 0xffffffffull) return fail(c, SPHIP_E_INVALID, "n = %zu pixels out of range", n);
+	HIP_TRY(c, hipSetDevice(c->device));
+	return display_dev(c, p, p->exposure, n, d_mean, d_out_rgba, d_out_rgb, (hipStream_t)stream);
+}
+
+int sphip_accum_display(sphip_t* c, const sphip_display* p, const sphip_metering* m, const sphip_denoise* dn, uint8_t* out_rgba, float* out_rgb,
+                        float* exposure_out) {
+	if (!c) return SPHIP_E_INVALID;
+	int rc;
+	if ((rc = check_display(c, p)) || (m && (rc = check_metering(c, m))) || (dn && (rc = check_denoise(c, dn)))) return rc;
+	if (!out_rgba) return fail(c, SPHIP_E_INVALID, "null output pointer");
+	if (!c->acc_on || c->acc_total == 0) return fail(c, SPHIP_E_STATE, "sphip_accum_display needs an accumulation with at least one step");
+	if (c->acc_stale) return fail(c, SPHIP_E_STATE, "the scene changed since sphip_accum_begin: begin a new accumulation");
+	if (c->acc_w >= (1u << 30) || c->acc_h >= (1u << 30)) return fail(c, SPHIP_E_INVALID, "image too wide or tall for the filter");
+	float E = p->exposure;
+	if (!c->kids.empty()) {
+		const DisplayTail post{ p, m, &E };
+		if ((rc = multi_accum_denoise(c, dn, out_rgba, out_rgb, &post))) return rc;
+		if (exposure_out) *exposure_out = E;
+		return SPHIP_OK;
+	}
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	const size_t n = c->acc_w * c->acc_h;
+	// the mean sphip_accum_step returns (plain, adaptive or blended with a history), or sphip_accum_denoise's output, in c->accum
+	if (!(rc = accum_denoise_dev(c, c, dn, c->acc_rays.p, false, c->adp_on, true, st)) &&
+	    !(rc = display_tail(c, p, m, n, out_rgb != nullptr, st, &E))) {
+		if (hipMemcpyAsync(out_rgba, c->rgba.p, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+		    (out_rgb && hipMemcpyAsync(out_rgb, c->dp_rgb.p, n * 12, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+		    hipStreamSynchronize(st) != hipSuccess) rc = fail(c, SPHIP_E_DEVICE, "display readback failed: %s", hipGetErrorString(hipGetLastError()));
+	}
+	if (rc) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return rc; }
+	c->timed_upload = c->timed_download = false;
+	if (exposure_out) *exposure_out = E;
 	return SPHIP_OK;
 }
 

@@ -83,6 +83,12 @@ struct hip_r : public basic_renderer {
 	bool rp_on;
 	sphip_reproject rp;
 	unsigned long long rp_moves;
+	// display transform (set_display) of the progressive mode: the bitmap of every step is sphip_accum_display's (of the denoised image
+	// with set_denoise); dp_meter: the exposure is metered from the image; dp_exposure: the exposure the last step used
+	bool dp_on, dp_meter;
+	sphip_display dp;
+	sphip_metering dp_m;
+	float dp_exposure;
 	struct part { std::vector<float> v; uint32_t w, h; part() : w(0), h(0) {} };      // empty: not set; w, h: an image's size
 	part parts[N_PARTS];
 
@@ -91,8 +97,10 @@ struct hip_r : public basic_renderer {
 	hip_r(const int x, const int y, const int* ids, const int n_ids) : basic_renderer(x, y), ctx(0), seed(1), flags(0), scene_hash(0), scene_n(0), have_stats(false),
 	                                                                   progressive(false), acc_live(false), acc_cam(false), acc_w(0), acc_h(0), acc_scene_n(0),
 	                                                                   acc_scene_hash(0), acc_seed(0), acc_flags(0), dn_on(false), have_raw(false),
-	                                                                   cam_samples(false), rp_on(false), rp_moves(0) {
+	                                                                   cam_samples(false), rp_on(false), rp_moves(0), dp_on(false), dp_meter(false), dp_exposure(1.0f) {
 		std::memset(&rp, 0, sizeof rp);
+		std::memset(&dp, 0, sizeof dp);
+		std::memset(&dp_m, 0, sizeof dp_m);
 		std::memset(&acc_camera, 0, sizeof acc_camera);
 		std::memset(&lens, 0, sizeof lens);
 		std::memset(&acc_lens, 0, sizeof acc_lens);
@@ -178,8 +186,9 @@ struct hip_r : public basic_renderer {
 		if (dn_on) {
 			raw = out;
 			have_raw = true;
-			check(sphip_accum_denoise(ctx, &dn, (uint8_t*)out.values.data(), 0), "accum_denoise");
 		}
+		if (dp_on) check(sphip_accum_display(ctx, &dp, dp_meter ? &dp_m : 0, dn_on ? &dn : 0, (uint8_t*)out.values.data(), 0, &dp_exposure), "accum_display");
+		else if (dn_on) check(sphip_accum_denoise(ctx, &dn, (uint8_t*)out.values.data(), 0), "accum_denoise");
 	}
 
 	void frame_own_viewport(const geom::triangle* tris, const scene::material* mats, const size_t n_tris, const size_t n_samples,
@@ -374,6 +383,20 @@ namespace hip_renderer {
 			if (p) q->dn = *p;
 			q->have_raw = false;
 		}
+	}
+
+	void set_display(scene::renderer* r, const sphip_display* p, const sphip_metering* m) {
+		if (hip_r* q = dynamic_cast<hip_r*>(r)) {
+			q->dp_on = p != 0;                                   // a post-process of each step's image: the accumulation goes on
+			q->dp_meter = p != 0 && m != 0;
+			if (p) { q->dp = *p; q->dp_exposure = p->exposure; }
+			if (q->dp_meter) q->dp_m = *m;
+		}
+	}
+
+	float display_exposure(scene::renderer* r) {
+		hip_r* p = dynamic_cast<hip_r*>(r);
+		return p && p->dp_on ? p->dp_exposure : 1.0f;
 	}
 
 	const scene::bitmap* raw_bitmap(scene::renderer* r) {

@@ -96,6 +96,17 @@ namespace hip_renderer {
 	// runs without the variance.  Refused (std::runtime_error with the library's message) while an adaptive rule is set, as set_adaptive
 	// is while this is on.  NULL turns it off (the default).
 	extern void set_reproject(scene::renderer* r, const sphip_reproject* p);
+	// Display transform of the progressive mode (include/spath_hip.h: sphip_accum_display): with p != NULL (copied) the bitmap of every
+	// progressive step goes through exposure, tone curve and encoding instead of the linear clamp; with m != NULL (copied) the exposure is
+	// metered from each step's image, else it is p->exposure.  Composes with set_denoise (the filtered image is what is shown, and
+	// metered; raw_bitmap stays the clamp-only raw image) and with set_reproject (the blended mean).  A post-process: switching it on, off
+	// or changing it does not begin a new accumulation.  NULL turns it off (the default).  Like set_denoise it may be called before
+	// set_progressive and is kept: it acts on the progressive path-traced frames only, and every other frame (render_flat, or render with
+	// the progressive mode off) is the linear clamp as before.  (The Python HipRenderer fixes the progressive mode at construction and
+	// therefore refuses set_display on a renderer that is not progressive.)
+	extern void set_display(scene::renderer* r, const sphip_display* p, const sphip_metering* m);
+	// the exposure the last progressive step was shown with (the metered one with metering on); 1 without a display transform
+	extern float display_exposure(scene::renderer* r);
 	// the raw (not denoised) image of the last progressive step with denoising on; NULL if r is not a hip renderer or there is none
 	extern const scene::bitmap* raw_bitmap(scene::renderer* r);
 	// per-pixel sample counts (w*h, image order) and active pixels of the current accumulation; false if r is not a hip renderer

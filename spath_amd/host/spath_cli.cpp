@@ -7,7 +7,13 @@
 //             [--mov x y z] [--rot x y z] [--focal f] [--seed n] [--flags n] [--primary-reuse] [--nee] [--mis] [--aa] [--lens A,F] [--spec FILE.bin] [--normals FILE.bin] [--glass FILE.bin] [--rough FILE.bin] [--env FILE.bin] [--tex FILE.bin --uv FILE.bin] [--nmap FILE.bin --uv FILE.bin] [--out image.ppm|image.rgba] [--frames n]
 //             [--device-viewport] [--gpus n | --devices 0,1,... | --all-gpus] [--progressive n [--adaptive T[,FLOOR[,MIN]]] [--counts-out f.pgm]
 //              [--denoise [ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]]] [--raw-out FILE]]
-//              [--reproject [MAXH[,NMIN[,PTOL]]] --then-move X,Y,Z[,RX,RY] [--spp-after K] [--first-out FILE]]]
+//              [--reproject [MAXH[,NMIN[,PTOL]]] --then-move X,Y,Z[,RX,RY] [--spp-after K] [--first-out FILE]]
+//              [--display clamp|reinhard|filmic[,WHITE]] [--exposure auto[,KEY[,LOW,HIGH]]|EV] [--srgb]]
+// --display CURVE[,WHITE], --exposure auto[,KEY[,LOW,HIGH]] | EV, --srgb: with --progressive, the image of every step goes through the
+//   display transform (include/spath_hip.h: sphip_accum_display) instead of the linear clamp.  Any of the three turns it on, starting
+//   from the identity (curve clamp, exposure 2^0, linear encoding); each changes its own part: the tone curve (WHITE: Reinhard's white
+//   point, default 4), the exposure as 2^EV or metered from each step's image (the library's key and window for what is left out; the
+//   exposure used is printed with every step), the sRGB encoding.  With --denoise the filtered image is what is metered and shown
 // --reproject [MAXH[,NMIN[,PTOL]]] --then-move X,Y,Z[,RX,RY]: with --progressive (and the device-generated viewport), temporal
 //   reprojection (include/spath_hip.h: sphip_accum_reproject; the library's defaults for what is left out): after the --spp samples of
 //   the last frame the camera moves by X,Y,Z and turns by RX,RY, the accumulation is reprojected into the new view and --spp-after K
@@ -247,6 +253,12 @@ int main(int argc, char** argv) {
 		std::string first_path;
 		sphip_denoise dn;
 		sphip_denoise_defaults(&dn);
+		bool display = false, meter = false;
+		sphip_display dp;
+		sphip_display_defaults(&dp);
+		dp.curve = SPHIP_CURVE_CLAMP; dp.encode = SPHIP_ENCODE_LINEAR;  // the identity, until an option changes its part
+		sphip_metering mt;
+		sphip_metering_defaults(&mt);
 		unsigned long long seed = 1;
 		std::vector<std::pair<char, geom::vec3> > moves;
 		for (int i = 1; i < argc; ++i) {
@@ -308,6 +320,47 @@ int main(int argc, char** argv) {
 					if (*e) throw std::runtime_error("bad --denoise value (ITER[,SIGMA_L[,SIGMA_Z[,NLOG2]]])");
 				}
 			}
+			else if (k == "--display") {
+				need(1);
+				display = true;
+				const std::string v = argv[++i];
+				const size_t comma = v.find(',');
+				const std::string curve = v.substr(0, comma);
+				if (curve == "clamp") dp.curve = SPHIP_CURVE_CLAMP;
+				else if (curve == "reinhard") dp.curve = SPHIP_CURVE_REINHARD;
+				else if (curve == "filmic") dp.curve = SPHIP_CURVE_FILMIC;
+				else throw std::runtime_error("bad --display value (clamp|reinhard|filmic[,WHITE])");
+				if (comma != std::string::npos) {
+					const char* p = v.c_str() + comma + 1;
+					char* e = 0;
+					dp.white = std::strtof(p, &e);
+					if (e == p || *e || !std::isfinite(dp.white) || !(dp.white > 0.0f)) throw std::runtime_error("bad --display WHITE (finite, > 0)");
+				}
+			}
+			else if (k == "--exposure") {
+				need(1);
+				display = true;
+				const char* p = argv[++i];
+				char* e = 0;
+				if (std::strncmp(p, "auto", 4) == 0 && (p[4] == 0 || p[4] == ',')) {
+					meter = true;
+					e = (char*)p + 4;
+					if (*e == ',') { p = e + 1; mt.key = std::strtof(p, &e); if (e == p) throw std::runtime_error("bad --exposure KEY"); }
+					if (*e == ',') {
+						p = e + 1; mt.low = std::strtof(p, &e);
+						if (e == p || *e != ',') throw std::runtime_error("bad --exposure value (auto[,KEY[,LOW,HIGH]]: LOW and HIGH go together)");
+						p = e + 1; mt.high = std::strtof(p, &e);
+						if (e == p) throw std::runtime_error("bad --exposure HIGH");
+					}
+					if (*e) throw std::runtime_error("bad --exposure value (auto[,KEY[,LOW,HIGH]] | EV)");
+				} else {
+					const float ev = std::strtof(p, &e);
+					if (e == p || *e || !std::isfinite(ev)) throw std::runtime_error("bad --exposure value (auto[,KEY[,LOW,HIGH]] | EV)");
+					meter = false;
+					dp.exposure = std::exp2(ev);
+				}
+			}
+			else if (k == "--srgb") { display = true; dp.encode = SPHIP_ENCODE_SRGB; }
 			else if (k == "--raw-out") { need(1); raw_path = argv[++i]; }
 			else if (k == "--reproject") {
 				reproject = true;
@@ -349,6 +402,7 @@ int main(int argc, char** argv) {
 			else throw std::runtime_error("unknown argument " + k);
 		}
 		if (denoise && !(progressive && mode == "pt")) throw std::runtime_error("--denoise needs --progressive n and --mode pt");
+		if (display && !(progressive && mode == "pt")) throw std::runtime_error("--display, --exposure and --srgb need --progressive n and --mode pt");
 		if (!raw_path.empty() && !denoise) throw std::runtime_error("--raw-out needs --denoise");
 		if (reproject != then_move) throw std::runtime_error("--reproject and --then-move go together");
 		if (reproject && !(progressive && mode == "pt")) throw std::runtime_error("--reproject needs --progressive n and --mode pt");
@@ -418,6 +472,7 @@ int main(int argc, char** argv) {
 		hip_renderer::set_adaptive(r.get(), adp_t, adp_floor, adp_min);
 		hip_renderer::set_denoise(r.get(), denoise ? &dn : 0);
 		hip_renderer::set_reproject(r.get(), reproject ? &rp : 0);       // throws with --adaptive: the library's refusal
+		hip_renderer::set_display(r.get(), display ? &dp : 0, meter ? &mt : 0);
 		std::printf("Current renderer: %s [%d device(s)]\n", r->get_description(), hip_renderer::device_count(r.get()));     // main.cpp:30-32
 		for (size_t k = 0; k < moves.size(); ++k) {
 			if (moves[k].first == 'm') r->set_delta_mov(moves[k].second);
@@ -439,6 +494,7 @@ int main(int argc, char** argv) {
 					double kms = 0;
 					hip_renderer::last_stats(r.get(), &kms, 0);
 					unsigned long long active = 0;
+					if (display) std::printf("  step %zu: exposure %.9g\n", step, (double)hip_renderer::display_exposure(r.get()));
 					if (adp_t >= 0.0 && hip_renderer::accum_counts(r.get(), 0, &active))
 						std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms, %llu pixels active\n", step, n, done, kms, active);
 					else std::printf("  step %zu: %zu spp (%zu so far), kernel %.3f ms\n", step, n, done, kms);
@@ -481,6 +537,7 @@ int main(int argc, char** argv) {
 				double kms = 0;
 				hip_renderer::last_stats(r.get(), &kms, 0);
 				std::printf("  after the move, step %zu: %zu spp (%zu new so far), kernel %.3f ms\n", step, n, done, kms);
+				if (display) std::printf("  after the move, step %zu: exposure %.9g\n", step, (double)hip_renderer::display_exposure(r.get()));
 			}
 		}
 		if (!out_path.empty()) write_image(out_path, bmp);

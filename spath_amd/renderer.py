@@ -110,6 +110,8 @@ class HipRenderer(BasicRenderer):
         self.denoise = None if denoise is False or denoise is None else capi.Denoise.make(None if denoise is True else denoise)
         self.raw_bitmap = Bitmap()
         self.reproject = None                                  # set_reproject
+        self.display = None                                    # set_display: (capi.Display, capi.Metering or None)
+        self.display_exposure = 1.0                            # the exposure the last progressive step was shown with
         self._moves = 0
         self._scene_key = None
         self._accum_key = None
@@ -191,6 +193,21 @@ class HipRenderer(BasicRenderer):
             raise capi.SpathHipError("sphip_accum_reproject failed [-3]: sphip_accum_reproject needs a plain accumulation, not an adaptive one")
         self.reproject = capi.Reproject.make(None if params is True else params)
 
+    def set_display(self, params=True, metering=None):
+        """The display transform of the progressive mode, like hip_renderer::set_display: with params True (the library's defaults:
+        filmic, sRGB, exposure 1), a capi.Display or a dict of its fields, the bitmap of every progressive step goes through exposure,
+        tone curve and encoding (capi.Context.accum_display) instead of the linear clamp; metering True (the library's key and
+        window), a capi.Metering, a (key, low, high) tuple or a dict: the exposure is metered from each step's image and kept in
+        display_exposure.  Composes with denoising (the filtered image is metered and shown; raw_bitmap stays the clamp-only raw
+        image) and with set_reproject.  A post-process: it never begins a new accumulation.  None or False: off."""
+        if params is None or params is False:
+            self.display = None
+            return
+        if not self.progressive:
+            raise ValueError("the display transform needs progressive=True")
+        m = None if metering is None or metering is False else capi.Metering.make(None if metering is True else metering)
+        self.display = (capi.Display.make(None if params is True else params), m)
+
     def _flags(self, mode):
         """the flags word of a frame: FLAG_SPECULAR, FLAG_SMOOTH, FLAG_DIELECTRIC, FLAG_ENVIRONMENT, FLAG_GLOSSY, FLAG_TEXTURE and
         FLAG_NORMAL_MAP on while their tables, the maps or the atlas are set, and never on the flat pass"""
@@ -247,6 +264,9 @@ class HipRenderer(BasicRenderer):
         self.last_stats = self.ctx.stats()
         if self.denoise is not None:
             self.raw_bitmap.res_x, self.raw_bitmap.res_y, self.raw_bitmap.values = out.res_x, out.res_y, out.values
+        if self.display is not None:
+            out.values, self.display_exposure = self.ctx.accum_display(self.display[0], metering=self.display[1], denoise=self.denoise)
+        elif self.denoise is not None:
             out.values = self.ctx.accum_denoise(self.denoise)
 
     def _render(self, vp, tris, mats, n_tris, n_samples, out, mode):
