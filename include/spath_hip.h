@@ -248,6 +248,16 @@ int sphip_selftest_device(sphip_t* ctx, int what, const void* in, size_t n, void
  * Blocking; host pointers; single-device contexts. */
 int sphip_selftest_stage1(sphip_t* ctx, const float* rays, size_t n_rays, uint32_t* out_words, uint32_t* out_tri, int32_t* out_order, uint32_t* tiles_out);
 
+/* TEST-ONLY: the RE-TEST of stage 2 of the default scan alone (tests/test_hip_retest_audit.py): for the caller's n_rays rays (a multiple of 64)
+ * against EVERY triangle of the scene's stream, whatever stage 1 would say of the pair, the verdict of the f32 cylinder test that decides
+ * which triangles of a listed group go on to the exact test -- formed as the render kernels form it: the tile's records (the cylinder of a
+ * second edge of the triangle), the same chain, the doubled margin.  No pair the reference accepts may have its bit clear.
+ *   *tiles_out         as sphip_selftest_stage1 (call with out_bits = NULL first to size the outputs)
+ *   out_bits[(k * tiles + t) * (T / 4) + g]   bit 3 - u set = the triangle at place u of group g of tile t SURVIVES the re-test for ray k
+ *   out_order[t * T + 4 g + u]                as sphip_selftest_stage1
+ * Blocking; host pointers; single-device contexts.  Additive: the ABI version does not change. */
+int sphip_selftest_retest(sphip_t* ctx, const float* rays, size_t n_rays, uint8_t* out_bits, int32_t* out_order, uint32_t* tiles_out);
+
 /* TEST-ONLY: the code underneath the opt-in acceleration structure on its own (tests/test_hip_sort.py, tests/test_hip_bvh_build.py,
  * tests/bvh_checks.py).  Blocking; host pointers; single-device contexts.  Additive: the ABI version does not change.
  *

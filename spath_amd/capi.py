@@ -40,7 +40,7 @@ SYMBOLS = (
     "sphip_kernel_name", "sphip_set_scene", "sphip_render", "sphip_set_scene_device",
     "sphip_render_device", "sphip_closest_hit_device", "sphip_get_stats", "sphip_viewport_device", "sphip_render_camera",
     "sphip_create_multi", "sphip_device_count", "sphip_plan_tile_rows", "sphip_plan_shard", "sphip_selftest_device",
-    "sphip_kernel_available", "sphip_selftest_stage1", "sphip_build_info",
+    "sphip_kernel_available", "sphip_selftest_stage1", "sphip_selftest_retest", "sphip_build_info",
     "sphip_selftest_sort", "sphip_selftest_bvh_dump", "sphip_selftest_bvh_walk",
     "sphip_render_device_accum", "sphip_accum_begin", "sphip_accum_step",
     "sphip_accum_begin_adaptive", "sphip_accum_counts",
@@ -313,6 +313,9 @@ def load():
     if hasattr(L, "sphip_selftest_stage1"):
         L.sphip_selftest_stage1.restype = C.c_int
         L.sphip_selftest_stage1.argtypes = [vp, vp, sz, vp, vp, vp, C.POINTER(C.c_uint32)]
+    if hasattr(L, "sphip_selftest_retest"):
+        L.sphip_selftest_retest.restype = C.c_int
+        L.sphip_selftest_retest.argtypes = [vp, vp, sz, vp, vp, C.POINTER(C.c_uint32)]
     if hasattr(L, "sphip_selftest_sort"):
         L.sphip_selftest_sort.restype = C.c_int
         L.sphip_selftest_sort.argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp]
@@ -950,6 +953,27 @@ class Context:
                     tsurv[:, 32 * rb:32 * rb + 32, :, pos] = tb[:, hh, :, :, rb].reshape(nb, 32, t, Q * 32)
             tsurv = tsurv.reshape(n_pad, t * T)[:n]
         return surv[:n], tsurv, order
+
+    def selftest_retest(self, rays):
+        """sphip_selftest_retest (test-only): the re-test of stage 2 of the default scan alone for the given rays (padded to a multiple
+        of 64) against every triangle of the stream.  Returns (survives, order, T): survives[ray, stream position] bool, order[stream
+        position] = triangle index (n_tris = padding), T = triangles per tile of the shape that ran."""
+        import numpy as np
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        n_pad = (n + 63) // 64 * 64
+        if n_pad != n:
+            rays = np.concatenate([rays, np.repeat(rays[-1:], n_pad - n, axis=0)])
+        tiles = C.c_uint32(0)
+        self._check(self._L.sphip_selftest_retest(self._h, None, 0, None, None, C.byref(tiles)), "sphip_selftest_retest")
+        t, T = tiles.value & 0xFFFFF, (tiles.value >> 20) & 0x7FF
+        bits = np.zeros(n_pad * t * (T // 4), dtype=np.uint8)
+        order = np.zeros(t * T, dtype=np.int32)
+        self._check(self._L.sphip_selftest_retest(self._h, rays.ctypes.data, n_pad, bits.ctypes.data, order.ctypes.data, C.byref(tiles)),
+                    "sphip_selftest_retest")
+        # bits[ray, tile, group]: bit 3 - u = place u of the group
+        surv = ((bits.reshape(n_pad, t * (T // 4), 1) >> (3 - np.arange(4, dtype=np.uint8))) & 1).astype(bool).reshape(n_pad, t * T)
+        return surv[:n], order, T
 
     def stats(self) -> dict:
         s = Stats()

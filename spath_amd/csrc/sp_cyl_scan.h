@@ -96,25 +96,37 @@ SP_DEV CylGroup cyl_group(const float4* tile, uint32_t grp) {
 SP_DEV float cyl_mz(const CylGroup& G, int u) { return u == 0 ? G.mh01.x : u == 1 ? G.mh01.z : u == 2 ? G.mh23.x : G.mh23.z; }
 SP_DEV float cyl_h(const CylGroup& G, int u) { return u == 0 ? G.mh01.y : u == 1 ? G.mh01.w : u == 2 ? G.mh23.y : G.mh23.w; }
 
-// ---- record of one triangle (double arithmetic, each coefficient rounded once).  Returns the class.
-SP_DEV int cyl_record(const float* __restrict__ t, uint32_t idx, float4& q0, float4& q1) {
-	const double A[3] = { t[0], t[1], t[2] }, B[3] = { t[3], t[4], t[5] }, C[3] = { t[6], t[7], t[8] };
-	// e1, e2 exactly as the reference rounds them (geom.h:200-201); c = e2 - e1 is the third edge
-	const double e1[3] = { (double)(t[3] - t[0]), (double)(t[4] - t[1]), (double)(t[5] - t[2]) };
-	const double e2[3] = { (double)(t[6] - t[0]), (double)(t[7] - t[1]), (double)(t[8] - t[2]) };
-	const double c[3] = { e2[0] - e1[0], e2[1] - e1[1], e2[2] - e1[2] };
-	const double l1 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2];
-	const double l2 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
-	const double lc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-	// narrowest slab = along the longest edge
-	const double* w3; const double* p0; const double* p1; double len2;
-	if (l2 >= l1 && l2 >= lc) { w3 = e2; p0 = A; p1 = B; len2 = l2; }
-	else if (l1 >= lc)        { w3 = e1; p0 = A; p1 = C; len2 = l1; }
-	else                      { w3 = c;  p0 = B; p1 = A; len2 = lc; }
-	const double len = sqrt(len2);
+// the three edges of a triangle with the slab each spans: the line along the edge through p0, the parallel
+// line through the opposite vertex p1.  Edge numbers: 0 = e1, 1 = e2, 2 = c.
+struct CylEdges {
+	double v[3][3];            // A, B, C
+	double e[3][3];            // e1, e2 exactly as the reference rounds them (geom.h:200-201); c = e2 - e1 is the third edge
+	double l[3];               // squared lengths
+	SP_DEV explicit CylEdges(const float* __restrict__ t) {
+#pragma unroll
+		for (int k = 0; k < 3; ++k) {
+			v[0][k] = t[k]; v[1][k] = t[3 + k]; v[2][k] = t[6 + k];
+			e[0][k] = (double)(t[3 + k] - t[k]); e[1][k] = (double)(t[6 + k] - t[k]);
+			e[2][k] = e[1][k] - e[0][k];
+		}
+#pragma unroll
+		for (int j = 0; j < 3; ++j) l[j] = e[j][0] * e[j][0] + e[j][1] * e[j][1] + e[j][2] * e[j][2];
+	}
+	// the longest edge (the narrowest slab, section 4.1); ties: e2, e1, c
+	SP_DEV int longest() const { return (l[1] >= l[0] && l[1] >= l[2]) ? 1 : (l[0] >= l[2] ? 0 : 2); }
+	SP_DEV const double* p0(int j) const { return j == 2 ? v[1] : v[0]; }                 // e1: A, e2: A, c: B
+	SP_DEV const double* p1(int j) const { return j == 0 ? v[2] : j == 1 ? v[1] : v[0]; }  // e1: C, e2: B, c: A
+};
+
+// ---- record of the slab along edge j (double arithmetic, each coefficient rounded once), scaled by 1 / w_a of the edge's unit
+// direction w: a < 0 picks the direction's own dominant axis, a >= 0 is imposed by the caller (cyl_retest_record).  Returns a, or
+// -1 for a record that always survives; wa_out = w_a.
+SP_DEV int cyl_slab_record(const CylEdges& E, int j, int a, uint32_t idx, float4& q0, float4& q1, double& wa_out) {
+	const double* w3 = E.e[j]; const double* p0 = E.p0(j); const double* p1 = E.p1(j);
+	const double len = sqrt(E.l[j]);
 	const double w[3] = { w3[0] / len, w3[1] / len, w3[2] / len };
 	const double ax = fabs(w[0]), ay = fabs(w[1]), az = fabs(w[2]);
-	const int a = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+	if (a < 0) a = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
 	const int b = a == 2 ? 0 : a + 1, cc = b == 2 ? 0 : b + 1;
 	const double s = 1.0 / w[a];
 	const double pc[3] = { 0.5 * (p0[0] + p1[0]), 0.5 * (p0[1] + p1[1]), 0.5 * (p0[2] + p1[2]) };
@@ -131,7 +143,43 @@ SP_DEV int cyl_record(const float* __restrict__ t, uint32_t idx, float4& q0, flo
 	const bool ok = (chk - chk) == 0.0f;
 	q0 = ok ? make_float4(beta, gamma, mx, my) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	q1 = make_float4(ok ? mz : 0.0f, ok ? H : __builtin_inff(), __uint_as_float(idx), 0.0f);
-	return ok ? a : 0;
+	wa_out = w[a];
+	return ok ? a : -1;
+}
+
+// ---- record of one triangle: the slab along its LONGEST edge, scaled by that direction's dominant component.  Returns the class.
+SP_DEV int cyl_record(const float* __restrict__ t, uint32_t idx, float4& q0, float4& q1) {
+	const CylEdges E(t);
+	double wa;
+	const int a = cyl_slab_record(E, E.longest(), -1, idx, q0, q1, wa);
+	return a < 0 ? 0 : a;
+}
+
+// ---- the record stage 2 of the default scan re-tests with (sp_cylm_scan.h; DESIGN.md section 4.3, "the re-test's cylinder"): the slab
+// along a SECOND edge of the triangle, in the frame of the triangle's class -- scaled by 1 / w_a with a the dominant axis of the
+// LONGEST edge's direction, so that the kernel's chain P_a + beta P_b + gamma P_c - dir.Mc' serves unchanged.  The edge vectors sum
+// to zero and the longest has |w_a| >= 1/sqrt(3), so of the other two at least one has |w_a| >= 1/(2 sqrt(3)): the second-longest
+// if its does, else the third (ties in length: the lower edge number).  Scale <= 2 sqrt(3) where cyl_record's is <= sqrt(3): the
+// re-test doubles its margin.  Should |w_a| still come out below 0.28 (rounding), or anything be non-finite, or the triangle's own
+// record be the always-surviving one: the always-surviving record (H = +inf).
+constexpr double kCylRetestWa = 0.28867513459481287;      // 1 / (2 sqrt(3)), rounded down
+SP_DEV void cyl_retest_record(const float* __restrict__ t, uint32_t idx, float4& q0, float4& q1) {
+	const CylEdges E(t);
+	float4 a0, a1;
+	double wa;
+	const int a = cyl_slab_record(E, E.longest(), -1, idx, a0, a1, wa);
+	int r = -1;
+	if (a >= 0) {
+		const int jl = E.longest(), j1 = jl == 0 ? 1 : 0, j2 = jl == 2 ? 1 : 2;       // the other two, by edge number
+		const int jb = E.l[j2] > E.l[j1] ? j2 : j1, jc = jb == j1 ? j2 : j1;          // second-longest, third
+		const bool second = fabs(E.e[jb][a]) / sqrt(E.l[jb]) >= kCylRetestWa;
+		r = cyl_slab_record(E, second ? jb : jc, a, idx, q0, q1, wa);
+		if (!(fabs(wa) >= 0.28)) r = -1;
+	}
+	if (r < 0) {
+		q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		q1 = make_float4(0.0f, __builtin_inff(), __uint_as_float(idx), 0.0f);
+	}
 }
 
 SP_DEV int cyl_class(const float* __restrict__ t) {

@@ -15,8 +15,10 @@
 //     min_i (|gm_i| - H_i D)  >=  min_i |gm_i| - Hmax D      (Hmax = the largest H of the group, D > 0)
 // so  m = min(min3(|g0|, |g1|, |g2|), |g3|),  x = fma(-Hmax, D, m),  sign(x - Dq)  -- 5 instructions per 4 pairs instead of the
 // 8 that four separate x cost (round 2).  It can only keep MORE than the per-triangle form (every triangle of a rejected group
-// has |gm_i| - H_i D > Dq, the condition DESIGN.md 4.2 proves safe), and stage 2 re-tests each triangle of a surviving group with
-// its own H.  The prepass orders every class by H (k_cylm_keys + sp_radix_sort.h), so Hmax ~ H_i and next to nothing is lost.
+// has |gm_i| - H_i D > Dq, the condition DESIGN.md 4.2 proves safe), and stage 2 re-tests each triangle of a surviving group on its
+// own -- against the cylinder of a SECOND edge of the triangle (cyl_retest_record, cylm_retest): an independent necessary condition,
+// which lets 0.12 triangles per list entry through where the same cylinder with the triangle's own H let 1.02.
+// The prepass orders every class by H (k_cylm_keys + sp_radix_sort.h), so Hmax ~ H_i and next to nothing is lost.
 // And the margin is FOLDED INTO THE BOUND, once per tile and ray instead of once per group (k_cylm_hmax, cylm_tile_bound):
 //     D' = D + kappa Dq  with  Hmax kappa >= 1 for every group of the tile   =>   Hmax D' >= Hmax D + Dq,
 // so  x' = fma(-Hmax, D', m),  sign(x')  -- 4 instructions per 4 pairs -- rejects only what the subtracted form rejects, and x',
@@ -117,13 +119,15 @@ SP_DEV void half_split(float v, _Float16& hi, _Float16& lo) {
 	lo = to_half(v - (float)hi);
 }
 
-// triangle `in_tile` of a tile: f32 part as cyl_store (chunks 0-6), the A-fragment row
-SP_DEV void cylm_store(float4* __restrict__ tile, uint32_t in_tile, const float4 q0, const float4 q1, float S) {
+// triangle `in_tile` of a tile: the f32 part, laid out as cyl_store does (chunks 0-6), holds the record (r0, r1) that stage 2 re-tests
+// with -- the cylinder of a second edge, cyl_retest_record -- and the A-fragment row the record (q0, q1) of the longest edge's cylinder,
+// which is stage 1's.  The two are independent necessary conditions; padding passes the same record twice.
+SP_DEV void cylm_store(float4* __restrict__ tile, uint32_t in_tile, const float4 q0, const float4 q1, const float4 r0, const float4 r1, float S) {
 	const uint32_t grp = in_tile >> 2, u = in_tile & 3u;
-	tile[cylm_slot(grp, u)] = q0;
+	tile[cylm_slot(grp, u)] = r0;
 	float* mh = (float*)(tile + cylm_slot(grp, 4u + (u >> 1))) + 2u * (u & 1u);
-	mh[0] = q1.x; mh[1] = q1.y;
-	((float*)(tile + cylm_slot(grp, 6u)))[u] = q1.z;
+	mh[0] = r1.x; mh[1] = r1.y;
+	((float*)(tile + cylm_slot(grp, 6u)))[u] = r1.z;
 	const float m = S > 0.0f ? 16.0f / S : 0.0f;                                        // exact: S is a power of two
 	_Float16 bh, bl, ch, cl, xh, xl, yh, yl, zh, zl;
 	half_split(S > 0.0f ? 16.0f * q0.x : 0.0f, bh, bl); half_split(S > 0.0f ? 16.0f * q0.y : 0.0f, ch, cl);
@@ -226,7 +230,9 @@ __global__ void __launch_bounds__(256) k_cylm_scatter(const float* __restrict__ 
 	const uint32_t c0 = cls == 0 ? 0u : cls == 1 ? hdr[0] : hdr[0] + hdr[1];
 	const size_t pos = (size_t)hdr[3 + cls] * kMTile + (p - c0);
 	const size_t tile = pos / kMTile;
-	cylm_store(rec + tile * kMTileQ, (uint32_t)(pos - tile * kMTile), q0, q1, S);
+	float4 r0, r1;
+	cyl_retest_record(tris + (size_t)i * 12, i, r0, r1);
+	cylm_store(rec + tile * kMTileQ, (uint32_t)(pos - tile * kMTile), q0, q1, r0, r1, S);
 }
 
 // ---- prepass 4: the ragged end of each class's last tile.  f32 record with H = -inf (stage 2's re-test rejects it; a ray whose
@@ -238,9 +244,17 @@ __global__ void __launch_bounds__(256) k_cylm_pad(const uint32_t* __restrict__ h
 	const float S = ((const float*)hdr)[7];
 	for (uint32_t pos = n + tid; pos < (n + kMTile - 1u) / kMTile * kMTile; pos += 256u) {
 		const size_t gpos = (size_t)first + pos, tile = gpos / kMTile;
-		cylm_store(rec + tile * kMTileQ, (uint32_t)(gpos - tile * kMTile), make_float4(0.0f, 0.0f, 0.0f, 0.0f),
-		           make_float4(0.0f, -__builtin_inff(), __uint_as_float(n_tris), 0.0f), S);
+		const float4 z0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), z1 = make_float4(0.0f, -__builtin_inff(), __uint_as_float(n_tris), 0.0f);
+		cylm_store(rec + tile * kMTileQ, (uint32_t)(gpos - tile * kMTile), z0, z1, z0, z1, S);
 	}
+}
+
+// H of the longest edge's cylinder (stage 1's; the sort key of k_cylm_keys) of the triangle with index idx; padding (idx = n_tris): -inf
+SP_DEV float cylm_ha(const float* __restrict__ tris, uint32_t n_tris, uint32_t idx) {
+	if (idx >= n_tris) return -__builtin_inff();
+	float4 q0, q1;
+	(void)cyl_record(tris + (size_t)idx * 12, idx, q0, q1);
+	return q1.y;
 }
 
 // ---- prepass 5: Hmax^ = 256 max(H) / S of every group (one thread per group, one block per tile): +inf if the group holds a
@@ -251,7 +265,8 @@ __global__ void __launch_bounds__(256) k_cylm_pad(const uint32_t* __restrict__ h
 // regular Hmax^).  The classes are sorted by H, so Hmax^ hardly varies inside a tile and next to nothing is lost; where it does vary
 // (or is 0: a triangle of no height), the small values are RAISED to 2^-10 of the tile's largest (a larger H only keeps more), which
 // bounds the amplification of the margin (2^-16 of the magnitudes) by 2^10.
-__global__ void __launch_bounds__(kMGroups) k_cylm_hmax(const uint32_t* __restrict__ hdr, float4* __restrict__ rec) {
+// The f32 part of a tile holds the re-test's records, so the H of stage 1's cylinder is computed again from the triangle (cylm_ha).
+__global__ void __launch_bounds__(kMGroups) k_cylm_hmax(const float* __restrict__ tris, uint32_t n_tris, const uint32_t* __restrict__ hdr, float4* __restrict__ rec) {
 	__shared__ uint32_t s_max, s_min;
 	__shared__ float s_h[kMGroups];
 	if (blockIdx.x >= hdr[6]) return;
@@ -260,8 +275,10 @@ __global__ void __launch_bounds__(kMGroups) k_cylm_hmax(const uint32_t* __restri
 	const uint32_t grp = threadIdx.x, tb = grp >> 3, j = (grp & 7u) >> 1, hh = grp & 1u;
 	const float S = ((const float*)hdr)[7];
 	const float k = S > 0.0f ? 256.0f / S : 1.0f;                                       // exact: S is a power of two
-	const float4 a = tile[cylm_slot(grp, 4u)], b = tile[cylm_slot(grp, 5u)];           // (Mz H Mz H) of triangles 0,1 and 2,3
-	s_h[grp] = fmaxf(fmaxf(a.y, a.w), fmaxf(b.y, b.w)) * k;                             // the group of four; +-inf stay +-inf
+	const float4 gi = tile[cylm_slot(grp, 6u)];                                         // the four indices
+	const float h0 = cylm_ha(tris, n_tris, __float_as_uint(gi.x)), h1 = cylm_ha(tris, n_tris, __float_as_uint(gi.y));
+	const float h2 = cylm_ha(tris, n_tris, __float_as_uint(gi.z)), h3 = cylm_ha(tris, n_tris, __float_as_uint(gi.w));
+	s_h[grp] = fmaxf(fmaxf(h0, h1), fmaxf(h2, h3)) * k;                                 // the group of four; +-inf stay +-inf
 	__syncthreads();
 	// octets: this quad and its partner (grp ^ 2: the other j of the same q and lane half); both threads hold the same value
 	float hm = kMGrp == 8u ? fmaxf(s_h[grp], s_h[grp ^ 2u]) : s_h[grp];
@@ -544,11 +561,33 @@ SP_DEV uint32_t wave_incl_scan(uint32_t x) {
 	return x;
 }
 
+// The re-test of one list entry (stage 2 (a); k_selftest_retest runs the same function): the f32 cylinder test of sp_cyl_scan.h on the entry's
+// kMGrp records (group grp; for an octet grp + 2 as well), each with its own H: which of them survive.  The records are those of a SECOND edge's
+// cylinder (cyl_retest_record), whose scale is up to twice that of stage 1's: the caller passes the doubled margin Dq2 = 2 Dq.
+// The SIGN of x - Dq2, shifted in as in stage 1 (bit kMGrp - 1 - u = triangle u = 4 (second group) + place): one half-rate instruction per
+// triangle instead of compare, mask, select and or.  (survive <=> !(x - Dq2 >= 0); where the difference is a NaN -- inf - inf: padding
+// records under a ray whose filter is off, or an idle lane -- either answer is right.)
+SP_DEV uint32_t cylm_retest(const float4* cur, uint32_t grp, float Pa, float Pb, float Pc, float dx, float dy, float dz, float D, float Dq2) {
+	uint32_t cand = 0;
+#pragma unroll
+	for (int h = 0; h < (int)(kMGrp / 4u); ++h) {
+		const CylmGroup G = cylm_group(cur, grp + 2u * (uint32_t)h);
+#pragma unroll
+		for (int u = 0; u < 4; ++u) {
+			const float mz = u == 0 ? G.mh01.x : u == 1 ? G.mh01.z : u == 2 ? G.mh23.x : G.mh23.z;
+			const float Hh = u == 0 ? G.mh01.y : u == 1 ? G.mh01.w : u == 2 ? G.mh23.y : G.mh23.w;
+			const float x = cyl_x(G.q0[u], mz, Hh, Pa, Pb, Pc, -dx, -dy, -dz, D);
+			cand = __builtin_amdgcn_alignbit(cand, __float_as_uint(x - Dq2), 31);
+		}
+	}
+	return cand;
+}
+
 // Closest hit for the ray of every lane.  Block-uniform call (barriers inside).
 //
 // Stage 2 in two steps, both shared by the whole wave:
 //   (a) per tile: the set group bits become a list of (ray, group) entries (list space by a wave prefix sum); 64 entries per round,
-//       one per lane: the f32 cylinder test of sp_cyl_scan.h on the group's four records, each with its own H -> candidates;
+//       one per lane: the f32 cylinder test of sp_cyl_scan.h on the group's four records -- a second edge's cylinder, margin 2 Dq -> candidates;
 //   (b) the candidates (ray, triangle index) go to a per-wave stack that OUTLIVES the tile -- the exact test reads the
 //       exact record from L2 and the ray from the donor lane's registers, nothing of the tile -- and ray_tri_strict runs only on
 //       full batches of 64 (and on what is left at the end of the scan): every lane busy in every exact turn, where one turn
@@ -757,22 +796,8 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 				const float dx = wave_fetch(la, s.dir[0].x), dy = wave_fetch(la, s.dir[0].y), dz = wave_fetch(la, s.dir[0].z);
 				const float Pa = wave_fetch(la, f.Pa[0]), Pb = wave_fetch(la, f.Pb[0]), Pc = wave_fetch(la, f.Pc[0]);
 				const float D = wave_fetch(la, f.D[0]), Dq = wave_fetch(la, f.Dq[0]);
-				// the f32 cylinder test of sp_cyl_scan.h on the entry's kMGrp records (group grp; for an octet grp + 2 as well), each with its own H:
-				// which of them survive.  The SIGN of x - Dq, shifted in as in stage 1 (bit kMGrp - 1 - u = triangle u = 4 (second group) + place):
-				// one half-rate instruction per triangle instead of compare, mask, select and or.  (survive <=> !(x - Dq >= 0); where the difference
-				// is a NaN -- inf - inf: padding records under a ray whose filter is off, or an idle lane -- either answer is right.)
-				uint32_t cand = 0;
-#pragma unroll
-				for (int h = 0; h < (int)(kMGrp / 4u); ++h) {
-					const CylmGroup G = cylm_group(cur, grp + 2u * (uint32_t)h);
-#pragma unroll
-					for (int u = 0; u < 4; ++u) {
-						const float mz = u == 0 ? G.mh01.x : u == 1 ? G.mh01.z : u == 2 ? G.mh23.x : G.mh23.z;
-						const float Hh = u == 0 ? G.mh01.y : u == 1 ? G.mh01.w : u == 2 ? G.mh23.y : G.mh23.w;
-						const float x = cyl_x(G.q0[u], mz, Hh, Pa, Pb, Pc, -dx, -dy, -dz, D);
-						cand = __builtin_amdgcn_alignbit(cand, __float_as_uint(x - Dq), 31);
-					}
-				}
+				// the entry's kMGrp triangles against the cylinder of their second edge, margin 2 Dq (+-inf stay +-inf): cylm_retest
+				uint32_t cand = cylm_retest(cur, grp, Pa, Pb, Pc, dx, dy, dz, D, Dq + Dq);
 				cand = ok ? cand : 0u;
 				SP_PH_STAMP(ph_t1); SP_PH_ADD(ph_retest, ph_t0, ph_t1);
 				// ---- (b): the candidates go on the wave's stack; a full batch of 64 is tested as soon as the next ones would not fit
@@ -857,9 +882,12 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 // out_tri[(((block * 64 + lane) * tiles + tile) * 2 + rb) * (T / 64) + tb / 2], bit 31 - (16 (tb & 1) + 4 j + i) = triangle 32 tb + 8 j + 4 (lane >> 5) + i.
 // A quad / octet bit may be set where none of its triangle bits is (its bound is weaker), never the other way round.
 // Block 0 also writes the stream order: out_order[tile * T + 4 group + u] = triangle index at that place (n_tris = padding).
+// (The triangle's own H is that of stage 1's cylinder, computed again from the triangle: the tile's f32 part holds the re-test's records.)
 __global__ void __launch_bounds__(64) k_selftest_stage1(const float* __restrict__ rays, uint32_t n_rays, const CylStream cs, const unsigned int* __restrict__ bounds,
+                                                      const float* __restrict__ tris, uint32_t n_tris,
                                                       uint32_t* __restrict__ out_words, uint32_t* __restrict__ out_tri, int* __restrict__ out_order) {
 	__shared__ float4 sm[kMTileQ];
+	__shared__ float s_ha[kMTile];
 	const uint32_t lane = threadIdx.x, hh = lane >> 5;
 	const float rv = __uint_as_float(bounds[0]);
 	CylmHdr hd;
@@ -878,6 +906,10 @@ __global__ void __launch_bounds__(64) k_selftest_stage1(const float* __restrict_
 		__syncthreads();
 		for (uint32_t q = lane; q < kMTileQ; q += 64u) sm[q] = cs.rec[(size_t)gt * kMTileQ + q];
 		__syncthreads();
+		if (out_tri) {
+			for (uint32_t p = lane; p < kMTile; p += 64u) s_ha[p] = cylm_ha(tris, n_tris, ((const uint32_t*)(sm + cylm_slot(p >> 2, 6u)))[p & 3u]);
+			__syncthreads();
+		}
 		const uint32_t nblk = hd.fragments(gt);
 		float Dt[2];
 		cylm_tile_bound(sm, R, Dt);
@@ -906,8 +938,7 @@ __global__ void __launch_bounds__(64) k_selftest_stage1(const float* __restrict_
 #pragma unroll
 					for (int j = 0; j < 4; ++j) {
 						const uint32_t grp = tb * 8u + 2u * (uint32_t)j + hh;
-						const float4 a = sm[cylm_slot(grp, 4u)], b = sm[cylm_slot(grp, 5u)];
-						const float H4[4] = { a.y * kH, a.w * kH, b.y * kH, b.w * kH };
+						const float H4[4] = { s_ha[4u * grp] * kH, s_ha[4u * grp + 1u] * kH, s_ha[4u * grp + 2u] * kH, s_ha[4u * grp + 3u] * kH };
 #pragma unroll
 						for (int i = 0; i < 4; ++i) {
 							const float x = __builtin_fmaf(-H4[i], R.Dn[rb], __builtin_fabsf(g[4 * j + i]));
@@ -928,6 +959,51 @@ __global__ void __launch_bounds__(64) k_selftest_stage1(const float* __restrict_
 				const float4 gi = sm[cylm_slot(grp, 6u)];
 				int* o = out_order + (size_t)gt * kMTile + 4u * grp;
 				o[0] = (int)__float_as_uint(gi.x); o[1] = (int)__float_as_uint(gi.y); o[2] = (int)__float_as_uint(gi.z); o[3] = (int)__float_as_uint(gi.w);
+			}
+		}
+	}
+}
+
+// ---- test-only (sphip_selftest_retest): the RE-TEST of stage 2 alone, for every (ray, triangle) pair of the stream whatever stage 1 would say:
+// the f32 ray state of scan_cylm (cyl_setup, rotated class by class), the tile's records, cylm_retest with the margin 2 Dq.  One ray per lane,
+// one wave per workgroup (n_rays a multiple of 64), the tile's f32 part in LDS.
+// out_bits[(ray * tiles + tile) * G + g] (G = kMTile / 4 groups per tile): bit 3 - u set = the triangle at place u of group g SURVIVES the re-test.
+// Block 0 also writes the stream order as k_selftest_stage1 does.
+__global__ void __launch_bounds__(64) k_selftest_retest(const float* __restrict__ rays, uint32_t n_rays, const CylStream cs, const unsigned int* __restrict__ bounds,
+                                                      unsigned char* __restrict__ out_bits, int* __restrict__ out_order) {
+	__shared__ float4 sm[kMRecQ];
+	const uint32_t lane = threadIdx.x;
+	const float rv = __uint_as_float(bounds[0]);
+	CylmHdr hd;
+	hd.load(cs.hdr);
+	const uint32_t k = blockIdx.x * 64u + lane, kk = k < n_rays ? k : n_rays - 1u;
+	RaySlots<1> s;
+	const float* p = rays + (size_t)kk * 6;
+	s.o[0] = mk3(p[0], p[1], p[2]); s.dir[0] = mk3(p[3], p[4], p[5]); s.src[0] = -1; s.act[0] = true;
+	CylmRay R;
+	R.setup(rv, hd.S, s);
+	CylRay<1>& f = R.f;
+	const uint32_t total_tiles = hd.tiles;
+	for (uint32_t gt = 0; gt < total_tiles; ++gt) {
+		while (hd.next_class(gt)) { const float t0 = f.Pa[0]; f.Pa[0] = f.Pb[0]; f.Pb[0] = f.Pc[0]; f.Pc[0] = t0; }
+		__syncthreads();
+		for (uint32_t q = lane; q < kMRecQ; q += 64u) sm[q] = cs.rec[(size_t)gt * kMTileQ + q];
+		__syncthreads();
+		const float Dq = f.Dq[0];
+		unsigned char* o = out_bits + ((size_t)k * total_tiles + gt) * kMGroups;
+		for (uint32_t grp = 0; grp < kMGroups; ++grp) {
+			if (kMGrp == 8u && (grp & 2u)) continue;                       // an octet's entry names its first group; grp + 2 is its second
+			const uint32_t cand = cylm_retest(sm, grp, f.Pa[0], f.Pb[0], f.Pc[0], s.dir[0].x, s.dir[0].y, s.dir[0].z, f.D[0], Dq + Dq);
+			if (k < n_rays) {
+				if (kMGrp == 8u) { o[grp] = (unsigned char)(cand >> 4); o[grp + 2u] = (unsigned char)(cand & 15u); }
+				else o[grp] = (unsigned char)cand;
+			}
+		}
+		if (blockIdx.x == 0) {
+			for (uint32_t grp = lane; grp < kMGroups; grp += 64u) {
+				const float4 gi = sm[cylm_slot(grp, 6u)];
+				int* oo = out_order + (size_t)gt * kMTile + 4u * grp;
+				oo[0] = (int)__float_as_uint(gi.x); oo[1] = (int)__float_as_uint(gi.y); oo[2] = (int)__float_as_uint(gi.z); oo[3] = (int)__float_as_uint(gi.w);
 			}
 		}
 	}

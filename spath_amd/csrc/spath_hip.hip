@@ -311,7 +311,7 @@ int build_cylm(sphip_ctx* c, hipStream_t st) {
 	hipLaunchKernelGGL(SP_CM(k_cylm_hdr), dim3(1), dim3(1), 0, st, hdr, bnd);
 	hipLaunchKernelGGL(SP_CM(k_cylm_scatter), dim3(nblocks), dim3(256), 0, st, tris, n, sorted, (const uint32_t*)hdr, rec, (const float4*)c->scan.p, (float4*)c->cylm_big.p);
 	hipLaunchKernelGGL(SP_CM(k_cylm_pad), dim3(3), dim3(256), 0, st, (const uint32_t*)hdr, n, rec);
-	hipLaunchKernelGGL(SP_CM(k_cylm_hmax), dim3(max_tiles), dim3(SP_CM(kMGroups)), 0, st, (const uint32_t*)hdr, rec);
+	hipLaunchKernelGGL(SP_CM(k_cylm_hmax), dim3(max_tiles), dim3(SP_CM(kMGroups)), 0, st, tris, n, (const uint32_t*)hdr, rec);
 #undef SP_CM
 	HIP_TRY(c, hipGetLastError());
 	c->cylm_valid = true;
@@ -2392,7 +2392,8 @@ int sphip_selftest_stage1(sphip_t* c, const float* rays, size_t n_rays, uint32_t
 	if (e == hipSuccess) {
 		sp::CylStream cs{ (const float4*)c->cylm_rec.p, (const uint32_t*)c->cylm_hdr.p, (const float4*)c->cylm_big.p };
 		hipLaunchKernelGGL(c->cylm_wide ? sp::cylm512::k_selftest_stage1 : sp::cylm256::k_selftest_stage1, dim3((unsigned)(n_rays / 64)), dim3(64), 0, st,
-		                   (const float*)d_rays, (uint32_t)n_rays, cs, (const unsigned int*)c->bounds.p, (uint32_t*)d_words, (uint32_t*)d_tri, (int*)d_order);
+		                   (const float*)d_rays, (uint32_t)n_rays, cs, (const unsigned int*)c->bounds.p, (const float*)c->tris.p, (uint32_t)c->n_tris,
+		                   (uint32_t*)d_words, (uint32_t*)d_tri, (int*)d_order);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(out_words, d_words, words_b, hipMemcpyDeviceToHost, st);
@@ -2404,6 +2405,46 @@ int sphip_selftest_stage1(sphip_t* c, const float* rays, size_t n_rays, uint32_t
 	if (d_order) (void)hipFree(d_order);
 	if (d_tri) (void)hipFree(d_tri);
 	if (e != hipSuccess) return fail(c, SPHIP_E_DEVICE, "stage-1 selftest failed: %s", hipGetErrorString(e));
+	return SPHIP_OK;
+}
+
+int sphip_selftest_retest(sphip_t* c, const float* rays, size_t n_rays, uint8_t* out_bits, int32_t* out_order, uint32_t* tiles_out) {
+	if (!c) return SPHIP_E_INVALID;
+	if (!c->kids.empty()) return fail(c, SPHIP_E_STATE, "sphip_selftest_retest needs a single-device context (sphip_create)");
+	if (!c->have_scene) return fail(c, SPHIP_E_STATE, "sphip_selftest_retest called before a scene was set");
+	if (!tiles_out) return fail(c, SPHIP_E_INVALID, "tiles_out is NULL");
+	HIP_TRY(c, hipSetDevice(c->device));
+	hipStream_t st = c->own_stream;
+	int rc = ensure_cylm(c, st);
+	if (rc) return rc;
+	uint32_t hdr[8];
+	HIP_TRY(c, hipMemcpyAsync(hdr, c->cylm_hdr.p, sizeof hdr, hipMemcpyDeviceToHost, st));
+	HIP_TRY(c, hipStreamSynchronize(st));
+	const uint32_t tiles = hdr[6];
+	const uint32_t T = c->cylm_wide ? sp::cylm512::kMTile : sp::cylm256::kMTile;
+	const uint32_t grp8 = (c->cylm_wide ? sp::cylm512::kMGrp : sp::cylm256::kMGrp) == 8u ? 1u : 0u;
+	*tiles_out = tiles | (T << 20) | (grp8 << 31);         // as sphip_selftest_stage1
+	if (!out_bits) return SPHIP_OK;
+	if (!rays || !out_order || n_rays == 0 || n_rays % 64 || n_rays > 0x7fffffffull) return fail(c, SPHIP_E_INVALID, "bad re-test selftest arguments (n_rays=%zu)", n_rays);
+	const size_t bits_b = n_rays * tiles * (T / 4), order_b = (size_t)tiles * T * sizeof(int32_t);
+	void *d_rays = nullptr, *d_bits = nullptr, *d_order = nullptr;
+	hipError_t e = hipMalloc(&d_rays, n_rays * 24);
+	if (e == hipSuccess) e = hipMalloc(&d_bits, bits_b ? bits_b : 1);
+	if (e == hipSuccess) e = hipMalloc(&d_order, order_b ? order_b : 1);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_rays, rays, n_rays * 24, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) {
+		sp::CylStream cs{ (const float4*)c->cylm_rec.p, (const uint32_t*)c->cylm_hdr.p, (const float4*)c->cylm_big.p };
+		hipLaunchKernelGGL(c->cylm_wide ? sp::cylm512::k_selftest_retest : sp::cylm256::k_selftest_retest, dim3((unsigned)(n_rays / 64)), dim3(64), 0, st,
+		                   (const float*)d_rays, (uint32_t)n_rays, cs, (const unsigned int*)c->bounds.p, (unsigned char*)d_bits, (int*)d_order);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && bits_b) e = hipMemcpyAsync(out_bits, d_bits, bits_b, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess && order_b) e = hipMemcpyAsync(out_order, d_order, order_b, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (d_rays) (void)hipFree(d_rays);
+	if (d_bits) (void)hipFree(d_bits);
+	if (d_order) (void)hipFree(d_order);
+	if (e != hipSuccess) return fail(c, SPHIP_E_DEVICE, "re-test selftest failed: %s", hipGetErrorString(e));
 	return SPHIP_OK;
 }
 
@@ -2830,7 +2871,7 @@ int sphip_get_stats(sphip_t* c, sphip_stats* out) {
 		unsigned long long x[6] = {0, 0, 0, 0, 0, 0};
 		(void)hipMemcpy(x, c->counter.p, sizeof x, hipMemcpyDeviceToHost);
 		if (c->stats.kernel_variant >= 15)
-			fprintf(stderr, "[cyl stats] group bits set=%llu stage-2 rounds(per wave)=%llu wave-tiles=%llu exact tests=%llu -> bits/lane/tile=%.3f rounds/tile=%.2f exact per bit=%.3f lane utilisation in stage 2=%.3f wave-wide exact turns=%llu (%.2f per round, %.3f of their lanes used)\n",
+			fprintf(stderr, "[cyl stats] group bits set=%llu stage-2 rounds(per wave)=%llu wave-tiles=%llu exact tests=%llu -> bits/lane/tile=%.3f rounds/tile=%.2f exact per bit=%.3f (= exact-test candidates per list entry: what the re-test lets through) lane utilisation in stage 2=%.3f wave-wide exact turns=%llu (%.2f per round, %.3f of their lanes used)\n",
 			        x[1], x[2], x[3], x[4], (double)x[1] / (64.0 * (double)x[3]), (double)x[2] / (double)x[3], (double)x[4] / (double)x[1], (double)x[4] / (64.0 * (double)x[2]),
 			        x[5], (double)x[5] / (double)x[2], (double)x[4] / (64.0 * (double)x[5]));
 	}
