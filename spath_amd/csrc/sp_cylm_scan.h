@@ -824,6 +824,9 @@ SP_DEV void scan_cylm(const KArgs& a, const CylStream cs, float rv, const RaySlo
 				SP_PH_STAMP(ph_t0); SP_PH_ADD(ph_exact, ph_t1, ph_t0);
 			}
 			SP_PH_STAMP(ph_t1);
+			// everything fitted (nearly always): every word is zero, which the compiler cannot know -- a second trip would spend two popcounts,
+			// the prefix sum, a readlane and a branch to find nothing.  Only the overflow path left bits in the words and goes round again.
+			if (all <= kMCap) break;
 		}
 		// full batches now rather than later: the exact turns overlap the arrival of the next tile
 #ifdef SP_EXP_DRAIN_ALL      // experiment: every wave empties its stack at the end of every tile (same number of exact turns for the waves of a workgroup)
